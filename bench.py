@@ -8,7 +8,10 @@ the C ABI (`ldpc_decode_device`) on torch's current stream.  The channel is all-
 codeword + AWGN at sigma = 0.95: no frame's syndrome becomes clean, so all 50 rounds do
 full work with the reference's freeze-on-clean-syndrome semantics switched ON.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+--dump-outputs DIR: after the timed steps, what the last step gave its caller (the decoded bytes) goes to
+DIR/*.npy as float32 (dump_outputs); the inputs are seeded, so two builds can be compared output for output.
 
 N > 1: one rank per GPU (torch.distributed, backend "nccl" = RCCL).  Invoked plainly
 (`python bench.py --gpus N`, no WORLD_SIZE in the environment) this script starts the N
@@ -18,9 +21,10 @@ children's status; invoked under torch.distributed.run it is one of the ranks.  
 shard across ranks with no exchange while decoding; the decoded bytes are all-gathered at
 the end of every step (weak scaling: 4096 frames per GPU).
 
-Prints ONE JSON line (rank 0): metric/value/unit (whole-job Mbit/s), ms_per_step,
-`roofline` for the dominant kernel (HIP-event time on the launch stream, live) and, at
-N = 1, `cpu_baseline` (the oracle's restatement of the reference's CPU decoder,
+Prints ONE JSON line (rank 0): metric/value/unit (whole-job Mbit/s), ms_per_step, `config` and
+`ranks`.  A plain run does nothing else: set up, warm up, time the K steps, dump, print.  With --full
+the line also carries `roofline` for the dominant kernel (HIP-event time on the launch stream, live,
+and the HBM copy probes) and, at N = 1, `cpu_baseline` (the oracle's restatement of the reference's CPU decoder,
 MyLdpc.cpp:684-784, on a bounded sample), `extra` (BASELINE.json configs[3] and [4] at
 their full batch sizes), `ber` (BER @ SNR points, the other half of BASELINE's metric), `host_path` (the reference's own
 signature: host buffers in, host buffers out, PCIe included, in both input modes), `host_path_devices`
@@ -45,6 +49,24 @@ SIGMA = 0.95
 SEED = 20260101
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 VALU_PEAK_GINST = 256 * 4 * 2.4 / 4     # G wave64 VALU instructions per second: 256 CUs x 4 SIMDs x 2.4 GHz / 4 cycles
+DUMP_BYTES = 48 << 20          # --dump-outputs: at most this many bytes in one dump (the limit is 64 MB)
+
+
+def dump_outputs(dirname, out, frames):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step -- the packed decoded
+    bytes, one row of K/8 bytes per frame -- as float32 .npy files.  A batch larger than DUMP_BYTES is cut to
+    a fixed, seeded sample of frames, the same in every run with the same arguments; frame_index.npy names
+    the frames kept."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    rows = out.cpu().numpy().reshape(frames, -1)
+    per_frame = 4 * rows.shape[1] + 8
+    idx = np.arange(frames)
+    if frames * per_frame > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(SEED).choice(frames, DUMP_BYTES // per_frame, replace=False))
+    np.save(os.path.join(dirname, "decoded_bytes.npy"), rows[idx].astype(np.float32))
+    np.save(os.path.join(dirname, "frame_index.npy"), idx.astype(np.float64))
+
 
 # Extra measurement points (BASELINE.json configs[3], configs[4]); reported under "extra" of the
 # headline line at N = 1, or alone with   python bench.py --config bg1_layered | dvbs2_910_f16
@@ -358,8 +380,13 @@ def main():
     ap.add_argument("--config", default="dvbs2_sp", choices=["dvbs2_sp"] + sorted(EXTRA_CONFIGS),
                     help="dvbs2_sp = the headline workload (default); others are extra measurement points")
     ap.add_argument("--algo", default="sp")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip `extra` and `host_path` (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: roofline, per-kernel times and HBM probes, "
+                         "cpu_baseline, extra, ber, host_path, coder_path, host_path_devices")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's decoded bytes to DIR/*.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without `cpu_baseline`")
+    ap.add_argument("--no-extras", action="store_true", help="--full without `extra` and `host_path` (profiling runs)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: rehearsal of the N > 1 flow on fewer GPUs than ranks (collectives on CPU copies)")
     ap.add_argument("--sigma", type=float, default=0.0, help="extra configs: noise level override")
@@ -367,6 +394,10 @@ def main():
     ap.add_argument("--poll", type=int, default=-1, help="extra configs: poll_interval override (0 = asynchronous)")
     ap.add_argument("--tune", default="", help='tuning fields as JSON, e.g. \'{"merge": false}\' (A/B experiments)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.config != "dvbs2_sp":
+        ap.error("--dump-outputs writes the headline workload's outputs (--config dvbs2_sp)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args)
@@ -434,10 +465,11 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    # per-launch HIP events on the launch stream, inside the timed region: on two of the K steps (the
-    # events cost 2 % of a step, tools/gpu_timing_overhead.py), i.e. >= 100 launches of every kernel
-    dec.set_timing(max(1, args.steps // 2))
-    fence()
+    if args.full:
+        # per-launch HIP events on the launch stream, inside the timed region: on two of the K steps (the
+        # events cost 2 % of a step, tools/gpu_timing_overhead.py), i.e. >= 100 launches of every kernel
+        dec.set_timing(max(1, args.steps // 2))
+        fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -455,65 +487,37 @@ def main():
         per_rank_ms = [float(a.item()) / args.steps * 1e3 for a in alls]
         # the gathered bytes really are every rank's output: this rank's slice equals its own buffer
         assert torch.equal(gathered[rank * out.numel():(rank + 1) * out.numel()], out)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered if world > 1 else out, B * world)
 
     st = dec.stats()
-    kt = dec.kernel_times()
-    link_form = dec.link_form()          # which form of the column-fused check kernel the creation-time timing picked
-    placement = dec.placement()          # ... and on which of the candidate sets of arrays it runs
     assert st["iterations_launched"] == ITERS
     launch_frames = B
-    flood = [k for k in kt if k["phase"] in (0, 1)]
-    dom = max(flood, key=lambda k: k["ms_total"])
-    # what this rank's box delivers right now: float4 copy of 1 GiB, the better of the default cache policy and
-    # the streaming kernels' non-temporal one -- on EVERY rank, at the same moment, so that a GPU in a slow
-    # state shows in the record (ranks.per_rank)
-    try:
-        probe, probe_default, probe_nt = L.capi.hbm_probe(local_rank, 1 << 30, 5, by_policy=True)
-    except Exception:
-        probe = probe_default = probe_nt = None
-    mine = {"rank": rank, "device": local_rank, "ms_per_step": round(dt_own / args.steps * 1e3, 3),
-            "kernel": dom["name"], "kernel_form": None if not link_form else link_form["form"], "placement": placement, "avg_launch_ms": round(dom["ms_total"] / dom["launches"], 4),
-            "hbm_probe_gbs": None if probe is None else round(probe, 1)}
+    mine = {"rank": rank, "device": local_rank, "ms_per_step": round(dt_own / args.steps * 1e3, 3)}
+    if args.full:
+        kt = dec.kernel_times()
+        link_form = dec.link_form()          # which form of the column-fused check kernel the creation-time timing picked
+        placement = dec.placement()          # ... and on which of the candidate sets of arrays it runs
+        flood = [k for k in kt if k["phase"] in (0, 1)]
+        dom = max(flood, key=lambda k: k["ms_total"])
+        # what this rank's box delivers right now: float4 copy of 1 GiB, the better of the default cache policy and
+        # the streaming kernels' non-temporal one -- on EVERY rank, at the same moment, so that a GPU in a slow
+        # state shows in the record (ranks.per_rank)
+        try:
+            probe, probe_default, probe_nt = L.capi.hbm_probe(local_rank, 1 << 30, 5, by_policy=True)
+        except Exception:
+            probe = probe_default = probe_nt = None
+        mine.update({"kernel": dom["name"], "kernel_form": None if not link_form else link_form["form"], "placement": placement,
+                     "avg_launch_ms": round(dom["ms_total"] / dom["launches"], 4),
+                     "hbm_probe_gbs": None if probe is None else round(probe, 1)})
     per_rank = [mine]
     if world > 1:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
+    extras = args.full and not args.no_extras
     if rank == 0:
         frames_total = B * world * args.steps
         value = frames_total * K_CODE / dt / 1e6
-        dom_avg_ms = dom["ms_total"] / dom["launches"]
-        # bytes the dominant kernel's own loads and stores move per launch (for the column-fused check
-        # kernel: less than its share of 16 E + 4 N, the fused columns' messages stay in registers) ...
-        dom_bytes = dom["bytes_moved"] / dom["launches"]
-        achieved = dom_bytes / (dom_avg_ms * 1e-3) / 1e9
-        # ... and its share of SURVEY 8(d)'s two-kernel figure, for comparison
-        dom_alg = dom["bytes_total"] / dom["launches"]
-        all_bytes = sum(k["bytes_total"] for k in flood)
-        all_moved = sum(k["bytes_moved"] for k in flood)
-        all_ms = sum(k["ms_total"] for k in flood)
-        traffic, traffic_note = None, None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                tc = tj.get("__config__", {})
-                per = tj.get(dom["name"])
-                if per is not None and tc.get("frames_per_gpu"):
-                    traffic = int(per * launch_frames / tc["frames_per_gpu"])         # linear in the frames of a launch
-                    fcal = (tc.get("fetch_calibration") or {}).get("fetch_factor")
-                    traffic_note = ("PMC FETCH_SIZE x %s + WRITE_SIZE per launch from %s (rocprofv3, separate passes, "
-                                    "%d frames per launch%s)" % ("%.3f (calibrated on the run's copy probe)" % fcal if fcal else "2",
-                                                                 tc.get("source", "profiles/"), tc["frames_per_gpu"],
-                                                                 "" if tc["frames_per_gpu"] == launch_frames else ", scaled to %d" % launch_frames))
-            except Exception:
-                traffic = None
-        # what the box SUSTAINS right now, the GPU still hot from the timed steps: the same copy back to
-        # back for 0.3 s (these boxes drop to about 5.2 TB/s under load at times; a burst does not see it)
-        try:
-            sustained = L.capi.hbm_sustained(local_rank, 1 << 30, 300)
-        except Exception:
-            sustained = None
-        step_alg = (16 * g.E + 4 * N_CODE) * ITERS * B
         res = {
             "metric": "decoded Mbit/s (info bits), DVB-S2 N=64800 rate-1/2, 50 iters",
             "value": round(value, 2), "unit": "Mbit/s", "n_gpus": world, "steps": args.steps,
@@ -535,10 +539,45 @@ def main():
                       "backend": ("gloo (rehearsal)" if rehearsal else "nccl (RCCL)") if world > 1 else None,
                       "self_launched": os.environ.get("LDPC_BENCH_SELF_LAUNCHED") == "1",
                       "ms_per_step_min": round(min(per_rank_ms), 3), "ms_per_step_max": round(max(per_rank_ms), 3),
-                      # one entry per rank: its own step time, its dominant kernel's HIP-event launch time and the
-                      # copy rate its GPU delivered right after the timed steps
+                      # one entry per rank: its own step time and, with --full, its dominant kernel's HIP-event launch
+                      # time and the copy rate its GPU delivered right after the timed steps
                       "per_rank": per_rank},
-            "roofline": {
+        }
+        if args.full:
+            dom_avg_ms = dom["ms_total"] / dom["launches"]
+            # bytes the dominant kernel's own loads and stores move per launch (for the column-fused check
+            # kernel: less than its share of 16 E + 4 N, the fused columns' messages stay in registers) ...
+            dom_bytes = dom["bytes_moved"] / dom["launches"]
+            achieved = dom_bytes / (dom_avg_ms * 1e-3) / 1e9
+            # ... and its share of SURVEY 8(d)'s two-kernel figure, for comparison
+            dom_alg = dom["bytes_total"] / dom["launches"]
+            all_bytes = sum(k["bytes_total"] for k in flood)
+            all_moved = sum(k["bytes_moved"] for k in flood)
+            all_ms = sum(k["ms_total"] for k in flood)
+            traffic, traffic_note = None, None
+            tpath = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tpath):
+                try:
+                    tj = json.load(open(tpath))
+                    tc = tj.get("__config__", {})
+                    per = tj.get(dom["name"])
+                    if per is not None and tc.get("frames_per_gpu"):
+                        traffic = int(per * launch_frames / tc["frames_per_gpu"])         # linear in the frames of a launch
+                        fcal = (tc.get("fetch_calibration") or {}).get("fetch_factor")
+                        traffic_note = ("PMC FETCH_SIZE x %s + WRITE_SIZE per launch from %s (rocprofv3, separate passes, "
+                                        "%d frames per launch%s)" % ("%.3f (calibrated on the run's copy probe)" % fcal if fcal else "2",
+                                                                     tc.get("source", "profiles/"), tc["frames_per_gpu"],
+                                                                     "" if tc["frames_per_gpu"] == launch_frames else ", scaled to %d" % launch_frames))
+                except Exception:
+                    traffic = None
+            # what the box SUSTAINS right now, the GPU still hot from the timed steps: the same copy back to
+            # back for 0.3 s (these boxes drop to about 5.2 TB/s under load at times; a burst does not see it)
+            try:
+                sustained = L.capi.hbm_sustained(local_rank, 1 << 30, 300)
+            except Exception:
+                sustained = None
+            step_alg = (16 * g.E + 4 * N_CODE) * ITERS * B
+            res["roofline"] = {
                 "bound": "hbm", "kernel": dom["name"], "kernel_form": link_form, "placement": placement, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                 "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                 "traffic_source": traffic_note,
@@ -575,11 +614,10 @@ def main():
                 # (16 E + 4 N) x iterations x frames over the whole step's wall time
                 "whole_step_frac": round(step_alg / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
                 "whole_step_frac_of_probe": None if not probe else round(step_alg / (dt / args.steps) / 1e9 / probe, 4),
-            },
-        }
-        if world == 1 and not args.no_cpu_baseline:
+            }
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(rows, cols, gpu_graph=g, gpu_y=y)
-        if world == 1 and not args.no_extras:
+        if world == 1 and extras:
             dec.close()
             del y, out
             torch.cuda.empty_cache()
@@ -608,7 +646,7 @@ def main():
                 res["coder_path"] = coder_path()
             except Exception as e:
                 res["coder_path"] = {"error": repr(e)}
-        if not args.no_extras:
+        if extras:
             # the drop-in signature over a device list: ONE handle over every visible GPU, rank 0 only (the other
             # ranks have released their GPUs' memory and wait at the barrier below)
             if world > 1:
@@ -622,7 +660,7 @@ def main():
             except Exception as e:
                 res["host_path_devices"] = {"error": repr(e)}
         print(json.dumps(res), flush=True)
-    elif world > 1 and not args.no_extras:
+    elif world > 1 and extras:
         dec.close()
         del y, out, gathered
         torch.cuda.empty_cache()

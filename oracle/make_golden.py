@@ -77,6 +77,35 @@ def channel(N, frames, sigma, seed):
     return (1.0 + sigma * rng.standard_normal((frames, N))).astype(np.float32)
 
 
+# frames from one more generator (numpy's default_rng, seed 20261004) drawn in this order:
+# (rate index, N, sigma, frames); tests/test_host_cpu.py::test_oracle_against_reference_kernels_on_fresh_seeds
+FRESH_CASES = [(0, 648, 0.8, 6), (3, 576, 0.55, 6), (1, 672, 0.7, 4), (0, 1152, 0.95, 3)]
+
+
+def fresh_seeds():
+    """tests/golden/fresh_seeds.npz: per case i the channel values y<i>, the flooding chains' packed bytes,
+    hard bits and `Time=` (<algo>_out<i>, <algo>_hard<i>, <algo>_time<i>, 40 iterations) and, except at
+    rate 2/3A, the fused layered kernel's bytes (layered_out<i>)."""
+    rng = np.random.default_rng(20261004)
+    data = dict(cases=np.array([(rate, N) for rate, N, _, _ in FRESH_CASES], np.int32))
+    for i, (rate, N, sigma, B) in enumerate(FRESH_CASES):
+        rows, cols = oracle.wimax_edges(rate, N)
+        z = N // 24
+        M = len(SEEDS[rate]) * z
+        rg = rk.RefGraph(rows, cols, M, N, N - M)
+        y = (1.0 + sigma * rng.standard_normal((B, N))).astype(np.float32)
+        data["y%d" % i] = y
+        for algo in ("ms", "sp"):
+            r = rk.decode(rg, y, algo)
+            data["%s_out%d" % (algo, i)] = r["out"]
+            data["%s_hard%d" % (algo, i)] = r["hard"]
+            data["%s_time%d" % (algo, i)] = r["time"]
+        if rate != 1:
+            data["layered_out%d" % i] = rk.decode_tdmp_fused(z, np.array(SEEDS[rate], np.int8), y)
+    np.savez_compressed(os.path.join(OUT, "fresh_seeds.npz"), **data)
+    print("fresh seeds", len(FRESH_CASES), "cases")
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     for name, rate, N, sigma, B, seed, tap in FLOOD_CASES:
@@ -132,6 +161,7 @@ def main():
     # (E printed by the reference's initCheckMatrix + adjacency build)
     np.savez_compressed(os.path.join(OUT, "graph_facts.npz"),
                         cases=np.array([[4, 576, 2112], [0, 648, 2052], [0, 2304, 7296], [0, 64800, 205200]]))
+    fresh_seeds()
 
 
 if __name__ == "__main__":

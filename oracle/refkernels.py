@@ -3,7 +3,7 @@
 
 TEST INFRASTRUCTURE ONLY, and only in the build container: the library exists
 only where /root/reference exists.  Used by oracle/make_golden.py (to make the
-committed fixtures) and by tests that skip when it is absent.
+committed fixtures, which the tests read instead).
 """
 import ctypes
 import os

@@ -1,8 +1,10 @@
 """BASELINE.json's full-size code on the GPU: DVB-S2-profile (64800, 32400).
 Bit-exact against the oracle on sampled frames, plus size-independent properties
 (codeword symmetry, noiseless idempotence, all-zero decode)."""
+import json
 import os
 import subprocess
+import sys
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -537,3 +539,26 @@ def test_single_group_host_call_is_cut_in_two_and_gives_the_same_bytes(built, co
     assert np.array_equal(out, want_out) and np.array_equal(iters, want_it)
     small.close()
     assert L.capi.host_locked_ranges() == (0, 0)
+
+
+def test_bench_plain_run_dumps_what_its_last_step_decoded(built, code, tmp_path):
+    """`bench.py` without --full prints the headline fields only (no roofline, baselines or extra points),
+    and --dump-outputs writes the decoded bytes of its last timed step: those of the same seeded frames
+    decoded here with the benchmark's settings."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "256",
+                        "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout + p.stderr
+    r = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["value"] > 0
+    assert r["unit"] == "Mbit/s" and r["higher_is_better"] is True and r["dtype"] == "f32"
+    assert not {"roofline", "cpu_baseline", "extra", "ber", "host_path", "coder_path", "host_path_devices"} & set(r)
+    got, idx = np.load(d / "decoded_bytes.npy"), np.load(d / "frame_index.npy")
+    assert got.dtype == np.float32 and got.shape == (256, K // 8) and np.array_equal(idx, np.arange(256))
+    rows, cols, g, og = code
+    y = channel.awgn_device(N, 0, 256, 0.95, seed=20260101).cpu().numpy()
+    dec = L.Decoder(g, K, max_batch=256, algo="sp", max_iter=50, llr_scale=8.0, early_term=True)
+    out, _ = dec.decode(y)
+    dec.close()
+    assert np.array_equal(got, out.reshape(256, -1).astype(np.float32))

@@ -152,7 +152,7 @@ def test_bench_starts_its_own_ranks(built):
     share this box's one GPU (the collective runs on CPU copies; decoding is the HIP path)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "256", "--backend", "gloo", "--no-cpu-baseline"],
+                        "--batch", "256", "--backend", "gloo", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert p.returncode == 0, p.stdout + p.stderr
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -179,7 +179,7 @@ def test_bench_over_rccl_runs_where_two_gpus_are_visible(built):
         pytest.skip("one GPU visible: RCCL with two ranks needs two")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "512", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900)
+                        "--batch", "512", "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900)
     assert p.returncode == 0, p.stdout + p.stderr
     r = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert r["n_gpus"] == 2 and r["ranks"]["backend"] == "nccl (RCCL)" and len(r["ranks"]["per_rank"]) == 2

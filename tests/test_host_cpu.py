@@ -189,6 +189,29 @@ def test_bench_multi_gpu_form_starts_its_own_ranks(built):
     assert "torch.distributed" in p.stderr or "ChildFailedError" in p.stderr or "local_rank" in p.stderr
 
 
+def test_bench_dump_outputs_is_a_fixed_sample_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: the headline batch (4096 frames of K/8 = 4050 bytes) is cut to the same seeded
+    sample of whole frames in every run, float32 / float64 files of at most 64 MB in all; a small batch is
+    written whole."""
+    import torch
+    import bench
+    out = torch.randint(0, 256, (4096 * 4050,), dtype=torch.uint8, generator=torch.Generator().manual_seed(1))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out, 4096)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["decoded_bytes.npy", "frame_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 10 ** 6
+    got, idx = np.load(tmp_path / "a" / "decoded_bytes.npy"), np.load(tmp_path / "a" / "frame_index.npy")
+    assert got.dtype == np.float32 and idx.dtype == np.float64 and len(idx) > 2048
+    assert np.array_equal(idx, np.unique(idx)) and idx[-1] < 4096
+    assert np.array_equal(got, out.numpy().reshape(4096, 4050)[idx.astype(np.int64)].astype(np.float32))
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    bench.dump_outputs(str(tmp_path / "c"), out[:256 * 4050], 256)
+    assert np.array_equal(np.load(tmp_path / "c" / "frame_index.npy"), np.arange(256))
+    assert np.array_equal(np.load(tmp_path / "c" / "decoded_bytes.npy"), out[:256 * 4050].numpy().reshape(256, 4050))
+
+
 # ---------------------------------------------------------------- host-side data
 
 @pytest.mark.parametrize("rate", range(6))
@@ -311,26 +334,24 @@ def test_counter_based_channel_generator(tmp_path):
 
 # ------------------------------------------------------------- oracle vs reference
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/decodeCL.c"),
-                    reason="the reference exists only in the build container")
 def test_oracle_against_reference_kernels_on_fresh_seeds():
-    from oracle import refkernels as rk
-    rng = np.random.default_rng(20261004)
-    for rate, N, sigma, B in [(0, 648, 0.8, 6), (3, 576, 0.55, 6), (1, 672, 0.7, 4), (0, 1152, 0.95, 3)]:
+    """The reference kernels' results on frames of a generator no other fixture uses
+    (tests/golden/fresh_seeds.npz, made by oracle/make_golden.py's fresh_seeds)."""
+    from util import GOLDEN, load_golden
+    gd = load_golden(os.path.join(GOLDEN, "fresh_seeds.npz"))
+    assert len(gd["cases"]) == 4
+    for i, (rate, N) in enumerate(gd["cases"].tolist()):
         K, M, z = codes.wimax_dims(rate, N)
         rows, cols = codes.wimax_edges(rate, N)
         g = oracle.Graph(rows, cols, M, N, K)
-        rg = rk.RefGraph(rows, cols, M, N, K)
-        y = (1.0 + sigma * rng.standard_normal((B, N))).astype(np.float32)
+        y = gd["y%d" % i]
         for algo in ("ms", "sp"):
             o = oracle.decode(g, y, algo)
-            r = rk.decode(rg, y, algo)
-            assert np.array_equal(o["out"], r["out"]) and np.array_equal(o["hard"], r["hard"])
-            assert int(o["iters"].max()) == r["time"]
+            assert np.array_equal(o["out"], gd["%s_out%d" % (algo, i)]) and np.array_equal(o["hard"], gd["%s_hard%d" % (algo, i)])
+            assert int(o["iters"].max()) == int(gd["%s_time%d" % (algo, i)])
         if rate != 1:
-            from myldpccppapi_amd.wimax_seeds import SEEDS
             o = oracle.decode(g, y, "layered", layer_rows=z)
-            assert np.array_equal(o["out"], rk.decode_tdmp_fused(z, np.array(SEEDS[rate], np.int8), y))
+            assert np.array_equal(o["out"], gd["layered_out%d" % i])
 
 
 # ------------------------------------------------------------------- C++ Coder

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of the per-launch HIP events bench.py keeps on during its timed region: the headline
+"""Cost of the per-launch HIP events bench.py --full keeps on during its timed region: the headline
 step with set_timing(True) vs set_timing(False), alternating on one box."""
 import sys, os, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))

@@ -4,7 +4,7 @@
 N=${1:-12}; shift
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 for i in $(seq 1 $N); do
-  python3 $REPO/bench.py --no-extras --no-cpu-baseline --steps 2 --warmup 1 "$@" 2>/dev/null | python3 -c "
+  python3 $REPO/bench.py --full --no-extras --no-cpu-baseline --steps 2 --warmup 1 "$@" 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 p=d['roofline']['placement']
