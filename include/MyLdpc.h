@@ -84,6 +84,13 @@ public:
      * through the library's own pinned ring) or LDPC_HOST_INPUT_LOCK_PAGES (page-locks the caller's pages
      * for the call; include/ldpc_hip.h).  Before addDecodeType(). */
     void setHostInput(int mode) { hostInput = mode; }
+    /* Normalized / offset min-sum for DecodeMS, DecodeCPU and DecodeTDMPCL: each check row's two smallest
+     * magnitudes m become fmaxf(m - offset, 0) * scale (scale 0 = 1; offset in units of postCode, include/ldpc_hip.h:
+     * ms_scale / ms_offset).  DecodeSP ignores it.  DecodeTDMP on a code whose rows differ in weight runs the
+     * layered schedule of DecodeTDMPCL and takes the correction too; where it follows the reference's host-layered
+     * path (every row of one weight) it fails in addDecodeType while a correction is set, as DecodeMSCL always
+     * does (both reproduce reference kernels).  (0, 0) = off.  Before addDecodeType(). */
+    void setMinSumCorrection(float scale, float offset) { msScale = scale; msOffset = offset; }
     int lastIterations() const { return lastTime; }             /* the reference's "Time=" */
     const char *lastError() const { return err.c_str(); }
     int getNonZeros() const { return nonZeros; }
@@ -103,6 +110,7 @@ private:
     int device;
     std::vector<int> devices;        /* setDevices(); empty: `device` alone */
     int hostInput = 0;               /* setHostInput() */
+    float msScale = 0.0f, msOffset = 0.0f; /* setMinSumCorrection() */
     int makeDecoder(const ldpc_decoder_config &cfg, ldpc_decoder **out);
     const signed char *hSeed;
     int seedRowLength;

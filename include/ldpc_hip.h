@@ -147,6 +147,20 @@ typedef struct ldpc_decoder_config {
                                    writers produce it (variable-node kernels column by column), so that every store
                                    of a round streams and the check kernels gather their inputs instead
                                    (0 = automatic: on; 1 = on; -1 = off: edge order, as the check->variable array) */
+    /* ---- normalized / offset min-sum (appended; a struct_size of offsetof(ldpc_decoder_config, ms_scale), the
+     *      size before these fields, is accepted and means both off).  Each of a check row's two magnitude
+     *      candidates m (the two smallest |q|) becomes
+     *          m' = fmaxf(m - ms_offset, 0) * ms_scale        (fp32, in this order)
+     *      once per row and frame, before the per-edge selection and sign; with LDPC_MSG_F16 the result is
+     *      rounded to fp16 where it is produced.  ms_offset is in the units of the channel values passed to
+     *      ldpc_decode (with the reference's convention, BPSK +-1 plus noise: units of y, not of LLRs): offset
+     *      min-sum depends on the scale of the input, normalized min-sum does not.
+     *      LDPC_ALGO_MS and LDPC_ALGO_LAYERED only (others: LDPC_ERR_UNSUPPORTED when either is non-zero).  The
+     *      record kernels and the streaming kernels carry the correction; the LDS-resident one-launch kernels do
+     *      not and are not selected (forcing them, LDPC_TUNE_ON(FUSED) with LDPC_TUNE_OFF(LDSP):
+     *      LDPC_ERR_UNSUPPORTED).  NaN, inf or a value out of range: LDPC_ERR_ARG. ----------------------------- */
+    float ms_scale;             /* alpha: 0 = off (factor 1), else 0 < alpha <= 1                            */
+    float ms_offset;            /* beta: 0 = off, else 0 < beta < 1000                                        */
 } ldpc_decoder_config;
 
 /* two-bit fields of tune_flags: LDPC_TUNE_ON(f) forces the choice on, LDPC_TUNE_OFF(f) off */

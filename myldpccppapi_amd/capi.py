@@ -160,7 +160,8 @@ class Decoder:
 
     def __init__(self, graph, K, max_batch, algo="sp", max_iter=40, llr_scale=8.0, early_term=True,
                  device=0, layer_rows=0, pack_mode=PACK_BYTES, frames_per_lane=0, poll_interval=0,
-                 msg_dtype=MSG_F32, tune=None, devices=None, host_input="auto", host_copy_threads=0):
+                 msg_dtype=MSG_F32, tune=None, devices=None, host_input="auto", host_copy_threads=0,
+                 ms_scale=0.0, ms_offset=0.0):
         L = _lib.load()
         cfg = DecoderConfig()
         L.ldpc_decoder_config_init(ctypes.byref(cfg))
@@ -175,6 +176,8 @@ class Decoder:
         # page-locking the caller's pages for the call (include/ldpc_hip.h: enum ldpc_host_input)
         cfg.host_input = HOST_INPUT[host_input] if isinstance(host_input, str) else int(host_input)
         cfg.host_copy_threads = int(host_copy_threads)
+        # normalized / offset min-sum, algo "ms" / "layered": R = fmaxf(min - ms_offset, 0) * ms_scale (0 = off)
+        cfg.ms_scale, cfg.ms_offset = float(ms_scale), float(ms_offset)
         self.cfg = cfg
         self.graph = graph
         self.K, self.N, self.E = int(K), graph.N, graph.E

@@ -339,6 +339,15 @@ int Coder::addDecodeType(enum decodeType deType)
         if (uniform) cfg.algo = LDPC_ALGO_LAYERED_HOST;
     }
     if (deType == DecodeMSCL) cfg.max_iter = 120;      /* hard-coded in the reference kernel, decodeCL.c:479 */
+    if (msScale != 0.0f || msOffset != 0.0f) {
+        if (cfg.algo == LDPC_ALGO_MS_FUSED)
+            return fail(LDPC_ERR_UNSUPPORTED, "addDecodeType: DecodeMSCL reproduces the reference's fused min-sum "
+                        "kernel and takes no min-sum correction (setMinSumCorrection)");
+        if (cfg.algo == LDPC_ALGO_LAYERED_HOST)
+            return fail(LDPC_ERR_UNSUPPORTED, "addDecodeType: DecodeTDMP follows the reference's host-layered path on "
+                        "this code and takes no min-sum correction (setMinSumCorrection); DecodeTDMPCL does");
+        if (cfg.algo != LDPC_ALGO_SP) { cfg.ms_scale = msScale; cfg.ms_offset = msOffset; }   /* DecodeSP: ignored */
+    }
     ldpc_decoder *d = nullptr;
     int rc = makeDecoder(cfg, &d);
     if (rc) return fail(rc, ldpc_last_error());
@@ -363,7 +372,9 @@ int Coder::decode(float *postCode, char *srcCode, int srcLength, enum decodeType
             ldpc_decoder_config_init(&cfg);
             cfg.K = ldpcK; cfg.max_batch = codeSize; cfg.max_iter = times; cfg.device = device;
             cfg.algo = LDPC_ALGO_MS; cfg.pack_mode = LDPC_PACK_BITS; cfg.early_term = 1; cfg.poll_interval = 4;
-            cfg.layer_rows = z;                              /* circulant size: lets the one-launch kernels apply */
+            cfg.layer_rows = z;                              /* circulant size: lets the record / one-launch kernels apply
+                                                                (with a correction: the record kernel or the streaming ones) */
+            cfg.ms_scale = msScale; cfg.ms_offset = msOffset;
             int rc = makeDecoder(cfg, &d);
             if (rc) return fail(rc, ldpc_last_error());
             decoders[(int)DecodeCPU] = d;

@@ -46,6 +46,7 @@ namespace ldpc {
 
 constexpr int kAlgoSP = 0;
 constexpr int kAlgoMS = 1;
+constexpr int kAlgoMSC = 2;   /* min-sum with the normalized / offset correction (check_ms, MsCorr) */
 constexpr int kCompactCapacity = 512;   /* frames a child decoder takes over (8 tiles of 64) */
 constexpr int kLastCapacity = 64;       /* ... and the last decoder of the chain: one tile */
 constexpr int kBlock = 256;          /* 4 waves */
@@ -189,8 +190,10 @@ struct CheckArgs {
     int32_t n_rows;
     int32_t rows_per_wave;
     int32_t degree;                      /* generic kernel only */
+    float ms_scale = 1.0f;               /* kAlgoMSC only: alpha (fills what was padding before `tail`) */
     TailRef tail;
     int32_t tiles_first = 0;             /* grid is (tiles, blocks) instead of (blocks, tiles): grid_pos() */
+    float ms_offset = 0.0f;              /* kAlgoMSC only: beta (fills what was padding before `first_chan`) */
     /* min-sum, round 1 only: the variable->check messages of round 0 are the channel values (decodeInitMS,
      * decodeCL.c:121: q = y), so they are read from the channel array by column instead of from Q, which the input
      * transpose then does not have to write at all (a third of its traffic).  nullptr: read Q. */
@@ -258,11 +261,26 @@ __device__ __forceinline__ void check_sp(const float (&x)[D][V], float (&out)[D]
     }
 }
 
+/* Normalized / offset min-sum (LDPC_ALGO_MS / LAYERED with ms_scale or ms_offset set): each of a row's
+ * two magnitude candidates m becomes fmaxf(m - beta, 0) * alpha, fp32, once per row and frame, before the
+ * per-edge selection and sign.  With fp16 messages the result is rounded to fp16 right here, where R is
+ * produced: alpha * m is generally no binary16 value (+-min always was), and the column-fused kernels keep
+ * some R in registers without ever storing them. */
+struct MsCorr {
+    float scale, offset;
+};
+template <typename T> __device__ __forceinline__ float ms_corr(float m, const MsCorr &c)
+{
+    const float r = fmaxf(m - c.offset, 0.0f) * c.scale;
+    return sizeof(T) == 2 ? (float)(hf)r : r;
+}
+
 /* Min-sum, decodeCL.c:132-146: sign = XOR of (x_j < 0) over j != k, magnitude =
  * fmin chain over |x_j| starting at 1000.  min is exact and order-free, so the
- * two-smallest form gives the same floats; NaNs are skipped as fmin skips them. */
-template <int D, int V>
-__device__ __forceinline__ void check_ms(const float (&x)[D][V], float (&out)[D][V])
+ * two-smallest form gives the same floats; NaNs are skipped as fmin skips them.
+ * CORR: the candidates go through ms_corr<T> first. */
+template <int D, int V, bool CORR = false, typename T = float>
+__device__ __forceinline__ void check_ms(const float (&x)[D][V], float (&out)[D][V], MsCorr c = MsCorr{1.0f, 0.0f})
 {
 #pragma unroll
     for (int v = 0; v < V; ++v) {
@@ -276,6 +294,7 @@ __device__ __forceinline__ void check_ms(const float (&x)[D][V], float (&out)[D]
             if (a < m1) { m2 = m1; m1 = a; idx = j; }
             else if (a < m2) { m2 = a; }
         }
+        if (CORR) { m1 = ms_corr<T>(m1, c); m2 = ms_corr<T>(m2, c); }
 #pragma unroll
         for (int k = 0; k < D; ++k) {
             const float b = (k == idx) ? m2 : m1;
@@ -284,6 +303,8 @@ __device__ __forceinline__ void check_ms(const float (&x)[D][V], float (&out)[D]
         }
     }
 }
+
+__device__ __forceinline__ MsCorr ms_corr_of(const CheckArgs &a) { return MsCorr{a.ms_scale, a.ms_offset}; }
 
 /* V = frames per lane of the LAYOUT (tile = 64*V frames); W <= V = floats per lane this
  * kernel moves: a row's 64*V-float segment is covered by V/W waves of 64*W floats each
@@ -306,12 +327,12 @@ __global__ __launch_bounds__(kBlock) void check_kernel(const CheckArgs a)
     const T *Qu = static_cast<const T *>(a.Q) + (size_t)tile * (size_t)a.E * F;      /* wave-uniform: + slot * F + lane_off */
     T *Rt = static_cast<T *>(a.R) + (size_t)tile * (size_t)a.E * F + lane_off;
 
-    const T *Ct = (ALGO == kAlgoMS && a.first_chan)
+    const T *Ct = (ALGO != kAlgoSP && a.first_chan)
                       ? static_cast<const T *>(a.first_chan) + (size_t)tile * (size_t)a.N * F + lane_off : nullptr;
     for (int r = r_begin; r < r_end; ++r) {
         const int e0 = a.cls_e0[r];
         float x[D][W], out[D][W];
-        if (ALGO == kAlgoMS && Ct) {
+        if (ALGO != kAlgoSP && Ct) {
 #pragma unroll
             for (int k = 0; k < D; ++k) vload<W>(x[k], Ct + (size_t)a.edge_col[e0 + k] * F);
         } else {
@@ -320,7 +341,7 @@ __global__ __launch_bounds__(kBlock) void check_kernel(const CheckArgs a)
 #pragma unroll
             for (int k = 0; k < D; ++k) vload<W>(x[k], Qu + (size_t)sl[k] * F + lane_off);
         }
-        if (ALGO == kAlgoSP) check_sp<D, W>(x, out); else check_ms<D, W>(x, out);
+        if (ALGO == kAlgoSP) check_sp<D, W>(x, out); else if (ALGO == kAlgoMS) check_ms<D, W>(x, out); else check_ms<D, W, true, T>(x, out, ms_corr_of(a));
 #pragma unroll
         for (int k = 0; k < D; ++k) vstore<W>(Rt + (size_t)(e0 + k) * F, out[k]);
     }
@@ -332,10 +353,10 @@ __global__ __launch_bounds__(kBlock) void check_kernel(const CheckArgs a)
  * repeats).  Qt / Rt: this lane's V values of the tile. */
 template <int ALGO, int V, typename T>
 __device__ __forceinline__ void check_row_generic(const T *Qu, unsigned lane_off, T *Rt, int e0, int D,
-                                                  const int32_t *__restrict__ qpos)
+                                                  const int32_t *__restrict__ qpos, const MsCorr &c)
 {
     constexpr size_t F = 64 * V;
-    if (ALGO == kAlgoMS) {
+    if (ALGO != kAlgoSP) {
         /* two passes over the row instead of one per output: min1/min2/argmin and the sign
          * parity first, then each output from its own re-read value (L2 serves the re-read) */
         float m1[V], m2[V];
@@ -353,6 +374,10 @@ __device__ __forceinline__ void check_row_generic(const T *Qu, unsigned lane_off
                 if (m < m1[v]) { m2[v] = m1[v]; m1[v] = m; idx[v] = j; }
                 else if (m < m2[v]) { m2[v] = m; }
             }
+        }
+        if (ALGO == kAlgoMSC) {
+#pragma unroll
+            for (int v = 0; v < V; ++v) { m1[v] = ms_corr<T>(m1[v], c); m2[v] = ms_corr<T>(m2[v], c); }
         }
         for (int k = 0; k < D; ++k) {
             float xk[V], o[V];
@@ -399,7 +424,7 @@ __global__ __launch_bounds__(kBlock) void check_kernel_generic(const CheckArgs a
     const int r_end = min(r_begin + a.rows_per_wave, a.n_rows);
     const T *Qu = static_cast<const T *>(a.Q) + (size_t)tile * (size_t)a.E * F;
     T *Rt = static_cast<T *>(a.R) + (size_t)tile * (size_t)a.E * F + (size_t)lane * V;
-    for (int r = r_begin; r < r_end; ++r) check_row_generic<ALGO, V, T>(Qu, (unsigned)lane * V, Rt, a.cls_e0[r], a.degree, a.qpos);
+    for (int r = r_begin; r < r_end; ++r) check_row_generic<ALGO, V, T>(Qu, (unsigned)lane * V, Rt, a.cls_e0[r], a.degree, a.qpos, ms_corr_of(a));
 }
 
 /* ---- several degree classes in ONE launch -------------------------------------------------
@@ -421,14 +446,14 @@ struct GroupClass {
 template <int ALGO, int D, int V, int W, typename T>
 __device__ __forceinline__ void check_rows(const T *Qu, unsigned lane_off, T *Rt, const int32_t *__restrict__ e0s, int r_begin, int r_end,
                                            const T *Ct, const int32_t *__restrict__ edge_col,
-                                           const int32_t *__restrict__ qpos)
+                                           const int32_t *__restrict__ qpos, const MsCorr &c)
 {
     const int lane = threadIdx.x & 63;
     constexpr size_t F = 64 * V;
     for (int r = r_begin; r < r_end; ++r) {
         const int e0 = e0s[r];
         float x[D][W], out[D][W];
-        if (ALGO == kAlgoMS && Ct) {            /* round 1: q = y, by column (CheckArgs::first_chan) */
+        if (ALGO != kAlgoSP && Ct) {            /* round 1: q = y, by column (CheckArgs::first_chan) */
 #pragma unroll
             for (int k = 0; k < D; ++k) vload<W>(x[k], Ct + (size_t)edge_col[e0 + k] * F);
         } else {
@@ -437,7 +462,7 @@ __device__ __forceinline__ void check_rows(const T *Qu, unsigned lane_off, T *Rt
 #pragma unroll
             for (int k = 0; k < D; ++k) vload<W>(x[k], Qu + (size_t)sl[k] * F + lane_off);
         }
-        if (ALGO == kAlgoSP) check_sp<D, W>(x, out); else check_ms<D, W>(x, out);
+        if (ALGO == kAlgoSP) check_sp<D, W>(x, out); else if (ALGO == kAlgoMS) check_ms<D, W>(x, out); else check_ms<D, W, true, T>(x, out, c);
 #pragma unroll
         for (int k = 0; k < D; ++k) vstore<W>(Rt + (size_t)(e0 + k) * F, out[k]);
     }
@@ -445,17 +470,17 @@ __device__ __forceinline__ void check_rows(const T *Qu, unsigned lane_off, T *Rt
 
 template <int ALGO, int V, typename T, int D, int DLO, int W = 1> struct CheckDispatch {
     static __device__ __forceinline__ void run(int deg, const T *Qu, unsigned lane_off, T *Rt, const int32_t *e0s, int rb, int re,
-                                               const T *Ct, const int32_t *edge_col, const int32_t *qpos)
+                                               const T *Ct, const int32_t *edge_col, const int32_t *qpos, const MsCorr &c)
     {
-        if (deg == D) check_rows<ALGO, D, V, W, T>(Qu, lane_off, Rt, e0s, rb, re, Ct, edge_col, qpos);
-        else CheckDispatch<ALGO, V, T, D - 1, DLO, W>::run(deg, Qu, lane_off, Rt, e0s, rb, re, Ct, edge_col, qpos);
+        if (deg == D) check_rows<ALGO, D, V, W, T>(Qu, lane_off, Rt, e0s, rb, re, Ct, edge_col, qpos, c);
+        else CheckDispatch<ALGO, V, T, D - 1, DLO, W>::run(deg, Qu, lane_off, Rt, e0s, rb, re, Ct, edge_col, qpos, c);
     }
 };
 template <int ALGO, int V, typename T, int DLO, int W> struct CheckDispatch<ALGO, V, T, DLO, DLO, W> {
     static __device__ __forceinline__ void run(int, const T *Qu, unsigned lane_off, T *Rt, const int32_t *e0s, int rb, int re,
-                                               const T *Ct, const int32_t *edge_col, const int32_t *qpos)
+                                               const T *Ct, const int32_t *edge_col, const int32_t *qpos, const MsCorr &c)
     {
-        check_rows<ALGO, DLO, V, W, T>(Qu, lane_off, Rt, e0s, rb, re, Ct, edge_col, qpos);
+        check_rows<ALGO, DLO, V, W, T>(Qu, lane_off, Rt, e0s, rb, re, Ct, edge_col, qpos, c);
     }
 };
 
@@ -481,9 +506,9 @@ __global__ __launch_bounds__(kBlock) void check_group_kernel(const CheckArgs a, 
     const unsigned lane_off = (unsigned)sub * 64 * W + (unsigned)lane * W;
     const T *Qu = static_cast<const T *>(a.Q) + (size_t)tile * (size_t)a.E * F;
     T *Rt = static_cast<T *>(a.R) + (size_t)tile * (size_t)a.E * F + lane_off;
-    const T *Ct = (ALGO == kAlgoMS && a.first_chan)
+    const T *Ct = (ALGO != kAlgoSP && a.first_chan)
                       ? static_cast<const T *>(a.first_chan) + (size_t)tile * (size_t)a.N * F + lane_off : nullptr;
-    CheckDispatch<ALGO, V, T, DHI, DLO, W>::run(cls[c].degree, Qu, lane_off, Rt, cls[c].ids, r_begin, r_end, Ct, a.edge_col, a.qpos);
+    CheckDispatch<ALGO, V, T, DHI, DLO, W>::run(cls[c].degree, Qu, lane_off, Rt, cls[c].ids, r_begin, r_end, Ct, a.edge_col, a.qpos, ms_corr_of(a));
 }
 
 /* checkResult, decodeCL.c:88-108, on the bit masks: one thread per row XORs the
@@ -682,7 +707,7 @@ __device__ __forceinline__ void link_extra_rows(const CheckArgs &a, const LinkAr
     if (w >= g.n_extra) return;
     const T *Qu = static_cast<const T *>(a.Q) + (size_t)tile * (size_t)a.E * F;
     T *Rt = static_cast<T *>(a.R) + (size_t)tile * (size_t)a.E * F + (size_t)lane * V;
-    check_row_generic<ALGO, V, T>(Qu, (unsigned)lane * V, Rt, g.extra_e0[w], g.extra_deg[w], a.qpos);
+    check_row_generic<ALGO, V, T>(Qu, (unsigned)lane * V, Rt, g.extra_e0[w], g.extra_deg[w], a.qpos, ms_corr_of(a));
 }
 
 /* build-time experiment hook: -DLDPC_LINK_WIDE_WAVES=n asks the compiler for n waves per SIMD */
@@ -748,7 +773,7 @@ __global__ __launch_bounds__(kBlock) LDPC_LINK_WIDE_ATTR void check_link_kernel(
             for (int v = 0; v < V; ++v) old_w[v] = hard_t[(size_t)pend_col * V + v];
         }
         float out[D][V];
-        if (ALGO == kAlgoSP) check_sp<D, V>(x, out); else check_ms<D, V>(x, out);
+        if (ALGO == kAlgoSP) check_sp<D, V>(x, out); else if (ALGO == kAlgoMS) check_ms<D, V>(x, out); else check_ms<D, V, true, T>(x, out, ms_corr_of(a));
         if (r + 1 < r_end) {
 #pragma unroll
             for (int k = 0; k < D; ++k) vload<V>(x[k], Qt + (size_t)qn[k] * F + lane_q);
@@ -915,7 +940,7 @@ __global__ __launch_bounds__(kBlock) void check_link_narrow_kernel(const CheckAr
             for (int w = 0; w < W; ++w) old_mine[w] = load_field(pend_col, (W * lane + w) % V);
         }
         float out[D][W];
-        if (ALGO == kAlgoSP) check_sp<D, W>(x, out); else check_ms<D, W>(x, out);
+        if (ALGO == kAlgoSP) check_sp<D, W>(x, out); else if (ALGO == kAlgoMS) check_ms<D, W>(x, out); else check_ms<D, W, true, T>(x, out, ms_corr_of(a));
         if (r + 1 < r_end) {
 #pragma unroll
             for (int k = 0; k < D; ++k) vload<W>(x[k], Qt + (size_t)qn[k] * F + lane_q);
@@ -1058,7 +1083,7 @@ __global__ __launch_bounds__(kBlock) void check_link_narrow2_kernel(const CheckA
         float xx[D][1], out[D][1];
 #pragma unroll
         for (int k = 0; k < D; ++k) xx[k][0] = x[k];
-        if (ALGO == kAlgoSP) check_sp<D, 1>(xx, out); else check_ms<D, 1>(xx, out);
+        if (ALGO == kAlgoSP) check_sp<D, 1>(xx, out); else if (ALGO == kAlgoMS) check_ms<D, 1>(xx, out); else check_ms<D, 1, true, T>(xx, out, ms_corr_of(a));
 #pragma unroll
         for (int k = 0; k < D; ++k)
             if ((k != ka && k != kb) || g.store_all) vstore<1>(Rt + (size_t)(e0 + k) * F, out[k]);

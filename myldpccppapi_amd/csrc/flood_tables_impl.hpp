@@ -29,14 +29,14 @@ template <int ALGO, int V, typename T> struct FloodTable<ALGO, V, T, 0> {
 };
 
 /* min-sum rows of degree 17..32: narrow unrolled kernels only */
-template <int V, typename T, int D> struct CheckTableMS {
+template <int ALGO, int V, typename T, int D> struct CheckTableMS {
     static void fill(CheckFn *c, CheckFn *cw)
     {
-        c[D] = cw[D] = check_kernel<kAlgoMS, D, V, 1, T>;
-        CheckTableMS<V, T, D - 1>::fill(c, cw);
+        c[D] = cw[D] = check_kernel<ALGO, D, V, 1, T>;
+        CheckTableMS<ALGO, V, T, D - 1>::fill(c, cw);
     }
 };
-template <int V, typename T> struct CheckTableMS<V, T, kMaxUnrolledDegree> {
+template <int ALGO, int V, typename T> struct CheckTableMS<ALGO, V, T, kMaxUnrolledDegree> {
     static void fill(CheckFn *, CheckFn *) {}
 };
 
@@ -76,10 +76,10 @@ template <int ALGO, int V, typename T> void fill_v(FloodFns *f)
     f->var_group[2] = var_group_kernel<ALGO, V, T, 9, 16>;
     f->init = init_kernel<ALGO, V, T>;
     f->max_check_unrolled = DM;
-    if (ALGO == kAlgoMS) {       /* min-sum rows of degree 17..32: narrow unrolled kernels */
-        CheckTableMS<V, T, kMaxUnrolledCheckDegreeMS>::fill(f->check, f->check_wide);
-        f->check_group[2] = check_group_kernel<kAlgoMS, V, T, 17, 24, GW>;
-        f->check_group[3] = check_group_kernel<kAlgoMS, V, T, 25, 32, GW>;
+    if (ALGO != kAlgoSP) {       /* min-sum rows of degree 17..32: narrow unrolled kernels */
+        CheckTableMS<ALGO, V, T, kMaxUnrolledCheckDegreeMS>::fill(f->check, f->check_wide);
+        f->check_group[2] = check_group_kernel<ALGO, V, T, 17, 24, GW>;
+        f->check_group[3] = check_group_kernel<ALGO, V, T, 25, 32, GW>;
         f->max_check_unrolled = kMaxUnrolledCheckDegreeMS;
     }
 }

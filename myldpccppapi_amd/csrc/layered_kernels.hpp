@@ -61,150 +61,32 @@ __device__ __forceinline__ float cl_sign(float x)
 template <int D, int V, bool HOST = false>
 __global__ __launch_bounds__(kBlock) void layer_kernel(const LayerArgs a)
 {
-    constexpr size_t F = 64 * V;
-    const int lane = threadIdx.x & 63;
-    const int tile = blockIdx.y;
-    if (tile_finished<V>(a.done, tile)) return;
-    const int wave = (int)blockIdx.x * kWavesPerBlock + wave_id_in_block();
-    const int r_begin = wave * a.rows_per_wave;
-    const int r_end = min(r_begin + a.rows_per_wave, a.n_rows);
-    float *Pt = a.P + (size_t)tile * (size_t)a.N * F + (size_t)lane * V;
-    float *Rt = a.R + (size_t)tile * (size_t)a.E * F + (size_t)lane * V;
-    uint64_t *hard_t = a.hard + (size_t)tile * (size_t)a.N * V;
-    uint64_t frozen[V];
-#pragma unroll
-    for (int v = 0; v < V; ++v) frozen[v] = a.done[(size_t)tile * V + v];
-
-    for (int r = r_begin; r < r_end; ++r) {
-        const int e0 = a.cls_e0[r];
-        int col[D];
-#pragma unroll
-        for (int k = 0; k < D; ++k) col[k] = a.edge_col[e0 + k];
-        float p[D][V], m[D][V];
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            vload<V>(m[k], Rt + (size_t)(e0 + k) * F);
-            vload<V>(p[k], Pt + (size_t)col[k] * F);
-        }
-        if (HOST) {
-#pragma unroll
-            for (int k = 0; k < D; ++k)
-#pragma unroll
-                for (int v = 0; v < V; ++v) p[k][v] = p[k][v] - m[k][v];      /* refreshQTDMP */
-            check_ms<D, V>(p, m);                                                 /* refreshRTDMP */
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-#pragma unroll
-                for (int v = 0; v < V; ++v) p[k][v] = p[k][v] + m[k][v];      /* refreshPostPTDMP */
-                vstore<V>(Rt + (size_t)(e0 + k) * F, m[k]);
-                vstore<V>(Pt + (size_t)col[k] * F, p[k]);
-            }
-            continue;
-        }
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            float prod = 1.0f, b = 1000.0f, c = 1001.0f;   /* decodeCL.c:346-348 */
-            int bind = -1;
-            float sg[D];
-#pragma unroll
-            for (int k = 0; k < D; ++k) {                  /* :350-367 */
-                const float q = p[k][v] - m[k][v];
-                sg[k] = cl_sign(q);
-                prod *= q;
-                p[k][v] = q;
-                const float mag = __builtin_fabsf(q);
-                if (mag <= b) { c = b; b = mag; bind = k; }
-                else if (mag > b && mag <= c) { c = mag; }
-            }
-            const float sa = cl_sign(prod);                /* :369 */
-            const float ab = sa * b, ac = sa * c;
-#pragma unroll
-            for (int k = 0; k < D; ++k) {                  /* :371-383 */
-                const float rn = sg[k] * ((k == bind) ? ac : ab);
-                m[k][v] = rn;
-                p[k][v] = p[k][v] + rn;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            vstore<V>(Rt + (size_t)(e0 + k) * F, m[k]);
-            vstore<V>(Pt + (size_t)col[k] * F, p[k]);
-#pragma unroll
-            for (int v = 0; v < V; ++v) {                  /* :388-389, kept current per write */
-                const uint64_t w = __ballot(p[k][v] < 0.0f);
-                if (lane == 0) {
-                    const uint64_t old = hard_t[(size_t)col[k] * V + v];
-                    hard_t[(size_t)col[k] * V + v] = (old & frozen[v]) | (w & ~frozen[v]);
-                }
-            }
-        }
-    }
+    constexpr bool CORR = false;
+    const MsCorr corr{1.0f, 0.0f};
+#include "layer_kernel.inc"
+}
+/* Normalized / offset min-sum (LayeredPlan::corr): the row's two candidates b, c go through ms_corr (flood_kernels.hpp)
+ * before the sign and the per-edge selection -- two operations per row, not per edge. */
+template <int D, int V>
+__global__ __launch_bounds__(kBlock) void layer_corr_kernel(const LayerArgs a, const MsCorr corr)
+{
+    constexpr bool HOST = false, CORR = true;
+#include "layer_kernel.inc"
 }
 
 /* Rows of any degree: same arithmetic with run-time loops, values re-read. */
 template <int V>
 __global__ __launch_bounds__(kBlock) void layer_kernel_generic(const LayerArgs a)
 {
-    constexpr size_t F = 64 * V;
-    const int lane = threadIdx.x & 63;
-    const int tile = blockIdx.y;
-    if (tile_finished<V>(a.done, tile)) return;
-    const int wave = (int)blockIdx.x * kWavesPerBlock + wave_id_in_block();
-    const int r_begin = wave * a.rows_per_wave;
-    const int r_end = min(r_begin + a.rows_per_wave, a.n_rows);
-    const int D = a.degree;
-    float *Pt = a.P + (size_t)tile * (size_t)a.N * F + (size_t)lane * V;
-    float *Rt = a.R + (size_t)tile * (size_t)a.E * F + (size_t)lane * V;
-    uint64_t *hard_t = a.hard + (size_t)tile * (size_t)a.N * V;
-    uint64_t frozen[V];
-#pragma unroll
-    for (int v = 0; v < V; ++v) frozen[v] = a.done[(size_t)tile * V + v];
-
-    for (int r = r_begin; r < r_end; ++r) {
-        const int e0 = a.cls_e0[r];
-        float prod[V], b[V], c[V], sa[V];
-        int bind[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) { prod[v] = 1.0f; b[v] = 1000.0f; c[v] = 1001.0f; bind[v] = -1; }
-        for (int k = 0; k < D; ++k) {
-            const int col = a.edge_col[e0 + k];
-            float m[V], p[V];
-            vload<V>(m, Rt + (size_t)(e0 + k) * F);
-            vload<V>(p, Pt + (size_t)col * F);
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                const float q = p[v] - m[v];
-                prod[v] *= q;
-                p[v] = q;
-                const float mag = __builtin_fabsf(q);
-                if (mag <= b[v]) { c[v] = b[v]; b[v] = mag; bind[v] = k; }
-                else if (mag > b[v] && mag <= c[v]) { c[v] = mag; }
-            }
-            vstore<V>(Pt + (size_t)col * F, p);        /* q parked in P, as decodeCL.c:357 */
-        }
-#pragma unroll
-        for (int v = 0; v < V; ++v) sa[v] = cl_sign(prod[v]);
-        for (int k = 0; k < D; ++k) {
-            const int col = a.edge_col[e0 + k];
-            float q[V], rn[V];
-            vload<V>(q, Pt + (size_t)col * F);
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                rn[v] = cl_sign(q[v]) * ((k == bind[v]) ? sa[v] * c[v] : sa[v] * b[v]);
-                q[v] = q[v] + rn[v];
-            }
-            vstore<V>(Rt + (size_t)(e0 + k) * F, rn);
-            vstore<V>(Pt + (size_t)col * F, q);
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                const uint64_t w = __ballot(q[v] < 0.0f);
-                if (lane == 0) {
-                    const uint64_t old = hard_t[(size_t)col * V + v];
-                    hard_t[(size_t)col * V + v] = (old & frozen[v]) | (w & ~frozen[v]);
-                }
-            }
-        }
-    }
+    constexpr bool CORR = false;
+    const MsCorr corr{1.0f, 0.0f};
+#include "layer_kernel_generic.inc"
+}
+template <int V>
+__global__ __launch_bounds__(kBlock) void layer_corr_kernel_generic(const LayerArgs a, const MsCorr corr)
+{
+    constexpr bool CORR = true;
+#include "layer_kernel_generic.inc"
 }
 
 /* hardDecisionTDMP, decodeCL.c:261-280, after the last layer of an iteration: P > 0 -> 0, P < 0 -> 1,
@@ -291,6 +173,8 @@ struct LayeredPlan {
     int64_t E = 0;
     int T = 0, V = 1;
     int host_arith = 0;             /* 1: LDPC_ALGO_LAYERED_HOST (layer_kernel<.., HOST = true>) */
+    int corr = 0;                   /* 1: normalized / offset min-sum (layer_corr_kernel) with these: */
+    float ms_scale = 1.0f, ms_offset = 0.0f;
     float *P = nullptr, *R = nullptr;
     std::vector<LayerGroup> groups; /* ordered by layer */
 };
@@ -366,6 +250,13 @@ template <int V, int D, bool HOST = false> struct LayerTable {
 template <int V, bool HOST> struct LayerTable<V, 0, HOST> {
     static void fill(LayerFn *t) { t[0] = HOST ? nullptr : layer_kernel_generic<V>; }
 };
+using LayerCorrFn = void (*)(const LayerArgs, const MsCorr);
+template <int V, int D> struct LayerCorrTable {
+    static void fill(LayerCorrFn *t) { t[D] = layer_corr_kernel<D, V>; LayerCorrTable<V, D - 1>::fill(t); }
+};
+template <int V> struct LayerCorrTable<V, 0> {
+    static void fill(LayerCorrFn *t) { t[0] = layer_corr_kernel_generic<V>; }
+};
 
 
 template <int V> __global__ void layered_summary_kernel(const int32_t *iters, const uint64_t *done,
@@ -387,8 +278,11 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
     const int tiles = (int)((r.frames + F - 1) / F);
     const size_t slot = (size_t)pl->T * V;
     LayerFn table[kMaxUnrolledLayerDegree + 1];
+    LayerCorrFn corr_table[kMaxUnrolledLayerDegree + 1];
     if (pl->host_arith) LayerTable<V, kMaxUnrolledLayerDegree, true>::fill(table);
     else LayerTable<V, kMaxUnrolledLayerDegree>::fill(table);
+    LayerCorrTable<V, kMaxUnrolledLayerDegree>::fill(corr_table);
+    const MsCorr corr{pl->ms_scale, pl->ms_offset};
     const int rounds = r.tap_iter ? (r.tap_iter < r.max_iter ? r.tap_iter : r.max_iter) : r.max_iter;
     hipError_t e;
     if ((e = hipMemsetAsync(r.failw, 0, (size_t)(r.max_iter + 2) * slot * sizeof(uint64_t), s))) return e;
@@ -412,7 +306,8 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
             if (!table[k]) return hipErrorInvalidValue;      /* host arithmetic: unrolled degrees only */
             if (r.span_begin && (e = r.span_begin(r.span_ctx, s, 2, g.degree,
                                                   (int64_t)16 * g.degree * g.count * r.frames))) return e;
-            table[k]<<<grid, kBlock, 0, s>>>(a);
+            if (pl->corr) corr_table[k]<<<grid, kBlock, 0, s>>>(a, corr);
+            else table[k]<<<grid, kBlock, 0, s>>>(a);
             if (r.span_end && (e = r.span_end(r.span_ctx, s))) return e;
         }
         if (pl->host_arith) {

@@ -235,6 +235,10 @@ struct ldpc_decoder {
     bool use_fused = false;
     ldpc::LdspPlan ldsp;                /* LDPC_ALGO_LAYERED, mid-size QC codes: posterior in LDS, check records in cache */
     bool use_ldsp = false;
+    /* normalized / offset min-sum (cfg.ms_scale / ms_offset): the streaming kernels of kAlgoMSC (flooding) or
+     * layer_corr_kernel (layered) run with alpha = ms_scale (1 when 0) and beta = ms_offset */
+    bool ms_corr = false;
+    float ms_scale = 1.0f, ms_offset = 0.0f;
 
     /* staging for the host-buffer entry point: three slots, so the H2D copy of group k+1
      * (copy_stream) overlaps the decode of group k (stream) and the copy-out of group k-1 */
@@ -466,7 +470,8 @@ template <int V> int enqueue_check_phase(ldpc_decoder *d, hipStream_t s, int til
                            msz * ((int64_t)rc.degree * rc.count + rc.linked +
                                   ((int64_t)rc.degree * rc.count - 2 * rc.linked) +
                                   (it < max_iter ? 2 * rc.linked : 0) + 2 * d->extra_edges) * frames));
-        CheckArgs a{d->Q.p, d->R.p, rc.e0.p, d->done.p, d->E, rc.count, 1, rc.degree, tr};
+        CheckArgs a{d->Q.p, d->R.p, rc.e0.p, d->done.p, d->E, rc.count, 1, rc.degree, d->ms_scale, tr};
+        a.ms_offset = d->ms_offset;
         a.qpos = d->qpos.p;
         LinkArgs lk{rc.link_col.p, rc.link_pos.p, d->chan.p, d->Q.p, d->hard.p, d->N,
                     (it < max_iter) ? 1 : 0, d->tap_iter ? 1 : 0, d->extra_e0.p, d->extra_deg.p, d->n_extra, 0,
@@ -485,7 +490,8 @@ template <int V> int enqueue_check_phase(ldpc_decoder *d, hipStream_t s, int til
         int64_t edges = 0;
         for (int i : g.members) edges += (int64_t)d->row_classes[i].degree * d->row_classes[i].count;
         HIP_TRY(span_begin(d, s, 5, g.hi, 2 * msz * edges * frames, -1, g.lo));
-        CheckArgs a{d->Q.p, d->R.p, nullptr, d->done.p, d->E, 0, (d->tune_rpw ? d->tune_rpw : 2) * (fat ? kIdleFat : 1), 0, tr};
+        CheckArgs a{d->Q.p, d->R.p, nullptr, d->done.p, d->E, 0, (d->tune_rpw ? d->tune_rpw : 2) * (fat ? kIdleFat : 1), 0, d->ms_scale, tr};
+        a.ms_offset = d->ms_offset;
         a.qpos = d->qpos.p;
         if (it == 1 && d->first_round_from_chan) { a.first_chan = d->chan.p; a.edge_col = d->edge_col.p; a.N = d->N; }
         const dim3 grid = flood_grid(d, fat ? g.blocks_fat : g.blocks, tiles, &a.tiles_first);
@@ -495,7 +501,8 @@ template <int V> int enqueue_check_phase(ldpc_decoder *d, hipStream_t s, int til
     for (int ci : d->check_solo) {
         RowClass &rc = d->row_classes[ci];
         HIP_TRY(span_begin(d, s, 0, rc.degree, 2 * msz * rc.degree * rc.count * frames));
-        CheckArgs a{d->Q.p, d->R.p, rc.e0.p, d->done.p, d->E, rc.count, 1, rc.degree, tr};
+        CheckArgs a{d->Q.p, d->R.p, rc.e0.p, d->done.p, d->E, rc.count, 1, rc.degree, d->ms_scale, tr};
+        a.ms_offset = d->ms_offset;
         a.qpos = d->qpos.p;
         if (it == 1 && d->first_round_from_chan) { a.first_chan = d->chan.p; a.edge_col = d->edge_col.p; a.N = d->N; }
         const int slotk = rc.degree <= d->max_check_unrolled ? rc.degree : 0;
@@ -960,9 +967,11 @@ int setup_flooding(ldpc_decoder *d, const ldpc_graph *g, size_t TF)
     HIP_TRY(d->R.alloc(TF * (size_t)d->E * d->msg_size));
     int rc = build_classes(d, g);
     if (rc) return rc;
-    /* the kernels live in flood_sp.hip / flood_ms.hip / flood_ms16.hip (flood_tables.hpp) */
+    /* the kernels live in flood_sp.hip / flood_ms.hip / flood_ms16.hip / flood_msc*.hip (flood_tables.hpp) */
     ldpc::FloodFns fns;
     if (cfg->algo == LDPC_ALGO_SP) ldpc::fill_flood_sp(d->V, &fns);
+    else if (d->ms_corr && cfg->msg_dtype == LDPC_MSG_F16) ldpc::fill_flood_msc16(d->V, &fns);
+    else if (d->ms_corr) ldpc::fill_flood_msc(d->V, &fns);
     else if (cfg->msg_dtype == LDPC_MSG_F16) ldpc::fill_flood_ms16(d->V, &fns);
     else ldpc::fill_flood_ms(d->V, &fns);
     memcpy(d->check_fn, fns.check, sizeof fns.check);
@@ -1009,7 +1018,9 @@ template <int V> int calibrate_link(ldpc_decoder *d)
     hipError_t err = hipSuccess;
     for (int rep = 0; rep < 4 && err == hipSuccess; ++rep) {
         for (int nar = 0; nar < candidates && err == hipSuccess; ++nar) {
-            CheckArgs a{d->Q.p, d->R.p, rc.e0.p, d->done.p, d->E, rc.count, d->link_rpw, rc.degree, TailRef{nullptr, 0, 0}};
+            CheckArgs a{d->Q.p, d->R.p, rc.e0.p, d->done.p, d->E, rc.count, d->link_rpw, rc.degree, d->ms_scale,
+                        TailRef{nullptr, 0, 0}};
+            a.ms_offset = d->ms_offset;
             a.qpos = d->qpos.p;
             LinkArgs lk{rc.link_col.p, rc.link_pos.p, d->chan.p, d->Q.p, d->hard.p, d->N, 1, 0, nullptr, nullptr, 0, 0,
                         rc.n_big, rc.small_rows};
@@ -1243,20 +1254,43 @@ void ldpc_decoder_config_init(ldpc_decoder_config *cfg)
     cfg->pack_mode = LDPC_PACK_BYTES;
 }
 
-int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg, ldpc_decoder **out)
+/* The caller's config as the current struct: callers built against the header before ms_scale / ms_offset pass
+ * the shorter struct, of which only struct_size bytes are read; the fields it lacks are 0 (off). */
+static int config_in(const ldpc_decoder_config *cfg, ldpc_decoder_config *full)
+{
+    constexpr size_t kSizeBeforeMsCorr = offsetof(ldpc_decoder_config, ms_scale);
+    if (cfg->struct_size != sizeof(ldpc_decoder_config) && cfg->struct_size != kSizeBeforeMsCorr)
+        return fail(LDPC_ERR_ARG, "config struct_size %u is neither %zu nor %zu (ABI mismatch)", cfg->struct_size,
+                    sizeof(ldpc_decoder_config), kSizeBeforeMsCorr);
+    memset(full, 0, sizeof *full);
+    memcpy(full, cfg, cfg->struct_size);
+    full->struct_size = sizeof *full;
+    return LDPC_OK;
+}
+
+int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, ldpc_decoder **out)
 {
     if (!out) return fail(LDPC_ERR_ARG, "out is NULL");
     *out = nullptr;
-    if (!g || !cfg) return fail(LDPC_ERR_ARG, "graph/config is NULL");
-    if (cfg->struct_size != sizeof(ldpc_decoder_config))
-        return fail(LDPC_ERR_ARG, "config struct_size %u != %zu (ABI mismatch)", cfg->struct_size,
-                    sizeof(ldpc_decoder_config));
+    if (!g || !cfg_in) return fail(LDPC_ERR_ARG, "graph/config is NULL");
+    ldpc_decoder_config cfg_full;
+    if (int rc = config_in(cfg_in, &cfg_full)) return rc;
+    const ldpc_decoder_config *cfg = &cfg_full;
     if (cfg->K <= 0 || cfg->K > g->N) return fail(LDPC_ERR_ARG, "K=%d out of range", cfg->K);
     if (cfg->max_batch <= 0) return fail(LDPC_ERR_ARG, "max_batch must be positive");
     if (cfg->max_iter <= 0 || cfg->max_iter > 100000) return fail(LDPC_ERR_ARG, "max_iter out of range");
     if (cfg->algo != LDPC_ALGO_SP && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED &&
         cfg->algo != LDPC_ALGO_MS_FUSED && cfg->algo != LDPC_ALGO_LAYERED_HOST)
         return fail(LDPC_ERR_ARG, "unknown algo %d", cfg->algo);
+    /* comparisons written so that NaN fails them */
+    if (!(cfg->ms_scale >= 0.0f && cfg->ms_scale <= 1.0f))
+        return fail(LDPC_ERR_ARG, "ms_scale must be 0 (off) or in (0, 1]");
+    if (!(cfg->ms_offset >= 0.0f && cfg->ms_offset < 1000.0f))
+        return fail(LDPC_ERR_ARG, "ms_offset must be 0 (off) or in (0, 1000)");
+    const bool ms_corr = cfg->ms_scale != 0.0f || cfg->ms_offset != 0.0f;
+    if (ms_corr && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED)
+        return fail(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset apply to LDPC_ALGO_MS and LDPC_ALGO_LAYERED only "
+                    "(SP has no minimum to correct; MS_FUSED and LAYERED_HOST reproduce reference kernels)");
     if (cfg->algo == LDPC_ALGO_LAYERED_HOST) {
         for (int32_t m = 1; m < g->M; ++m)
             if (g->row_ptr[m + 1] - g->row_ptr[m] != g->row_ptr[1] - g->row_ptr[0])
@@ -1287,6 +1321,9 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg, ldp
     if (!d) return fail(LDPC_ERR_NOMEM, "out of memory");
     std::unique_ptr<ldpc_decoder> guard(d);
     d->cfg = *cfg;
+    d->ms_corr = ms_corr;
+    d->ms_scale = cfg->ms_scale != 0.0f ? cfg->ms_scale : 1.0f;
+    d->ms_offset = cfg->ms_offset;
     d->M = g->M; d->N = g->N; d->E = g->E;
     d->h_col_ptr = g->col_ptr; d->h_col_edge = g->col_edge; d->h_rows = g->rows; d->h_cols = g->cols;
     const ldpc::Tune tune = d->tune = ldpc::tune_from_config(*cfg);
@@ -1360,15 +1397,24 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg, ldp
     } else if (cfg->algo == LDPC_ALGO_LAYERED) {
         /* short quasi-cyclic codes decode entirely in LDS, one launch (fused_kernels.hpp);
          * LDPC_TUNE_OFF(LDPC_TUNE_FUSED) keeps the streaming kernels (same results, bit for bit) */
+        /* the correction (ms_scale / ms_offset) is carried by the record kernel (layered_ldsp_corr_kernel) and the
+         * streaming one (layer_corr_kernel), not by the LDS-resident fused_layered_kernel */
+        if (d->ms_corr && ldpc::tune_forced_on(tune.fused) && ldpc::tune_forced_off(tune.ldsp))
+            return fail(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset: the LDS-resident layered kernel (LDPC_TUNE_FUSED on, "
+                        "LDPC_TUNE_LDSP off) carries no correction; the record or the streaming kernels do");
         if (!ldpc::tune_forced_off(tune.fused) && (cfg->pack_mode == LDPC_PACK_BYTES || cfg->K % 8 == 0)) {
-            HIP_TRY(ldpc::fused_plan_create(&d->fused, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows));
-            d->use_fused = d->fused.eligible;
+            if (!d->ms_corr) {
+                HIP_TRY(ldpc::fused_plan_create(&d->fused, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows));
+                d->use_fused = d->fused.eligible;
+            }
             /* layered_ldsp_kernel (posterior in LDS, 16-byte check records in cache) is the default for
              * every QC code it fits: larger codes cannot use the fully LDS-resident kernel at all, and on
              * short ones it is 1.2-2.9x faster (exact-width rows, bit-level sign algebra: 800 against 280 G
              * edge updates/s; circulants of <= 32 rows run several frames per wave in both).
              * LDPC_TUNE_OFF(LDPC_TUNE_LDSP) forbids it (the LDS-resident kernel is then used where it applies). */
             if (!ldpc::tune_forced_off(tune.ldsp)) {
+                d->ldsp.corr = d->ms_corr;
+                d->ldsp.mc = ldpc::MsCorr{d->ms_scale, d->ms_offset};
                 HIP_TRY(ldpc::engine_ldsp_plan_create(&d->ldsp, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows,
                                                cfg->K, cfg->max_batch, cfg->device, tune, /*flood=*/0));
                 if (d->ldsp.eligible) d->use_fused = d->use_ldsp = true;
@@ -1376,6 +1422,9 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg, ldp
         }
         /* the streaming plan (and its P / R arrays in HBM) only when no LDS-resident kernel applies;
          * a detected QC structure already implies that rows of a layer share no column */
+        d->layered.corr = d->ms_corr;
+        d->layered.ms_scale = d->ms_scale;
+        d->layered.ms_offset = d->ms_offset;
         int rc = d->use_fused ? 0 : ldpc::layered_plan_create(&d->layered, g->M, g->N, g->E, g->row_ptr, g->cols,
                                                               cfg->layer_rows, d->T, d->V);
         if (rc == -1) return fail(LDPC_ERR_ARG, "layer_rows=%d must divide M=%d and rows of a layer "
@@ -1389,10 +1438,15 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg, ldp
          * full work once the batch is large (HBM-bound, 1.3-1.9x), the fused kernels win on latency
          * and for small batches; crossover near max_batch * E = 2^23 edge-frames.
          * LDPC_TUNE_ON(LDPC_TUNE_FUSED) forces the fused kernels, LDPC_TUNE_OFF the streaming ones. */
+        /* the correction (ms_scale / ms_offset) is carried by the record kernel (flood_ldsp_corr_kernel) and the streaming
+         * kernels (kAlgoMSC), not by the LDS-resident fused_flood_kernel */
+        if (d->ms_corr && ldpc::tune_forced_on(tune.fused) && ldpc::tune_forced_off(tune.ldsp))
+            return fail(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset: the LDS-resident flooding kernel (LDPC_TUNE_FUSED on, "
+                        "LDPC_TUNE_LDSP off) carries no correction; the record or the streaming kernels do");
         if (cfg->msg_dtype == LDPC_MSG_F32 && cfg->layer_rows > 0 && cfg->frames_per_lane == 0 &&
             (cfg->pack_mode == LDPC_PACK_BYTES || cfg->K % 8 == 0)) {
             const bool small = (int64_t)cfg->max_batch * g->E <= (int64_t)1 << 23;
-            if (ldpc::tune_pick(tune.fused, small)) {
+            if (!d->ms_corr && ldpc::tune_pick(tune.fused, small)) {
                 HIP_TRY(ldpc::fused_plan_create(&d->fused, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows));
                 d->use_fused = d->fused.eligible && (cfg->algo == LDPC_ALGO_MS || d->fused.eligible_sp);
             }
@@ -1402,6 +1456,8 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg, ldp
              * at 16 384 frames, 2.6 / 0.9 / 1.3 at full work), 2.4 / 2.0 / 1.7 / 1.2x the streaming kernels on
              * BG1-profile codes at Z = 64 / 128 / 256 / 384.  LDPC_TUNE_ON / OFF(LDPC_TUNE_LDSP) forces / forbids it. */
             if (cfg->algo == LDPC_ALGO_MS && !ldpc::tune_forced_off(tune.fused) && !ldpc::tune_forced_off(tune.ldsp)) {
+                d->ldsp.corr = d->ms_corr;
+                d->ldsp.mc = ldpc::MsCorr{d->ms_scale, d->ms_offset};
                 HIP_TRY(ldpc::engine_ldsp_plan_create(&d->ldsp, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows,
                                                cfg->K, cfg->max_batch, cfg->device, tune, /*flood=*/1));
                 if (d->ldsp.eligible && (ldpc::tune_forced_on(tune.ldsp) || d->ldsp.lds_bytes <= 80 * 1024))
@@ -1517,6 +1573,9 @@ int ldpc_decoder_create_multi(const ldpc_graph *g, const ldpc_decoder_config *cf
     *out = nullptr;
     if (!g || !cfg) return fail(LDPC_ERR_ARG, "graph/config is NULL");
     if (!devices || n_devices <= 0 || n_devices > 64) return fail(LDPC_ERR_ARG, "devices[] must hold 1..64 ordinals");
+    ldpc_decoder_config cfg_full;
+    if (int rc = config_in(cfg, &cfg_full)) return rc;
+    cfg = &cfg_full;
     ldpc_decoder *grp = new (std::nothrow) ldpc_decoder;
     if (!grp) return fail(LDPC_ERR_NOMEM, "out of memory");
     std::unique_ptr<ldpc_decoder> guard(grp);
@@ -2076,12 +2135,15 @@ int ldpc_decoder_kernel_times(ldpc_decoder *d, ldpc_kernel_time *out, int32_t ca
     if (!d->have_last) return fail(LDPC_ERR_STATE, "no decode call to report on");
     HIP_TRY(hipSetDevice(d->cfg.device));
     HIP_TRY(hipEventSynchronize(d->ev_end));
-    const char *phase_name[] = {"check_kernel", "var_kernel", "layer_kernel", "other",
+    const char *phase_name[] = {"check_kernel", "var_kernel", d->ms_corr ? "layer_corr_kernel" : "layer_kernel", "other",
                                 d->tune_link_narrow == 2 ? "check_link_half_kernel"
                                 : d->tune_link_narrow ? "check_link_narrow_kernel" : "check_link_kernel"};
     static const char *algo_name_f32[] = {"sp", "ms", "layered", "ms_fused", "layered_host"};
     static const char *algo_name_f16[] = {"sp16", "ms16", "layered16", "ms_fused16", "layered_host16"};
-    const char **algo_name = d->msg_size == 2 ? algo_name_f16 : algo_name_f32;
+    static const char *algo_name_corr_f32[] = {"sp", "msc", "layered", "ms_fused", "layered_host"};  /* kAlgoMSC */
+    static const char *algo_name_corr_f16[] = {"sp16", "msc16", "layered16", "ms_fused16", "layered_host16"};
+    const char **algo_name = d->ms_corr ? (d->msg_size == 2 ? algo_name_corr_f16 : algo_name_corr_f32)
+                                        : (d->msg_size == 2 ? algo_name_f16 : algo_name_f32);
     for (size_t i = 0; i < d->spans_used; ++i) {
         const TimedSpan &sp = d->spans[i];
         float ms = 0;
@@ -2090,7 +2152,9 @@ int ldpc_decoder_kernel_times(ldpc_decoder *d, ldpc_kernel_time *out, int32_t ca
         char name[64];
         if (sp.kind == 3) snprintf(name, sizeof name, "other");
         else if (d->use_fused && d->use_ldsp)   /* whole decode in one launch; [persistent grid x workgroup size, frames per workgroup] */
-            snprintf(name, sizeof name, "%s[%dx%d,%d]", d->cfg.algo == LDPC_ALGO_LAYERED ? "layered_ldsp_kernel" : "flood_ldsp_kernel",
+            snprintf(name, sizeof name, "%s[%dx%d,%d]", d->cfg.algo == LDPC_ALGO_LAYERED
+                     ? (d->ms_corr ? "layered_ldsp_corr_kernel" : "layered_ldsp_kernel")
+                     : (d->ms_corr ? "flood_ldsp_corr_kernel" : "flood_ldsp_kernel"),
                      d->ldsp.grid, d->ldsp.block, d->ldsp.wg_frames);
         else if (d->use_fused)      /* bytes = channel values in + packed bits out */
             snprintf(name, sizeof name, "%s", d->cfg.algo == LDPC_ALGO_SP ? "fused_sp_kernel"

@@ -126,8 +126,9 @@ __device__ __forceinline__ uint32_t ldsp_old_message(const uint4 rec, uint32_t z
 
 /* Any input: the reference's operations one by one (decodeCL.c:345-383) with run-time loops, q
  * parked in P between the two passes as the reference does. */
+template <bool CORR = false>
 __device__ __forceinline__ uint4 ldsp_row_any(float *P, ldpc_const_i32 pk, int dl, int ext, int z, int r,
-                                              const uint4 old, uint32_t *zfp, uint32_t *par)
+                                              const uint4 old, uint32_t *zfp, uint32_t *par, const MsCorr corr = MsCorr{1.0f, 0.0f})
 {
     *par = 0;
     const int d = dl + ext;
@@ -150,6 +151,7 @@ __device__ __forceinline__ uint4 ldsp_row_any(float *P, ldpc_const_i32 pk, int d
         if (mag <= b) { c = b; b = mag; bind = k; }
         else if (mag > b && mag <= c) { c = mag; }
     }
+    if (CORR) { b = ms_corr<float>(b, corr); c = ms_corr<float>(c, corr); }     /* normalized / offset min-sum */
     const float sa = cl_sign(prod);
     const float ab = sa * b, ac = sa * c;
     const uint32_t mab = __float_as_uint(ab) & 0x7fffffffu, mac = __float_as_uint(ac) & 0x7fffffffu;
@@ -182,9 +184,9 @@ __device__ __forceinline__ uint4 ldsp_row_any(float *P, ldpc_const_i32 pk, int d
  * wave-uniformly and with P untouched, when some row of the wave needs ldsp_row_any.  ABS: the
  * posteriors start at LDS address 0 (ldsp_at_abs).  PAR = false: *par is left alone (the caller takes
  * the parity of the one layer it needs from the posteriors, ldsp_row_parity). */
-template <int DL, int EXT, bool ABS = false, bool PAR = true>
+template <int DL, int EXT, bool ABS = false, bool PAR = true, bool CORR = false>
 __device__ __forceinline__ bool ldsp_row(float *P, ldpc_const_i32 pk, int z, int r, const uint4 old, uint4 *out,
-                                         uint32_t *par)
+                                         uint32_t *par, const MsCorr corr = MsCorr{1.0f, 0.0f})
 {
     constexpr int D = DL + EXT;
     constexpr int DLA = DL > 0 ? DL : 1;
@@ -215,6 +217,8 @@ __device__ __forceinline__ bool ldsp_row(float *P, ldpc_const_i32 pk, int z, int
         c = __builtin_amdgcn_fmed3f(b, mag, c);                     /* b <= c: the branches of decodeCL.c:359-365 */
         b = __builtin_amdgcn_fmed3f(0.0f, mag, b);                  /* min(b, mag): both >= 0 */
     }
+    /* normalized / offset min-sum: the record holds the corrected magnitudes (a 0 keeps the sign algebra: pn = q) */
+    if (CORR) { b = ms_corr<float>(b, corr); c = ms_corr<float>(c, corr); }
     const uint32_t pb = __float_as_uint(prod);
     if (__ballot(!ldsp_regular(pb)) != 0ull) return false;
     const uint32_t ps = pb & 0x80000000u;                           /* cl_sign(prod) = +-1 */
@@ -264,157 +268,17 @@ template <int MAXW>
 __global__ __launch_bounds__(64 * MAXW) __attribute__((amdgpu_waves_per_eu(LDPC_LDSP_WAVES_PER_EU)))
 void layered_ldsp_kernel(const LdspArgs a)
 {
-    extern __shared__ float lds[];
-    float *P = lds;                                                             /* [lds_cols][z] */
-    const int r = (int)threadIdx.x, LANES = (int)blockDim.x;
-    const int z = a.z;
-    uint32_t *wg_flag = reinterpret_cast<uint32_t *>(lds + (((size_t)a.lds_cols * z + 1) & ~(size_t)1));
-    const bool row = r < z;
-    const size_t ring = (size_t)blockIdx.x * ((size_t)a.layers * z) + r;        /* [layer][z], mine: + r */
-    uint4 *recs = a.recs + ring;
-    uint32_t *zfs = a.zf + ring;
-    const ldpc_const_i32 hdr = as_constant(a.hdr), pack = as_constant(a.pack), cslot = as_constant(a.col_slot);
-    /* OR over the workgroup through one LDS word (no static LDS: P sits at LDS address 0 and the
-     * table's byte offsets are final addresses) */
-    auto wg_any = [&](bool pred) {
-        if (r == 0) *wg_flag = 0u;
-        lds_barrier();
-        if (__ballot(pred) != 0ull && (r & 63) == 0) *wg_flag = 1u;
-        lds_barrier();
-        const uint32_t f = *wg_flag;
-        lds_barrier();                                             /* before the word is cleared again */
-        return f != 0u;
-    };
-    for (int64_t frame = blockIdx.x; frame < a.frames; frame += gridDim.x) {
-        const float *y = a.llr + (size_t)frame * a.N;
-        if (row) {
-            for (int bc = 0; bc < a.nb; ++bc) {
-                const int slot = cslot[bc];
-                if (slot >= 0) P[slot * z + r] = y[bc * z + r];
-            }
-            /* iteration 0: R = 0 (|ab| = |ac| = 0, signs +); an external column starts from its
-             * channel value.  Written to the ring so that every layer step finds its record there. */
-            for (int l = 0; l < a.layers; ++l) {
-                uint4 rec = uint4{0u, 0u, 0u, 0u};
-                if (hdr[l * 4 + 1]) rec.w = __float_as_uint(y[hdr[l * 4 + 2] + ldsp_wrap(r, hdr[l * 4 + 3], z)]);
-                recs[(size_t)l * z] = rec;
-            }
-        }
-        uint4 cur = uint4{0u, 0u, 0u, 0u};
-        if (row) cur = recs[0];
-        __syncthreads();
-        int time = 0;
-        bool clean = false;
-        /* lane mask of the wave's rows of layer l whose hard decisions have odd parity */
-        auto layer_odd = [&](const int l) {
-            const int dl = hdr[l * 4], ext = hdr[l * 4 + 1];
-            const ldpc_const_i32 pk = pack + (size_t)l * kLdspPackStride;
-            uint64_t par = 0;
-            switch (dl) {
-#define LDPC_LDSP_CASE(D) case D + 1: par = ldsp_row_parity<D + 1>(P, pk, z, r); break;
-                LDPC_LDSP_WIDTHS(LDPC_LDSP_CASE)
-#undef LDPC_LDSP_CASE
-            default: break;
-            }
-            /* hard decision of the layer's external column: its posterior is in my record */
-            if (ext) par ^= __ballot(__uint_as_float(recs[(size_t)l * z].w) < 0.0f);
-            return par;
-        };
-        while (true) {
-            for (int l = 0; l < a.layers; ++l) {
-                /* the next layer step's record (wrapping into the next iteration), requested before
-                 * this step's work; with a single layer it is this step's own output */
-                const int ln = l + 1 < a.layers ? l + 1 : 0;
-                /* by every lane, outside any branch: a conditional request makes the compiler copy the
-                 * registers, and wait for them, where the branch ends -- at once.  Lanes beyond the last row
-                 * read their neighbours' records (the rings end with spare ones). */
-                uint4 nxt = recs[(size_t)ln * z];
-                const int dl = hdr[l * 4], ext = hdr[l * 4 + 1];
-                const ldpc_const_i32 pk = pack + (size_t)l * kLdspPackStride;
-                uint4 rec = uint4{0u, 0u, 0u, 0u};
-                if (row) {
-                    uint32_t par = 0;                               /* (ldsp_row_any's; not used here) */
-                    bool done = false;
-                    if (ext) {
-                        switch (dl) {
-#define LDPC_LDSP_CASE(D) case D: done = ldsp_row<D, 1, true, false>(P, pk, z, r, cur, &rec, &par); break;
-                            LDPC_LDSP_WIDTHS(LDPC_LDSP_CASE)
-#undef LDPC_LDSP_CASE
-                        default: break;
-                        }
-                    } else {
-                        switch (dl) {
-#define LDPC_LDSP_CASE(D) case D + 1: done = ldsp_row<D + 1, 0, true, false>(P, pk, z, r, cur, &rec, &par); break;
-                            LDPC_LDSP_WIDTHS(LDPC_LDSP_CASE)
-#undef LDPC_LDSP_CASE
-                        default: break;
-                        }
-                    }
-                    if (!done) rec = ldsp_row_any(P, pk, dl, ext, z, r, cur, zfs + (size_t)l * z, &par);
-                }
-                /* the requested record has had this step's work to arrive: take it -- on every path, not
-                 * inside the branch above -- BEFORE the store below is issued, or the wait for it would
-                 * cover the store as well and put a full memory round trip into every layer step */
-                asm volatile("" : "+v"(nxt.x), "+v"(nxt.y), "+v"(nxt.z), "+v"(nxt.w) : : "memory");
-                if (row) recs[(size_t)l * z] = rec;
-                if (a.layers == 1) nxt = rec;
-                lds_barrier();
-                cur = nxt;
-            }
-            /* syndrome of the hard decisions: every round when a clean frame stops early, else only
-             * after the last one (its only use then is the frame's converged flag) */
-            ++time;
-            int any_bad = 1;
-            if (a.early_term || time == a.rounds) {
-                /* the rows of the last layer first (their columns are in the iteration's final state like all
-                 * others, but a frame that has not converged nearly always shows it there already): only
-                 * when all of them are even the other layers are looked at.  The row code does not
-                 * keep parities: one layer's worth of reads here is cheaper than an instruction per edge. */
-                uint64_t bad = row ? layer_odd(a.layers - 1) : 0ull;
-                if (!wg_any(bad != 0ull)) {
-                    if (row)
-                        for (int l = 0; l + 1 < a.layers; ++l) bad |= layer_odd(l);
-                    any_bad = wg_any(bad != 0ull) ? 1 : 0;
-                }
-            }
-            clean = !any_bad;
-            if ((clean && a.early_term) || time == a.rounds) break;
-        }
-        /* toChar (decodeCL.c:414-423): the information columns sit in LDS at slot = block column */
-        const int64_t base = frame * (int64_t)a.K / 8;
-        for (int j = r; j < a.K / 8; j += LANES) {
-            unsigned byte = 0;
-#pragma unroll
-            for (int bit = 0; bit < 8; ++bit) byte |= (P[j * 8 + bit] < 0.0f ? 1u : 0u) << bit;
-            if (base + j < a.out_bytes) a.out[base + j] = (uint8_t)byte;
-        }
-        if (a.dump_p && row) {
-            for (int bc = 0; bc < a.nb; ++bc) {
-                const int slot = cslot[bc];
-                if (slot >= 0) a.dump_p[(size_t)frame * a.N + bc * z + r] = P[slot * z + r];
-            }
-            for (int l = 0; l < a.layers; ++l)
-                if (hdr[l * 4 + 1])
-                    a.dump_p[(size_t)frame * a.N + hdr[l * 4 + 2] + ldsp_wrap(r, hdr[l * 4 + 3], z)] =
-                        __uint_as_float(recs[(size_t)l * z].w);
-        }
-        if (a.dump_r && row) {
-            for (int l = 0; l < a.layers; ++l) {
-                const int d = hdr[l * 4] + hdr[l * 4 + 1], e0 = a.layer_e0[l];
-                const uint4 rec = recs[(size_t)l * z];
-                const uint32_t zf = (rec.z & kLdspIrregular) ? zfs[(size_t)l * z] : 0u;
-                for (int k = 0; k < d; ++k)
-                    a.dump_r[(size_t)frame * a.E + e0 + r * d + k] = __uint_as_float(ldsp_old_message(rec, zf, k, d));
-            }
-        }
-        if (r == 0) {
-            const int it = clean ? time : a.max_iter;
-            if (a.iters) a.iters[frame] = it;
-            atomicMax(&a.summary[0], it);
-            if (clean) atomicAdd(&a.summary[1], 1);
-        }
-        __syncthreads();                                           /* P is refilled for the next frame */
-    }
+    constexpr bool CORR = false;
+    const MsCorr corr{1.0f, 0.0f};
+#include "ldsp_layered_kernel.inc"
+}
+/* normalized / offset min-sum (LdspPlan::corr): b and c of every row through ms_corr, once per row */
+template <int MAXW>
+__global__ __launch_bounds__(64 * MAXW) __attribute__((amdgpu_waves_per_eu(LDPC_LDSP_WAVES_PER_EU)))
+void layered_ldsp_corr_kernel(const LdspArgs a, const MsCorr corr)
+{
+    constexpr bool CORR = true;
+#include "ldsp_layered_kernel.inc"
 }
 
 
@@ -426,149 +290,16 @@ template <int kUnused = 0>       /* a template only so that several translation 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LDPC_LDSP_WAVES_PER_EU)))
 void layered_ldsp_packed_kernel(const LdspArgs a, const int G)
 {
-    extern __shared__ float lds[];
-    const int lane = (int)threadIdx.x;
-    const int z = a.z;
-    const int g = lane / z, r = lane - g * z;
-    const bool member = g < G;                                      /* lane belongs to a frame slot */
-    const size_t frame_floats = ((size_t)a.lds_cols * z + 1) & ~(size_t)1;
-    float *P = lds + (size_t)(member ? g : 0) * frame_floats;       /* [lds_cols][z] of my frame */
-    uint64_t *extneg = reinterpret_cast<uint64_t *>(lds + (size_t)G * frame_floats);   /* [layers] lane masks */
-    const size_t ring = ((size_t)blockIdx.x * G + (member ? g : 0)) * ((size_t)a.layers * z) + r;
-    uint4 *recs = a.recs + ring;
-    uint32_t *zfs = a.zf + ring;
-    const ldpc_const_i32 hdr = as_constant(a.hdr), pack = as_constant(a.pack), cslot = as_constant(a.col_slot);
-    const uint64_t gmask = (z >= 64 ? ~0ull : ((1ull << z) - 1ull)) << (member ? g * z : 0);
-    for (int64_t frame0 = (int64_t)blockIdx.x * G; frame0 < a.frames; frame0 += (int64_t)gridDim.x * G) {
-        const int64_t frame = frame0 + g;
-        const bool mine = member && frame < a.frames;
-        const float *y = a.llr + (size_t)(mine ? frame : 0) * a.N;
-        if (mine) {
-            for (int bc = 0; bc < a.nb; ++bc) {
-                const int slot = cslot[bc];
-                if (slot >= 0) P[slot * z + r] = y[bc * z + r];
-            }
-            for (int l = 0; l < a.layers; ++l) {
-                uint4 rec = uint4{0u, 0u, 0u, 0u};
-                if (hdr[l * 4 + 1]) rec.w = __float_as_uint(y[hdr[l * 4 + 2] + ldsp_wrap(r, hdr[l * 4 + 3], z)]);
-                recs[(size_t)l * z] = rec;
-            }
-        }
-        uint4 cur = uint4{0u, 0u, 0u, 0u};
-        if (mine) cur = recs[0];
-        lds_barrier();
-        int time = 0, my_iters = a.max_iter;
-        bool active = mine, clean = false;
-        while (__ballot(active) != 0ull) {
-            uint32_t last_bad = 0;
-            for (int l = 0; l < a.layers; ++l) {
-                const int ln = l + 1 < a.layers ? l + 1 : 0;
-                uint4 nxt = uint4{0u, 0u, 0u, 0u};
-                if (active && a.layers > 1) nxt = recs[(size_t)ln * z];
-                const int dl = hdr[l * 4], ext = hdr[l * 4 + 1];
-                const ldpc_const_i32 pk = pack + (size_t)l * kLdspPackStride;
-                if (active) {
-                    uint4 rec;
-                    uint32_t par = 0;
-                    bool done = false;
-                    if (ext) {
-                        switch (dl) {
-#define LDPC_LDSP_CASE(D) case D: done = ldsp_row<D, 1>(P, pk, z, r, cur, &rec, &par); break;
-                            LDPC_LDSP_WIDTHS(LDPC_LDSP_CASE)
-#undef LDPC_LDSP_CASE
-                        default: break;
-                        }
-                    } else {
-                        switch (dl) {
-#define LDPC_LDSP_CASE(D) case D + 1: done = ldsp_row<D + 1, 0>(P, pk, z, r, cur, &rec, &par); break;
-                            LDPC_LDSP_WIDTHS(LDPC_LDSP_CASE)
-#undef LDPC_LDSP_CASE
-                        default: break;
-                        }
-                    }
-                    if (!done) rec = ldsp_row_any(P, pk, dl, ext, z, r, cur, zfs + (size_t)l * z, &par);
-                    last_bad = par;
-                    asm volatile("" : "+v"(nxt.x), "+v"(nxt.y), "+v"(nxt.z), "+v"(nxt.w) : : "memory");
-                    recs[(size_t)l * z] = rec;
-                    if (a.layers == 1) nxt = rec;
-                    if (ext) {
-                        const uint64_t neg = __ballot(__uint_as_float(rec.w) < 0.0f);
-                        const uint64_t act = __ballot(true);
-                        if (lane == (int)__builtin_ctzll(act)) extneg[l] = neg;
-                    }
-                }
-                lds_barrier();
-                cur = nxt;
-            }
-            ++time;
-            const bool check = a.early_term || time == a.rounds;
-            const uint64_t last_mask = __ballot(active && last_bad);
-            bool any_bad = true;
-            if (check && __ballot(active && (last_mask & gmask) == 0ull) != 0ull) {
-                /* some frame's last layer is all even: the full syndrome, for the frames that need it */
-                uint64_t bad = 0;
-                const bool need = active && (last_mask & gmask) == 0ull;
-                if (need) {
-                    for (int l = 0; l < a.layers; ++l) {
-                        const int dl = hdr[l * 4], ext = hdr[l * 4 + 1];
-                        const ldpc_const_i32 pk = pack + (size_t)l * kLdspPackStride;
-                        uint64_t par = 0;
-                        switch (dl) {
-#define LDPC_LDSP_CASE(D) case D + 1: par = ldsp_row_parity<D + 1>(P, pk, z, r); break;
-                            LDPC_LDSP_WIDTHS(LDPC_LDSP_CASE)
-#undef LDPC_LDSP_CASE
-                        default: break;
-                        }
-                        if (ext) par ^= extneg[l];
-                        bad |= par;
-                    }
-                    any_bad = (bad & gmask) != 0ull;
-                }
-            }
-            if (active) {
-                clean = check && !any_bad;
-                if ((clean && a.early_term) || time == a.rounds) {
-                    active = false;
-                    my_iters = clean ? time : a.max_iter;
-                }
-            }
-            lds_barrier();
-        }
-        if (mine) {
-            const int64_t base = frame * (int64_t)a.K / 8;
-            for (int j = r; j < a.K / 8; j += z) {
-                unsigned byte = 0;
-#pragma unroll
-                for (int bit = 0; bit < 8; ++bit) byte |= (P[j * 8 + bit] < 0.0f ? 1u : 0u) << bit;
-                if (base + j < a.out_bytes) a.out[base + j] = (uint8_t)byte;
-            }
-            if (a.dump_p) {
-                for (int bc = 0; bc < a.nb; ++bc) {
-                    const int slot = cslot[bc];
-                    if (slot >= 0) a.dump_p[(size_t)frame * a.N + bc * z + r] = P[slot * z + r];
-                }
-                for (int l = 0; l < a.layers; ++l)
-                    if (hdr[l * 4 + 1])
-                        a.dump_p[(size_t)frame * a.N + hdr[l * 4 + 2] + ldsp_wrap(r, hdr[l * 4 + 3], z)] =
-                            __uint_as_float(recs[(size_t)l * z].w);
-            }
-            if (a.dump_r) {
-                for (int l = 0; l < a.layers; ++l) {
-                    const int d = hdr[l * 4] + hdr[l * 4 + 1], e0 = a.layer_e0[l];
-                    const uint4 rec = recs[(size_t)l * z];
-                    const uint32_t zf = (rec.z & kLdspIrregular) ? zfs[(size_t)l * z] : 0u;
-                    for (int k = 0; k < d; ++k)
-                        a.dump_r[(size_t)frame * a.E + e0 + r * d + k] = __uint_as_float(ldsp_old_message(rec, zf, k, d));
-                }
-            }
-            if (r == 0) {
-                if (a.iters) a.iters[frame] = my_iters;
-                atomicMax(&a.summary[0], my_iters);
-                if (clean) atomicAdd(&a.summary[1], 1);
-            }
-        }
-        lds_barrier();                                             /* P is refilled for the next frames */
-    }
+    constexpr bool CORR = false;
+    const MsCorr corr{1.0f, 0.0f};
+#include "ldsp_layered_packed_kernel.inc"
+}
+template <int kUnused = 0>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LDPC_LDSP_WAVES_PER_EU)))
+void layered_ldsp_packed_corr_kernel(const LdspArgs a, const int G, const MsCorr corr)
+{
+    constexpr bool CORR = true;
+#include "ldsp_layered_packed_kernel.inc"
 }
 
 
@@ -581,10 +312,10 @@ void layered_ldsp_packed_kernel(const LdspArgs a, const int G)
  * NEW posteriors, which start from the channel values: two LDS images, layers in ascending order
  * with a barrier in between, so that every column receives y + R_1 + R_2 + ... in ascending row
  * order as refreshPostPMS computes it.  Hard decision !(p > 0), syndrome, stop when clean. */
-template <int DL, int EXT>
+template <int DL, int EXT, bool CORR = false>
 __device__ __forceinline__ void ldsp_flood_row(const float *Pold, float *Pnew, ldpc_const_i32 pk, int z, int r,
                                                const uint4 old, float pext_old, float yext, uint4 *out,
-                                               uint64_t *par_mask, uint64_t *ext_mask)
+                                               uint64_t *par_mask, uint64_t *ext_mask, const MsCorr corr = MsCorr{1.0f, 0.0f})
 {
     constexpr int D = DL + EXT;
     constexpr int DLA = DL > 0 ? DL : 1;
@@ -618,6 +349,7 @@ __device__ __forceinline__ void ldsp_flood_row(const float *Pold, float *Pnew, l
         m1 = lt1 ? mag : m1;
         idx = lt1 ? k : idx;
     }
+    if (CORR) { m1 = ms_corr<float>(m1, corr); m2 = ms_corr<float>(m2, corr); }  /* the record holds the corrected values */
     const uint32_t b1 = __float_as_uint(m1), b2 = __float_as_uint(m2);
     uint32_t signs = 0, pext = 0;
     uint64_t pm = 0;
@@ -776,148 +508,18 @@ template <int MAXW, bool CHAIN>
 __global__ __launch_bounds__(64 * MAXW) __attribute__((amdgpu_waves_per_eu(LDPC_LDSP_WAVES_PER_EU)))
 void flood_ldsp_kernel(const LdspArgs a)
 {
-    extern __shared__ float lds[];
-    const int r = (int)threadIdx.x, LANES = (int)blockDim.x, MW = LANES >> 6, wave = r >> 6;
-    const int z = a.z;
-    const size_t image = ((size_t)a.lds_cols * z + 1) & ~(size_t)1;
-    float *Pa = lds, *Pb = lds + image;                             /* old / new posteriors, [lds_cols][z] each */
-    uint64_t *extneg = reinterpret_cast<uint64_t *>(lds + 2 * image);   /* [layers][MW] */
-    uint32_t *wg_flag = reinterpret_cast<uint32_t *>(extneg + (size_t)a.layers * MW);
-    const bool row = r < z;
-    uint4 *recs = a.recs + (size_t)blockIdx.x * ((size_t)a.layers * z) + r;
-    uint32_t *zfs = a.zf + (size_t)blockIdx.x * ((size_t)a.layers * z) + r;
-    const ldpc_const_i32 hdr = as_constant(a.hdr), pack = as_constant(a.pack), cslot = as_constant(a.col_slot);
-    auto wg_any = [&](bool pred) {
-        if (r == 0) *wg_flag = 0u;
-        lds_barrier();
-        if (__ballot(pred) != 0ull && (r & 63) == 0) *wg_flag = 1u;
-        lds_barrier();
-        const uint32_t f = *wg_flag;
-        lds_barrier();
-        return f != 0u;
-    };
-    auto fill = [&](float *P, const float *y) {                    /* the LDS-resident columns' channel values */
-        if (row)
-            for (int bc = 0; bc < a.nb; ++bc) {
-                const int slot = cslot[bc];
-                if (slot >= 0) P[slot * z + r] = y[bc * z + r];
-            }
-    };
-    for (int64_t frame = blockIdx.x; frame < a.frames; frame += gridDim.x) {
-        const float *y = a.llr + (size_t)frame * a.N;
-        fill(Pa, y);                                               /* Q_0 = y: P_0 = y, R_0 = 0 */
-        int time = 0;
-        bool clean = false;
-        uint4 cur = uint4{0u, 0u, 0u, 0u};
-        while (true) {
-            fill(Pb, y);                                           /* refreshPostPMS starts from the channel value */
-            __syncthreads();
-            uint64_t last_bad = 0;
-            for (int l = 0; l < a.layers; ++l) {
-                const int ln = l + 1 < a.layers ? l + 1 : 0;
-                uint4 nxt = uint4{0u, 0u, 0u, 0u};
-                if (row && a.layers > 1 && (time > 0 || ln == 0)) nxt = recs[(size_t)ln * z];
-                const int dl = hdr[l * 4], ext = hdr[l * 4 + 1];
-                const ldpc_const_i32 pk = pack + (size_t)l * kLdspPackStride;
-                if (row) {
-                    float yext = 0.0f;
-                    if (ext) yext = y[hdr[l * 4 + 2] + ldsp_wrap(r, hdr[l * 4 + 3], z)];
-                    const float pext_old = time == 0 ? yext : __uint_as_float(cur.w);
-                    uint4 rec = cur;
-                    uint64_t pm = 0, em = 0;
-                    bool done = CHAIN;                             /* the chain arithmetic has no slow path */
-                    if (ext) {
-                        switch (dl) {
-#define LDPC_LDSP_CASE(D) case D:                                                                                  \
-                            if (CHAIN) ldsp_flood_row<D, 1>(Pa, Pb, pk, z, r, cur, pext_old, yext, &rec, &pm, &em);        \
-                            else done = ldsp_mscl_row<D, 1>(Pa, Pb, pk, z, r, cur, pext_old, yext, &rec, &pm, &em);         \
-                            break;
-                            LDPC_LDSP_WIDTHS(LDPC_LDSP_CASE)
-#undef LDPC_LDSP_CASE
-                        default: break;
-                        }
-                    } else {
-                        switch (dl) {
-#define LDPC_LDSP_CASE(D) case D + 1:                                                                              \
-                            if (CHAIN) ldsp_flood_row<D + 1, 0>(Pa, Pb, pk, z, r, cur, 0.0f, 0.0f, &rec, &pm, &em);        \
-                            else done = ldsp_mscl_row<D + 1, 0>(Pa, Pb, pk, z, r, cur, 0.0f, 0.0f, &rec, &pm, &em);         \
-                            break;
-                            LDPC_LDSP_WIDTHS(LDPC_LDSP_CASE)
-#undef LDPC_LDSP_CASE
-                        default: break;
-                        }
-                    }
-                    if (!CHAIN && !done)
-                        rec = ldsp_mscl_row_any(Pa, Pb, pk, dl, ext, z, r, cur, pext_old, yext, zfs + (size_t)l * z, &pm, &em);
-                    if (ext && (r & 63) == 0) extneg[l * MW + wave] = em;
-                    last_bad = pm;
-                    asm volatile("" : "+v"(nxt.x), "+v"(nxt.y), "+v"(nxt.z), "+v"(nxt.w) : : "memory");
-                    recs[(size_t)l * z] = rec;
-                    if (a.layers == 1) nxt = rec;
-                }
-                lds_barrier();
-                cur = nxt;
-            }
-            ++time;
-            int any_bad = 1;
-            /* the last layer's rows have just written the final posteriors of their columns */
-            if ((a.early_term || time == a.rounds) && !wg_any(row && last_bad != 0ull)) {
-                uint64_t bad = 0;
-                if (row) {
-                    for (int l = 0; l < a.layers; ++l) {
-                        const ldpc_const_i32 pk = pack + (size_t)l * kLdspPackStride;
-                        uint64_t par = 0;
-                        switch (hdr[l * 4]) {
-#define LDPC_LDSP_CASE(D) case D: par = ldsp_flood_parity<D, CHAIN>(Pb, pk, z, r); break;
-                            LDPC_LDSP_WIDTHS1(LDPC_LDSP_CASE)
-#undef LDPC_LDSP_CASE
-                        default: break;
-                        }
-                        if (hdr[l * 4 + 1]) par ^= extneg[l * MW + wave];
-                        bad |= par;
-                    }
-                }
-                any_bad = wg_any(bad != 0ull) ? 1 : 0;
-            }
-            clean = !any_bad;
-            float *t = Pa; Pa = Pb; Pb = t;                         /* the new posteriors are the next round's old ones */
-            if ((clean && a.early_term) || time == a.rounds) break;
-        }
-        /* Pa holds the final posteriors; the information columns sit at slot = block column */
-        const int64_t base = frame * (int64_t)a.K / 8;
-        for (int j = r; j < a.K / 8; j += LANES) {
-            unsigned byte = 0;
-#pragma unroll
-            for (int bit = 0; bit < 8; ++bit) byte |= (ldsp_flood_bit<CHAIN>(Pa[j * 8 + bit]) ? 1u : 0u) << bit;
-            if (base + j < a.out_bytes) a.out[base + j] = (uint8_t)byte;
-        }
-        if (a.dump_p && row) {
-            for (int bc = 0; bc < a.nb; ++bc) {
-                const int slot = cslot[bc];
-                if (slot >= 0) a.dump_p[(size_t)frame * a.N + bc * z + r] = Pa[slot * z + r];
-            }
-            for (int l = 0; l < a.layers; ++l)
-                if (hdr[l * 4 + 1])
-                    a.dump_p[(size_t)frame * a.N + hdr[l * 4 + 2] + ldsp_wrap(r, hdr[l * 4 + 3], z)] =
-                        __uint_as_float(recs[(size_t)l * z].w);
-        }
-        if (a.dump_r && row) {
-            for (int l = 0; l < a.layers; ++l) {
-                const int d = hdr[l * 4] + hdr[l * 4 + 1], e0 = a.layer_e0[l];
-                const uint4 rec = recs[(size_t)l * z];
-                const uint32_t zf = (rec.z & kLdspIrregular) ? zfs[(size_t)l * z] : 0u;
-                for (int k = 0; k < d; ++k)
-                    a.dump_r[(size_t)frame * a.E + e0 + r * d + k] = __uint_as_float(ldsp_old_message(rec, zf, k, d));
-            }
-        }
-        if (r == 0) {
-            const int it = clean ? time : a.max_iter;
-            if (a.iters) a.iters[frame] = it;
-            atomicMax(&a.summary[0], it);
-            if (clean) atomicAdd(&a.summary[1], 1);
-        }
-        __syncthreads();
-    }
+    constexpr bool CORR = false;
+    const MsCorr corr{1.0f, 0.0f};
+#include "ldsp_flood_kernel.inc"
+}
+/* normalized / offset min-sum on the MS chain: the records hold the corrected magnitudes */
+template <int MAXW>
+__global__ __launch_bounds__(64 * MAXW) __attribute__((amdgpu_waves_per_eu(LDPC_LDSP_WAVES_PER_EU)))
+void flood_ldsp_corr_kernel(const LdspArgs a, const MsCorr corr)
+{
+    constexpr bool CHAIN = true;
+    constexpr bool CORR = true;
+#include "ldsp_flood_kernel.inc"
 }
 
 /* flood_ldsp_kernel for circulants of <= 32 rows: G = 64 / z frames per wave, one wave per
@@ -926,116 +528,17 @@ template <bool CHAIN>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LDPC_LDSP_WAVES_PER_EU)))
 void flood_ldsp_packed_kernel(const LdspArgs a, const int G)
 {
-    extern __shared__ float lds[];
-    const int lane = (int)threadIdx.x;
-    const int z = a.z;
-    const int g = lane / z, r = lane - g * z;
-    const bool member = g < G;
-    const size_t image = ((size_t)a.N + 1) & ~(size_t)1;
-    float *Pa = lds + (size_t)(member ? g : 0) * 2 * image, *Pb = Pa + image;
-    uint4 *recs = a.recs + ((size_t)blockIdx.x * G + (member ? g : 0)) * ((size_t)a.layers * z) + r;
-    uint32_t *zfs = a.zf + ((size_t)blockIdx.x * G + (member ? g : 0)) * ((size_t)a.layers * z) + r;
-    const ldpc_const_i32 hdr = as_constant(a.hdr), pack = as_constant(a.pack);
-    const uint64_t gmask = (z >= 64 ? ~0ull : ((1ull << z) - 1ull)) << (member ? g * z : 0);
-    for (int64_t frame0 = (int64_t)blockIdx.x * G; frame0 < a.frames; frame0 += (int64_t)gridDim.x * G) {
-        const int64_t frame = frame0 + g;
-        const bool mine = member && frame < a.frames;
-        const float *y = a.llr + (size_t)(mine ? frame : 0) * a.N;
-        if (mine)
-            for (int n = r; n < a.N; n += z) Pa[n] = y[n];
-        int time = 0, my_iters = a.max_iter;
-        bool active = mine, clean = false;
-        uint4 cur = uint4{0u, 0u, 0u, 0u};
-        while (__ballot(active) != 0ull) {
-            if (active)
-                for (int n = r; n < a.N; n += z) Pb[n] = y[n];
-            lds_barrier();
-            uint64_t last_bad = 0;
-            for (int l = 0; l < a.layers; ++l) {
-                const int ln = l + 1 < a.layers ? l + 1 : 0;
-                uint4 nxt = uint4{0u, 0u, 0u, 0u};
-                if (active && a.layers > 1 && (time > 0 || ln == 0)) nxt = recs[(size_t)ln * z];
-                const int d = hdr[l * 4];
-                const ldpc_const_i32 pk = pack + (size_t)l * kLdspPackStride;
-                if (active) {
-                    uint4 rec = cur;
-                    uint64_t pm = 0, em = 0;
-                    bool done = CHAIN;
-                    switch (d) {
-#define LDPC_LDSP_CASE(D) case D:                                                                                  \
-                        if (CHAIN) ldsp_flood_row<D, 0>(Pa, Pb, pk, z, r, cur, 0.0f, 0.0f, &rec, &pm, &em);                \
-                        else done = ldsp_mscl_row<D, 0>(Pa, Pb, pk, z, r, cur, 0.0f, 0.0f, &rec, &pm, &em);                 \
-                        break;
-                        LDPC_LDSP_WIDTHS1(LDPC_LDSP_CASE)
-#undef LDPC_LDSP_CASE
-                    default: break;
-                    }
-                    if (!CHAIN && !done)
-                        rec = ldsp_mscl_row_any(Pa, Pb, pk, d, 0, z, r, cur, 0.0f, 0.0f, zfs + (size_t)l * z, &pm, &em);
-                    last_bad = pm;
-                    asm volatile("" : "+v"(nxt.x), "+v"(nxt.y), "+v"(nxt.z), "+v"(nxt.w) : : "memory");
-                    recs[(size_t)l * z] = rec;
-                    if (a.layers == 1) nxt = rec;
-                }
-                lds_barrier();
-                cur = nxt;
-            }
-            ++time;
-            const bool check = a.early_term || time == a.rounds;
-            bool any_bad = true;
-            const bool need = active && check && (last_bad & gmask) == 0ull;
-            if (__ballot(need) != 0ull) {
-                uint64_t bad = 0;
-                if (need) {
-                    for (int l = 0; l < a.layers; ++l) {
-                        const ldpc_const_i32 pk = pack + (size_t)l * kLdspPackStride;
-                        switch (hdr[l * 4]) {
-#define LDPC_LDSP_CASE(D) case D: bad |= ldsp_flood_parity<D, CHAIN>(Pb, pk, z, r); break;
-                            LDPC_LDSP_WIDTHS1(LDPC_LDSP_CASE)
-#undef LDPC_LDSP_CASE
-                        default: break;
-                        }
-                    }
-                    any_bad = (bad & gmask) != 0ull;
-                }
-            }
-            if (active) {
-                clean = check && !any_bad;
-                float *t = Pa; Pa = Pb; Pb = t;
-                if ((clean && a.early_term) || time == a.rounds) {
-                    active = false;
-                    my_iters = clean ? time : a.max_iter;
-                }
-            }
-            lds_barrier();
-        }
-        if (mine) {
-            const int64_t base = frame * (int64_t)a.K / 8;
-            for (int j = r; j < a.K / 8; j += z) {
-                unsigned byte = 0;
-#pragma unroll
-                for (int bit = 0; bit < 8; ++bit) byte |= (ldsp_flood_bit<CHAIN>(Pa[j * 8 + bit]) ? 1u : 0u) << bit;
-                if (base + j < a.out_bytes) a.out[base + j] = (uint8_t)byte;
-            }
-            if (a.dump_p)
-                for (int n = r; n < a.N; n += z) a.dump_p[(size_t)frame * a.N + n] = Pa[n];
-            if (a.dump_r) {
-                for (int l = 0; l < a.layers; ++l) {
-                    const int d = hdr[l * 4], e0 = a.layer_e0[l];
-                    const uint4 rec = recs[(size_t)l * z];
-                    const uint32_t zf = (rec.z & kLdspIrregular) ? zfs[(size_t)l * z] : 0u;
-                    for (int k = 0; k < d; ++k)
-                        a.dump_r[(size_t)frame * a.E + e0 + r * d + k] = __uint_as_float(ldsp_old_message(rec, zf, k, d));
-                }
-            }
-            if (r == 0) {
-                if (a.iters) a.iters[frame] = my_iters;
-                atomicMax(&a.summary[0], my_iters);
-                if (clean) atomicAdd(&a.summary[1], 1);
-            }
-        }
-        lds_barrier();
-    }
+    constexpr bool CORR = false;
+    const MsCorr corr{1.0f, 0.0f};
+#include "ldsp_flood_packed_kernel.inc"
+}
+template <int kUnused = 0>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LDPC_LDSP_WAVES_PER_EU)))
+void flood_ldsp_packed_corr_kernel(const LdspArgs a, const int G, const MsCorr corr)
+{
+    constexpr bool CHAIN = true;
+    constexpr bool CORR = true;
+#include "ldsp_flood_packed_kernel.inc"
 }
 
 /* ---------------------------------------------------------------- host side */
@@ -1051,6 +554,9 @@ struct LdspPlan {
     int flood = 0;                      /* 0 layered kernels; flood_ldsp_kernel with 1: the MS chain's arithmetic (DecodeMS /
                                            DecodeCPU), 2: the fused reference kernel's (DecodeMSCL) */
     int32_t grid = 0, block = 0, maxw = 0, per_cu = 0, wg_frames = 1;   /* wg_frames: frames per one-wave workgroup (z <= 32) */
+    int corr = 0;                       /* 1: normalized / offset min-sum (the *_corr_kernel forms, flood 0 or 1) with mc; set
+                                           before ldsp_plan_create */
+    MsCorr mc{1.0f, 0.0f};
     size_t lds_bytes = 0;
 };
 
@@ -1067,6 +573,9 @@ inline void ldsp_plan_destroy(LdspPlan *pl)
 #ifdef LDPC_ENGINE_LDSP
 typedef void (*LdspKernel)(const LdspArgs);
 inline LdspKernel ldsp_kernel_for(int maxw) { return maxw <= 8 ? layered_ldsp_kernel<8> : layered_ldsp_kernel<16>; }
+typedef void (*LdspCorrKernel)(const LdspArgs, const MsCorr);
+inline LdspCorrKernel ldsp_corr_kernel_for(int maxw) { return maxw <= 8 ? layered_ldsp_corr_kernel<8> : layered_ldsp_corr_kernel<16>; }
+inline LdspCorrKernel flood_ldsp_corr_kernel_for(int maxw) { return maxw <= 8 ? flood_ldsp_corr_kernel<8> : flood_ldsp_corr_kernel<16>; }
 
 /* Detect the QC structure, decide which block columns travel with a record (met by one layer
  * only, last entry of that layer's rows, not an information column), lay the others out in LDS,
@@ -1146,6 +655,11 @@ inline hipError_t ldsp_plan_create(LdspPlan *pl, int32_t M, int32_t N, int64_t E
     const void *k = flood ? (pl->wg_frames > 1 ? (flood == 1 ? (const void *)flood_ldsp_packed_kernel<true> : (const void *)flood_ldsp_packed_kernel<false>)
                                                : (const void *)flood_ldsp_kernel_for(mw <= 8 ? 8 : 16, flood))
                     : pl->wg_frames > 1 ? (const void *)layered_ldsp_packed_kernel<0> : (const void *)ldsp_kernel_for(mw <= 8 ? 8 : 16);
+    if (pl->corr) {
+        if (flood == 2) return hipErrorInvalidValue;                /* the reference's fused arithmetic takes no correction */
+        k = flood ? (pl->wg_frames > 1 ? (const void *)flood_ldsp_packed_corr_kernel<0> : (const void *)flood_ldsp_corr_kernel_for(mw <= 8 ? 8 : 16))
+                  : pl->wg_frames > 1 ? (const void *)layered_ldsp_packed_corr_kernel<0> : (const void *)ldsp_corr_kernel_for(mw <= 8 ? 8 : 16);
+    }
     /* the attribute belongs to the function, not to this plan: always the maximum, so that decoders
      * of different codes can coexist */
     if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdspMaxLds))) return e;
@@ -1191,7 +705,11 @@ inline hipError_t ldsp_run(LdspPlan *pl, const FusedRun &r, hipStream_t s, int32
                r.max_iter, rounds, r.early_term};
     const unsigned grid = (unsigned)std::min<int64_t>((r.frames + pl->wg_frames - 1) / pl->wg_frames, pl->grid);
     if (!pl->eligible || grid == 0) return hipErrorInvalidValue;
-    if (pl->flood == 1 && pl->wg_frames > 1) flood_ldsp_packed_kernel<true><<<grid, 64, pl->lds_bytes, s>>>(a, pl->wg_frames);
+    if (pl->corr && pl->flood == 1 && pl->wg_frames > 1) flood_ldsp_packed_corr_kernel<0><<<grid, 64, pl->lds_bytes, s>>>(a, pl->wg_frames, pl->mc);
+    else if (pl->corr && pl->flood == 1) flood_ldsp_corr_kernel_for(pl->maxw)<<<grid, pl->block, pl->lds_bytes, s>>>(a, pl->mc);
+    else if (pl->corr && pl->wg_frames > 1) layered_ldsp_packed_corr_kernel<0><<<grid, 64, pl->lds_bytes, s>>>(a, pl->wg_frames, pl->mc);
+    else if (pl->corr) ldsp_corr_kernel_for(pl->maxw)<<<grid, pl->block, pl->lds_bytes, s>>>(a, pl->mc);
+    else if (pl->flood == 1 && pl->wg_frames > 1) flood_ldsp_packed_kernel<true><<<grid, 64, pl->lds_bytes, s>>>(a, pl->wg_frames);
     else if (pl->flood && pl->wg_frames > 1) flood_ldsp_packed_kernel<false><<<grid, 64, pl->lds_bytes, s>>>(a, pl->wg_frames);
     else if (pl->flood) flood_ldsp_kernel_for(pl->maxw, pl->flood)<<<grid, pl->block, pl->lds_bytes, s>>>(a);
     else if (pl->wg_frames > 1) layered_ldsp_packed_kernel<0><<<grid, 64, pl->lds_bytes, s>>>(a, pl->wg_frames);

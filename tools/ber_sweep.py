@@ -25,6 +25,8 @@ ap.add_argument("--iters", type=int, default=50)
 ap.add_argument("--llr-scale", type=float, default=8.0)
 ap.add_argument("--batches", type=int, default=1, help="batches of --frames per SNR point")
 ap.add_argument("--seed", type=int, default=20260101)
+ap.add_argument("--ms-scale", type=float, default=0.0, help="normalized min-sum factor (ms / layered; 0 = off)")
+ap.add_argument("--ms-offset", type=float, default=0.0, help="offset min-sum offset, units of y (0 = off)")
 args = ap.parse_args()
 
 layer = 0
@@ -47,14 +49,14 @@ M = N - K
 g = L.Graph(rows, cols, M, N)
 B = args.frames
 dec = L.Decoder(g, K, max_batch=B, algo=args.algo, max_iter=args.iters, llr_scale=args.llr_scale,
-                layer_rows=layer, poll_interval=2)
+                layer_rows=layer, poll_interval=2, ms_scale=args.ms_scale, ms_offset=args.ms_offset)
 out = torch.empty(L.out_bytes(K, B), dtype=torch.uint8, device="cuda")
 it = torch.empty(B, dtype=torch.int32, device="cuda")
 from myldpccppapi_amd import channel
 import time
 y = torch.empty((B, N), dtype=torch.float32, device="cuda")
-print("code=%s algo=%s frames=%d x %d max_iter=%d (info bits per point: %d)" % (
-    args.code, args.algo, B, args.batches, args.iters, B * K * args.batches))
+print("code=%s algo=%s ms_scale=%g ms_offset=%g frames=%d x %d max_iter=%d (info bits per point: %d)" % (
+    args.code, args.algo, args.ms_scale, args.ms_offset, B, args.batches, args.iters, B * K * args.batches))
 points = [float(x) for x in args.snr.split(",")]
 # one untimed batch first: the first launch of every kernel (the library's and torch's) pays one-time costs
 channel.awgn_device(N, 0, B, 10.0 ** (-points[-1] / 20.0), seed=args.seed + 1, out=y)
