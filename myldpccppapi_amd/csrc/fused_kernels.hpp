@@ -898,7 +898,10 @@ inline hipError_t fused_run(FusedPlan *pl, const FusedRun &r, hipStream_t s, int
     }
 #define LDPC_COMMA ,
     if (r.flooding == 3) {
-        switch (mw * 100 + dm) {
+        /* fused_sp_kernel exists in the unrolled widths only (eligible_sp: rows <= 24); run-time row loops
+         * (loop_rows) do not apply to it */
+        const int dms = pl->max_deg <= 8 ? 8 : pl->max_deg <= 16 ? 16 : 24;
+        switch (mw * 100 + dms) {
 #define LDPC_SP_CASE(MWV, DMV) case MWV * 100 + DMV:                                                                     \
         if (pl->lds_sp > 60 * 1024 &&                                                                                   \
             (e = hipFuncSetAttribute((const void *)fused_sp_kernel<MWV, DMV, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, \
