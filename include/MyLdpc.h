@@ -30,6 +30,7 @@
  *   - `times` (MyLdpc.cpp:24) and the SP channel scale 8 (decodeCL.c:9) stay the
  *     defaults and can be changed with setMaxIterations()/setLlrScale().
  *   - setDevices(): one Coder over several GPUs (the reference uses devices[0] only).
+ *   - setEncodeOnDevice(): encode() on the GPU (the "encoder" section of ldpc_hip.h) instead of the host.
  */
 #ifndef MYLDPC_H_
 #define MYLDPC_H_
@@ -91,6 +92,11 @@ public:
      * path (every row of one weight) it fails in addDecodeType while a correction is set, as DecodeMSCL always
      * does (both reproduce reference kernels).  (0, 0) = off.  Before addDecodeType(). */
     void setMinSumCorrection(float scale, float offset) { msScale = scale; msOffset = offset; }
+    /* encode() on the GPU `setDevice` names (ldpc_encode, include/ldpc_hip.h) instead of the host: same bytes.
+     * forEncoder() then creates the device encoder and skips the host precompute, so it also serves the seed whose
+     * parity part the host solves by dense elimination only (rate_3_4_b: any N, where the host path stops at
+     * M > 8192).  Off by default.  Before forEncoder(). */
+    void setEncodeOnDevice(bool on);
     int lastIterations() const { return lastTime; }             /* the reference's "Time=" */
     const char *lastError() const { return err.c_str(); }
     int getNonZeros() const { return nonZeros; }
@@ -127,6 +133,10 @@ private:
     int encX;                        /* block row of the weight-3 parity column's middle entry */
     std::vector<unsigned char> denseInv; /* fallback: bit-packed inverse of the parity part */
     bool structured;
+
+    bool encodeOnDevice = false;     /* setEncodeOnDevice() */
+    ldpc_encoder *encoder = nullptr; /* forEncoder() with encodeOnDevice */
+    int makeGraph();
 
     ldpc_graph *graph;
     std::map<int, ldpc_decoder *> decoders; /* decodeType -> handle */

@@ -333,6 +333,45 @@ int ldpc_awgn_device(float *llr_dev, int64_t frames, int32_t N, const uint8_t *b
 int ldpc_count_errors_device(const uint8_t *out_dev, const uint8_t *ref_dev, int64_t frames,
                              int64_t bytes_per_frame, int64_t errors[3], int32_t device, void *stream);
 
+/* ---- encoder: replaces Coder::forEncoder / encode / encodeOnce (MyLdpc.cpp:137-165, 554-569, 633-682) for whole
+ *      batches on the device, so that encode -> channel -> decode -> count can stay in HBM.
+ * Systematic: the codeword is [K information bits | M = N - K parity bits], the unique solution of H c = 0.  The
+ * parity part H[:, K..N) must have one of two structures, recognised from the graph alone:
+ *   LDPC_PARITY_DUAL_DIAGONAL (needs block_rows = z > 0): circulant blocks of z rows; the first parity block column
+ *     has three blocks, in block rows 0, x, c-1 with shifts (a, b, a), any b; parity block columns 1 .. c-1 are the
+ *     zero-shift dual diagonal; block rows c .. M/z - 1 ("extension", possibly none) each own one zero-shift
+ *     identity parity column and otherwise touch information and core parity columns only.  802.16e: c = M/z for
+ *     all six seeds; codes.nr_bg1_profile_edges: c = 4, x = 1, 42 extension block rows.
+ *   LDPC_PARITY_STAIRCASE: parity column K + m has its ones in rows m and m + 1 only (codes.dvbs2_profile_edges).
+ * Anything else is LDPC_ERR_UNSUPPORTED with a message that names the condition that failed; there is no dense
+ * elimination on the device.
+ * ldpc_parity_structure (host only, no device is touched): out[0] = enum ldpc_parity_kind, out[1] = c, out[2] = x,
+ *   out[3] = a, out[4] = b, out[5] = extension block rows, out[6] = z, out[7] = 0 (all 0 but out[0] for a staircase).
+ * Data (Coder::encode's): frame f reads the K/8 WHOLE source bytes from byte (f*K)/8 on (the product first: for
+ *   K % 8 != 0 frames start at 0, 40, 81, 121, ... for K = 324); bytes at index >= src_bytes read as zero;
+ *   information bits K - K%8 .. K-1 are zero; bits LSB first.  Code formats: enum ldpc_code_format.
+ * ldpc_encode_device: buffers in the encoder's device memory, frames <= max_frames, every frame's first byte inside
+ *   src_bytes; enqueued on `stream` (a hipStream_t, NULL = default stream), returns without waiting; allocates
+ *   nothing (the handle owns scratch for max_frames frames: N bits per frame plus the row sums).
+ * ldpc_encode: host buffers, LDPC_CODE_PACKED, blocking, in chunks of max_frames; the frame count follows from
+ *   src_bytes as in Coder::encode (the last frame is the first one with (f+1)*K/8 >= src_bytes).
+ * An encoder handle is not re-entrant: one per host thread / stream. */
+typedef struct ldpc_encoder ldpc_encoder;
+enum ldpc_code_format {
+    LDPC_CODE_PACKED = 0, /* N/8 bytes per frame at byte f*N/8, LSB first (Coder::encode's priorCode); N % 8 == 0 */
+    LDPC_CODE_BITS = 1    /* N bytes per frame, 0/1: what ldpc_awgn_device takes as bits_dev                      */
+};
+enum ldpc_parity_kind { LDPC_PARITY_DUAL_DIAGONAL = 1, LDPC_PARITY_STAIRCASE = 2 };
+int ldpc_parity_structure(const ldpc_graph *g, int32_t K, int32_t block_rows, int32_t out[8]);
+int ldpc_encoder_create(const ldpc_graph *g, int32_t K, int32_t block_rows, int32_t max_frames, int32_t device,
+                        ldpc_encoder **out);
+int ldpc_encoder_destroy(ldpc_encoder *e);
+int ldpc_encode_device(ldpc_encoder *e, const uint8_t *src_dev, int64_t src_bytes, int64_t frames, uint8_t *code_dev,
+                       int64_t code_bytes, int32_t format, void *stream);
+int ldpc_encode(ldpc_encoder *e, const uint8_t *src_host, int64_t src_bytes, uint8_t *code_host, int64_t code_bytes);
+/* bytes of `frames` codewords in `format` (0 for an unknown format, or LDPC_CODE_PACKED with N % 8 != 0) */
+int64_t ldpc_code_bytes(int32_t N, int64_t frames, int32_t format);
+
 /* ---- measurement aid: the rate a plain float4 copy of `bytes` bytes (read + write counted)
  *      sustains on `device` right now, best of `reps` launches each with the default cache policy
  *      and with non-temporal loads and stores (the streaming kernels' policy), HIP-event timed on

@@ -64,6 +64,7 @@ EXPORTS = (
     "ldpc_decoder_set_timing", "ldpc_decoder_stats", "ldpc_decoder_kernel_times", "ldpc_decoder_set_tap",
     "ldpc_decoder_dump", "ldpc_awgn_device", "ldpc_count_errors_device", "ldpc_hbm_probe_device", "ldpc_hbm_sustained_device",
     "ldpc_host_block_plan", "ldpc_host_locked_ranges", "ldpc_decoder_link_form", "ldpc_decoder_placement", "ldpc_decoder_array_addresses",
+    "ldpc_parity_structure", "ldpc_encoder_create", "ldpc_encoder_destroy", "ldpc_encode_device", "ldpc_encode", "ldpc_code_bytes",
 )
 
 
@@ -122,6 +123,13 @@ def load():
     L.ldpc_decoder_array_addresses.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.ldpc_decoder_placement.argtypes = [vp, i32p, i32p, ctypes.POINTER(ctypes.c_float)]
     L.ldpc_decoder_link_form.argtypes = [vp, i32p, i32p, ctypes.POINTER(ctypes.c_float)]
+    L.ldpc_parity_structure.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, i32p]
+    L.ldpc_encoder_create.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(vp)]
+    L.ldpc_encoder_destroy.argtypes = [vp]
+    L.ldpc_encode_device.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int32, vp]
+    L.ldpc_encode.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64]
+    L.ldpc_code_bytes.argtypes = [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]
+    L.ldpc_code_bytes.restype = ctypes.c_int64
     _lib = L
     return L
 

@@ -1,4 +1,4 @@
-"""Thin Python objects over the C ABI (include/ldpc_hip.h): Graph and Decoder.
+"""Thin Python objects over the C ABI (include/ldpc_hip.h): Graph, Decoder and Encoder.
 
 Host-side plumbing only -- every decode runs in the HIP kernels of
 libldpc_hip.so.  numpy arrays are passed as host pointers, integers (e.g. a
@@ -14,6 +14,9 @@ from ._lib import DecoderConfig, DecodeStats, LdpcError  # noqa: F401
 ALGO_SP, ALGO_MS, ALGO_LAYERED, ALGO_MS_FUSED, ALGO_LAYERED_HOST = 0, 1, 2, 3, 4
 MSG_F32, MSG_F16 = 0, 1
 PACK_BYTES, PACK_BITS = 0, 1
+CODE_PACKED, CODE_BITS = 0, 1                              # enum ldpc_code_format
+CODE_FORMATS = {"packed": CODE_PACKED, "bits": CODE_BITS}
+PARITY_KINDS = {1: "dual_diagonal", 2: "staircase"}        # enum ldpc_parity_kind
 HOST_INPUT = {"auto": 0, "staged": 1, "lock_pages": 2}     # enum ldpc_host_input
 ALGOS = {"sp": ALGO_SP, "ms": ALGO_MS, "layered": ALGO_LAYERED, "ms_fused": ALGO_MS_FUSED,
          "layered_host": ALGO_LAYERED_HOST}
@@ -116,6 +119,19 @@ def device_count():
 
 def out_bytes(K, frames, pack_mode=PACK_BYTES):
     return int(_lib.load().ldpc_out_bytes(K, frames, pack_mode))
+
+
+def code_bytes(N, frames, fmt="packed"):
+    """ldpc_code_bytes: bytes of `frames` codewords (0: unknown format, or packed with N % 8 != 0)."""
+    return int(_lib.load().ldpc_code_bytes(int(N), int(frames), CODE_FORMATS.get(fmt, fmt)))
+
+
+def parity_structure(graph, K, block_rows=0):
+    """ldpc_parity_structure: how the encoder would solve the parity part H[:, K..N) -- host analysis only.
+    dict(kind="dual_diagonal" | "staircase", c, x, a, b, ext_rows, z); LdpcError code 4 for any other structure."""
+    out = (ctypes.c_int32 * 8)()
+    _lib.check(_lib.load().ldpc_parity_structure(graph._h, int(K), int(block_rows), out))
+    return dict(kind=PARITY_KINDS[out[0]], c=out[1], x=out[2], a=out[3], b=out[4], ext_rows=out[5], z=out[6])
 
 
 class Graph:
@@ -265,6 +281,51 @@ class Decoder:
         h, self._h = getattr(self, "_h", None), None
         if h and _lib is not None and _lib._lib is not None:
             _lib.check(_lib._lib.ldpc_decoder_destroy(h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Encoder:
+    """One encoder handle (ldpc_encoder_create): systematic encoding of up to `max_frames` frames per call in HIP
+    kernels, data conventions of Coder::encode.  block_rows: circulant size z of a quasi-cyclic code (0: staircase
+    codes).  There is no CPU path: without a device the constructor raises LdpcError code 2."""
+
+    def __init__(self, graph, K, block_rows=0, max_frames=4096, device=0):
+        L = _lib.load()
+        self.graph, self.K, self.N = graph, int(K), graph.N
+        self.block_rows, self.max_frames, self.device = int(block_rows), int(max_frames), int(device)
+        self._h = ctypes.c_void_p()
+        _lib.check(L.ldpc_encoder_create(graph._h, self.K, self.block_rows, self.max_frames, self.device,
+                                         ctypes.byref(self._h)))
+
+    def structure(self):
+        return parity_structure(self.graph, self.K, self.block_rows)
+
+    def encode(self, src_bytes):
+        """Host buffers: the source byte stream (bytes / uint8 array) -> packed codewords, uint8 [frames * N/8];
+        the frame count follows from the length as in Coder::encode."""
+        src = np.ascontiguousarray(np.frombuffer(bytes(src_bytes), np.uint8) if isinstance(src_bytes, (bytes, bytearray))
+                                   else src_bytes, np.uint8).reshape(-1)
+        frames = 1
+        while frames * self.K // 8 < src.size:
+            frames += 1
+        out = np.zeros(code_bytes(self.N, frames, "packed"), np.uint8)
+        _lib.check(_lib.load().ldpc_encode(self._h, src.ctypes.data, src.size, out.ctypes.data, out.size))
+        return out
+
+    def encode_device(self, src_ptr, src_nbytes, frames, code_ptr, code_nbytes, fmt="bits", stream=None):
+        """Buffers already in HBM (integers, e.g. a torch tensor's data_ptr()); enqueued on `stream`, no wait."""
+        _lib.check(_lib.load().ldpc_encode_device(self._h, src_ptr, int(src_nbytes), int(frames), code_ptr,
+                                                  int(code_nbytes), CODE_FORMATS.get(fmt, fmt), stream))
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None and _lib._lib is not None:
+            _lib.check(_lib._lib.ldpc_encoder_destroy(h))
 
     def __del__(self):
         try:

@@ -36,6 +36,7 @@ Coder::Coder(int ldpcK, int ldpcN, enum rate_type rate)
 Coder::~Coder()
 {
     for (auto &kv : decoders) ldpc_decoder_destroy(kv.second);
+    if (encoder) ldpc_encoder_destroy(encoder);
     if (graph) ldpc_graph_destroy(graph);
 }
 
@@ -87,9 +88,29 @@ int Coder::getCodeSize(int srcLength) { return (srcLength + (ldpcK / 8) - 1) / (
  * 802.16e seeds have a weight-3 parity block column (rows 0, x, mb-1; equal
  * outer shifts, middle shift 0) followed by a dual diagonal, which solves in
  * O(E): p1 = sum of all block rows of A s, then forward substitution. */
+void Coder::setEncodeOnDevice(bool on) { encodeOnDevice = on; }
+
+int Coder::makeGraph()
+{
+    if (graph) return LDPC_SUCCESS;
+    int rc = ldpc_graph_create(rows.data(), cols.data(), nonZeros, ldpcM, ldpcN, &graph);
+    return rc ? fail(rc, ldpc_last_error()) : LDPC_SUCCESS;
+}
+
 int Coder::forEncoder()
 {
     if (!hSeed) return fail(LDPC_ERR_STATE, "Coder was not constructed");
+    if (encodeOnDevice) {
+        /* the device encoder recognises the parity structure from the graph (any middle shift of the weight-3
+         * column): no host precompute.  4096 frames per launch group */
+        if (int rc = makeGraph()) return rc;
+        if (!encoder) {
+            int rc = ldpc_encoder_create(graph, ldpcK, z, 4096, device, &encoder);
+            if (rc) return fail(rc, ldpc_last_error());
+        }
+        isEncoder = true;
+        return LDPC_SUCCESS;
+    }
     const int mb = seedRowLength, kb = kSeedCols - mb;
     structured = true;
     encX = -1;
@@ -149,6 +170,10 @@ int Coder::encode(char *srcCode, char *priorCode, int srcLength)
 {
     if (!isEncoder) return fail(LDPC_ERR_STATE, "encode: call forEncoder() first");
     if (!srcCode || !priorCode || srcLength <= 0) return fail(LDPC_ERR_ARG, "encode: bad arguments");
+    if (encodeOnDevice && encoder) {
+        int rc = ldpc_encode(encoder, (const uint8_t *)srcCode, srcLength, (uint8_t *)priorCode, getPriorCodeLength(srcLength));
+        return rc ? fail(rc, ldpc_last_error()) : LDPC_SUCCESS;
+    }
     /* frames [0, last]: frame `offset` starts at byte offset*K/8 and is the last one once (offset+1)*K/8 >= srcLength
      * (:557-565).  The frames are independent and encodeOnce only reads the object: large payloads are spread over host
      * threads, contiguous frame ranges each (4096 frames of the (64800, 32400) code: 41 ms on one core). */
@@ -291,10 +316,7 @@ int Coder::forDecoder(int batchSize)
     if (!hSeed) return fail(LDPC_ERR_STATE, "Coder was not constructed");
     if (batchSize <= 0) return fail(LDPC_ERR_ARG, "forDecoder: batchSize must be positive");
     this->batchSize = batchSize;
-    if (!graph) {
-        int rc = ldpc_graph_create(rows.data(), cols.data(), nonZeros, ldpcM, ldpcN, &graph);
-        if (rc) return fail(rc, ldpc_last_error());
-    }
+    if (int rc = makeGraph()) return rc;
     isDecoder = true;
     return LDPC_SUCCESS;
 }

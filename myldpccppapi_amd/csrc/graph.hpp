@@ -1,0 +1,25 @@
+/*
+ * graph.hpp -- what the translation units of the host driver share: the graph behind an
+ * `ldpc_graph *` and the setter of the calling thread's ldpc_last_error() message.
+ */
+#pragma once
+
+#include <stdint.h>
+
+#include <vector>
+
+struct ldpc_graph {
+    int32_t M = 0, N = 0;
+    int64_t E = 0;
+    std::vector<int32_t> rows, cols;        /* [E] hRows, hCols           */
+    std::vector<int32_t> row_ptr;           /* [M+1] hRowRange            */
+    std::vector<int32_t> col_ptr, col_edge; /* CSC, edges ascending       */
+    int32_t max_row_deg = 0, max_col_deg = 0;
+};
+
+namespace ldpc {
+
+/* stores the formatted message for ldpc_last_error() and returns `code` (ldpc_hip.hip) */
+int set_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+
+}  // namespace ldpc

@@ -47,6 +47,7 @@
 #include "channel_kernels.hpp"
 #include "tune.hpp"
 #include "host_stage.hpp"
+#include "graph.hpp"
 
 #ifndef LDPC_IDLE_FAT
 #define LDPC_IDLE_FAT 8
@@ -113,14 +114,18 @@ template <typename T> struct DevBuf {
 
 /* ------------------------------------------------------------------ graph */
 
-struct ldpc_graph {
-    int32_t M = 0, N = 0;
-    int64_t E = 0;
-    std::vector<int32_t> rows, cols;        /* [E] hRows, hCols           */
-    std::vector<int32_t> row_ptr;           /* [M+1] hRowRange            */
-    std::vector<int32_t> col_ptr, col_edge; /* CSC, edges ascending       */
-    int32_t max_row_deg = 0, max_col_deg = 0;
-};
+/* struct ldpc_graph: graph.hpp (shared with encoder.hip) */
+
+int ldpc::set_error(int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
 
 /* ---------------------------------------------------------------- decoder */
 

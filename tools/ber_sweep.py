@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """BER / FER versus SNR on the GPU, in the reference's convention (Test.cpp:56-57):
-BPSK +-1, sd = 10^(-SNR_dB/20), all-zero codeword (valid for every linear code), channel values
+BPSK +-1, sd = 10^(-SNR_dB/20), all-zero codeword (valid for every linear code; --payload random: random source
+bytes drawn on the device and encoded there by ldpc_encode_device, which also sees a decoder that is biased towards 0), channel values
 generated in HBM by ldpc_awgn_device (counter-based noise, csrc/ldpc_channel.h: frame f of batch
 b is frame b*frames + f of the seed's stream, so a point can be extended or re-run on any rank)
 and errors counted by ldpc_count_errors_device; nothing crosses PCIe but the counts.  The
 reference counts differing BYTES (Test.cpp:105-110); this prints byte errors too.
 
     python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N>] [--algo sp|ms|layered]
-                              [--snr=1.0,1.5,...]  (write --snr=-0.5,0 for a list that starts with a minus) [--frames 4096] [--iters 50]
+                              [--payload zero|random] [--snr=1.0,1.5,...]  (write --snr=-0.5,0 for a list that starts with a minus) [--frames 4096] [--iters 50]
 The DVB-S2 / BG1 codes are PROFILE SURROGATES (codes.py): the numbers are not the standards'."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -27,6 +28,8 @@ ap.add_argument("--batches", type=int, default=1, help="batches of --frames per 
 ap.add_argument("--seed", type=int, default=20260101)
 ap.add_argument("--ms-scale", type=float, default=0.0, help="normalized min-sum factor (ms / layered; 0 = off)")
 ap.add_argument("--ms-offset", type=float, default=0.0, help="offset min-sum offset, units of y (0 = off)")
+ap.add_argument("--payload", choices=("zero", "random"), default="zero",
+                help="random: source bytes drawn on the device, encoded by ldpc_encode_device, errors counted against them")
 args = ap.parse_args()
 
 layer = 0
@@ -55,13 +58,32 @@ it = torch.empty(B, dtype=torch.int32, device="cuda")
 from myldpccppapi_amd import channel
 import time
 y = torch.empty((B, N), dtype=torch.float32, device="cuda")
-print("code=%s algo=%s ms_scale=%g ms_offset=%g frames=%d x %d max_iter=%d (info bits per point: %d)" % (
-    args.code, args.algo, args.ms_scale, args.ms_offset, B, args.batches, args.iters, B * K * args.batches))
+enc = src = code = None
+if args.payload == "random":
+    assert K % 8 == 0, "--payload random compares whole bytes per frame: K % 8 must be 0"
+    enc = L.Encoder(g, K, layer, max_frames=B)
+    src = torch.empty(B * K // 8, dtype=torch.uint8, device="cuda")
+    code = torch.empty((B, N), dtype=torch.uint8, device="cuda")
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(args.seed)
+
+
+def channel_batch(first, sd, seed):
+    """Channel values of one batch into y; with a random payload: fresh source bytes -> code bits -> BPSK + noise."""
+    if enc is not None:
+        src.random_(0, 256, generator=gen)
+        enc.encode_device(src.data_ptr(), src.numel(), B, code.data_ptr(), code.numel(), "bits",
+                          torch.cuda.current_stream().cuda_stream)
+    channel.awgn_device(N, first, B, sd, seed=seed, codewords=code, out=y)
+
+
+print("code=%s algo=%s payload=%s ms_scale=%g ms_offset=%g frames=%d x %d max_iter=%d (info bits per point: %d)" % (
+    args.code, args.algo, args.payload, args.ms_scale, args.ms_offset, B, args.batches, args.iters, B * K * args.batches))
 points = [float(x) for x in args.snr.split(",")]
 # one untimed batch first: the first launch of every kernel (the library's and torch's) pays one-time costs
-channel.awgn_device(N, 0, B, 10.0 ** (-points[-1] / 20.0), seed=args.seed + 1, out=y)
+channel_batch(0, 10.0 ** (-points[-1] / 20.0), args.seed + 1)
 dec.decode_device(y.data_ptr(), B, out.data_ptr(), out.numel(), it.data_ptr(), None)
-channel.count_errors_device(out, None, B)
+channel.count_errors_device(out, src, B)
 float(it.float().sum())
 torch.cuda.synchronize()
 for snr in points:
@@ -70,9 +92,9 @@ for snr in points:
     it_sum, conv = 0.0, 0
     t0 = time.perf_counter()
     for b in range(args.batches):
-        channel.awgn_device(N, b * B, B, sd, seed=args.seed, out=y)
+        channel_batch(b * B, sd, args.seed)
         dec.decode_device(y.data_ptr(), B, out.data_ptr(), out.numel(), it.data_ptr(), None)
-        e = channel.count_errors_device(out, None, B)
+        e = channel.count_errors_device(out, src, B)
         tot = [t + x for t, x in zip(tot, e)]
         it_sum += float(it.float().sum())
         conv += dec.stats()["frames_converged"]
