@@ -31,6 +31,8 @@
  *     defaults and can be changed with setMaxIterations()/setLlrScale().
  *   - setDevices(): one Coder over several GPUs (the reference uses devices[0] only).
  *   - setEncodeOnDevice(): encode() on the GPU (the "encoder" section of ldpc_hip.h) instead of the host.
+ *   - setRateMatch(): puncturing, filler bits and a circular-buffer transmission of E bits per frame around
+ *     encode() / decode() (the "rate matching" section of ldpc_hip.h).
  */
 #ifndef MYLDPC_H_
 #define MYLDPC_H_
@@ -97,6 +99,16 @@ public:
      * parity part the host solves by dense elimination only (rate_3_4_b: any N, where the host path stops at
      * M > 8192).  Off by default.  Before forEncoder(). */
     void setEncodeOnDevice(bool on);
+    /* Rate matching (ldpc_hip.h, "rate matching"): code bits [0, punctured) are never sent, code bits
+     * [fillerLo, fillerHi) are known zeros (the caller keeps those source bits zero) and are not sent either, and each
+     * frame sends E bits of the circular buffer from position k0 on (E above the buffer's length repeats).  Then
+     * encode() writes E / 8 bytes per frame (E % 8 == 0), test() and decode() take E floats per frame, and
+     * getPriorCodeLength / getPostCodeLength follow; getCodeSize is the frame count as before.  erasureLlr: what
+     * decode() feeds the decoder at positions that were not received -- 0, or the distinct-value rule of ldpc_hip.h:
+     * pass 1e-6 with DecodeTDMP / DecodeTDMPCL, whose layered arithmetic cannot take an exact 0.  Host buffers go
+     * through ldpc_rate_match / ldpc_rate_recover on the GPU `setDevice` names.  Off by default: without this call every
+     * byte and length is as in the reference.  Before forEncoder() and forDecoder().  Returns 0 or an ldpc_status. */
+    int setRateMatch(int E, int k0, int punctured = 0, int fillerLo = 0, int fillerHi = 0, float erasureLlr = 0);
     int lastIterations() const { return lastTime; }             /* the reference's "Time=" */
     const char *lastError() const { return err.c_str(); }
     int getNonZeros() const { return nonZeros; }
@@ -135,6 +147,9 @@ private:
     bool structured;
 
     bool encodeOnDevice = false;     /* setEncodeOnDevice() */
+    int rmE = 0, rmK0 = 0;           /* setRateMatch(); rmE = 0: off */
+    ldpc_rate_spec rmSpec = {};
+    int encodeFrames(char *srcCode, char *priorCode, int srcLength);
     ldpc_encoder *encoder = nullptr; /* forEncoder() with encodeOnDevice */
     int makeGraph();
 

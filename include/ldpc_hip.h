@@ -372,6 +372,67 @@ int ldpc_encode(ldpc_encoder *e, const uint8_t *src_host, int64_t src_bytes, uin
 /* bytes of `frames` codewords in `format` (0 for an unknown format, or LDPC_CODE_PACKED with N % 8 != 0) */
 int64_t ldpc_code_bytes(int32_t N, int64_t frames, int32_t format);
 
+/* ---- rate matching: puncturing, shortening (filler bits), repetition and HARQ soft combining between the encoder and
+ *      the decoders, for data that stays in HBM.  The reference has no counterpart: it sends whole mother codewords.
+ * Spec: plain parameters -- no handle, no device state; the index map is closed-form.
+ * Buffer: the circular buffer is code bits [P, N) in order, Ncb = N - P positions, fillers included (TS 38.212
+ *   section 5.4.2.1 without the bit interleaver and without a limited buffer).  L = Ncb - (hi - lo) >= 1 of them can be
+ *   sent.  A transmission is (k0, E), 0 <= k0 < Ncb, E >= 1: walk the buffer from position k0, wrap at Ncb, skip
+ *   fillers (a k0 on a filler starts at the next non-filler), emit E bits; E > L repeats.  In closed form
+ *       r0 = k0 - clamp(k0 - (lo - P), 0, hi - lo),  rank(e) = (r0 + e) mod L,
+ *       index(e) = P + rank + (rank >= lo - P ? hi - lo : 0).
+ *   filler_lo == filler_hi means no fillers (the common value is then ignored).
+ * Match:   tx[f][e] = code[f][index(e)].
+ * Recover: for every frame f and code bit n
+ *       s = accumulate ? soft[f][n] : 0.0f;  s += rx[f][e] for every e with index(e) = n, in ASCENDING e
+ *       (fp32, no reassociation: the result is bit-defined; a gather, no atomics);  fillers: s = 0;
+ *       soft[f][n] = s                                             (if a soft buffer is given)
+ *       y[f][n] = fill_llr at fillers, else s if s != 0.0f, else
+ *                 erasure_llr > 0 ? erasure_llr * (1.0f + (float)n / (float)N) : 0.0f      (fp32, IEEE divide)
+ *   `soft` holds pure sums of everything received so far (HARQ: first transmission accumulate = 0, retransmissions
+ *   accumulate = 1 with their own k0 / E; the sums stay exact because the erasure values never enter them); `y` is
+ *   what a decoder reads.  soft and y must not overlap.  Conventions of the channel values as for ldpc_decode:
+ *   positive <-> bit 0, so a filler (a known zero) reads +fill_llr.
+ * The erasure rule -- why erasure_llr exists.  A position that was never received (punctured, or not reached by a
+ *   short transmission) carries no information: 0.  The layered arithmetic the project reproduces from the reference
+ *   cannot take an exact 0: a check row's sign is the running product of its inputs (a *= tmp with the message sign
+ *   taken from tmp), so one input of exactly 0 zeroes every message of its row for good, and two erased columns of
+ *   EQUAL tiny magnitude cancel back to exactly 0 in the layered update.  With erased = 0 LDPC_ALGO_LAYERED fails on
+ *   every frame that has a punctured column; the flooding decoders (LDPC_ALGO_SP, LDPC_ALGO_MS) handle zeros.  Small,
+ *   pairwise DISTINCT positive values repair the layered decoders completely (DESIGN.md has the figures):
+ *   erasure_llr = 1e-6 is the recommended value whenever a layered decoder reads y; it is harmless for SP and MS.
+ *   With LDPC_MSG_F16 messages the values collapse to a few fp16 levels and stop being distinct -- the flooding
+ *   decoders, the only ones with fp16 messages, do not need the rule.  erasure_llr > 0 needs N <= 2^22 (beyond that
+ *   the values are no longer pairwise distinct in fp32): LDPC_ERR_ARG.
+ * Formats are enum ldpc_code_format for code and tx alike: LDPC_CODE_PACKED needs N % 8 == 0 on the code side and
+ *   E % 8 == 0 on the tx side (E/8 bytes per frame, LSB first); tx in LDPC_CODE_BITS is exactly what
+ *   ldpc_awgn_device(..., N = E, ...) takes as bits_dev, and rx is what it writes.
+ * The *_device calls enqueue on `stream` (a hipStream_t, NULL = default stream), return without waiting and allocate
+ *   nothing.  ldpc_rate_match / ldpc_rate_recover take host buffers, block, and run the same kernels over chunks of
+ *   frames (device scratch is allocated and released inside the call).  There is no CPU path.
+ * ldpc_rate_index is host-only arithmetic (no device is touched): index_out[e] = index(e) for e < E.
+ * Every argument error is LDPC_ERR_ARG with a message that names the field. */
+typedef struct ldpc_rate_spec {
+    uint32_t struct_size;          /* = sizeof(ldpc_rate_spec); ABI guard                                              */
+    int32_t  N;                    /* mother code length (columns of H)                                                */
+    int32_t  punctured;            /* P: code bits [0, P) are never transmitted (NR: 2Z)                               */
+    int32_t  filler_lo, filler_hi; /* code bits [lo, hi) are known zeros, never transmitted; P <= lo <= hi <= N       */
+    float    fill_llr;             /* decoder input at fillers (init: 10; SP needs llr_scale * fill_llr < 88)          */
+    float    erasure_llr;          /* eps: 0 = erased positions read 0.0f; > 0 = the distinct-value rule above         */
+} ldpc_rate_spec;
+void ldpc_rate_spec_init(ldpc_rate_spec *spec, int32_t N);   /* no puncturing, no fillers, fill_llr 10, erasure_llr 0 */
+int ldpc_rate_lengths(const ldpc_rate_spec *spec, int32_t *Ncb, int32_t *L);
+int ldpc_rate_index(const ldpc_rate_spec *spec, int32_t k0, int32_t E, int32_t *index_out);
+int ldpc_rate_match_device(const ldpc_rate_spec *spec, const uint8_t *code_dev, int32_t code_format, int64_t frames, int32_t k0,
+                           int32_t E, uint8_t *tx_dev, int64_t tx_bytes, int32_t tx_format, int32_t device, void *stream);
+/* soft_dev: nullable, read when accumulate != 0, written; y_dev: nullable; at least one of the two; accumulate needs soft_dev */
+int ldpc_rate_recover_device(const ldpc_rate_spec *spec, const float *rx_dev, int64_t frames, int32_t k0, int32_t E, float *soft_dev,
+                             int32_t accumulate, float *y_dev, int32_t device, void *stream);
+int ldpc_rate_match(const ldpc_rate_spec *spec, const uint8_t *code_host, int32_t code_format, int64_t frames, int32_t k0, int32_t E,
+                    uint8_t *tx_host, int64_t tx_bytes, int32_t tx_format, int32_t device);
+int ldpc_rate_recover(const ldpc_rate_spec *spec, const float *rx_host, int64_t frames, int32_t k0, int32_t E, float *soft_host,
+                      int32_t accumulate, float *y_host, int32_t device);
+
 /* ---- measurement aid: the rate a plain float4 copy of `bytes` bytes (read + write counted)
  *      sustains on `device` right now, best of `reps` launches each with the default cache policy
  *      and with non-temporal loads and stores (the streaming kernels' policy), HIP-event timed on

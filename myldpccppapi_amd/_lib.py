@@ -56,6 +56,13 @@ class KernelTime(ctypes.Structure):
                 ("bytes_moved", ctypes.c_int64)]
 
 
+class RateSpec(ctypes.Structure):
+    """Mirror of `ldpc_rate_spec`."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("N", ctypes.c_int32), ("punctured", ctypes.c_int32),
+                ("filler_lo", ctypes.c_int32), ("filler_hi", ctypes.c_int32),
+                ("fill_llr", ctypes.c_float), ("erasure_llr", ctypes.c_float)]
+
+
 #: every symbol include/ldpc_hip.h declares
 EXPORTS = (
     "ldpc_abi_version", "ldpc_last_error", "ldpc_device_count", "ldpc_graph_create",
@@ -65,6 +72,8 @@ EXPORTS = (
     "ldpc_decoder_dump", "ldpc_awgn_device", "ldpc_count_errors_device", "ldpc_hbm_probe_device", "ldpc_hbm_sustained_device",
     "ldpc_host_block_plan", "ldpc_host_locked_ranges", "ldpc_decoder_link_form", "ldpc_decoder_placement", "ldpc_decoder_array_addresses",
     "ldpc_parity_structure", "ldpc_encoder_create", "ldpc_encoder_destroy", "ldpc_encode_device", "ldpc_encode", "ldpc_code_bytes",
+    "ldpc_rate_spec_init", "ldpc_rate_lengths", "ldpc_rate_index", "ldpc_rate_match_device", "ldpc_rate_recover_device",
+    "ldpc_rate_match", "ldpc_rate_recover",
 )
 
 
@@ -130,6 +139,19 @@ def load():
     L.ldpc_encode.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64]
     L.ldpc_code_bytes.argtypes = [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]
     L.ldpc_code_bytes.restype = ctypes.c_int64
+    rsp = ctypes.POINTER(RateSpec)
+    L.ldpc_rate_spec_init.argtypes = [rsp, ctypes.c_int32]
+    L.ldpc_rate_spec_init.restype = None
+    L.ldpc_rate_lengths.argtypes = [rsp, i32p, i32p]
+    L.ldpc_rate_index.argtypes = [rsp, ctypes.c_int32, ctypes.c_int32, vp]
+    L.ldpc_rate_match_device.argtypes = [rsp, vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, vp,
+                                         ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, vp]
+    L.ldpc_rate_recover_device.argtypes = [rsp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp,
+                                           ctypes.c_int32, vp]
+    L.ldpc_rate_match.argtypes = [rsp, vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, vp,
+                                  ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
+    L.ldpc_rate_recover.argtypes = [rsp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp,
+                                    ctypes.c_int32]
     _lib = L
     return L
 

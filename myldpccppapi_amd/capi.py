@@ -332,3 +332,68 @@ class Encoder:
             self.close()
         except Exception:
             pass
+
+
+class RateMatcher:
+    """Rate matching between the encoder and the decoders (ldpc_rate_*, include/ldpc_hip.h): puncturing of the first
+    `punctured` code bits, filler bits [filler[0], filler[1]) that are known zeros, a transmission (k0, E) read from the
+    circular buffer, repetition for E > L and soft combining of retransmissions.  A plain parameter set: no handle.
+    erasure_llr: 0 = never-received positions read 0.0; 1e-6 whenever a layered decoder reads `y` (the header says why)."""
+
+    def __init__(self, N, punctured=0, filler=(0, 0), fill_llr=10.0, erasure_llr=0.0, device=0):
+        L = _lib.load()
+        self.spec = _lib.RateSpec()
+        L.ldpc_rate_spec_init(ctypes.byref(self.spec), int(N))
+        self.spec.punctured = int(punctured)
+        self.spec.filler_lo, self.spec.filler_hi = int(filler[0]), int(filler[1])
+        self.spec.fill_llr, self.spec.erasure_llr = float(fill_llr), float(erasure_llr)
+        self.N, self.device = int(N), int(device)
+        self.lengths()      # an unusable spec fails here
+
+    def lengths(self):
+        """(Ncb, L): circular-buffer positions and the transmittable ones among them."""
+        ncb, l = ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(_lib.load().ldpc_rate_lengths(ctypes.byref(self.spec), ctypes.byref(ncb), ctypes.byref(l)))
+        return ncb.value, l.value
+
+    def index(self, k0, E):
+        """int32 [E]: the code bit behind each transmitted position (host arithmetic only)."""
+        out = np.zeros(max(int(E), 0), np.int32)
+        _lib.check(_lib.load().ldpc_rate_index(ctypes.byref(self.spec), int(k0), int(E), out.ctypes.data))
+        return out
+
+    # -- buffers already in HBM (integers, e.g. a torch tensor's data_ptr()); enqueued on `stream`, no wait --------
+    def match_device(self, code_ptr, frames, k0, E, tx_ptr, tx_nbytes, code_fmt="bits", tx_fmt="bits", stream=None):
+        _lib.check(_lib.load().ldpc_rate_match_device(ctypes.byref(self.spec), code_ptr, CODE_FORMATS.get(code_fmt, code_fmt),
+                                                      int(frames), int(k0), int(E), tx_ptr, int(tx_nbytes),
+                                                      CODE_FORMATS.get(tx_fmt, tx_fmt), self.device, stream))
+
+    def recover_device(self, rx_ptr, frames, k0, E, soft_ptr=None, accumulate=False, y_ptr=None, stream=None):
+        _lib.check(_lib.load().ldpc_rate_recover_device(ctypes.byref(self.spec), rx_ptr, int(frames), int(k0), int(E), soft_ptr,
+                                                        int(bool(accumulate)), y_ptr, self.device, stream))
+
+    # -- host buffers (numpy); blocking ---------------------------------------------------------------------------
+    def match(self, code, k0, E, code_fmt="bits", tx_fmt="bits"):
+        """code: uint8 [frames, N] (bits) or [frames, N/8] (packed) -> uint8 [frames, E] or [frames, E/8]."""
+        per_in = self.N if code_fmt == "bits" else self.N // 8
+        code = np.ascontiguousarray(code, np.uint8).reshape(-1, per_in)
+        frames = code.shape[0]
+        per_out = int(E) if tx_fmt == "bits" else int(E) // 8
+        tx = np.zeros((frames, max(per_out, 0)), np.uint8)
+        _lib.check(_lib.load().ldpc_rate_match(ctypes.byref(self.spec), code.ctypes.data, CODE_FORMATS.get(code_fmt, code_fmt), frames,
+                                               int(k0), int(E), tx.ctypes.data, tx.size, CODE_FORMATS.get(tx_fmt, tx_fmt), self.device))
+        return tx
+
+    def recover(self, rx, k0, E, soft=None, want_y=True):
+        """rx: float32 [frames, E].  soft: None, or float32 [frames, N] that is accumulated into IN PLACE.
+        Returns (soft, y); without `soft` the sums of this transmission alone are returned as a new array."""
+        rx = np.ascontiguousarray(rx, np.float32).reshape(-1, int(E))
+        frames = rx.shape[0]
+        accumulate = soft is not None
+        if soft is None:
+            soft = np.zeros((frames, self.N), np.float32)
+        assert soft.dtype == np.float32 and soft.flags.c_contiguous and soft.size == frames * self.N
+        y = np.zeros((frames, self.N), np.float32) if want_y else None
+        _lib.check(_lib.load().ldpc_rate_recover(ctypes.byref(self.spec), rx.ctypes.data, frames, int(k0), int(E), soft.ctypes.data,
+                                                 int(accumulate), None if y is None else y.ctypes.data, self.device))
+        return soft, y

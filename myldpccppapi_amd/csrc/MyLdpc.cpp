@@ -74,9 +74,9 @@ int Coder::initCheckMatrix()
     return LDPC_SUCCESS;
 }
 
-/* Length helpers, MyLdpc.cpp:620-631. */
-int Coder::getPriorCodeLength(int srcLength) { return (srcLength + (ldpcK / 8) - 1) / (ldpcK / 8) * (ldpcN / 8); }
-int Coder::getPostCodeLength(int srcLength) { return (srcLength + (ldpcK / 8) - 1) / (ldpcK / 8) * ldpcN; }
+/* Length helpers, MyLdpc.cpp:620-631; with setRateMatch(): E transmitted bits per frame take the place of the N code bits. */
+int Coder::getPriorCodeLength(int srcLength) { return getCodeSize(srcLength) * ((rmE ? rmE : ldpcN) / 8); }
+int Coder::getPostCodeLength(int srcLength) { return getCodeSize(srcLength) * (rmE ? rmE : ldpcN); }
 int Coder::getCodeSize(int srcLength) { return (srcLength + (ldpcK / 8) - 1) / (ldpcK / 8); }
 
 /* ----------------------------------------------------------------- encoder */
@@ -89,6 +89,26 @@ int Coder::getCodeSize(int srcLength) { return (srcLength + (ldpcK / 8) - 1) / (
  * outer shifts, middle shift 0) followed by a dual diagonal, which solves in
  * O(E): p1 = sum of all block rows of A s, then forward substitution. */
 void Coder::setEncodeOnDevice(bool on) { encodeOnDevice = on; }
+
+/* Rate matching (the "rate matching" section of ldpc_hip.h) around encode() and decode(): host buffers through
+ * ldpc_rate_match / ldpc_rate_recover; the fast path is the device chain of the C ABI. */
+int Coder::setRateMatch(int E, int k0, int punctured, int fillerLo, int fillerHi, float erasureLlr)
+{
+    ldpc_rate_spec spec;
+    ldpc_rate_spec_init(&spec, ldpcN);
+    spec.punctured = punctured;
+    spec.filler_lo = fillerLo;
+    spec.filler_hi = fillerHi;
+    spec.erasure_llr = erasureLlr;
+    int32_t Ncb = 0, L = 0;
+    if (int rc = ldpc_rate_lengths(&spec, &Ncb, &L)) return fail(rc, ldpc_last_error());
+    if (E < 8 || E % 8) return fail(LDPC_ERR_ARG, "setRateMatch: E must be a positive multiple of 8 (encode() writes whole bytes)");
+    if (k0 < 0 || k0 >= Ncb) return fail(LDPC_ERR_ARG, "setRateMatch: k0 outside the circular buffer [0, N - punctured)");
+    rmSpec = spec;
+    rmE = E;
+    rmK0 = k0;
+    return LDPC_SUCCESS;
+}
 
 int Coder::makeGraph()
 {
@@ -170,8 +190,21 @@ int Coder::encode(char *srcCode, char *priorCode, int srcLength)
 {
     if (!isEncoder) return fail(LDPC_ERR_STATE, "encode: call forEncoder() first");
     if (!srcCode || !priorCode || srcLength <= 0) return fail(LDPC_ERR_ARG, "encode: bad arguments");
+    if (!rmE) return encodeFrames(srcCode, priorCode, srcLength);
+    /* the mother codewords go to a buffer of their own, the caller receives E / 8 bytes per frame */
+    const int frames = getCodeSize(srcLength);
+    std::vector<char> mother((size_t)frames * (ldpcN / 8));
+    if (int rc = encodeFrames(srcCode, mother.data(), srcLength)) return rc;
+    const int rc = ldpc_rate_match(&rmSpec, (const uint8_t *)mother.data(), LDPC_CODE_PACKED, frames, rmK0, rmE,
+                                   (uint8_t *)priorCode, (int64_t)frames * (rmE / 8), LDPC_CODE_PACKED, device);
+    return rc ? fail(rc, ldpc_last_error()) : LDPC_SUCCESS;
+}
+
+/* whole codewords: N / 8 bytes per frame */
+int Coder::encodeFrames(char *srcCode, char *priorCode, int srcLength)
+{
     if (encodeOnDevice && encoder) {
-        int rc = ldpc_encode(encoder, (const uint8_t *)srcCode, srcLength, (uint8_t *)priorCode, getPriorCodeLength(srcLength));
+        int rc = ldpc_encode(encoder, (const uint8_t *)srcCode, srcLength, (uint8_t *)priorCode, (int64_t)getCodeSize(srcLength) * (ldpcN / 8));
         return rc ? fail(rc, ldpc_last_error()) : LDPC_SUCCESS;
     }
     /* frames [0, last]: frame `offset` starts at byte offset*K/8 and is the last one once (offset+1)*K/8 >= srcLength
@@ -408,6 +441,14 @@ int Coder::decode(float *postCode, char *srcCode, int srcLength, enum decodeType
         auto it = decoders.find((int)deType);
         if (it == decoders.end()) return fail(LDPC_ERR_STATE, "decode: addDecodeType() was not called for this type");
         d = it->second;
+    }
+    std::vector<float> recovered;
+    if (rmE) {
+        /* E received values per frame -> the N channel values the decoder reads */
+        recovered.resize((size_t)codeSize * ldpcN);
+        int rm = ldpc_rate_recover(&rmSpec, postCode, codeSize, rmK0, rmE, nullptr, 0, recovered.data(), device);
+        if (rm) return fail(rm, ldpc_last_error());
+        postCode = recovered.data();
     }
     int rc = ldpc_decode(d, postCode, codeSize, (uint8_t *)srcCode, srcLength, nullptr);
     if (rc) return fail(rc, ldpc_last_error());

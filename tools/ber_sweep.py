@@ -8,7 +8,11 @@ and errors counted by ldpc_count_errors_device; nothing crosses PCIe but the cou
 reference counts differing BYTES (Test.cpp:105-110); this prints byte errors too.
 
     python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N>] [--algo sp|ms|layered]
-                              [--payload zero|random] [--snr=1.0,1.5,...]  (write --snr=-0.5,0 for a list that starts with a minus) [--frames 4096] [--iters 50]
+                              [--payload zero|random] [--rate-match P,FLO,FHI,E[,K0]] [--erasure-llr X] [--snr=1.0,1.5,...]  (write --snr=-0.5,0 for a list that starts with a minus) [--frames 4096] [--iters 50]
+--rate-match: code bits [0, P) punctured, [FLO, FHI) filler bits (known zeros; multiples of 8, inside the information part),
+E bits per frame sent from circular-buffer position K0 (default 0): ldpc_rate_match_device between the encoder and the
+channel, ldpc_rate_recover_device between the channel and the decoder -- the whole chain stays in HBM.  --erasure-llr 1e-6
+whenever --algo layered reads punctured or unsent positions (include/ldpc_hip.h, "the erasure rule").
 The DVB-S2 / BG1 codes are PROFILE SURROGATES (codes.py): the numbers are not the standards'."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -30,6 +34,8 @@ ap.add_argument("--ms-scale", type=float, default=0.0, help="normalized min-sum 
 ap.add_argument("--ms-offset", type=float, default=0.0, help="offset min-sum offset, units of y (0 = off)")
 ap.add_argument("--payload", choices=("zero", "random"), default="zero",
                 help="random: source bytes drawn on the device, encoded by ldpc_encode_device, errors counted against them")
+ap.add_argument("--rate-match", default=None, metavar="P,FLO,FHI,E[,K0]", help="puncture [0,P), fillers [FLO,FHI), send E bits from K0")
+ap.add_argument("--erasure-llr", type=float, default=0.0, help="decoder input at positions that were not received (0, or 1e-6 for layered)")
 args = ap.parse_args()
 
 layer = 0
@@ -66,17 +72,40 @@ if args.payload == "random":
     code = torch.empty((B, N), dtype=torch.uint8, device="cuda")
     gen = torch.Generator(device="cuda")
     gen.manual_seed(args.seed)
+rm = tx = rx = None
+rate = K / N
+if args.rate_match:
+    rmv = [int(x) for x in args.rate_match.split(",")]
+    P, FLO, FHI, E = rmv[:4]
+    K0 = rmv[4] if len(rmv) > 4 else 0
+    assert FLO % 8 == 0 and FHI % 8 == 0 and FLO <= FHI <= K, "--rate-match: FLO and FHI are multiples of 8 inside the information part"
+    rm = L.RateMatcher(N, punctured=P, filler=(FLO, FHI), erasure_llr=args.erasure_llr)
+    rx = torch.empty((B, E), dtype=torch.float32, device="cuda")
+    if enc is not None:
+        tx = torch.empty((B, E), dtype=torch.uint8, device="cuda")
+    rate = (K - (FHI - FLO)) / E
 
 
 def channel_batch(first, sd, seed):
     """Channel values of one batch into y; with a random payload: fresh source bytes -> code bits -> BPSK + noise."""
+    stream = torch.cuda.current_stream().cuda_stream
     if enc is not None:
         src.random_(0, 256, generator=gen)
-        enc.encode_device(src.data_ptr(), src.numel(), B, code.data_ptr(), code.numel(), "bits",
-                          torch.cuda.current_stream().cuda_stream)
-    channel.awgn_device(N, first, B, sd, seed=seed, codewords=code, out=y)
+        if rm is not None:
+            src.view(B, K // 8)[:, FLO // 8:FHI // 8] = 0          # filler bits are known zeros
+        enc.encode_device(src.data_ptr(), src.numel(), B, code.data_ptr(), code.numel(), "bits", stream)
+    if rm is None:
+        channel.awgn_device(N, first, B, sd, seed=seed, codewords=code, out=y)
+        return
+    if enc is not None:
+        rm.match_device(code.data_ptr(), B, K0, E, tx.data_ptr(), tx.numel(), "bits", "bits", stream)
+    channel.awgn_device(E, first, B, sd, seed=seed, codewords=tx, out=rx)
+    rm.recover_device(rx.data_ptr(), B, K0, E, None, False, y.data_ptr(), stream)
 
 
+if rm is not None:
+    print("rate matching: punctured=%d fillers=[%d,%d) E=%d k0=%d erasure_llr=%g effective rate (K - fillers)/E = %.4f" % (
+        P, FLO, FHI, E, K0, args.erasure_llr, rate))
 print("code=%s algo=%s payload=%s ms_scale=%g ms_offset=%g frames=%d x %d max_iter=%d (info bits per point: %d)" % (
     args.code, args.algo, args.payload, args.ms_scale, args.ms_offset, B, args.batches, args.iters, B * K * args.batches))
 points = [float(x) for x in args.snr.split(",")]
