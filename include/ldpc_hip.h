@@ -257,7 +257,24 @@ int ldpc_decode(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
 
 /* Same, on buffers already resident in this decoder's device memory; enqueued on
  * `stream` (a hipStream_t, NULL = default stream), returns without waiting unless
- * poll_interval > 0.  frames <= max_batch.  iters_dev nullable. */
+ * poll_interval > 0.  0 <= frames <= max_batch (frames == 0 enqueues nothing).
+ *   llr_dev:   frames * N floats; rows behind them (up to max_batch) are not part of the call.
+ *   out_dev:   nullable: iteration counts and stats only.  Otherwise out_bytes bytes, of which the first
+ *              min(out_bytes, ldpc_out_bytes(K, frames, pack_mode)) are written (LDPC_PACK_BYTES: a short buffer
+ *              truncates, bytes from out_bytes on stay as they were; the bits between frames with K % 8 != 0
+ *              read 0.  LDPC_PACK_BITS: a short buffer is LDPC_ERR_ARG).  out_bytes < 0 is LDPC_ERR_ARG, with or
+ *              without out_dev.
+ *   iters_dev: nullable; frames counts.  Written by every engine whether or not out_dev is given.
+ *   With out_dev == NULL the call still decodes: it writes iters_dev (if given) and what ldpc_decoder_stats
+ *   reports (iterations, batch_time, frames, frames_converged, frame_rounds); with out_dev == NULL and
+ *   iters_dev == NULL the stats alone.
+ *   A call refused with LDPC_ERR_ARG has enqueued nothing.
+ * Device pointers, here and in every *_device entry point below:
+ *   - float and int32 buffers (llr_dev, iters_dev, the rate matcher's rx_dev / soft_dev / y_dev) need their natural
+ *     4-byte alignment and no more: the kernels take their 16-byte paths only where the address allows;
+ *   - byte buffers (out_dev, bits_dev, ref_dev, src_dev, code_dev, tx_dev) may have any alignment;
+ *   - a call reads and writes nothing outside [ptr, ptr + size) of the buffers it is given, size being what the call
+ *     states for `frames` frames -- not for max_batch. */
 int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, uint8_t *out_dev,
                        int64_t out_bytes, int32_t *iters_dev, void *stream);
 

@@ -219,6 +219,7 @@ class Decoder:
 
     # -- buffers already in HBM ----------------------------------------------
     def decode_device(self, llr_ptr, frames, out_ptr, out_nbytes, iters_ptr=None, stream=None):
+        """ldpc_decode_device: out_ptr None = iteration counts and stats() only; iters_ptr None = bytes only."""
         _lib.check(_lib.load().ldpc_decode_device(self._h, llr_ptr, frames, out_ptr, out_nbytes,
                                                   iters_ptr, stream))
 

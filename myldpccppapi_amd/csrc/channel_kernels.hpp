@@ -33,7 +33,9 @@ __global__ __launch_bounds__(256) void awgn_kernel(float *__restrict__ llr, cons
         const int bit = (bits && n < N) ? (bits[base + i] & 1) : 0;
         v[i] = ldpc_ch_sample(bit, sd, z[i]);
     }
-    if ((N & 3) == 0) {
+    /* the 16-byte store only where every group is 16-byte aligned (as init_kernel's loads): llr is a float *,
+     * 4-byte alignment is all the caller owes */
+    if ((N & 3) == 0 && (reinterpret_cast<uintptr_t>(llr) & 15) == 0) {
         *reinterpret_cast<float4 *>(llr + base) = float4{v[0], v[1], v[2], v[3]};
     } else {
 #pragma unroll

@@ -1973,7 +1973,7 @@ template <int V> __global__ __launch_bounds__(kBlock) void tail_scatter_kernel(c
 
 struct PackArgs {
     const uint64_t *__restrict__ hard;  /* [T][N][V] */
-    uint8_t *__restrict__ out;
+    uint8_t *__restrict__ out;          /* nullptr: no bytes are stored (iteration counts only) */
     const int32_t *__restrict__ iters_tile; /* [T][F] */
     int32_t *__restrict__ iters_out;    /* [frames] or nullptr */
     int64_t frames;
@@ -2008,6 +2008,7 @@ template <int V> __global__ __launch_bounds__(kBlock) void pack_kernel(const Pac
                 if (frame < a.frames) a.iters_out[frame] = a.iters_tile[frame];
             }
         }
+        if (!a.out) return;                 /* iteration counts only */
         const int unit = (int)blockIdx.x * kWavesPerBlock + wave_id_in_block();
         const int v = unit % V;
         const int j = (unit / V) * 64 + (threadIdx.x & 63);
@@ -2028,7 +2029,7 @@ template <int V> __global__ __launch_bounds__(kBlock) void pack_kernel(const Pac
     } else {
         const int64_t ob = (int64_t)blockIdx.x * kBlock + threadIdx.x;
         if (ob < a.frames && a.iters_out) a.iters_out[ob] = a.iters_tile[ob];
-        if (ob >= a.out_bytes) return;
+        if (!a.out || ob >= a.out_bytes) return;
         unsigned byte = 0;
         for (int b = 0; b < 8; ++b) {
             const int64_t bit = ob * 8 + b;

@@ -325,7 +325,7 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
     }
     *launched = rounds;
     PackArgs pa{r.hard, r.out_dev, r.iters, r.iters_dev, r.frames, r.out_bytes, pl->N, r.K, r.pack_mode};
-    if (r.out_dev) {
+    if (r.out_dev || r.iters_dev) {     /* the pack launch carries the iteration counts too (out_dev NULL: out_bytes is 0) */
         if (r.pack_mode == 0) {
             pack_kernel<V><<<pack_grid<V>(r.K, tiles), kBlock, 0, s>>>(pa);
         } else {

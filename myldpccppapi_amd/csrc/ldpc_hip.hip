@@ -753,12 +753,14 @@ template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t
     {
         PackArgs pa{d->hard.p, out_dev, d->iters.p, iters_dev, frames, out_bytes, d->N, d->cfg.K,
                     d->cfg.pack_mode};
+        /* the pack launch also carries the iteration counts out: it runs for either buffer (out_dev NULL: out_bytes is 0) */
+        const bool pack = (out_dev || iters_dev) && frames;
         if (d->cfg.pack_mode == LDPC_PACK_BYTES) {
-            if (out_dev && frames) pack_kernel<V><<<pack_grid<V>(d->cfg.K, tiles), kBlock, 0, s>>>(pa);
+            if (pack) pack_kernel<V><<<pack_grid<V>(d->cfg.K, tiles), kBlock, 0, s>>>(pa);
         } else {
             const int64_t n = std::max<int64_t>(out_bytes, frames);
             dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-            if (out_dev && frames) pack_kernel<V><<<grid, kBlock, 0, s>>>(pa);
+            if (pack) pack_kernel<V><<<grid, kBlock, 0, s>>>(pa);
         }
         /* after the final state_kernel `done` marks exactly the converged frames */
         summary_kernel<V><<<(unsigned)((frames + 255) / 256), 256, 0, s>>>(
@@ -1613,9 +1615,12 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
     if (frames < 0 || frames > d->cfg.max_batch)
         return fail(LDPC_ERR_ARG, "frames=%lld outside [0, max_batch=%d]", (long long)frames,
                     d->cfg.max_batch);
+    if (out_bytes < 0) return fail(LDPC_ERR_ARG, "out_bytes < 0");
     if (frames == 0) { d->last_frames = 0; d->have_last = false; return LDPC_OK; }
     if (!llr_dev) return fail(LDPC_ERR_ARG, "llr is NULL");
     const int64_t need = ldpc_out_bytes(d->cfg.K, frames, d->cfg.pack_mode);
+    /* bytes this call may store: none without out_dev (iteration counts and stats only) */
+    const int64_t room = out_dev ? std::min(out_bytes, need) : 0;
     if (out_dev && out_bytes < need && d->cfg.pack_mode == LDPC_PACK_BITS)
         return fail(LDPC_ERR_ARG, "out_bytes=%lld < %lld", (long long)out_bytes, (long long)need);
     HIP_TRY(hipSetDevice(d->cfg.device));
@@ -1626,10 +1631,10 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
     d->call.valid = false;          /* ldpc_decode() sets it again once all its groups are in */
     HIP_TRY(hipEventRecord(d->ev_begin, s));
     /* gaps between frames (K % 8 != 0, decodeCL.c:191-192 leaves them alone) read as 0 */
-    if (out_dev) HIP_TRY(hipMemsetAsync(out_dev, 0, (size_t)std::min(out_bytes, need), s));
+    if (out_dev) HIP_TRY(hipMemsetAsync(out_dev, 0, (size_t)room, s));
     int rc;
     if (d->use_fused) {
-        ldpc::FusedRun run{llr_dev, frames, out_dev, std::min(out_bytes, need), iters_dev, d->cfg.K,
+        ldpc::FusedRun run{llr_dev, frames, out_dev, room, iters_dev, d->cfg.K,
                            d->cfg.max_iter, d->tap_iter, d->cfg.early_term, d->summary.p,
                            d->cfg.algo == LDPC_ALGO_MS_FUSED ? 1 : (d->cfg.algo == LDPC_ALGO_MS ? 2 : (d->cfg.algo == LDPC_ALGO_SP ? 3 : 0)),
                            d->cfg.llr_scale, ldpc::tune_pick(d->tune.fused_loop, false) ? 1 : 0,
@@ -1648,7 +1653,7 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
         run.span_end = [](void *c, hipStream_t st) { return span_end((ldpc_decoder *)c, st); };
         run.span_ctx = d;
         run.llr_dev = llr_dev; run.frames = frames; run.out_dev = out_dev;
-        run.out_bytes = std::min(out_bytes, need); run.iters_dev = iters_dev;
+        run.out_bytes = room; run.iters_dev = iters_dev;
         run.K = d->cfg.K; run.max_iter = d->cfg.max_iter; run.tap_iter = d->tap_iter;
         run.early_term = d->cfg.early_term; run.pack_mode = d->cfg.pack_mode;
         run.hard = d->hard.p; run.failw = d->failw.p; run.done = d->done.p; run.iters = d->iters.p;
@@ -1656,9 +1661,9 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
         hipError_t e = ldpc::engine_layered_run(&d->layered, run, s, &d->last_iterations);
         rc = (e == hipSuccess) ? LDPC_OK
                                : fail(LDPC_ERR_HIP, "layered decode: %s", hipGetErrorString(e));
-    } else if (d->V == 1) rc = run_flooding<1>(d, llr_dev, frames, out_dev, std::min(out_bytes, need), iters_dev, s);
-    else if (d->V == 2) rc = run_flooding<2>(d, llr_dev, frames, out_dev, std::min(out_bytes, need), iters_dev, s);
-    else rc = run_flooding<4>(d, llr_dev, frames, out_dev, std::min(out_bytes, need), iters_dev, s);
+    } else if (d->V == 1) rc = run_flooding<1>(d, llr_dev, frames, out_dev, room, iters_dev, s);
+    else if (d->V == 2) rc = run_flooding<2>(d, llr_dev, frames, out_dev, room, iters_dev, s);
+    else rc = run_flooding<4>(d, llr_dev, frames, out_dev, room, iters_dev, s);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(d->ev_end, s));
     d->have_last = true;
