@@ -33,6 +33,7 @@
  *   - setEncodeOnDevice(): encode() on the GPU (the "encoder" section of ldpc_hip.h) instead of the host.
  *   - setRateMatch(): puncturing, filler bits and a circular-buffer transmission of E bits per frame around
  *     encode() / decode() (the "rate matching" section of ldpc_hip.h).
+ *   - setModulation(): test() sends QPSK / 16- / 64- / 256-QAM symbols through the "modem" section of ldpc_hip.h.
  */
 #ifndef MYLDPC_H_
 #define MYLDPC_H_
@@ -109,6 +110,15 @@ public:
      * through ldpc_rate_match / ldpc_rate_recover on the GPU `setDevice` names.  Off by default: without this call every
      * byte and length is as in the reference.  Before forEncoder() and forDecoder().  Returns 0 or an ldpc_status. */
     int setRateMatch(int E, int k0, int punctured = 0, int fillerLo = 0, int fillerHi = 0, float erasureLlr = 0);
+    /* Modulation of test() (ldpc_hip.h, "modem"): Qm = 1 (BPSK), 2 (QPSK), 4, 6 or 8 (16-, 64-, 256-QAM) bits per symbol,
+     * with or without the bit interleaver of TS 38.212.  test() then maps each frame's bits -- E per frame with
+     * setRateMatch(), N otherwise; they must be a multiple of Qm -- to symbols of unit mean energy, adds noise of standard
+     * deviation `rate` PER REAL DIMENSION from the counter-based generator (its seed is drawn from two rand() calls, so
+     * srand() still governs it) and writes the max-log demapped values into postCode: same length as without the call, so
+     * decode(), getPostCodeLength() and callers are unchanged.  Runs on the GPU `setDevice` names (ldpc_modem_transmit +
+     * ldpc_modem_demap).  DecodeSP reads values of very unequal reliability then: setLlrScale(2 / (rate * rate)).
+     * Off by default: without this call every byte is as in the reference.  Returns 0 or an ldpc_status. */
+    int setModulation(int Qm, bool interleave = true);
     int lastIterations() const { return lastTime; }             /* the reference's "Time=" */
     const char *lastError() const { return err.c_str(); }
     int getNonZeros() const { return nonZeros; }
@@ -149,6 +159,7 @@ private:
     bool encodeOnDevice = false;     /* setEncodeOnDevice() */
     int rmE = 0, rmK0 = 0;           /* setRateMatch(); rmE = 0: off */
     ldpc_rate_spec rmSpec = {};
+    ldpc_modem_spec modSpec = {};    /* setModulation(); Qm = 0: off */
     int encodeFrames(char *srcCode, char *priorCode, int srcLength);
     ldpc_encoder *encoder = nullptr; /* forEncoder() with encodeOnDevice */
     int makeGraph();

@@ -450,6 +450,65 @@ int ldpc_rate_match(const ldpc_rate_spec *spec, const uint8_t *code_host, int32_
 int ldpc_rate_recover(const ldpc_rate_spec *spec, const float *rx_host, int64_t frames, int32_t k0, int32_t E, float *soft_host,
                       int32_t accumulate, float *y_host, int32_t device);
 
+/* ---- modem: bit interleaver, Gray mapper, AWGN channel and max-log demapper for QPSK and 16-, 64-, 256-QAM (and the
+ *      reference's BPSK), between ldpc_rate_match_device and ldpc_rate_recover_device, for data that stays in HBM.  The
+ *      reference has no counterpart: Coder::test sends one real +-1 sample per code bit.
+ * Spec: plain parameters -- no handle, no device state.  Qm in {1, 2, 4, 6, 8} bits per symbol; a transmission of E bits
+ *   per frame needs E % Qm == 0 and has S = E / Qm symbols.  A frame's row of symbols holds ldpc_modem_symbol_floats
+ *   floats: E real samples for Qm = 1, else 2 S (I0 Q0 I1 Q1 ...).  ldpc_modem_spec_init sets interleave = (Qm >= 2).
+ * Interleaver (TS 38.212 section 5.4.2.2): bit i (0 <= i < Qm) of symbol j is tx bit
+ *       e(i, j) = interleave ? i * S + j : j * Qm + i
+ *   (Qm = 1: e = j either way).  ldpc_modem_index is host-only arithmetic: index_out[j * Qm + i] = e(i, j).
+ * Mapper (TS 38.211 section 5.1, Gray): with m = Qm / 2 the I axis takes the symbol's bits c0, c1, ... = b0, b2, ...,
+ *   the Q axis b1, b3, ....  The integer level of an axis is
+ *       amp_0 = 0,  amp_k(c0, c1, ...) = (1 - 2 c0) * (2^(k-1) - amp_(k-1)(c1, ...))         level = amp_m
+ *   ((1 - 2 b0) [2 - (1 - 2 b2)] for 16-QAM, and so on): the odd integers in +-(2^m - 1), neighbours differ in one bit.
+ *       x = (float)amp * A,  A = (float)(1.0 / sqrt((double)norm)),  norm = 2, 10, 42, 170 for Qm = 2, 4, 6, 8
+ *   (one fp32 multiply).  Qm = 1: x = 1 - 2 b exactly, one real sample per bit -- the reference's BPSK.
+ *   ldpc_modem_points is host-only: the 2^Qm points, the one of label v = sum b_i 2^(Qm-1-i) at iq[2v], iq[2v+1]
+ *   (Qm = 1: (1, 0) and (-1, 0)).
+ * Channel: real sample n of frame f (n = 2 j for I and 2 j + 1 for Q of symbol j; n = e for Qm = 1) is
+ *       r = (float)((double)x + (double)sd * z(seed, first_frame + f, n))
+ *   with z the counter-based normal of csrc/ldpc_channel.h: component n % 4 of ldpc_ch_normal4(seed, frame, n / 4).  With
+ *   Qm = 1 this is ldpc_ch_sample: the call reproduces ldpc_awgn_device bit for bit.  sd == 0 writes x itself and does not
+ *   run the generator; sd < 0, NaN or inf is LDPC_ERR_ARG.  For Qm >= 2 the symbols have unit mean energy and sd is the
+ *   standard deviation PER REAL DIMENSION, so Es/N0 = 1 / (2 sd^2); for Qm = 1 (one real dimension of energy 1) the
+ *   reference's convention holds, Es/N0 = 1 / (2 sd^2) as well.
+ * Demapper (max-log; fp32, no contraction, no knowledge of sd): per axis value r and axis bit k
+ *       D_b = min over the 2^(m-1) levels x_j whose bit k is b of (r - x_j) * (r - x_j),     y = (D_1 - D_0) * 0.25f
+ *   written to rx[f][e(i, j)], i.e. de-interleaved.  The x_j are the mapper's fp32 values; min is exact, so the result is
+ *   bit-defined whatever order the minima are taken in.  Qm = 1: y = r.  y is in the decoders' units of channel values:
+ *   positive <-> bit 0, the true max-log LLR is 2 y / sd^2 (for QPSK y = r A).  It is what ldpc_rate_recover_device takes
+ *   as rx_dev, and what a decoder takes directly when E = N.  The values of one symbol's bits differ widely in
+ *   reliability: LDPC_ALGO_SP then wants llr_scale = 2 / sd^2 instead of the reference's constant 8 (DESIGN.md has the
+ *   figures), with llr_scale * |y| below the fp32 exp limit of 88.  Inputs must be finite (not checked).  sym and rx
+ *   must not overlap (LDPC_ERR_ARG); neither may tx and sym.
+ * tx_format is LDPC_CODE_BITS or LDPC_CODE_PACKED, the two forms ldpc_rate_match_device writes (packed: E % 8 == 0).
+ *   sym_floats is the capacity of sym; less than frames * ldpc_modem_symbol_floats is LDPC_ERR_ARG.
+ * The *_device calls enqueue on `stream` (a hipStream_t, NULL = default stream), return without waiting and allocate
+ *   nothing; frames == 0 enqueues nothing.  ldpc_modem_transmit / ldpc_modem_demap take host buffers, block, and run the
+ *   same kernels over chunks of frames (device scratch is allocated and released inside the call).  There is no CPU path.
+ *   The pointer rules of ldpc_decode_device apply: sym_dev and rx_dev need 4-byte alignment and no more, tx_dev none.
+ * Every argument error is LDPC_ERR_ARG with a message that names the field. */
+typedef struct ldpc_modem_spec {
+    uint32_t struct_size;          /* = sizeof(ldpc_modem_spec); ABI guard                                              */
+    int32_t  Qm;                   /* bits per symbol: 1 (BPSK, real), 2 (QPSK), 4, 6, 8 (16-, 64-, 256-QAM)            */
+    int32_t  interleave;           /* 1: the bit interleaver of TS 38.212 section 5.4.2.2; 0: a symbol takes Qm consecutive bits */
+} ldpc_modem_spec;
+void ldpc_modem_spec_init(ldpc_modem_spec *spec, int32_t Qm);
+/* floats per frame of symbols; 0 (and a message) for a spec or E the other calls refuse */
+int64_t ldpc_modem_symbol_floats(const ldpc_modem_spec *spec, int32_t E);
+int ldpc_modem_index(const ldpc_modem_spec *spec, int32_t E, int32_t *index_out);
+int ldpc_modem_points(int32_t Qm, float *iq);
+int ldpc_modem_transmit_device(const ldpc_modem_spec *spec, const uint8_t *tx_dev, int32_t tx_format, int64_t frames, int32_t E,
+                               float sd, uint64_t seed, int64_t first_frame, float *sym_dev, int64_t sym_floats, int32_t device,
+                               void *stream);
+int ldpc_modem_demap_device(const ldpc_modem_spec *spec, const float *sym_dev, int64_t frames, int32_t E, float *rx_dev,
+                            int32_t device, void *stream);
+int ldpc_modem_transmit(const ldpc_modem_spec *spec, const uint8_t *tx_host, int32_t tx_format, int64_t frames, int32_t E, float sd,
+                        uint64_t seed, int64_t first_frame, float *sym_host, int64_t sym_floats, int32_t device);
+int ldpc_modem_demap(const ldpc_modem_spec *spec, const float *sym_host, int64_t frames, int32_t E, float *rx_host, int32_t device);
+
 /* ---- measurement aid: the rate a plain float4 copy of `bytes` bytes (read + write counted)
  *      sustains on `device` right now, best of `reps` launches each with the default cache policy
  *      and with non-temporal loads and stores (the streaming kernels' policy), HIP-event timed on

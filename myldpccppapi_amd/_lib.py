@@ -63,6 +63,11 @@ class RateSpec(ctypes.Structure):
                 ("fill_llr", ctypes.c_float), ("erasure_llr", ctypes.c_float)]
 
 
+class ModemSpec(ctypes.Structure):
+    """Mirror of `ldpc_modem_spec`."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("Qm", ctypes.c_int32), ("interleave", ctypes.c_int32)]
+
+
 #: every symbol include/ldpc_hip.h declares
 EXPORTS = (
     "ldpc_abi_version", "ldpc_last_error", "ldpc_device_count", "ldpc_graph_create",
@@ -74,6 +79,8 @@ EXPORTS = (
     "ldpc_parity_structure", "ldpc_encoder_create", "ldpc_encoder_destroy", "ldpc_encode_device", "ldpc_encode", "ldpc_code_bytes",
     "ldpc_rate_spec_init", "ldpc_rate_lengths", "ldpc_rate_index", "ldpc_rate_match_device", "ldpc_rate_recover_device",
     "ldpc_rate_match", "ldpc_rate_recover",
+    "ldpc_modem_spec_init", "ldpc_modem_symbol_floats", "ldpc_modem_index", "ldpc_modem_points", "ldpc_modem_transmit_device",
+    "ldpc_modem_demap_device", "ldpc_modem_transmit", "ldpc_modem_demap",
 )
 
 
@@ -152,6 +159,19 @@ def load():
                                   ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
     L.ldpc_rate_recover.argtypes = [rsp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32, vp,
                                     ctypes.c_int32]
+    msp = ctypes.POINTER(ModemSpec)
+    L.ldpc_modem_spec_init.argtypes = [msp, ctypes.c_int32]
+    L.ldpc_modem_spec_init.restype = None
+    L.ldpc_modem_symbol_floats.argtypes = [msp, ctypes.c_int32]
+    L.ldpc_modem_symbol_floats.restype = ctypes.c_int64
+    L.ldpc_modem_index.argtypes = [msp, ctypes.c_int32, vp]
+    L.ldpc_modem_points.argtypes = [ctypes.c_int32, vp]
+    L.ldpc_modem_transmit_device.argtypes = [msp, vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_uint64,
+                                             ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int32, vp]
+    L.ldpc_modem_demap_device.argtypes = [msp, vp, ctypes.c_int64, ctypes.c_int32, vp, ctypes.c_int32, vp]
+    L.ldpc_modem_transmit.argtypes = [msp, vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_uint64,
+                                      ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int32]
+    L.ldpc_modem_demap.argtypes = [msp, vp, ctypes.c_int64, ctypes.c_int32, vp, ctypes.c_int32]
     _lib = L
     return L
 

@@ -1,4 +1,4 @@
-"""Thin Python objects over the C ABI (include/ldpc_hip.h): Graph, Decoder and Encoder.
+"""Thin Python objects over the C ABI (include/ldpc_hip.h): Graph, Decoder, Encoder, RateMatcher and Modem.
 
 Host-side plumbing only -- every decode runs in the HIP kernels of
 libldpc_hip.so.  numpy arrays are passed as host pointers, integers (e.g. a
@@ -398,3 +398,66 @@ class RateMatcher:
         _lib.check(_lib.load().ldpc_rate_recover(ctypes.byref(self.spec), rx.ctypes.data, frames, int(k0), int(E), soft.ctypes.data,
                                                  int(accumulate), None if y is None else y.ctypes.data, self.device))
         return soft, y
+
+
+class Modem:
+    """The modem stage between RateMatcher.match and RateMatcher.recover (ldpc_modem_*, include/ldpc_hip.h): bit
+    interleaver, Gray mapper (Qm = 1: the reference's BPSK, 2: QPSK, 4 / 6 / 8: 16-, 64-, 256-QAM at unit mean energy),
+    AWGN of standard deviation `sd` per real dimension from the counter-based generator, and the max-log demapper, whose
+    output is in the decoders' units (true LLR = 2 y / sd^2; a sum-product decoder wants llr_scale = 2 / sd^2).
+    interleave: None = the library's default (on for Qm >= 2).  A plain parameter set: no handle."""
+
+    def __init__(self, Qm, interleave=None, device=0):
+        L = _lib.load()
+        self.spec = _lib.ModemSpec()
+        L.ldpc_modem_spec_init(ctypes.byref(self.spec), int(Qm))
+        if interleave is not None:
+            self.spec.interleave = int(bool(interleave))
+        self.Qm, self.device = int(Qm), int(device)
+        self.points()       # an unusable Qm fails here
+
+    def symbol_floats(self, E):
+        """Floats of one frame's row of symbols: E for Qm = 1, else 2 E / Qm."""
+        n = int(_lib.load().ldpc_modem_symbol_floats(ctypes.byref(self.spec), int(E)))
+        if n == 0:
+            _lib.check(1)
+        return n
+
+    def index(self, E):
+        """int32 [E]: entry j * Qm + i is the tx bit that becomes bit i of symbol j (host arithmetic only)."""
+        out = np.zeros(max(int(E), 0), np.int32)
+        _lib.check(_lib.load().ldpc_modem_index(ctypes.byref(self.spec), int(E), out.ctypes.data))
+        return out
+
+    def points(self):
+        """float32 [2^Qm, 2]: (I, Q) of every label v = sum b_i 2^(Qm-1-i)."""
+        out = np.zeros((1 << max(min(self.Qm, 8), 0), 2), np.float32)
+        _lib.check(_lib.load().ldpc_modem_points(self.Qm, out.ctypes.data))
+        return out
+
+    # -- buffers already in HBM (integers, e.g. a torch tensor's data_ptr()); enqueued on `stream`, no wait --------
+    def transmit_device(self, tx_ptr, frames, E, sd, seed, sym_ptr, sym_floats, first_frame=0, tx_fmt="bits", stream=None):
+        _lib.check(_lib.load().ldpc_modem_transmit_device(ctypes.byref(self.spec), tx_ptr, CODE_FORMATS.get(tx_fmt, tx_fmt), int(frames),
+                                                          int(E), float(sd), int(seed), int(first_frame), sym_ptr, int(sym_floats),
+                                                          self.device, stream))
+
+    def demap_device(self, sym_ptr, frames, E, rx_ptr, stream=None):
+        _lib.check(_lib.load().ldpc_modem_demap_device(ctypes.byref(self.spec), sym_ptr, int(frames), int(E), rx_ptr, self.device, stream))
+
+    # -- host buffers (numpy); blocking ---------------------------------------------------------------------------
+    def transmit(self, tx, sd, seed, first_frame=0, tx_fmt="bits"):
+        """tx: uint8 [frames, E] (bits) or [frames, E/8] (packed) -> float32 [frames, symbol_floats(E)]."""
+        tx = np.ascontiguousarray(tx, np.uint8)
+        assert tx.ndim == 2
+        frames, E = tx.shape[0], tx.shape[1] * (1 if tx_fmt == "bits" else 8)
+        sym = np.zeros((frames, self.symbol_floats(E)), np.float32)
+        _lib.check(_lib.load().ldpc_modem_transmit(ctypes.byref(self.spec), tx.ctypes.data, CODE_FORMATS.get(tx_fmt, tx_fmt), frames, E,
+                                                   float(sd), int(seed), int(first_frame), sym.ctypes.data, sym.size, self.device))
+        return sym
+
+    def demap(self, sym, E):
+        """sym: float32 [frames, symbol_floats(E)] -> float32 [frames, E], de-interleaved."""
+        sym = np.ascontiguousarray(sym, np.float32).reshape(-1, self.symbol_floats(E))
+        rx = np.zeros((sym.shape[0], int(E)), np.float32)
+        _lib.check(_lib.load().ldpc_modem_demap(ctypes.byref(self.spec), sym.ctypes.data, sym.shape[0], int(E), rx.ctypes.data, self.device))
+        return rx

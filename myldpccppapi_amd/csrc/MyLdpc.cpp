@@ -110,6 +110,18 @@ int Coder::setRateMatch(int E, int k0, int punctured, int fillerLo, int fillerHi
     return LDPC_SUCCESS;
 }
 
+/* Modulation of test() (the "modem" section of ldpc_hip.h) */
+int Coder::setModulation(int Qm, bool interleave)
+{
+    ldpc_modem_spec spec;
+    ldpc_modem_spec_init(&spec, Qm);
+    spec.interleave = interleave ? 1 : 0;
+    const int bits = rmE ? rmE : ldpcN;
+    if (ldpc_modem_symbol_floats(&spec, bits) == 0) return fail(LDPC_ERR_ARG, std::string("setModulation: ") + ldpc_last_error());
+    modSpec = spec;
+    return LDPC_SUCCESS;
+}
+
 int Coder::makeGraph()
 {
     if (graph) return LDPC_SUCCESS;
@@ -475,6 +487,20 @@ float gaussian(float ave, float sd)
 int Coder::test(char *priorCode, float *postCode, int priorCodeLength, float rate)
 {
     if (!priorCode || !postCode || priorCodeLength < 0) return fail(LDPC_ERR_ARG, "test: bad arguments");
+    if (modSpec.Qm) {
+        /* symbols through the modem stage on the device; the demapped values take the place of the +-1 samples */
+        const int bits = rmE ? rmE : ldpcN;
+        const int64_t row = ldpc_modem_symbol_floats(&modSpec, bits);
+        if (row == 0) return fail(LDPC_ERR_ARG, std::string("test: ") + ldpc_last_error());
+        if (priorCodeLength % (bits / 8)) return fail(LDPC_ERR_ARG, "test: priorCodeLength is not a whole number of frames");
+        const int64_t frames = priorCodeLength / (bits / 8);
+        const uint64_t hi = (uint64_t)(unsigned)rand(), lo = (uint64_t)(unsigned)rand();
+        std::vector<float> sym((size_t)(frames * row));
+        int rc = ldpc_modem_transmit(&modSpec, (const uint8_t *)priorCode, LDPC_CODE_PACKED, frames, bits, rate, (hi << 32) | lo, 0,
+                                     sym.data(), (int64_t)sym.size(), device);
+        if (!rc) rc = ldpc_modem_demap(&modSpec, sym.data(), frames, bits, postCode, device);
+        return rc ? fail(rc, ldpc_last_error()) : LDPC_SUCCESS;
+    }
     for (int c = 0; c < priorCodeLength; ++c)
         for (int b = 0; b < 8; ++b)
             postCode[c * 8 + b] = (priorCode[c] & (1 << b)) ? -1.0f : 1.0f;

@@ -8,11 +8,19 @@ and errors counted by ldpc_count_errors_device; nothing crosses PCIe but the cou
 reference counts differing BYTES (Test.cpp:105-110); this prints byte errors too.
 
     python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N>] [--algo sp|ms|layered]
-                              [--payload zero|random] [--rate-match P,FLO,FHI,E[,K0]] [--erasure-llr X] [--snr=1.0,1.5,...]  (write --snr=-0.5,0 for a list that starts with a minus) [--frames 4096] [--iters 50]
+                              [--payload zero|random] [--rate-match P,FLO,FHI,E[,K0]] [--erasure-llr X]
+                              [--modulation bpsk|qpsk|qam16|qam64|qam256] [--no-interleave] [--snr=1.0,1.5,...]  (write --snr=-0.5,0 for a list that starts with a minus) [--frames 4096] [--iters 50]
 --rate-match: code bits [0, P) punctured, [FLO, FHI) filler bits (known zeros; multiples of 8, inside the information part),
 E bits per frame sent from circular-buffer position K0 (default 0): ldpc_rate_match_device between the encoder and the
 channel, ldpc_rate_recover_device between the channel and the decoder -- the whole chain stays in HBM.  --erasure-llr 1e-6
 whenever --algo layered reads punctured or unsent positions (include/ldpc_hip.h, "the erasure rule").
+--modulation: the ldpc_awgn_device step becomes ldpc_modem_transmit_device + ldpc_modem_demap_device (include/ldpc_hip.h,
+"modem"): the bits of a frame (E with --rate-match, else N; a multiple of the bits per symbol) travel as symbols of unit
+mean energy, sd = 10^(-SNR_dB/20) is the noise PER REAL DIMENSION, and every point also prints Es/N0 = 1/(2 sd^2) and
+Eb/N0 = Es/N0 / (bits per symbol x rate).  --no-interleave switches the bit interleaver of TS 38.212 off.  With --algo sp
+the decoder's llr_scale follows the noise, 2 / sd^2 per point (and the fillers read min(10, 80 / llr_scale)), unless
+--llr-scale is given.  From 16-QAM up use --payload random: the all-zero codeword sends one corner point only, and the
+bits of a QAM symbol are not equally protected.
 The DVB-S2 / BG1 codes are PROFILE SURROGATES (codes.py): the numbers are not the standards'."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -27,7 +35,7 @@ ap.add_argument("--algo", default="sp")
 ap.add_argument("--snr", default="2.5,3.0,3.5,4.0,4.5,5.0")
 ap.add_argument("--frames", type=int, default=4096)
 ap.add_argument("--iters", type=int, default=50)
-ap.add_argument("--llr-scale", type=float, default=8.0)
+ap.add_argument("--llr-scale", type=float, default=None, help="sum-product channel scale (default 8; with --modulation: 2 / sd^2 per point)")
 ap.add_argument("--batches", type=int, default=1, help="batches of --frames per SNR point")
 ap.add_argument("--seed", type=int, default=20260101)
 ap.add_argument("--ms-scale", type=float, default=0.0, help="normalized min-sum factor (ms / layered; 0 = off)")
@@ -36,7 +44,13 @@ ap.add_argument("--payload", choices=("zero", "random"), default="zero",
                 help="random: source bytes drawn on the device, encoded by ldpc_encode_device, errors counted against them")
 ap.add_argument("--rate-match", default=None, metavar="P,FLO,FHI,E[,K0]", help="puncture [0,P), fillers [FLO,FHI), send E bits from K0")
 ap.add_argument("--erasure-llr", type=float, default=0.0, help="decoder input at positions that were not received (0, or 1e-6 for layered)")
+ap.add_argument("--modulation", choices=("bpsk", "qpsk", "qam16", "qam64", "qam256"), default=None,
+                help="send symbols through ldpc_modem_transmit_device + ldpc_modem_demap_device instead of ldpc_awgn_device")
+ap.add_argument("--no-interleave", action="store_true", help="with --modulation: no bit interleaver")
 args = ap.parse_args()
+assert args.modulation or not args.no_interleave, "--no-interleave needs --modulation"
+QM = {None: 0, "bpsk": 1, "qpsk": 2, "qam16": 4, "qam64": 6, "qam256": 8}[args.modulation]
+matched = bool(QM) and args.algo == "sp" and args.llr_scale is None       # llr_scale = 2 / sd^2 per SNR point
 
 layer = 0
 if args.code == "dvbs2_12":
@@ -57,8 +71,14 @@ else:
 M = N - K
 g = L.Graph(rows, cols, M, N)
 B = args.frames
-dec = L.Decoder(g, K, max_batch=B, algo=args.algo, max_iter=args.iters, llr_scale=args.llr_scale,
-                layer_rows=layer, poll_interval=2, ms_scale=args.ms_scale, ms_offset=args.ms_offset)
+
+
+def make_decoder(llr_scale):
+    return L.Decoder(g, K, max_batch=B, algo=args.algo, max_iter=args.iters, llr_scale=llr_scale,
+                     layer_rows=layer, poll_interval=2, ms_scale=args.ms_scale, ms_offset=args.ms_offset)
+
+
+dec = None if matched else make_decoder(8.0 if args.llr_scale is None else args.llr_scale)
 out = torch.empty(L.out_bytes(K, B), dtype=torch.uint8, device="cuda")
 it = torch.empty(B, dtype=torch.int32, device="cuda")
 from myldpccppapi_amd import channel
@@ -84,6 +104,14 @@ if args.rate_match:
     if enc is not None:
         tx = torch.empty((B, E), dtype=torch.uint8, device="cuda")
     rate = (K - (FHI - FLO)) / E
+md = sym = zeros = None
+if QM:
+    sent = E if rm is not None else N                              # bits per frame on the air
+    assert sent % QM == 0, "--modulation: the %d bits of a frame do not fill symbols of %d bits" % (sent, QM)
+    md = L.Modem(QM, interleave=not args.no_interleave)
+    sym = torch.empty((B, md.symbol_floats(sent)), dtype=torch.float32, device="cuda")
+    if enc is None:
+        zeros = torch.zeros((B, sent), dtype=torch.uint8, device="cuda")
 
 
 def channel_batch(first, sd, seed):
@@ -95,21 +123,50 @@ def channel_batch(first, sd, seed):
             src.view(B, K // 8)[:, FLO // 8:FHI // 8] = 0          # filler bits are known zeros
         enc.encode_device(src.data_ptr(), src.numel(), B, code.data_ptr(), code.numel(), "bits", stream)
     if rm is None:
-        channel.awgn_device(N, first, B, sd, seed=seed, codewords=code, out=y)
+        if md is None:
+            channel.awgn_device(N, first, B, sd, seed=seed, codewords=code, out=y)
+        else:
+            modem_batch(code if enc is not None else zeros, N, first, sd, seed, y, stream)
         return
     if enc is not None:
         rm.match_device(code.data_ptr(), B, K0, E, tx.data_ptr(), tx.numel(), "bits", "bits", stream)
-    channel.awgn_device(E, first, B, sd, seed=seed, codewords=tx, out=rx)
+    if md is None:
+        channel.awgn_device(E, first, B, sd, seed=seed, codewords=tx, out=rx)
+    else:
+        modem_batch(tx if enc is not None else zeros, E, first, sd, seed, rx, stream)
     rm.recover_device(rx.data_ptr(), B, K0, E, None, False, y.data_ptr(), stream)
+
+
+def modem_batch(bits, n, first, sd, seed, dst, stream):
+    """bits uint8 [B, n] -> symbols + noise -> demapped values float32 [B, n] in dst."""
+    md.transmit_device(bits.data_ptr(), B, n, sd, seed, sym.data_ptr(), sym.numel(), first, "bits", stream)
+    md.demap_device(sym.data_ptr(), B, n, dst.data_ptr(), stream)
+
+
+def point_decoder(sd):
+    """The decoder of one SNR point: with the matched scale a new one per point (llr_scale is fixed at creation)."""
+    global dec
+    if not matched:
+        return
+    if dec is not None:
+        dec.close()
+    scale = 2.0 / (sd * sd)
+    if rm is not None:
+        rm.spec.fill_llr = min(10.0, 80.0 / scale)
+    dec = make_decoder(scale)
 
 
 if rm is not None:
     print("rate matching: punctured=%d fillers=[%d,%d) E=%d k0=%d erasure_llr=%g effective rate (K - fillers)/E = %.4f" % (
         P, FLO, FHI, E, K0, args.erasure_llr, rate))
+if md is not None:
+    print("modulation: %s (%d bits per symbol) interleave=%d llr_scale=%s" % (
+        args.modulation, QM, md.spec.interleave, "2/sd^2 per point" if matched else "%g" % (8.0 if args.llr_scale is None else args.llr_scale)))
 print("code=%s algo=%s payload=%s ms_scale=%g ms_offset=%g frames=%d x %d max_iter=%d (info bits per point: %d)" % (
     args.code, args.algo, args.payload, args.ms_scale, args.ms_offset, B, args.batches, args.iters, B * K * args.batches))
 points = [float(x) for x in args.snr.split(",")]
 # one untimed batch first: the first launch of every kernel (the library's and torch's) pays one-time costs
+point_decoder(10.0 ** (-points[-1] / 20.0))
 channel_batch(0, 10.0 ** (-points[-1] / 20.0), args.seed + 1)
 dec.decode_device(y.data_ptr(), B, out.data_ptr(), out.numel(), it.data_ptr(), None)
 channel.count_errors_device(out, src, B)
@@ -117,6 +174,7 @@ float(it.float().sum())
 torch.cuda.synchronize()
 for snr in points:
     sd = 10.0 ** (-snr / 20.0)
+    point_decoder(sd)
     tot = [0, 0, 0]
     it_sum, conv = 0.0, 0
     t0 = time.perf_counter()
@@ -129,7 +187,12 @@ for snr in points:
         conv += dec.stats()["frames_converged"]
     dt = time.perf_counter() - t0
     frames = B * args.batches
-    print(json.dumps({"snr_db": snr, "sd": round(sd, 4), "ber": tot[0] / (frames * K), "bit_errors": tot[0],
-                      "byte_errors": tot[1], "fer": tot[2] / frames, "avg_iters": round(it_sum / frames, 2),
-                      "frames_converged": conv, "frames": frames,
-                      "end_to_end_Mbit_s": round(frames * K / dt / 1e6, 1)}), flush=True)
+    res = {"snr_db": snr, "sd": round(sd, 4), "ber": tot[0] / (frames * K), "bit_errors": tot[0],
+           "byte_errors": tot[1], "fer": tot[2] / frames, "avg_iters": round(it_sum / frames, 2),
+           "frames_converged": conv, "frames": frames,
+           "end_to_end_Mbit_s": round(frames * K / dt / 1e6, 1)}
+    if md is not None:
+        es_n0 = 1.0 / (2.0 * sd * sd)
+        res.update({"es_n0_db": round(10.0 * np.log10(es_n0), 3), "eb_n0_db": round(10.0 * np.log10(es_n0 / (QM * rate)), 3),
+                    "llr_scale": round(2.0 / (sd * sd), 3) if matched else (8.0 if args.llr_scale is None else args.llr_scale)})
+    print(json.dumps(res), flush=True)
