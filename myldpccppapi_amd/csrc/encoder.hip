@@ -12,18 +12,12 @@
 #include "../../include/ldpc_hip.h"
 #include "encoder_kernels.hpp"
 #include "graph.hpp"
+#include "hip_host.hpp"
 
 using ldpc::set_error;
+using ldpc::DevBuf;
 
 namespace {
-
-#define ENC_HIP_TRY(expr)                                                                       \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return set_error(LDPC_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                             __FILE__, __LINE__);                                               \
-    } while (0)
 
 struct ParityStructure {
     int32_t kind = 0, c = 0, x = 0, a = 0, b = 0, ext = 0, z = 0;
@@ -104,30 +98,15 @@ int analyse(const ldpc_graph *g, int32_t K, int32_t z, ParityStructure *ps)
     return LDPC_OK;
 }
 
-template <typename T> struct Dev {
-    T *p = nullptr;
-    Dev() = default;
-    Dev(const Dev &) = delete;
-    Dev &operator=(const Dev &) = delete;
-    hipError_t alloc(size_t count) { return hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T)); }
-    hipError_t upload(const std::vector<T> &h)
-    {
-        hipError_t e = alloc(h.size());
-        if (e != hipSuccess || h.empty()) return e;
-        return hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-    }
-    ~Dev() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace
 
 struct ldpc_encoder {
     int32_t device = 0, N = 0, K = 0, M = 0, max_frames = 0, Wmax = 0, chunks = 0;
     ParityStructure ps;
-    Dev<uint64_t> X;        /* [N][W] bit-sliced codewords                                        */
-    Dev<uint64_t> aux;      /* dual diagonal: lambda of the core rows [c z][W]; staircase: chunk totals */
-    Dev<int32_t> ptr, col;  /* per row: the columns lambda_m (or an extension row's parity bit) sums  */
-    Dev<uint8_t> src_stage, code_stage;   /* ldpc_encode(): made on its first call               */
+    DevBuf<uint64_t> X;        /* [N][W] bit-sliced codewords                                        */
+    DevBuf<uint64_t> aux;      /* dual diagonal: lambda of the core rows [c z][W]; staircase: chunk totals */
+    DevBuf<int32_t> ptr, col;  /* per row: the columns lambda_m (or an extension row's parity bit) sums  */
+    DevBuf<uint8_t> src_stage, code_stage;   /* ldpc_encode(): made on its first call               */
 };
 
 namespace {
@@ -166,7 +145,7 @@ int enqueue(ldpc_encoder *e, const uint8_t *src_dev, int64_t src_bytes, int64_t 
         const int32_t align = ((e->N / 8) % 4 == 0 && at % 4 == 0) ? 4 : 1;
         enc_store_kernel<0><<<grid, kEncBlock, 0, s>>>(X, e->N, W, frames, code_dev, align);
     }
-    ENC_HIP_TRY(hipGetLastError());
+    LDPC_HIP_TRY(hipGetLastError());
     return LDPC_OK;
 }
 
@@ -202,11 +181,7 @@ int ldpc_encoder_create(const ldpc_graph *g, int32_t K, int32_t block_rows, int3
     ParityStructure ps;
     int rc = analyse(g, K, block_rows, &ps);
     if (rc) return rc;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-        return set_error(LDPC_ERR_HIP, "no usable HIP device (the encoder has no CPU fallback)");
-    if (device < 0 || device >= count) return set_error(LDPC_ERR_ARG, "device %d of %d", device, count);
-    ENC_HIP_TRY(hipSetDevice(device));
+    if ((rc = ldpc::use_device(device, "the encoder"))) return rc;
     ldpc_encoder *e = new (std::nothrow) ldpc_encoder;
     if (!e) return set_error(LDPC_ERR_NOMEM, "out of memory");
     e->device = device; e->N = g->N; e->K = K; e->M = g->M; e->max_frames = max_frames; e->ps = ps;
@@ -249,7 +224,7 @@ int ldpc_encoder_destroy(ldpc_encoder *e)
 int ldpc_encode_device(ldpc_encoder *e, const uint8_t *src_dev, int64_t src_bytes, int64_t frames, uint8_t *code_dev,
                        int64_t code_bytes, int32_t format, void *stream)
 {
-    if (format != LDPC_CODE_PACKED && format != LDPC_CODE_BITS) return set_error(LDPC_ERR_ARG, "unknown code format %d", format);
+    if (int rc = ldpc::known_code_format(format, "code format")) return rc;
     if (!e) return set_error(LDPC_ERR_ARG, "encoder is NULL");
     if (!src_dev || !code_dev) return set_error(LDPC_ERR_ARG, "src_dev/code_dev is NULL");
     if (format == LDPC_CODE_PACKED && e->N % 8) return set_error(LDPC_ERR_ARG, "LDPC_CODE_PACKED needs N %% 8 == 0 (N = %d)", e->N);
@@ -261,7 +236,7 @@ int ldpc_encode_device(ldpc_encoder *e, const uint8_t *src_dev, int64_t src_byte
     if (code_bytes < ldpc_code_bytes(e->N, frames, format))
         return set_error(LDPC_ERR_ARG, "code_bytes = %lld, %lld frames need %lld", (long long)code_bytes, (long long)frames,
                          (long long)ldpc_code_bytes(e->N, frames, format));
-    ENC_HIP_TRY(hipSetDevice(e->device));
+    LDPC_HIP_TRY(hipSetDevice(e->device));
     return enqueue(e, src_dev, src_bytes, 0, frames, code_dev, format, (hipStream_t)stream);
 }
 
@@ -279,17 +254,17 @@ int ldpc_encode(ldpc_encoder *e, const uint8_t *src_host, int64_t src_bytes, uin
     const int64_t frames = last + 1;
     if (code_bytes < frames * nb)
         return set_error(LDPC_ERR_ARG, "code_bytes = %lld, %lld frames need %lld", (long long)code_bytes, (long long)frames, (long long)(frames * nb));
-    ENC_HIP_TRY(hipSetDevice(e->device));
-    if (!e->src_stage.p) ENC_HIP_TRY(e->src_stage.alloc((size_t)((int64_t)e->max_frames * K / 8 + K / 8 + 1)));
-    if (!e->code_stage.p) ENC_HIP_TRY(e->code_stage.alloc((size_t)(e->max_frames * nb)));
+    LDPC_HIP_TRY(hipSetDevice(e->device));
+    if (!e->src_stage.p) LDPC_HIP_TRY(e->src_stage.alloc((size_t)((int64_t)e->max_frames * K / 8 + K / 8 + 1)));
+    if (!e->code_stage.p) LDPC_HIP_TRY(e->code_stage.alloc((size_t)(e->max_frames * nb)));
     for (int64_t f0 = 0; f0 < frames; f0 += e->max_frames) {
         const int64_t n = std::min<int64_t>(e->max_frames, frames - f0);
         const int64_t base = f0 * K / 8;
         const int64_t bytes = std::min<int64_t>(src_bytes, (f0 + n - 1) * K / 8 + K / 8) - base;
-        ENC_HIP_TRY(hipMemcpy(e->src_stage.p, src_host + base, (size_t)bytes, hipMemcpyHostToDevice));
+        LDPC_HIP_TRY(hipMemcpy(e->src_stage.p, src_host + base, (size_t)bytes, hipMemcpyHostToDevice));
         const int rc = enqueue(e, e->src_stage.p, bytes, f0, n, e->code_stage.p, LDPC_CODE_PACKED, nullptr);
         if (rc) return rc;
-        ENC_HIP_TRY(hipMemcpy(code_host + f0 * nb, e->code_stage.p, (size_t)(n * nb), hipMemcpyDeviceToHost));
+        LDPC_HIP_TRY(hipMemcpy(code_host + f0 * nb, e->code_stage.p, (size_t)(n * nb), hipMemcpyDeviceToHost));
     }
     return LDPC_OK;
 }

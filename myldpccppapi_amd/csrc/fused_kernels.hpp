@@ -722,27 +722,18 @@ __global__ __launch_bounds__(64 * MW) void fused_sp_kernel(const FusedArgs a)
 struct FusedPlan {
     bool eligible = false;
     int32_t z = 0, layers = 0, N = 0, E = 0, M = 0, max_deg = 0;
-    int32_t *layer_ptr = nullptr, *ent_bc = nullptr, *ent_sh = nullptr, *layer_e0 = nullptr; /* device */
-    int32_t *bcol_ptr = nullptr, *bcol_e0 = nullptr, *bcol_sh = nullptr;
-    int32_t *ent_pack = nullptr;
+    DevBuf<int32_t> layer_ptr, ent_bc, ent_sh, layer_e0;
+    DevBuf<int32_t> bcol_ptr, bcol_e0, bcol_sh;
+    DevBuf<int32_t> ent_pack;
     int32_t pack_w = 0;
-    float *dump_p = nullptr, *dump_r = nullptr, *dump_q = nullptr;
-    uint8_t *conv = nullptr, *dump_b = nullptr;
+    DevBuf<float> dump_p, dump_r, dump_q;       /* made by the first decode with a tap set */
+    DevBuf<uint8_t> dump_b;
     int32_t max_col_deg = 0;
     bool eligible_sp = false;
     size_t lds_sp = 0;
     int64_t dump_frames = 0;
     size_t lds_per_frame = 0;
 };
-
-inline void fused_plan_destroy(FusedPlan *pl)
-{
-    for (void *p : {(void *)pl->layer_ptr, (void *)pl->ent_bc, (void *)pl->ent_sh, (void *)pl->layer_e0,
-                    (void *)pl->bcol_ptr, (void *)pl->bcol_e0, (void *)pl->bcol_sh, (void *)pl->ent_pack,
-                    (void *)pl->dump_p, (void *)pl->dump_r, (void *)pl->conv, (void *)pl->dump_q, (void *)pl->dump_b})
-        if (p) (void)hipFree(p);
-    *pl = FusedPlan();
-}
 
 /* Detect the circulant structure of every layer: all z rows of a layer have the same
  * degree and row r's k-th edge sits in column bc_k*z + (r + s_k) mod z.  Returns true and
@@ -794,14 +785,9 @@ inline hipError_t fused_plan_create(FusedPlan *pl, int32_t M, int32_t N, int64_t
     pl->max_deg = 0;
     for (size_t l = 0; l + 1 < lp.size(); ++l) pl->max_deg = std::max(pl->max_deg, lp[l + 1] - lp[l]);
     pl->lds_per_frame = (size_t)(N + E) * 4;
-    auto up = [](int32_t **dst, const std::vector<int32_t> &v) {
-        hipError_t e = hipMalloc((void **)dst, v.size() * sizeof(int32_t));
-        if (e != hipSuccess) return e;
-        return hipMemcpy(*dst, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    };
     hipError_t e;
-    if ((e = up(&pl->layer_ptr, lp)) || (e = up(&pl->ent_bc, bc)) || (e = up(&pl->ent_sh, sh)) ||
-        (e = up(&pl->layer_e0, e0)))
+    if ((e = pl->layer_ptr.upload(lp)) || (e = pl->ent_bc.upload(bc)) || (e = pl->ent_sh.upload(sh)) ||
+        (e = pl->layer_e0.upload(e0)))
         return e;
     /* padded (block column << 16 | shift) rows, one wide scalar load per layer */
     pl->pack_w = pl->max_deg <= 8 ? 8 : pl->max_deg <= 16 ? 16 : 24;
@@ -812,7 +798,7 @@ inline hipError_t fused_plan_create(FusedPlan *pl, int32_t M, int32_t N, int64_t
                 const int j = lp[l] + (k < lp[l + 1] - lp[l] ? k : 0);
                 pk[(size_t)l * pl->pack_w + k] = (bc[j] << 16) | sh[j];
             }
-        if ((e = up(&pl->ent_pack, pk))) return e;
+        if ((e = pl->ent_pack.upload(pk))) return e;
     }
     /* column view: entries of every block column in ascending layer order */
     const int nb = N / z, layers = M / z;
@@ -828,7 +814,7 @@ inline hipError_t fused_plan_create(FusedPlan *pl, int32_t M, int32_t N, int64_t
             ce0[slot] = e0[l] + (j - lp[l]) * z;
             csh[slot] = sh[j];
         }
-    if ((e = up(&pl->bcol_ptr, cp)) || (e = up(&pl->bcol_e0, ce0)) || (e = up(&pl->bcol_sh, csh))) return e;
+    if ((e = pl->bcol_ptr.upload(cp)) || (e = pl->bcol_e0.upload(ce0)) || (e = pl->bcol_sh.upload(csh))) return e;
     pl->max_col_deg = 0;
     for (int b = 0; b < nb; ++b) pl->max_col_deg = std::max(pl->max_col_deg, cp[b + 1] - cp[b]);
     pl->lds_sp = (size_t)(N + 2 * E) * 4 + (((size_t)N + 3) & ~(size_t)3);
@@ -862,20 +848,16 @@ inline hipError_t fused_run(FusedPlan *pl, const FusedRun &r, hipStream_t s, int
     if ((e = hipMemsetAsync(r.summary, 0, 2 * sizeof(int32_t), s))) return e;
     const int rounds = r.tap_iter ? (r.tap_iter < r.max_iter ? r.tap_iter : r.max_iter) : r.max_iter;
     if (r.tap_iter && pl->dump_frames < r.frames) {
-        for (void *p : {(void *)pl->dump_p, (void *)pl->dump_r, (void *)pl->dump_q, (void *)pl->dump_b})
-            if (p) (void)hipFree(p);
-        pl->dump_p = pl->dump_r = pl->dump_q = nullptr;
-        pl->dump_b = nullptr;
-        if ((e = hipMalloc((void **)&pl->dump_p, (size_t)r.frames * pl->N * sizeof(float)))) return e;
-        if ((e = hipMalloc((void **)&pl->dump_r, (size_t)r.frames * pl->E * sizeof(float)))) return e;
-        if ((e = hipMalloc((void **)&pl->dump_q, (size_t)r.frames * pl->E * sizeof(float)))) return e;
-        if ((e = hipMalloc((void **)&pl->dump_b, (size_t)r.frames * pl->N))) return e;
+        if ((e = pl->dump_p.alloc((size_t)r.frames * pl->N))) return e;
+        if ((e = pl->dump_r.alloc((size_t)r.frames * pl->E))) return e;
+        if ((e = pl->dump_q.alloc((size_t)r.frames * pl->E))) return e;
+        if ((e = pl->dump_b.alloc((size_t)r.frames * pl->N))) return e;
         pl->dump_frames = r.frames;
     }
-    FusedArgs a{r.llr_dev, r.out_dev, r.iters_dev, r.summary, r.tap_iter ? pl->dump_p : nullptr,
-                r.tap_iter ? pl->dump_r : nullptr, nullptr, r.tap_iter ? pl->dump_q : nullptr,
-                r.tap_iter ? pl->dump_b : nullptr, r.llr_scale, pl->layer_ptr, pl->ent_bc, pl->ent_sh,
-                pl->layer_e0, pl->ent_pack, pl->pack_w, pl->bcol_ptr, pl->bcol_e0, pl->bcol_sh, r.frames, r.out_dev ? r.out_bytes : 0, pl->N, pl->E, r.K, pl->z, pl->layers,
+    FusedArgs a{r.llr_dev, r.out_dev, r.iters_dev, r.summary, r.tap_iter ? pl->dump_p.p : nullptr,
+                r.tap_iter ? pl->dump_r.p : nullptr, nullptr, r.tap_iter ? pl->dump_q.p : nullptr,
+                r.tap_iter ? pl->dump_b.p : nullptr, r.llr_scale, pl->layer_ptr.p, pl->ent_bc.p, pl->ent_sh.p,
+                pl->layer_e0.p, pl->ent_pack.p, pl->pack_w, pl->bcol_ptr.p, pl->bcol_e0.p, pl->bcol_sh.p, r.frames, r.out_dev ? r.out_bytes : 0, pl->N, pl->E, r.K, pl->z, pl->layers,
                 r.max_iter, rounds, r.early_term};
     const int mw = (pl->z + 63) / 64;
     const unsigned grid = (unsigned)r.frames;

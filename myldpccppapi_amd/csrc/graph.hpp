@@ -1,6 +1,5 @@
 /*
- * graph.hpp -- what the translation units of the host driver share: the graph behind an
- * `ldpc_graph *` and the setter of the calling thread's ldpc_last_error() message.
+ * graph.hpp -- the graph behind an `ldpc_graph *`, shared by the decoder driver and encoder.hip.
  */
 #pragma once
 
@@ -16,10 +15,3 @@ struct ldpc_graph {
     std::vector<int32_t> col_ptr, col_edge; /* CSC, edges ascending       */
     int32_t max_row_deg = 0, max_col_deg = 0;
 };
-
-namespace ldpc {
-
-/* stores the formatted message for ldpc_last_error() and returns `code` (ldpc_hip.hip) */
-int set_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-
-}  // namespace ldpc

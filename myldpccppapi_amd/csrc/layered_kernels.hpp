@@ -27,9 +27,11 @@
 #include <stdint.h>
 
 #include <map>
+#include <utility>
 #include <vector>
 
 #include "flood_kernels.hpp"
+#include "hip_host.hpp"
 
 namespace ldpc {
 
@@ -165,7 +167,7 @@ constexpr int kMaxUnrolledLayerDegree = 24;
 
 struct LayerGroup {
     int layer = 0, degree = 0, count = 0;
-    int32_t *e0 = nullptr; /* device */
+    DevBuf<int32_t> e0;
 };
 
 struct LayeredPlan {
@@ -175,19 +177,9 @@ struct LayeredPlan {
     int host_arith = 0;             /* 1: LDPC_ALGO_LAYERED_HOST (layer_kernel<.., HOST = true>) */
     int corr = 0;                   /* 1: normalized / offset min-sum (layer_corr_kernel) with these: */
     float ms_scale = 1.0f, ms_offset = 0.0f;
-    float *P = nullptr, *R = nullptr;
+    DevBuf<float> P, R;
     std::vector<LayerGroup> groups; /* ordered by layer */
 };
-
-inline void layered_plan_destroy(LayeredPlan *pl)
-{
-    for (auto &g : pl->groups)
-        if (g.e0) (void)hipFree(g.e0);
-    pl->groups.clear();
-    if (pl->P) (void)hipFree(pl->P);
-    if (pl->R) (void)hipFree(pl->R);
-    pl->P = pl->R = nullptr;
-}
 
 /* returns 0, -1 for an invalid layering, -2 for a HIP failure */
 inline int layered_plan_create(LayeredPlan *pl, int32_t M, int32_t N, int64_t E,
@@ -211,15 +203,13 @@ inline int layered_plan_create(LayeredPlan *pl, int32_t M, int32_t N, int64_t E,
         for (auto &kv : by_deg) {
             LayerGroup g;
             g.layer = l; g.degree = kv.first; g.count = (int)kv.second.size();
-            if (hipMalloc((void **)&g.e0, kv.second.size() * sizeof(int32_t)) != hipSuccess) return -2;
-            pl->groups.push_back(g);
-            if (hipMemcpy(g.e0, kv.second.data(), kv.second.size() * sizeof(int32_t),
-                          hipMemcpyHostToDevice) != hipSuccess) return -2;
+            if (g.e0.upload(kv.second) != hipSuccess) return -2;
+            pl->groups.push_back(std::move(g));
         }
     }
     const size_t TF = (size_t)T * 64 * V;
-    if (hipMalloc((void **)&pl->P, TF * N * sizeof(float)) != hipSuccess) return -2;
-    if (hipMalloc((void **)&pl->R, TF * (size_t)E * sizeof(float)) != hipSuccess) return -2;
+    if (pl->P.alloc(TF * N) != hipSuccess) return -2;
+    if (pl->R.alloc(TF * (size_t)E) != hipSuccess) return -2;
     return 0;
 }
 
@@ -287,9 +277,9 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
     hipError_t e;
     if ((e = hipMemsetAsync(r.failw, 0, (size_t)(r.max_iter + 2) * slot * sizeof(uint64_t), s))) return e;
     if ((e = hipMemsetAsync(r.summary, 0, 2 * sizeof(int32_t), s))) return e;
-    if ((e = hipMemsetAsync(pl->R, 0, (size_t)tiles * F * (size_t)pl->E * sizeof(float), s))) return e;
+    if ((e = hipMemsetAsync(pl->R.p, 0, (size_t)tiles * F * (size_t)pl->E * sizeof(float), s))) return e;
     {
-        LayeredInitArgs ia{r.llr_dev, pl->P, r.hard, r.frames, pl->N, pl->host_arith};
+        LayeredInitArgs ia{r.llr_dev, pl->P.p, r.hard, r.frames, pl->N, pl->host_arith};
         dim3 grid((pl->N + kInitCols - 1) / kInitCols, tiles);
         layered_init_kernel<V><<<grid, kBlock, 0, s>>>(ia);
         StateArgs st{r.done, nullptr, r.iters, nullptr, r.frames, 0, r.max_iter, 1};
@@ -298,7 +288,7 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
     int it = 0;
     for (it = 1; it <= rounds; ++it) {
         for (auto &g : pl->groups) {
-            LayerArgs a{pl->P, pl->R, g.e0, r.edge_col, r.hard, r.done, pl->E, pl->N, g.count,
+            LayerArgs a{pl->P.p, pl->R.p, g.e0.p, r.edge_col, r.hard, r.done, pl->E, pl->N, g.count,
                         4, g.degree};
             const int waves = (g.count + a.rows_per_wave - 1) / a.rows_per_wave;
             dim3 grid((waves + kWavesPerBlock - 1) / kWavesPerBlock, tiles);
@@ -312,7 +302,7 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
         }
         if (pl->host_arith) {
             dim3 hgrid((pl->N + kWavesPerBlock - 1) / kWavesPerBlock, tiles);
-            layered_hard_kernel<V><<<hgrid, kBlock, 0, s>>>(pl->P, r.hard, r.done, pl->N);
+            layered_hard_kernel<V><<<hgrid, kBlock, 0, s>>>(pl->P.p, r.hard, r.done, pl->N);
         }
         /* syndrome of this round's bits, freeze (decodeCL.c:393-410) */
         if (!r.early_term && it != rounds) continue;
@@ -356,7 +346,7 @@ inline hipError_t layered_dump(LayeredPlan *pl, int which, float *host_out, int6
     if (which == 0 || which == 2) {
         const int64_t per = which == 0 ? pl->E : pl->N;
         if (count != frames * per) return hipErrorInvalidValue;
-        const float *src = which == 0 ? pl->R : pl->P;
+        const float *src = which == 0 ? pl->R.p : pl->P.p;
         std::vector<float> tile((size_t)per * F);
         for (int t = 0; t < tiles; ++t) {
             hipError_t e = hipMemcpy(tile.data(), src + (size_t)t * per * F, tile.size() * sizeof(float),

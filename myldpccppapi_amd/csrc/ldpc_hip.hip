@@ -21,6 +21,11 @@
  * column-fused check kernel's form (calibrate_link) and the launch plan (plan_launches).  The
  * kernels themselves are instantiated in other translation units: flood_sp / flood_ms / flood_ms16
  * (flood_tables.hpp) and engine_ldsp / engine_fused / engine_layered (engines.hpp).
+ *
+ * Not here: the entry points that need no decoder (channel.hip: AWGN channel, error counter, HBM probes) and the
+ * encoder, rate-matching and modem sections (encoder.hip, ratematch.hip, modem.hip).  What all of them share lives in
+ * hip_host.hpp: LDPC_HIP_TRY, DevBuf (every device array of the handle and of the engine plans is one, so a handle
+ * frees its memory on whichever path it goes) and the declaration of set_error, whose body and message are below.
  */
 #include <hip/hip_runtime.h>
 
@@ -44,71 +49,21 @@
 #include "fused_kernels.hpp"
 #include "ldsp_kernels.hpp"
 #include "engines.hpp"
-#include "channel_kernels.hpp"
 #include "tune.hpp"
 #include "host_stage.hpp"
 #include "graph.hpp"
+#include "hip_host.hpp"
 
 #ifndef LDPC_IDLE_FAT
 #define LDPC_IDLE_FAT 8
 #endif
 
+using ldpc::DevBuf;
+using ldpc::set_error;
+
 namespace {
 
 thread_local std::string g_err;
-
-int fail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                  \
-    do {                                                                               \
-        hipError_t e_ = (expr);                                                        \
-        if (e_ != hipSuccess)                                                          \
-            return fail(LDPC_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                        __FILE__, __LINE__);                                           \
-    } while (0)
-
-template <typename T> struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
-    DevBuf &operator=(DevBuf &&o) noexcept
-    {
-        if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
-        return *this;
-    }
-    hipError_t alloc(size_t count)
-    {
-        release();
-        n = count;
-        if (!count) return hipSuccess;
-        return hipMalloc((void **)&p, count * sizeof(T));
-    }
-    hipError_t upload(const std::vector<T> &h)
-    {
-        hipError_t e = alloc(h.size());
-        if (e != hipSuccess || h.empty()) return e;
-        return hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    ~DevBuf() { release(); }
-};
 
 }  // namespace
 
@@ -366,25 +321,6 @@ struct ldpc_decoder {
 
 namespace {
 
-/* a plain float4 copy (the measurement aid ldpc_hbm_probe_device; also the placement search's second opinion) */
-template <bool NT>
-__global__ __launch_bounds__(256) void hbm_probe_copy_kernel(const ldpc::vf4 *__restrict__ src, ldpc::vf4 *__restrict__ dst, size_t n4)
-{
-    const size_t stride = (size_t)gridDim.x * 256 * 4;
-    for (size_t i = (size_t)blockIdx.x * 256 * 4 + threadIdx.x; i < n4; i += stride) {
-        ldpc::vf4 v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (i + (size_t)k * 256 < n4) v[k] = NT ? __builtin_nontemporal_load(&src[i + (size_t)k * 256]) : src[i + (size_t)k * 256];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (i + (size_t)k * 256 < n4) {
-                if (NT) __builtin_nontemporal_store(v[k], &dst[i + (size_t)k * 256]);
-                else dst[i + (size_t)k * 256] = v[k];
-            }
-    }
-}
-
 /* summary[0] = max over frames of iters (the reference's `Time=`), summary[1] =
  * number of frames whose syndrome ended clean. */
 template <int V>
@@ -470,7 +406,7 @@ template <int V> int enqueue_check_phase(ldpc_decoder *d, hipStream_t s, int til
          * two-kernel formulation (16 E + 4 N per frame-iteration in total).
          * moved: every Q of the class and the fused columns' channel values in; R of the unfused
          * edges and the fused columns' new Q out.  Rows riding along: Q in, R out. */
-        HIP_TRY(span_begin(d, s, 4, rc.degree,
+        LDPC_HIP_TRY(span_begin(d, s, 4, rc.degree,
                            (2 * msz * rc.degree * rc.count + msz * 5 * rc.linked + 2 * msz * d->extra_edges) * frames,
                            msz * ((int64_t)rc.degree * rc.count + rc.linked +
                                   ((int64_t)rc.degree * rc.count - 2 * rc.linked) +
@@ -489,23 +425,23 @@ template <int V> int enqueue_check_phase(ldpc_decoder *d, hipStream_t s, int til
         const dim3 grid = flood_grid(d, lk.link_blocks + (d->n_extra + kWavesPerBlock - 1) / kWavesPerBlock, tiles, &a.tiles_first, true);
         (variant == 2 ? d->link_half_fn : variant == 1 ? (d->tune_link_deep ? d->link_deep_fn : d->link_narrow_fn) : d->link_fn)
             [rc.degree]<<<grid, kBlock, 0, s>>>(a, lk);
-        HIP_TRY(span_end(d, s));
+        LDPC_HIP_TRY(span_end(d, s));
     }
     for (auto &g : d->check_groups) {
         int64_t edges = 0;
         for (int i : g.members) edges += (int64_t)d->row_classes[i].degree * d->row_classes[i].count;
-        HIP_TRY(span_begin(d, s, 5, g.hi, 2 * msz * edges * frames, -1, g.lo));
+        LDPC_HIP_TRY(span_begin(d, s, 5, g.hi, 2 * msz * edges * frames, -1, g.lo));
         CheckArgs a{d->Q.p, d->R.p, nullptr, d->done.p, d->E, 0, (d->tune_rpw ? d->tune_rpw : 2) * (fat ? kIdleFat : 1), 0, d->ms_scale, tr};
         a.ms_offset = d->ms_offset;
         a.qpos = d->qpos.p;
         if (it == 1 && d->first_round_from_chan) { a.first_chan = d->chan.p; a.edge_col = d->edge_col.p; a.N = d->N; }
         const dim3 grid = flood_grid(d, fat ? g.blocks_fat : g.blocks, tiles, &a.tiles_first);
         d->check_group_fn[g.bucket]<<<grid, kBlock, 0, s>>>(a, fat ? g.table_fat.p : g.table.p, (int)g.members.size());
-        HIP_TRY(span_end(d, s));
+        LDPC_HIP_TRY(span_end(d, s));
     }
     for (int ci : d->check_solo) {
         RowClass &rc = d->row_classes[ci];
-        HIP_TRY(span_begin(d, s, 0, rc.degree, 2 * msz * rc.degree * rc.count * frames));
+        LDPC_HIP_TRY(span_begin(d, s, 0, rc.degree, 2 * msz * rc.degree * rc.count * frames));
         CheckArgs a{d->Q.p, d->R.p, rc.e0.p, d->done.p, d->E, rc.count, 1, rc.degree, d->ms_scale, tr};
         a.ms_offset = d->ms_offset;
         a.qpos = d->qpos.p;
@@ -517,7 +453,7 @@ template <int V> int enqueue_check_phase(ldpc_decoder *d, hipStream_t s, int til
         const int waves = ((rc.count + rpw - 1) / rpw) * (narrow ? V : 1);
         const dim3 grid = flood_grid(d, (waves + kWavesPerBlock - 1) / kWavesPerBlock, tiles, &a.tiles_first);
         (narrow ? d->check_fn : d->check_fn_wide)[slotk]<<<grid, kBlock, 0, s>>>(a);
-        HIP_TRY(span_end(d, s));
+        LDPC_HIP_TRY(span_end(d, s));
     }
     return LDPC_OK;
 }
@@ -533,16 +469,16 @@ template <int V> int enqueue_var_phase(ldpc_decoder *d, hipStream_t s, int tiles
     for (auto &g : d->var_groups) {
         int64_t units = 0;          /* messages read + written + channel values read, per frame */
         for (int i : g.members) units += (int64_t)((wq ? 2 : 1) * d->col_classes[i].degree + 1) * d->col_classes[i].count;
-        HIP_TRY(span_begin(d, s, 6, g.hi, msz * units * frames, -1, g.lo));
+        LDPC_HIP_TRY(span_begin(d, s, 6, g.hi, msz * units * frames, -1, g.lo));
         VarArgs a{d->R.p, d->Q.p, d->chan.p, d->hard.p, d->done.p, nullptr, nullptr,
                   d->E, d->N, 0, (d->tune_cpw ? d->tune_cpw : 1) * (fat ? kIdleFat : 1), wq, 0, tr};
         const dim3 grid = flood_grid(d, fat ? g.blocks_fat : g.blocks, tiles, &a.tiles_first);
         d->var_group_fn[g.bucket]<<<grid, kBlock, 0, s>>>(a, fat ? g.table_fat.p : g.table.p, (int)g.members.size());
-        HIP_TRY(span_end(d, s));
+        LDPC_HIP_TRY(span_end(d, s));
     }
     for (int ci : d->var_solo) {
         ColClass &cc = d->col_classes[ci];
-        HIP_TRY(span_begin(d, s, 1, cc.degree, msz * ((wq ? 2 : 1) * cc.degree + 1) * cc.count * frames));
+        LDPC_HIP_TRY(span_begin(d, s, 1, cc.degree, msz * ((wq ? 2 : 1) * cc.degree + 1) * cc.count * frames));
         VarArgs a{d->R.p, d->Q.p, d->chan.p, d->hard.p, d->done.p, cc.col.p, cc.edge.p,
                   d->E, d->N, cc.count, 1, wq, cc.degree, tr};
         const int cpw = (d->tune_cpw ? d->tune_cpw : 1) * (fat ? kIdleFat : 1);
@@ -552,7 +488,7 @@ template <int V> int enqueue_var_phase(ldpc_decoder *d, hipStream_t s, int tiles
         const int waves = (cc.count + cpw - 1) / cpw;
         const dim3 grid = flood_grid(d, (waves + kWavesPerBlock - 1) / kWavesPerBlock, tiles, &a.tiles_first);
         d->var_fn[slotk]<<<grid, kBlock, 0, s>>>(a);
-        HIP_TRY(span_end(d, s));
+        LDPC_HIP_TRY(span_end(d, s));
     }
     return LDPC_OK;
 }
@@ -570,8 +506,8 @@ template <int V> int compact_and_finish(ldpc_decoder *d, int64_t frames, int cou
     const int cv = c->V, cf = 64 * cv;                      /* its frames per lane and per tile */
     const unsigned ct = (unsigned)((count + cf - 1) / cf);  /* child tiles in use */
     const unsigned cg = ct * (unsigned)cv;                  /* ... in groups of 64 slots */
-    if (cg > (unsigned)kBackWords) return fail(LDPC_ERR_STATE, "hand-over of %d frames: more than %d mask words per column", count, kBackWords);
-    HIP_TRY(hipMemsetAsync(d->active.p, 0, sizeof(int32_t), s));
+    if (cg > (unsigned)kBackWords) return set_error(LDPC_ERR_STATE, "hand-over of %d frames: more than %d mask words per column", count, kBackWords);
+    LDPC_HIP_TRY(hipMemsetAsync(d->active.p, 0, sizeof(int32_t), s));
     compact_list_kernel<V><<<(unsigned)((frames + kBlock - 1) / kBlock), kBlock, 0, s>>>(d->done.p, frames, d->cmap.p,
                                                                                          d->active.p, d->child_capacity);
     const dim3 ge((unsigned)((d->E + kWavesPerBlock - 1) / kWavesPerBlock), cg);
@@ -598,7 +534,7 @@ template <int V> int compact_and_finish(ldpc_decoder *d, int64_t frames, int cou
     }
     /* the hard bits travel only where the next decision can depend on the previous one: the sum-product rule keeps the old
      * bit on a tie or a NaN (decodeCL.c:78-82); min-sum decides every bit anew in every round (bit = !(p > 0), :161-165) */
-    HIP_TRY(hipMemsetAsync(c->hard.p, 0, (size_t)ct * d->N * cv * sizeof(uint64_t), s));
+    LDPC_HIP_TRY(hipMemsetAsync(c->hard.p, 0, (size_t)ct * d->N * cv * sizeof(uint64_t), s));
     if (d->cfg.algo == LDPC_ALGO_SP) {
         if (ptiles * V <= kGatherParentWords && count <= 2 * kCompactCapacity)
             compact_hard_lds_kernel<V><<<(unsigned)((d->N + 63) / 64), kBlock, 0, s>>>(d->hard.p, c->hard.p, d->cmap.p, count, d->N, cv, ptiles, (int)cg);
@@ -606,7 +542,7 @@ template <int V> int compact_and_finish(ldpc_decoder *d, int64_t frames, int cou
             compact_hard_kernel<V><<<gn, kBlock, 0, s>>>(d->hard.p, c->hard.p, d->cmap.p, count, d->N, cv);
     }
     compact_child_state_kernel<0><<<ct, 64, 0, s>>>(c->done.p, c->iters.p, count, d->cfg.max_iter, cv);
-    HIP_TRY(hipGetLastError());
+    LDPC_HIP_TRY(hipGetLastError());
     c->timing = false;
     c->tap_iter = 0;
     const int rc = cv == 1 ? run_flooding<1>(c, nullptr, count, nullptr, 0, nullptr, s, it + 1)
@@ -616,12 +552,12 @@ template <int V> int compact_and_finish(ldpc_decoder *d, int64_t frames, int cou
     d->handed_to = c;
     /* the bits back: every parent word collects its moved frames' bits (no atomics; the per-bit atomic scatter of
      * compact_hard_kernel took 53-80 us for a few dozen frames, this takes 10-30) */
-    HIP_TRY(hipMemsetAsync(d->cmoved.p, 0, d->cmoved.n * sizeof(unsigned long long), s));
+    LDPC_HIP_TRY(hipMemsetAsync(d->cmoved.p, 0, d->cmoved.n * sizeof(unsigned long long), s));
     compact_inverse_kernel<V><<<(unsigned)((count + 255) / 256), 256, 0, s>>>(d->cmap.p, count, d->cinv.p, d->cmoved.p, cv);
     compact_hard_back_kernel<V><<<dim3((unsigned)((d->N + kBlock - 1) / kBlock), (unsigned)ptiles), kBlock, 0, s>>>(
         d->hard.p, c->hard.p, d->cinv.p, d->cmoved.p, d->N, cv, (int)cg);
     compact_finish_kernel<V><<<(unsigned)((count + 63) / 64), 64, 0, s>>>(d->done.p, d->iters.p, c->done.p, c->iters.p, d->cmap.p, count, cv);
-    HIP_TRY(hipGetLastError());
+    LDPC_HIP_TRY(hipGetLastError());
     return LDPC_OK;
 }
 
@@ -639,8 +575,8 @@ template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t
     const size_t slot = (size_t)d->TA * V;  /* words per fail slot */
 
     const bool resume = start_round > 1;    /* a child taking over running frames: their state is in place */
-    HIP_TRY(hipMemsetAsync(d->failw.p, 0, d->failw.n * sizeof(uint64_t), s));
-    HIP_TRY(hipMemsetAsync(d->summary.p, 0, 4 * sizeof(int32_t), s));
+    LDPC_HIP_TRY(hipMemsetAsync(d->failw.p, 0, d->failw.n * sizeof(uint64_t), s));
+    LDPC_HIP_TRY(hipMemsetAsync(d->summary.p, 0, 4 * sizeof(int32_t), s));
     d->handed_to = nullptr;
     /* idle hint from the previous call (asynchronous early termination only) */
     if (!resume && d->summary_pending) {
@@ -657,8 +593,8 @@ template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t
     const TailRef tr{use_tail ? d->tail_state.p : nullptr, d->T, d->TO};
     TailArgs ta{};
     if (use_tail) {
-        HIP_TRY(hipMemsetAsync(d->tail_state.p, 0, 4 * sizeof(int32_t), s));
-        HIP_TRY(hipMemsetAsync(d->running.p, 0, d->running.n * sizeof(int32_t), s));
+        LDPC_HIP_TRY(hipMemsetAsync(d->tail_state.p, 0, 4 * sizeof(int32_t), s));
+        LDPC_HIP_TRY(hipMemsetAsync(d->running.p, 0, d->running.n * sizeof(int32_t), s));
         ta = TailArgs{d->tail_state.p, d->tail_map.p, d->running.p, d->done.p, d->iters.p, d->Q.p, d->chan.p, d->hard.p,
                       d->E, frames, d->N, tiles, d->T, d->TO * F, std::min(d->compact_threshold, d->TO * F), 0, max_iter};
     }
@@ -670,7 +606,7 @@ template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t
     for (int ci : d->check_solo) if (d->row_classes[ci].degree > d->max_check_unrolled) q_less = false;
     d->first_round_from_chan = q_less;
     if (!resume) {
-        HIP_TRY(span_begin(d, s, 3));
+        LDPC_HIP_TRY(span_begin(d, s, 3));
         InitArgs a{llr_dev, d->chan.p, q_less ? nullptr : d->Q.p, d->hard.p, d->col_ptr.p, d->col_qedge.p,
                    d->E, frames, d->N, d->cfg.llr_scale};
         dim3 grid((d->N + kInitCols - 1) / kInitCols, tiles);
@@ -678,7 +614,7 @@ template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t
         StateArgs st{d->done.p, nullptr, d->iters.p, nullptr, frames, 0, max_iter, freeze ? 1 : 0};
         /* overflow tiles (and unused tiles in between) are born finished: frames beyond `frames` */
         state_kernel<V><<<use_tail ? d->TA : tiles, 64, 0, s>>>(st);
-        HIP_TRY(span_end(d, s));
+        LDPC_HIP_TRY(span_end(d, s));
     }
 
     int launched = start_round - 1;
@@ -700,7 +636,7 @@ template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t
         launched = it;
         /* syndrome of bits_i, then freeze the frames that are clean (iters = i) */
         if (freeze || it == rounds) {
-            HIP_TRY(span_begin(d, s, 3));
+            LDPC_HIP_TRY(span_begin(d, s, 3));
             uint64_t *fw = d->failw.p + (size_t)it * slot;
             const int rbk = (d->M + kBlock - 1) / kBlock;
             SyndromeArgs sa{d->row_ptr.p, d->edge_col.p, d->hard.p, fw, d->done.p, d->M, d->N,
@@ -712,7 +648,7 @@ template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t
             const bool poll = freeze && it < rounds && d->cfg.poll_interval > 0 && !d->suppress_poll &&
                               ((it % d->cfg.poll_interval) == 0 || poll_dense);
             if (poll) {
-                HIP_TRY(hipMemsetAsync(d->active.p, 0, sizeof(int32_t), s));
+                LDPC_HIP_TRY(hipMemsetAsync(d->active.p, 0, sizeof(int32_t), s));
                 st.active = d->active.p;
             }
             state_kernel<V><<<tiles, 64, 0, s>>>(st);
@@ -724,11 +660,11 @@ template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t
                 if (d->msg_size == 2) tail_gather_kernel<V, _Float16><<<tg, kBlock, 0, s>>>(ta);
                 else tail_gather_kernel<V, float><<<tg, kBlock, 0, s>>>(ta);
             }
-            HIP_TRY(span_end(d, s));
+            LDPC_HIP_TRY(span_end(d, s));
             if (poll) {
-                HIP_TRY(hipMemcpyAsync(d->h_active, d->active.p, sizeof(int32_t),
+                LDPC_HIP_TRY(hipMemcpyAsync(d->h_active, d->active.p, sizeof(int32_t),
                                        hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
+                LDPC_HIP_TRY(hipStreamSynchronize(s));
                 const int running = *d->h_active;
                 if (running == 0) break;        /* every frame frozen: MyLdpc.cpp:1035-1036 */
                 /* ... where a round is long enough for a host round trip (about 25 us) not to matter: from 1.5 GB of
@@ -748,7 +684,7 @@ template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t
     d->last_tiles = tiles;
     if (resume) return LDPC_OK;             /* the parent packs */
 
-    HIP_TRY(span_begin(d, s, 3));
+    LDPC_HIP_TRY(span_begin(d, s, 3));
     if (use_tail) tail_scatter_kernel<V><<<2048, kBlock, 0, s>>>(ta);
     {
         PackArgs pa{d->hard.p, out_dev, d->iters.p, iters_dev, frames, out_bytes, d->N, d->cfg.K,
@@ -767,13 +703,13 @@ template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t
             d->iters.p, d->done.p, d->failw.p, frames, 1, d->summary.p);
         if (!d->is_child && d->cfg.poll_interval == 0 && freeze && !d->summary_pending) {
             /* the next call's idle hint */
-            HIP_TRY(hipMemcpyAsync(d->h_summary, d->summary.p, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipEventRecord(d->ev_summary, s));
+            LDPC_HIP_TRY(hipMemcpyAsync(d->h_summary, d->summary.p, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            LDPC_HIP_TRY(hipEventRecord(d->ev_summary, s));
             d->summary_pending = true;
         }
     }
-    HIP_TRY(span_end(d, s));
-    HIP_TRY(hipGetLastError());
+    LDPC_HIP_TRY(span_end(d, s));
+    LDPC_HIP_TRY(hipGetLastError());
     return LDPC_OK;
 }
 
@@ -793,7 +729,7 @@ int build_classes(ldpc_decoder *d, const ldpc_graph *g)
         rc.degree = kv.first;
         rc.count = (int)kv.second.size();
         rc.h_e0 = kv.second;
-        HIP_TRY(rc.e0.upload(kv.second));
+        LDPC_HIP_TRY(rc.e0.upload(kv.second));
         const std::vector<int32_t> &ids = rowids_by_deg[kv.first];
         const int rpw = d->link_rpw;
         if (rpw >= 2 && rc.degree >= 2 && rc.degree <= ldpc::kMaxUnrolledDegree) {
@@ -834,8 +770,8 @@ int build_classes(ldpc_decoder *d, const ldpc_graph *g)
                 }
             }
             if (rc.linked * 4 >= rc.count) {                    /* worth a specialised kernel */
-                HIP_TRY(rc.link_col.upload(lcol));
-                HIP_TRY(rc.link_pos.upload(lpos));
+                LDPC_HIP_TRY(rc.link_col.upload(lcol));
+                LDPC_HIP_TRY(rc.link_pos.upload(lpos));
             } else {
                 for (int idx = 0; idx < rc.count; ++idx)
                     if (lcol[idx] >= 0) fused_col[lcol[idx]] = 0;
@@ -858,8 +794,8 @@ int build_classes(ldpc_decoder *d, const ldpc_graph *g)
         for (int32_t n : kv.second)
             for (int32_t p = g->col_ptr[n]; p < g->col_ptr[n + 1]; ++p) edges.push_back(g->col_edge[p]);
         if (edges.empty()) edges.push_back(0);
-        HIP_TRY(cc.col.upload(kv.second));
-        HIP_TRY(cc.edge.upload(edges));
+        LDPC_HIP_TRY(cc.col.upload(kv.second));
+        LDPC_HIP_TRY(cc.edge.upload(edges));
     }
     {
         /* Q in the order its writers produce it (CheckArgs::qpos): the column classes one after the other, a class of degree D
@@ -881,8 +817,8 @@ int build_classes(ldpc_decoder *d, const ldpc_graph *g)
             if (d->h_qpos[(size_t)e] < 0) d->h_qpos[(size_t)e] = d->tune.q_order >= 0 ? (int32_t)slot++ : (int32_t)e;
         std::vector<int32_t> cq((size_t)g->E);
         for (int64_t p = 0; p < g->E; ++p) cq[(size_t)p] = d->h_qpos[(size_t)g->col_edge[(size_t)p]];
-        HIP_TRY(d->qpos.upload(d->h_qpos));
-        HIP_TRY(d->col_qedge.upload(cq));
+        LDPC_HIP_TRY(d->qpos.upload(d->h_qpos));
+        LDPC_HIP_TRY(d->col_qedge.upload(cq));
     }
     return LDPC_OK;
 }
@@ -917,8 +853,8 @@ int plan_launches(ldpc_decoder *d)
     }
     if (as_extra) {
         d->n_extra = (int)xe0.size();
-        HIP_TRY(d->extra_e0.upload(xe0));
-        HIP_TRY(d->extra_deg.upload(xdeg));
+        LDPC_HIP_TRY(d->extra_e0.upload(xe0));
+        LDPC_HIP_TRY(d->extra_deg.upload(xdeg));
     }
     for (int i = 0; i < (int)d->col_classes.size(); ++i) {
         const ColClass &cc = d->col_classes[i];
@@ -959,8 +895,8 @@ int plan_launches(ldpc_decoder *d)
         const hipError_t e = g.table.upload(tab);
         return e != hipSuccess ? e : g.table_fat.upload(tabf);
     };
-    for (int k = 0; k < kCheckBuckets; ++k) HIP_TRY(make(d->check_groups, d->check_solo, cb[k], k, kCheckBucketLo[k], kCheckBucketHi[k], true));
-    for (int k = 0; k < kVarBuckets; ++k) HIP_TRY(make(d->var_groups, d->var_solo, vb[k], k, kVarBucketLo[k], kVarBucketHi[k], false));
+    for (int k = 0; k < kCheckBuckets; ++k) LDPC_HIP_TRY(make(d->check_groups, d->check_solo, cb[k], k, kCheckBucketLo[k], kCheckBucketHi[k], true));
+    for (int k = 0; k < kVarBuckets; ++k) LDPC_HIP_TRY(make(d->var_groups, d->var_solo, vb[k], k, kVarBucketLo[k], kVarBucketHi[k], false));
     return LDPC_OK;
 }
 
@@ -969,9 +905,9 @@ int setup_flooding(ldpc_decoder *d, const ldpc_graph *g, size_t TF)
 {
     const ldpc_decoder_config *cfg = &d->cfg;
     d->msg_size = cfg->msg_dtype == LDPC_MSG_F16 ? 2 : 4;
-    HIP_TRY(d->chan.alloc(TF * d->N * d->msg_size));
-    HIP_TRY(d->Q.alloc(TF * (size_t)d->E * d->msg_size));
-    HIP_TRY(d->R.alloc(TF * (size_t)d->E * d->msg_size));
+    LDPC_HIP_TRY(d->chan.alloc(TF * d->N * d->msg_size));
+    LDPC_HIP_TRY(d->Q.alloc(TF * (size_t)d->E * d->msg_size));
+    LDPC_HIP_TRY(d->R.alloc(TF * (size_t)d->E * d->msg_size));
     int rc = build_classes(d, g);
     if (rc) return rc;
     /* the kernels live in flood_sp.hip / flood_ms.hip / flood_ms16.hip / flood_msc*.hip (flood_tables.hpp) */
@@ -1014,12 +950,12 @@ template <int V> int calibrate_link(ldpc_decoder *d)
     RowClass &rc = *rcp;
     const int tiles = d->T;
     hipStream_t s = d->stream;
-    HIP_TRY(hipMemsetAsync(d->Q.p, 0, d->Q.n, s));
-    HIP_TRY(hipMemsetAsync(d->chan.p, 0, d->chan.n, s));
-    HIP_TRY(hipMemsetAsync(d->done.p, 0, d->done.n * sizeof(uint64_t), s));
+    LDPC_HIP_TRY(hipMemsetAsync(d->Q.p, 0, d->Q.n, s));
+    LDPC_HIP_TRY(hipMemsetAsync(d->chan.p, 0, d->chan.n, s));
+    LDPC_HIP_TRY(hipMemsetAsync(d->done.p, 0, d->done.n * sizeof(uint64_t), s));
     hipEvent_t ev[2] = {nullptr, nullptr};
-    HIP_TRY(hipEventCreate(&ev[0]));
-    HIP_TRY(hipEventCreate(&ev[1]));
+    LDPC_HIP_TRY(hipEventCreate(&ev[0]));
+    LDPC_HIP_TRY(hipEventCreate(&ev[1]));
     float best[3] = {1e30f, 1e30f, 1e30f};
     const int candidates = d->link_half_fn[rc.degree] ? 3 : 2;
     hipError_t err = hipSuccess;
@@ -1045,8 +981,8 @@ template <int V> int calibrate_link(ldpc_decoder *d)
     }
     (void)hipEventDestroy(ev[0]);
     (void)hipEventDestroy(ev[1]);
-    if (err != hipSuccess) return fail(LDPC_ERR_HIP, "link calibration: %s", hipGetErrorString(err));
-    HIP_TRY(hipGetLastError());
+    if (err != hipSuccess) return set_error(LDPC_ERR_HIP, "link calibration: %s", hipGetErrorString(err));
+    LDPC_HIP_TRY(hipGetLastError());
     int pick = 0;
     for (int k = 0; k < candidates; ++k) { d->link_cal_ms[k] = best[k]; if (best[k] < best[pick]) pick = k; }
     d->tune_link_narrow = pick;
@@ -1059,12 +995,12 @@ template <int V> int calibrate_link(ldpc_decoder *d)
 template <int V> int time_check_phase(ldpc_decoder *d, float *ms_out)
 {
     hipStream_t s = d->stream;
-    HIP_TRY(hipMemsetAsync(d->Q.p, 0, d->Q.n, s));
-    HIP_TRY(hipMemsetAsync(d->chan.p, 0, d->chan.n, s));
-    HIP_TRY(hipMemsetAsync(d->done.p, 0, d->done.n * sizeof(uint64_t), s));
+    LDPC_HIP_TRY(hipMemsetAsync(d->Q.p, 0, d->Q.n, s));
+    LDPC_HIP_TRY(hipMemsetAsync(d->chan.p, 0, d->chan.n, s));
+    LDPC_HIP_TRY(hipMemsetAsync(d->done.p, 0, d->done.n * sizeof(uint64_t), s));
     hipEvent_t ev[2] = {nullptr, nullptr};
-    HIP_TRY(hipEventCreate(&ev[0]));
-    HIP_TRY(hipEventCreate(&ev[1]));
+    LDPC_HIP_TRY(hipEventCreate(&ev[0]));
+    LDPC_HIP_TRY(hipEventCreate(&ev[1]));
     float best = 1e30f;
     hipError_t err = hipSuccess;
     int rc = LDPC_OK;
@@ -1082,7 +1018,7 @@ template <int V> int time_check_phase(ldpc_decoder *d, float *ms_out)
     (void)hipEventDestroy(ev[0]);
     (void)hipEventDestroy(ev[1]);
     if (rc) return rc;
-    if (err != hipSuccess) return fail(LDPC_ERR_HIP, "placement search: %s", hipGetErrorString(err));
+    if (err != hipSuccess) return set_error(LDPC_ERR_HIP, "placement search: %s", hipGetErrorString(err));
     *ms_out = best;
     return LDPC_OK;
 }
@@ -1172,11 +1108,11 @@ const char *ldpc_last_error(void) { return g_err.c_str(); }
 
 int ldpc_device_count(int *count)
 {
-    if (!count) return fail(LDPC_ERR_ARG, "count is NULL");
+    if (!count) return set_error(LDPC_ERR_ARG, "count is NULL");
     *count = 0;
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess) return fail(LDPC_ERR_HIP, "hipGetDeviceCount: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return set_error(LDPC_ERR_HIP, "hipGetDeviceCount: %s", hipGetErrorString(e));
     *count = n;
     return LDPC_OK;
 }
@@ -1191,21 +1127,21 @@ int64_t ldpc_out_bytes(int32_t K, int64_t frames, int32_t pack_mode)
 int ldpc_graph_create(const int32_t *rows, const int32_t *cols, int64_t E, int32_t M, int32_t N,
                       ldpc_graph **out)
 {
-    if (!out) return fail(LDPC_ERR_ARG, "out is NULL");
+    if (!out) return set_error(LDPC_ERR_ARG, "out is NULL");
     *out = nullptr;
-    if (!rows || !cols) return fail(LDPC_ERR_ARG, "rows/cols is NULL");
-    if (M <= 0 || N <= 0 || E <= 0) return fail(LDPC_ERR_ARG, "M, N, E must be positive");
-    if (E > 0x7fffffffLL) return fail(LDPC_ERR_ARG, "E does not fit int32 edge ids");
+    if (!rows || !cols) return set_error(LDPC_ERR_ARG, "rows/cols is NULL");
+    if (M <= 0 || N <= 0 || E <= 0) return set_error(LDPC_ERR_ARG, "M, N, E must be positive");
+    if (E > 0x7fffffffLL) return set_error(LDPC_ERR_ARG, "E does not fit int32 edge ids");
     for (int64_t e = 0; e < E; ++e) {
         if (rows[e] < 0 || rows[e] >= M || cols[e] < 0 || cols[e] >= N)
-            return fail(LDPC_ERR_ARG, "edge %lld = (%d, %d) outside %d x %d", (long long)e, rows[e],
+            return set_error(LDPC_ERR_ARG, "edge %lld = (%d, %d) outside %d x %d", (long long)e, rows[e],
                         cols[e], M, N);
         if (e && (rows[e] < rows[e - 1] || (rows[e] == rows[e - 1] && cols[e] <= cols[e - 1])))
-            return fail(LDPC_ERR_ARG, "edges must be in strictly ascending row-major order (edge %lld)",
+            return set_error(LDPC_ERR_ARG, "edges must be in strictly ascending row-major order (edge %lld)",
                         (long long)e);
     }
     ldpc_graph *g = new (std::nothrow) ldpc_graph;
-    if (!g) return fail(LDPC_ERR_NOMEM, "out of memory");
+    if (!g) return set_error(LDPC_ERR_NOMEM, "out of memory");
     g->M = M; g->N = N; g->E = E;
     g->rows.assign(rows, rows + E);
     g->cols.assign(cols, cols + E);
@@ -1238,7 +1174,7 @@ int ldpc_graph_destroy(ldpc_graph *g)
 int ldpc_graph_info(const ldpc_graph *g, int32_t *M, int32_t *N, int64_t *E, int32_t *max_row_deg,
                     int32_t *max_col_deg)
 {
-    if (!g) return fail(LDPC_ERR_ARG, "graph is NULL");
+    if (!g) return set_error(LDPC_ERR_ARG, "graph is NULL");
     if (M) *M = g->M;
     if (N) *N = g->N;
     if (E) *E = g->E;
@@ -1267,7 +1203,7 @@ static int config_in(const ldpc_decoder_config *cfg, ldpc_decoder_config *full)
 {
     constexpr size_t kSizeBeforeMsCorr = offsetof(ldpc_decoder_config, ms_scale);
     if (cfg->struct_size != sizeof(ldpc_decoder_config) && cfg->struct_size != kSizeBeforeMsCorr)
-        return fail(LDPC_ERR_ARG, "config struct_size %u is neither %zu nor %zu (ABI mismatch)", cfg->struct_size,
+        return set_error(LDPC_ERR_ARG, "config struct_size %u is neither %zu nor %zu (ABI mismatch)", cfg->struct_size,
                     sizeof(ldpc_decoder_config), kSizeBeforeMsCorr);
     memset(full, 0, sizeof *full);
     memcpy(full, cfg, cfg->struct_size);
@@ -1277,55 +1213,55 @@ static int config_in(const ldpc_decoder_config *cfg, ldpc_decoder_config *full)
 
 int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, ldpc_decoder **out)
 {
-    if (!out) return fail(LDPC_ERR_ARG, "out is NULL");
+    if (!out) return set_error(LDPC_ERR_ARG, "out is NULL");
     *out = nullptr;
-    if (!g || !cfg_in) return fail(LDPC_ERR_ARG, "graph/config is NULL");
+    if (!g || !cfg_in) return set_error(LDPC_ERR_ARG, "graph/config is NULL");
     ldpc_decoder_config cfg_full;
     if (int rc = config_in(cfg_in, &cfg_full)) return rc;
     const ldpc_decoder_config *cfg = &cfg_full;
-    if (cfg->K <= 0 || cfg->K > g->N) return fail(LDPC_ERR_ARG, "K=%d out of range", cfg->K);
-    if (cfg->max_batch <= 0) return fail(LDPC_ERR_ARG, "max_batch must be positive");
-    if (cfg->max_iter <= 0 || cfg->max_iter > 100000) return fail(LDPC_ERR_ARG, "max_iter out of range");
+    if (cfg->K <= 0 || cfg->K > g->N) return set_error(LDPC_ERR_ARG, "K=%d out of range", cfg->K);
+    if (cfg->max_batch <= 0) return set_error(LDPC_ERR_ARG, "max_batch must be positive");
+    if (cfg->max_iter <= 0 || cfg->max_iter > 100000) return set_error(LDPC_ERR_ARG, "max_iter out of range");
     if (cfg->algo != LDPC_ALGO_SP && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED &&
         cfg->algo != LDPC_ALGO_MS_FUSED && cfg->algo != LDPC_ALGO_LAYERED_HOST)
-        return fail(LDPC_ERR_ARG, "unknown algo %d", cfg->algo);
+        return set_error(LDPC_ERR_ARG, "unknown algo %d", cfg->algo);
     /* comparisons written so that NaN fails them */
     if (!(cfg->ms_scale >= 0.0f && cfg->ms_scale <= 1.0f))
-        return fail(LDPC_ERR_ARG, "ms_scale must be 0 (off) or in (0, 1]");
+        return set_error(LDPC_ERR_ARG, "ms_scale must be 0 (off) or in (0, 1]");
     if (!(cfg->ms_offset >= 0.0f && cfg->ms_offset < 1000.0f))
-        return fail(LDPC_ERR_ARG, "ms_offset must be 0 (off) or in (0, 1000)");
+        return set_error(LDPC_ERR_ARG, "ms_offset must be 0 (off) or in (0, 1000)");
     const bool ms_corr = cfg->ms_scale != 0.0f || cfg->ms_offset != 0.0f;
     if (ms_corr && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED)
-        return fail(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset apply to LDPC_ALGO_MS and LDPC_ALGO_LAYERED only "
+        return set_error(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset apply to LDPC_ALGO_MS and LDPC_ALGO_LAYERED only "
                     "(SP has no minimum to correct; MS_FUSED and LAYERED_HOST reproduce reference kernels)");
     if (cfg->algo == LDPC_ALGO_LAYERED_HOST) {
         for (int32_t m = 1; m < g->M; ++m)
             if (g->row_ptr[m + 1] - g->row_ptr[m] != g->row_ptr[1] - g->row_ptr[0])
-                return fail(LDPC_ERR_UNSUPPORTED, "LAYERED_HOST follows the reference's host-layered path, which sizes its "
+                return set_error(LDPC_ERR_UNSUPPORTED, "LAYERED_HOST follows the reference's host-layered path, which sizes its "
                             "layers correctly only when every row of H has the same weight (MyLdpc.cpp:907,958)");
         if (g->max_row_deg > ldpc::kMaxUnrolledLayerDegree)
-            return fail(LDPC_ERR_UNSUPPORTED, "LAYERED_HOST: row weight %d > %d", g->max_row_deg, ldpc::kMaxUnrolledLayerDegree);
+            return set_error(LDPC_ERR_UNSUPPORTED, "LAYERED_HOST: row weight %d > %d", g->max_row_deg, ldpc::kMaxUnrolledLayerDegree);
     }
     if (cfg->pack_mode != LDPC_PACK_BYTES && cfg->pack_mode != LDPC_PACK_BITS)
-        return fail(LDPC_ERR_ARG, "unknown pack_mode %d", cfg->pack_mode);
+        return set_error(LDPC_ERR_ARG, "unknown pack_mode %d", cfg->pack_mode);
     if (cfg->frames_per_lane != 0 && cfg->frames_per_lane != 1 && cfg->frames_per_lane != 2 &&
         cfg->frames_per_lane != 4)
-        return fail(LDPC_ERR_ARG, "frames_per_lane must be 0, 1, 2 or 4");
+        return set_error(LDPC_ERR_ARG, "frames_per_lane must be 0, 1, 2 or 4");
     if (cfg->msg_dtype != LDPC_MSG_F32 && cfg->msg_dtype != LDPC_MSG_F16)
-        return fail(LDPC_ERR_ARG, "unknown msg_dtype %d", cfg->msg_dtype);
+        return set_error(LDPC_ERR_ARG, "unknown msg_dtype %d", cfg->msg_dtype);
     if (cfg->msg_dtype == LDPC_MSG_F16 && cfg->algo != LDPC_ALGO_MS)
-        return fail(LDPC_ERR_UNSUPPORTED, "fp16 messages are built for flooding min-sum only "
+        return set_error(LDPC_ERR_UNSUPPORTED, "fp16 messages are built for flooding min-sum only "
                     "(the probability-domain SP needs fp32 range; layered: not yet)");
-    if (!ldpc::tune_valid(*cfg)) return fail(LDPC_ERR_ARG, "tuning / streams config fields out of range");
+    if (!ldpc::tune_valid(*cfg)) return set_error(LDPC_ERR_ARG, "tuning / streams config fields out of range");
 
     int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
+    LDPC_HIP_TRY(hipGetDeviceCount(&ndev));
     if (cfg->device < 0 || cfg->device >= ndev)
-        return fail(LDPC_ERR_HIP, "device %d not present (%d HIP devices)", cfg->device, ndev);
-    HIP_TRY(hipSetDevice(cfg->device));
+        return set_error(LDPC_ERR_HIP, "device %d not present (%d HIP devices)", cfg->device, ndev);
+    LDPC_HIP_TRY(hipSetDevice(cfg->device));
 
     ldpc_decoder *d = new (std::nothrow) ldpc_decoder;
-    if (!d) return fail(LDPC_ERR_NOMEM, "out of memory");
+    if (!d) return set_error(LDPC_ERR_NOMEM, "out of memory");
     std::unique_ptr<ldpc_decoder> guard(d);
     d->cfg = *cfg;
     d->ms_corr = ms_corr;
@@ -1343,7 +1279,7 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     if (tune.link_rows) d->link_rpw = tune.link_rows < 0 ? 0 : tune.link_rows;
     d->tune_link_guided = tune.link_guided;
     d->tune_tiles_first = tune.tiles_first;
-    HIP_TRY(hipDeviceGetAttribute(&d->cus, hipDeviceAttributeMultiprocessorCount, cfg->device));
+    LDPC_HIP_TRY(hipDeviceGetAttribute(&d->cus, hipDeviceAttributeMultiprocessorCount, cfg->device));
     d->V = pick_frames_per_lane(*cfg, g->max_row_deg, g->max_col_deg);
     d->F = 64 * d->V;
     d->T = (cfg->max_batch + d->F - 1) / d->F;
@@ -1351,16 +1287,16 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
      * chunks per wave, 4.1 -> 3.4 ms for one 50-iteration decode of the (64800, 32400) code */
     if (d->T == 1 && !tune.link_rows) d->link_rpw = 4;
 
-    HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreate(&d->ev_begin));
-    HIP_TRY(hipEventCreate(&d->ev_end));
-    HIP_TRY(hipHostMalloc((void **)&d->h_active, sizeof(int32_t), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void **)&d->h_summary, 2 * sizeof(int32_t), hipHostMallocDefault));
-    HIP_TRY(hipEventCreateWithFlags(&d->ev_summary, hipEventDisableTiming));
-    HIP_TRY(d->row_ptr.upload(g->row_ptr));
-    HIP_TRY(d->edge_col.upload(g->cols));
-    HIP_TRY(d->col_ptr.upload(g->col_ptr));
-    HIP_TRY(d->col_edge.upload(g->col_edge));
+    LDPC_HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+    LDPC_HIP_TRY(hipEventCreate(&d->ev_begin));
+    LDPC_HIP_TRY(hipEventCreate(&d->ev_end));
+    LDPC_HIP_TRY(hipHostMalloc((void **)&d->h_active, sizeof(int32_t), hipHostMallocDefault));
+    LDPC_HIP_TRY(hipHostMalloc((void **)&d->h_summary, 2 * sizeof(int32_t), hipHostMallocDefault));
+    LDPC_HIP_TRY(hipEventCreateWithFlags(&d->ev_summary, hipEventDisableTiming));
+    LDPC_HIP_TRY(d->row_ptr.upload(g->row_ptr));
+    LDPC_HIP_TRY(d->edge_col.upload(g->cols));
+    LDPC_HIP_TRY(d->col_ptr.upload(g->col_ptr));
+    LDPC_HIP_TRY(d->col_edge.upload(g->col_edge));
     /* Device-side tail: for asynchronous callers (poll_interval == 0) of the streaming flooding kernels
      * with early termination, when the batch has clearly more tiles than the overflow area.
      * LDPC_TUNE_OFF(LDPC_TUNE_DEVICE_TAIL) switches it off. */
@@ -1370,48 +1306,48 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     if (!d->tail_enabled) d->TO = 0;
     d->TA = d->T + d->TO;
     const size_t TF = (size_t)d->TA * d->F;
-    HIP_TRY(d->hard.alloc((size_t)d->TA * d->N * d->V));
-    HIP_TRY(d->failw.alloc((size_t)(cfg->max_iter + 2) * d->TA * d->V));
-    HIP_TRY(d->done.alloc((size_t)d->TA * d->V));
-    HIP_TRY(d->iters.alloc(TF));
-    HIP_TRY(d->active.alloc(1));
-    HIP_TRY(d->summary.alloc(4));
+    LDPC_HIP_TRY(d->hard.alloc((size_t)d->TA * d->N * d->V));
+    LDPC_HIP_TRY(d->failw.alloc((size_t)(cfg->max_iter + 2) * d->TA * d->V));
+    LDPC_HIP_TRY(d->done.alloc((size_t)d->TA * d->V));
+    LDPC_HIP_TRY(d->iters.alloc(TF));
+    LDPC_HIP_TRY(d->active.alloc(1));
+    LDPC_HIP_TRY(d->summary.alloc(4));
 
     if (cfg->algo == LDPC_ALGO_MS_FUSED) {
         if (cfg->pack_mode != LDPC_PACK_BYTES && cfg->K % 8)
-            return fail(LDPC_ERR_UNSUPPORTED, "MS_FUSED packs whole bytes per frame only");
+            return set_error(LDPC_ERR_UNSUPPORTED, "MS_FUSED packs whole bytes per frame only");
         /* flood_ldsp_kernel<.., CHAIN = false> (posteriors in LDS, 16-byte check records) wherever it fits
          * with two workgroups per CU, else / with LDPC_TUNE_OFF(LDPC_TUNE_LDSP) the LDS-resident fused_flood_kernel */
         if (!ldpc::tune_forced_off(tune.ldsp)) {
-            HIP_TRY(ldpc::engine_ldsp_plan_create(&d->ldsp, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows, cfg->K,
+            LDPC_HIP_TRY(ldpc::engine_ldsp_plan_create(&d->ldsp, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows, cfg->K,
                                            cfg->max_batch, cfg->device, tune, /*flood=*/2));
             if (d->ldsp.eligible && (ldpc::tune_forced_on(tune.ldsp) || d->ldsp.lds_bytes <= 80 * 1024)) d->use_ldsp = true;
-            else ldpc::ldsp_plan_destroy(&d->ldsp);
+            else d->ldsp = ldpc::LdspPlan();
         }
         if (!d->use_ldsp) {
-            HIP_TRY(ldpc::fused_plan_create(&d->fused, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows));
+            LDPC_HIP_TRY(ldpc::fused_plan_create(&d->fused, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows));
             if (!d->fused.eligible)
-                return fail(LDPC_ERR_UNSUPPORTED, "MS_FUSED needs a quasi-cyclic H (circulant size = layer_rows) whose "
+                return set_error(LDPC_ERR_UNSUPPORTED, "MS_FUSED needs a quasi-cyclic H (circulant size = layer_rows) whose "
                             "posteriors fit in LDS");
         }
         d->use_fused = true;
     } else if (cfg->algo == LDPC_ALGO_LAYERED_HOST) {
         d->layered.host_arith = 1;
         int rc = ldpc::layered_plan_create(&d->layered, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows, d->T, d->V);
-        if (rc == -1) return fail(LDPC_ERR_ARG, "layer_rows=%d must divide M=%d and rows of a layer "
+        if (rc == -1) return set_error(LDPC_ERR_ARG, "layer_rows=%d must divide M=%d and rows of a layer "
                                   "must not share a column", cfg->layer_rows, g->M);
-        if (rc) return fail(LDPC_ERR_HIP, "layered plan allocation failed: %s", hipGetErrorString(hipGetLastError()));
+        if (rc) return set_error(LDPC_ERR_HIP, "layered plan allocation failed: %s", hipGetErrorString(hipGetLastError()));
     } else if (cfg->algo == LDPC_ALGO_LAYERED) {
         /* short quasi-cyclic codes decode entirely in LDS, one launch (fused_kernels.hpp);
          * LDPC_TUNE_OFF(LDPC_TUNE_FUSED) keeps the streaming kernels (same results, bit for bit) */
         /* the correction (ms_scale / ms_offset) is carried by the record kernel (layered_ldsp_corr_kernel) and the
          * streaming one (layer_corr_kernel), not by the LDS-resident fused_layered_kernel */
         if (d->ms_corr && ldpc::tune_forced_on(tune.fused) && ldpc::tune_forced_off(tune.ldsp))
-            return fail(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset: the LDS-resident layered kernel (LDPC_TUNE_FUSED on, "
+            return set_error(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset: the LDS-resident layered kernel (LDPC_TUNE_FUSED on, "
                         "LDPC_TUNE_LDSP off) carries no correction; the record or the streaming kernels do");
         if (!ldpc::tune_forced_off(tune.fused) && (cfg->pack_mode == LDPC_PACK_BYTES || cfg->K % 8 == 0)) {
             if (!d->ms_corr) {
-                HIP_TRY(ldpc::fused_plan_create(&d->fused, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows));
+                LDPC_HIP_TRY(ldpc::fused_plan_create(&d->fused, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows));
                 d->use_fused = d->fused.eligible;
             }
             /* layered_ldsp_kernel (posterior in LDS, 16-byte check records in cache) is the default for
@@ -1422,7 +1358,7 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
             if (!ldpc::tune_forced_off(tune.ldsp)) {
                 d->ldsp.corr = d->ms_corr;
                 d->ldsp.mc = ldpc::MsCorr{d->ms_scale, d->ms_offset};
-                HIP_TRY(ldpc::engine_ldsp_plan_create(&d->ldsp, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows,
+                LDPC_HIP_TRY(ldpc::engine_ldsp_plan_create(&d->ldsp, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows,
                                                cfg->K, cfg->max_batch, cfg->device, tune, /*flood=*/0));
                 if (d->ldsp.eligible) d->use_fused = d->use_ldsp = true;
             }
@@ -1434,9 +1370,9 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         d->layered.ms_offset = d->ms_offset;
         int rc = d->use_fused ? 0 : ldpc::layered_plan_create(&d->layered, g->M, g->N, g->E, g->row_ptr, g->cols,
                                                               cfg->layer_rows, d->T, d->V);
-        if (rc == -1) return fail(LDPC_ERR_ARG, "layer_rows=%d must divide M=%d and rows of a layer "
+        if (rc == -1) return set_error(LDPC_ERR_ARG, "layer_rows=%d must divide M=%d and rows of a layer "
                                   "must not share a column", cfg->layer_rows, g->M);
-        if (rc) return fail(LDPC_ERR_HIP, "layered plan allocation failed: %s",
+        if (rc) return set_error(LDPC_ERR_HIP, "layered plan allocation failed: %s",
                             hipGetErrorString(hipGetLastError()));
     } else {
         /* flooding min-sum on a short quasi-cyclic code (layer_rows = circulant size given): the
@@ -1448,13 +1384,13 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         /* the correction (ms_scale / ms_offset) is carried by the record kernel (flood_ldsp_corr_kernel) and the streaming
          * kernels (kAlgoMSC), not by the LDS-resident fused_flood_kernel */
         if (d->ms_corr && ldpc::tune_forced_on(tune.fused) && ldpc::tune_forced_off(tune.ldsp))
-            return fail(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset: the LDS-resident flooding kernel (LDPC_TUNE_FUSED on, "
+            return set_error(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset: the LDS-resident flooding kernel (LDPC_TUNE_FUSED on, "
                         "LDPC_TUNE_LDSP off) carries no correction; the record or the streaming kernels do");
         if (cfg->msg_dtype == LDPC_MSG_F32 && cfg->layer_rows > 0 && cfg->frames_per_lane == 0 &&
             (cfg->pack_mode == LDPC_PACK_BYTES || cfg->K % 8 == 0)) {
             const bool small = (int64_t)cfg->max_batch * g->E <= (int64_t)1 << 23;
             if (!d->ms_corr && ldpc::tune_pick(tune.fused, small)) {
-                HIP_TRY(ldpc::fused_plan_create(&d->fused, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows));
+                LDPC_HIP_TRY(ldpc::fused_plan_create(&d->fused, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows));
                 d->use_fused = d->fused.eligible && (cfg->algo == LDPC_ALGO_MS || d->fused.eligible_sp);
             }
             /* min-sum: posteriors in LDS (two images), one 16-byte record per check row (flood_ldsp_kernel).
@@ -1465,12 +1401,12 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
             if (cfg->algo == LDPC_ALGO_MS && !ldpc::tune_forced_off(tune.fused) && !ldpc::tune_forced_off(tune.ldsp)) {
                 d->ldsp.corr = d->ms_corr;
                 d->ldsp.mc = ldpc::MsCorr{d->ms_scale, d->ms_offset};
-                HIP_TRY(ldpc::engine_ldsp_plan_create(&d->ldsp, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows,
+                LDPC_HIP_TRY(ldpc::engine_ldsp_plan_create(&d->ldsp, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows,
                                                cfg->K, cfg->max_batch, cfg->device, tune, /*flood=*/1));
                 if (d->ldsp.eligible && (ldpc::tune_forced_on(tune.ldsp) || d->ldsp.lds_bytes <= 80 * 1024))
                     d->use_fused = d->use_ldsp = true;
                 else
-                    ldpc::ldsp_plan_destroy(&d->ldsp);
+                    d->ldsp = ldpc::LdspPlan();
             }
         }
         if (!d->use_fused) {
@@ -1486,9 +1422,9 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
                 if (rc) return rc;
             }
             if (d->tail_enabled) {
-                HIP_TRY(d->tail_state.alloc(4));
-                HIP_TRY(d->tail_map.alloc((size_t)d->TO * d->F));
-                HIP_TRY(d->running.alloc((size_t)cfg->max_iter + 2));
+                LDPC_HIP_TRY(d->tail_state.alloc(4));
+                LDPC_HIP_TRY(d->tail_map.alloc((size_t)d->TO * d->F));
+                LDPC_HIP_TRY(d->running.alloc((size_t)cfg->max_iter + 2));
             }
             /* tail compaction: with host polling on, the last <= 512 running frames of a batch of several
              * tiles are finished by a small (8 x 64 frames) child decoder (cfg.tune_compact = -1: off, n: threshold) */
@@ -1516,10 +1452,10 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
                 --t_child_depth;
                 if (rc) return rc;
                 d->child->is_child = true;
-                HIP_TRY(hipSetDevice(cfg->device));
-                HIP_TRY(d->cmap.alloc((size_t)d->child_capacity));
-                HIP_TRY(d->cinv.alloc((size_t)d->T * d->F));
-                HIP_TRY(d->cmoved.alloc((size_t)d->T * d->V));
+                LDPC_HIP_TRY(hipSetDevice(cfg->device));
+                LDPC_HIP_TRY(d->cmap.alloc((size_t)d->child_capacity));
+                LDPC_HIP_TRY(d->cinv.alloc((size_t)d->T * d->F));
+                LDPC_HIP_TRY(d->cmoved.alloc((size_t)d->T * d->V));
             }
         }
     }
@@ -1545,16 +1481,11 @@ int ldpc_decoder_destroy(ldpc_decoder *d)
     /* blocks of caller memory an LDPC_HOST_INPUT_LOCK_PAGES call could not release: said loudly, here too */
     size_t stuck = d->stuck_blocks.size() + d->locked_blocks.size();
     for (ldpc_decoder *sh : d->shards) stuck += sh->stuck_blocks.size() + sh->locked_blocks.size();
-    if (d->shards.empty()) {
-        wait_for_own_work(d);
-        ldpc::layered_plan_destroy(&d->layered);
-        ldpc::fused_plan_destroy(&d->fused);
-        ldpc::ldsp_plan_destroy(&d->ldsp);
-    }
+    if (d->shards.empty()) wait_for_own_work(d);    /* the buffers go only after the handle's streams have drained */
     delete d;            /* joins the handle's threads; a multi-device handle destroys its per-device decoders here */
     if (stuck) {
         fprintf(stderr, "ldpc_decoder_destroy: %zu page-locked block(s) of caller memory were never released\n", stuck);
-        return fail(LDPC_ERR_STATE, "%zu page-locked block(s) of caller memory could not be released "
+        return set_error(LDPC_ERR_STATE, "%zu page-locked block(s) of caller memory could not be released "
                     "(hipHostUnregister failed in an earlier ldpc_decode)", stuck);
     }
     return LDPC_OK;
@@ -1562,9 +1493,9 @@ int ldpc_decoder_destroy(ldpc_decoder *d)
 
 int ldpc_shard_range(int64_t frames, int32_t part, int32_t parts, int32_t unit, int64_t *lo, int64_t *hi)
 {
-    if (!lo || !hi) return fail(LDPC_ERR_ARG, "lo/hi is NULL");
+    if (!lo || !hi) return set_error(LDPC_ERR_ARG, "lo/hi is NULL");
     if (frames < 0 || parts <= 0 || part < 0 || part >= parts || unit <= 0)
-        return fail(LDPC_ERR_ARG, "shard_range(frames=%lld, part=%d, parts=%d, unit=%d)", (long long)frames, part, parts, unit);
+        return set_error(LDPC_ERR_ARG, "shard_range(frames=%lld, part=%d, parts=%d, unit=%d)", (long long)frames, part, parts, unit);
     const int64_t nu = (frames + unit - 1) / unit, base = nu / parts, rem = nu % parts;
     const int64_t lo_u = part * base + std::min<int64_t>(part, rem);
     const int64_t hi_u = lo_u + base + (part < rem ? 1 : 0);
@@ -1576,15 +1507,15 @@ int ldpc_shard_range(int64_t frames, int32_t part, int32_t parts, int32_t unit, 
 int ldpc_decoder_create_multi(const ldpc_graph *g, const ldpc_decoder_config *cfg, const int32_t *devices,
                               int32_t n_devices, ldpc_decoder **out)
 {
-    if (!out) return fail(LDPC_ERR_ARG, "out is NULL");
+    if (!out) return set_error(LDPC_ERR_ARG, "out is NULL");
     *out = nullptr;
-    if (!g || !cfg) return fail(LDPC_ERR_ARG, "graph/config is NULL");
-    if (!devices || n_devices <= 0 || n_devices > 64) return fail(LDPC_ERR_ARG, "devices[] must hold 1..64 ordinals");
+    if (!g || !cfg) return set_error(LDPC_ERR_ARG, "graph/config is NULL");
+    if (!devices || n_devices <= 0 || n_devices > 64) return set_error(LDPC_ERR_ARG, "devices[] must hold 1..64 ordinals");
     ldpc_decoder_config cfg_full;
     if (int rc = config_in(cfg, &cfg_full)) return rc;
     cfg = &cfg_full;
     ldpc_decoder *grp = new (std::nothrow) ldpc_decoder;
-    if (!grp) return fail(LDPC_ERR_NOMEM, "out of memory");
+    if (!grp) return set_error(LDPC_ERR_NOMEM, "out of memory");
     std::unique_ptr<ldpc_decoder> guard(grp);
     for (int32_t i = 0; i < n_devices; ++i) {
         ldpc_decoder_config c = *cfg;
@@ -1596,7 +1527,7 @@ int ldpc_decoder_create_multi(const ldpc_graph *g, const ldpc_decoder_config *cf
         /* the host thread that runs this device's frame range in every ldpc_decode of the handle */
         grp->shard_workers.emplace_back(new (std::nothrow) ldpc::Worker([] { return g_err; }));
         if (!grp->shard_workers.back() || !grp->shard_workers.back()->start())
-            return fail(LDPC_ERR_NOMEM, "cannot start the host thread of device-list entry %d", i);
+            return set_error(LDPC_ERR_NOMEM, "cannot start the host thread of device-list entry %d", i);
     }
     grp->cfg = *cfg;
     grp->cfg.device = devices[0];
@@ -1608,30 +1539,30 @@ int ldpc_decoder_create_multi(const ldpc_graph *g, const ldpc_decoder_config *cf
 int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, uint8_t *out_dev,
                        int64_t out_bytes, int32_t *iters_dev, void *stream)
 {
-    if (!d) return fail(LDPC_ERR_ARG, "decoder is NULL");
+    if (!d) return set_error(LDPC_ERR_ARG, "decoder is NULL");
     if (!d->shards.empty())
-        return fail(LDPC_ERR_STATE, "a multi-device handle decodes host buffers only (ldpc_decode): device "
+        return set_error(LDPC_ERR_STATE, "a multi-device handle decodes host buffers only (ldpc_decode): device "
                     "pointers belong to one device");
     if (frames < 0 || frames > d->cfg.max_batch)
-        return fail(LDPC_ERR_ARG, "frames=%lld outside [0, max_batch=%d]", (long long)frames,
+        return set_error(LDPC_ERR_ARG, "frames=%lld outside [0, max_batch=%d]", (long long)frames,
                     d->cfg.max_batch);
-    if (out_bytes < 0) return fail(LDPC_ERR_ARG, "out_bytes < 0");
+    if (out_bytes < 0) return set_error(LDPC_ERR_ARG, "out_bytes < 0");
     if (frames == 0) { d->last_frames = 0; d->have_last = false; return LDPC_OK; }
-    if (!llr_dev) return fail(LDPC_ERR_ARG, "llr is NULL");
+    if (!llr_dev) return set_error(LDPC_ERR_ARG, "llr is NULL");
     const int64_t need = ldpc_out_bytes(d->cfg.K, frames, d->cfg.pack_mode);
     /* bytes this call may store: none without out_dev (iteration counts and stats only) */
     const int64_t room = out_dev ? std::min(out_bytes, need) : 0;
     if (out_dev && out_bytes < need && d->cfg.pack_mode == LDPC_PACK_BITS)
-        return fail(LDPC_ERR_ARG, "out_bytes=%lld < %lld", (long long)out_bytes, (long long)need);
-    HIP_TRY(hipSetDevice(d->cfg.device));
+        return set_error(LDPC_ERR_ARG, "out_bytes=%lld < %lld", (long long)out_bytes, (long long)need);
+    LDPC_HIP_TRY(hipSetDevice(d->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     d->timing = d->timing_every > 0 && (d->timing_calls++ % d->timing_every) == 0;
     d->last_stream = s;
     d->last_frames = frames;
     d->call.valid = false;          /* ldpc_decode() sets it again once all its groups are in */
-    HIP_TRY(hipEventRecord(d->ev_begin, s));
+    LDPC_HIP_TRY(hipEventRecord(d->ev_begin, s));
     /* gaps between frames (K % 8 != 0, decodeCL.c:191-192 leaves them alone) read as 0 */
-    if (out_dev) HIP_TRY(hipMemsetAsync(out_dev, 0, (size_t)room, s));
+    if (out_dev) LDPC_HIP_TRY(hipMemsetAsync(out_dev, 0, (size_t)room, s));
     int rc;
     if (d->use_fused) {
         ldpc::FusedRun run{llr_dev, frames, out_dev, room, iters_dev, d->cfg.K,
@@ -1644,7 +1575,7 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
             e = d->use_ldsp ? ldpc::engine_ldsp_run(&d->ldsp, run, s, &d->last_iterations)
                             : ldpc::engine_fused_run(&d->fused, run, s, &d->last_iterations);
         if (e == hipSuccess) e = span_end(d, s);
-        rc = (e == hipSuccess) ? LDPC_OK : fail(LDPC_ERR_HIP, "fused decode: %s", hipGetErrorString(e));
+        rc = (e == hipSuccess) ? LDPC_OK : set_error(LDPC_ERR_HIP, "fused decode: %s", hipGetErrorString(e));
     } else if (d->cfg.algo == LDPC_ALGO_LAYERED || d->cfg.algo == LDPC_ALGO_LAYERED_HOST) {
         ldpc::LayeredRun run;
         run.span_begin = [](void *c, hipStream_t st, int kind, int deg, int64_t bytes) {
@@ -1660,12 +1591,12 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
         run.row_ptr = d->row_ptr.p; run.edge_col = d->edge_col.p; run.summary = d->summary.p;
         hipError_t e = ldpc::engine_layered_run(&d->layered, run, s, &d->last_iterations);
         rc = (e == hipSuccess) ? LDPC_OK
-                               : fail(LDPC_ERR_HIP, "layered decode: %s", hipGetErrorString(e));
+                               : set_error(LDPC_ERR_HIP, "layered decode: %s", hipGetErrorString(e));
     } else if (d->V == 1) rc = run_flooding<1>(d, llr_dev, frames, out_dev, room, iters_dev, s);
     else if (d->V == 2) rc = run_flooding<2>(d, llr_dev, frames, out_dev, room, iters_dev, s);
     else rc = run_flooding<4>(d, llr_dev, frames, out_dev, room, iters_dev, s);
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(d->ev_end, s));
+    LDPC_HIP_TRY(hipEventRecord(d->ev_end, s));
     d->have_last = true;
     return LDPC_OK;
 }
@@ -1701,18 +1632,18 @@ int ensure_stager(ldpc_decoder *d)
     if (d->stager) return LDPC_OK;
     if (d->ring.empty()) d->ring.resize(kRingChunks);
     for (auto &c : d->ring) {
-        if (!c.h) HIP_TRY(hipHostMalloc((void **)&c.h, kRingChunk, hipHostMallocDefault));
-        if (!c.ev) HIP_TRY(hipEventCreateWithFlags(&c.ev, hipEventDisableTiming));
+        if (!c.h) LDPC_HIP_TRY(hipHostMalloc((void **)&c.h, kRingChunk, hipHostMallocDefault));
+        if (!c.ev) LDPC_HIP_TRY(hipEventCreateWithFlags(&c.ev, hipEventDisableTiming));
     }
     const int threads = d->cfg.host_copy_threads > 0 ? d->cfg.host_copy_threads : 4;
     while ((int)d->copy_helpers.size() < threads - 1) {
         std::unique_ptr<ldpc::Worker> w(new (std::nothrow) ldpc::Worker([] { return g_err; }));
-        if (!w || !w->start()) return fail(LDPC_ERR_NOMEM, "cannot start a copy thread");
+        if (!w || !w->start()) return set_error(LDPC_ERR_NOMEM, "cannot start a copy thread");
         d->copy_helpers.push_back(std::move(w));
     }
     d->copy_jobs.resize(d->copy_helpers.size());
     std::unique_ptr<ldpc::Worker> st(new (std::nothrow) ldpc::Worker([] { return g_err; }));
-    if (!st || !st->start()) return fail(LDPC_ERR_NOMEM, "cannot start the staging thread");
+    if (!st || !st->start()) return set_error(LDPC_ERR_NOMEM, "cannot start the staging thread");
     d->stager = std::move(st);
     return LDPC_OK;
 }
@@ -1761,7 +1692,7 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
                 int64_t out_bytes, int32_t *iters, InputMode mode)
 {
     const int64_t total = ldpc_out_bytes(d->cfg.K, frames, d->cfg.pack_mode);
-    HIP_TRY(hipSetDevice(d->cfg.device));
+    LDPC_HIP_TRY(hipSetDevice(d->cfg.device));
     int64_t B = d->cfg.max_batch;
     /* A large call that is ONE launch group is cut into two: the second half's channel values travel while the first
      * half is decoded (one group exposes its whole copy: 21 ms of PCIe in front of a 94 ms decode for 4096 frames of the
@@ -1771,7 +1702,7 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
         (size_t)frames * d->N * sizeof(float) >= ((size_t)256 << 20))
         B = ((frames + 1) / 2 + 255) / 256 * 256;
     if (d->cfg.pack_mode == LDPC_PACK_BITS && (d->cfg.K % 8) && frames > B)
-        return fail(LDPC_ERR_UNSUPPORTED, "bit-packed output with K %% 8 != 0 cannot be chunked: "
+        return set_error(LDPC_ERR_UNSUPPORTED, "bit-packed output with K %% 8 != 0 cannot be chunked: "
                     "raise max_batch to cover all %lld frames", (long long)frames);
     const int64_t Bmax = d->cfg.max_batch;      /* the slots hold a full group whatever this call's groups are */
     const int64_t stage_out = ldpc_out_bytes(d->cfg.K, Bmax, d->cfg.pack_mode) + 8;
@@ -1780,18 +1711,18 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
      * results are copied out */
     const int nslots = frames > B ? 3 : 1;
     const int64_t ngroups = (frames + B - 1) / B;
-    if (!d->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&d->copy_stream, hipStreamNonBlocking));
+    if (!d->copy_stream) LDPC_HIP_TRY(hipStreamCreateWithFlags(&d->copy_stream, hipStreamNonBlocking));
     for (int i = 0; i < nslots; ++i) {
         auto &sl = d->slot[i];
-        if (!sl.llr.p) HIP_TRY(sl.llr.alloc((size_t)Bmax * d->N));
-        if (!sl.out.p) HIP_TRY(sl.out.alloc((size_t)stage_out));
-        if (!sl.iters.p) HIP_TRY(sl.iters.alloc((size_t)Bmax));
-        if (!sl.h_out) HIP_TRY(hipHostMalloc((void **)&sl.h_out, (size_t)stage_out, hipHostMallocDefault));
-        if (!sl.h_iters) HIP_TRY(hipHostMalloc((void **)&sl.h_iters, (size_t)Bmax * sizeof(int32_t), hipHostMallocDefault));
-        if (!sl.h_head) HIP_TRY(hipHostMalloc((void **)&sl.h_head, kStageBytes, hipHostMallocDefault));
-        if (!sl.h_sum) HIP_TRY(hipHostMalloc((void **)&sl.h_sum, 16 * sizeof(int32_t), hipHostMallocDefault));
-        if (!sl.h2d_done) HIP_TRY(hipEventCreateWithFlags(&sl.h2d_done, hipEventDisableTiming));
-        if (!sl.all_done) HIP_TRY(hipEventCreateWithFlags(&sl.all_done, hipEventDisableTiming));
+        if (!sl.llr.p) LDPC_HIP_TRY(sl.llr.alloc((size_t)Bmax * d->N));
+        if (!sl.out.p) LDPC_HIP_TRY(sl.out.alloc((size_t)stage_out));
+        if (!sl.iters.p) LDPC_HIP_TRY(sl.iters.alloc((size_t)Bmax));
+        if (!sl.h_out) LDPC_HIP_TRY(hipHostMalloc((void **)&sl.h_out, (size_t)stage_out, hipHostMallocDefault));
+        if (!sl.h_iters) LDPC_HIP_TRY(hipHostMalloc((void **)&sl.h_iters, (size_t)Bmax * sizeof(int32_t), hipHostMallocDefault));
+        if (!sl.h_head) LDPC_HIP_TRY(hipHostMalloc((void **)&sl.h_head, kStageBytes, hipHostMallocDefault));
+        if (!sl.h_sum) LDPC_HIP_TRY(hipHostMalloc((void **)&sl.h_sum, 16 * sizeof(int32_t), hipHostMallocDefault));
+        if (!sl.h2d_done) LDPC_HIP_TRY(hipEventCreateWithFlags(&sl.h2d_done, hipEventDisableTiming));
+        if (!sl.all_done) LDPC_HIP_TRY(hipEventCreateWithFlags(&sl.all_done, hipEventDisableTiming));
     }
     if (mode != kInputDirect && (size_t)std::min(B, frames) * d->N * sizeof(float) > kStageBytes) {
         const int rs = ensure_stager(d);
@@ -1804,7 +1735,7 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
     auto drain = [&](ldpc_decoder::HostSlot &sl) -> int {
         if (!sl.busy) return LDPC_OK;
         sl.busy = false;
-        HIP_TRY(hipEventSynchronize(sl.all_done));
+        LDPC_HIP_TRY(hipEventSynchronize(sl.all_done));
         if (sl.copy_bytes > 0) memcpy(out_host + sl.dst, sl.h_out, (size_t)sl.copy_bytes);
         if (iters) memcpy(iters + sl.off, sl.h_iters, (size_t)sl.n * sizeof(int32_t));
         /* the call's counts: sums over its groups, maxima for the iteration numbers (as ldpc_decoder_stats forms them) */
@@ -1855,7 +1786,7 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
                 if (je == hipSuccess) je = staged_copy(d, dst, src, bytes);
                 if (je == hipSuccess) je = hipEventRecord(done, d->copy_stream);
                 return je == hipSuccess ? LDPC_OK
-                                        : fail(LDPC_ERR_HIP, "staging through the pinned ring: %s", hipGetErrorString(je));
+                                        : set_error(LDPC_ERR_HIP, "staging through the pinned ring: %s", hipGetErrorString(je));
             };
             d->stager->submit(&job);
             d->stage_pending[si] = true;
@@ -1887,7 +1818,7 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
             }
         }
         if (e == hipSuccess) e = hipEventRecord(sl.h2d_done, d->copy_stream);
-        if (e != hipSuccess) return fail(LDPC_ERR_HIP, "host-to-device staging: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return set_error(LDPC_ERR_HIP, "host-to-device staging: %s", hipGetErrorString(e));
         LDPC_STAMP("H2D enqueued", kk);
         return LDPC_OK;
     };
@@ -1907,7 +1838,7 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
         if (k + 1 < ngroups && (rc = stage_in(k + 1))) break;   /* runs beside this group's decode */
         if ((rc = staged_ready(si))) break;
         hipError_t e = hipStreamWaitEvent(d->stream, sl.h2d_done, 0);
-        if (e != hipSuccess) { rc = fail(LDPC_ERR_HIP, "host-to-device staging: %s", hipGetErrorString(e)); break; }
+        if (e != hipSuccess) { rc = set_error(LDPC_ERR_HIP, "host-to-device staging: %s", hipGetErrorString(e)); break; }
         const int64_t chunk_bytes = ldpc_out_bytes(d->cfg.K, n, d->cfg.pack_mode);
         rc = ldpc_decode_device(d, sl.llr.p, n, sl.out.p, chunk_bytes, iters ? sl.iters.p : nullptr, d->stream);
         if (rc) break;
@@ -1928,7 +1859,7 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
             ++sl.g_children;
         }
         if (e == hipSuccess) e = hipEventRecord(sl.all_done, d->stream);
-        if (e != hipSuccess) { rc = fail(LDPC_ERR_HIP, "device-to-host staging: %s", hipGetErrorString(e)); break; }
+        if (e != hipSuccess) { rc = set_error(LDPC_ERR_HIP, "device-to-host staging: %s", hipGetErrorString(e)); break; }
         sl.busy = true;
     }
 #undef LDPC_STAMP
@@ -1946,7 +1877,7 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
     const hipError_t es2 = hipStreamSynchronize(d->stream);
     if (es == hipSuccess) es = es2;
     if (es != hipSuccess && rc == LDPC_OK) {
-        rc = fail(LDPC_ERR_HIP, "ldpc_decode: draining the streams: %s", hipGetErrorString(es));
+        rc = set_error(LDPC_ERR_HIP, "ldpc_decode: draining the streams: %s", hipGetErrorString(es));
         first_error = g_err;
     }
     /* lock mode: the pages go back to the caller; a block that cannot be released stays on record */
@@ -1955,7 +1886,7 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
         if (eu == hipSuccess) continue;
         d->stuck_blocks.push_back(p);
         if (rc == LDPC_OK) {
-            rc = fail(LDPC_ERR_HIP, "hipHostUnregister(%p) failed: %s -- the block stays page-locked and on this "
+            rc = set_error(LDPC_ERR_HIP, "hipHostUnregister(%p) failed: %s -- the block stays page-locked and on this "
                       "library's record", p, hipGetErrorString(eu));
             first_error = g_err;
         }
@@ -1989,11 +1920,11 @@ int32_t shard_unit(const ldpc_decoder_config &cfg, int64_t frames)
 int ldpc_decode(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t *out_host,
                 int64_t out_bytes, int32_t *iters)
 {
-    if (!d) return fail(LDPC_ERR_ARG, "decoder is NULL");
-    if (frames < 0) return fail(LDPC_ERR_ARG, "frames < 0");
+    if (!d) return set_error(LDPC_ERR_ARG, "decoder is NULL");
+    if (frames < 0) return set_error(LDPC_ERR_ARG, "frames < 0");
     if (frames == 0) return LDPC_OK;
-    if (!llr_host || !out_host) return fail(LDPC_ERR_ARG, "llr/out is NULL");
-    if (out_bytes < 0) return fail(LDPC_ERR_ARG, "out_bytes < 0");
+    if (!llr_host || !out_host) return set_error(LDPC_ERR_ARG, "llr/out is NULL");
+    if (out_bytes < 0) return set_error(LDPC_ERR_ARG, "out_bytes < 0");
     /* asked once, before any thread touches the buffer */
     const InputMode mode = resolve_input_mode(d->cfg, llr_host, (size_t)frames * d->N * sizeof(float));
     if (d->shards.empty()) return decode_host(d, llr_host, frames, out_host, out_bytes, iters, mode);
@@ -2036,9 +1967,9 @@ int ldpc_decode(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
 
 int ldpc_host_block_plan(uint64_t base, int64_t frames, int32_t N, int32_t max_batch, int64_t group, uint64_t out[6])
 {
-    if (!out) return fail(LDPC_ERR_ARG, "out is NULL");
+    if (!out) return set_error(LDPC_ERR_ARG, "out is NULL");
     if (frames <= 0 || N <= 0 || max_batch <= 0 || group < 0 || group * (int64_t)max_batch >= frames)
-        return fail(LDPC_ERR_ARG, "block_plan(frames=%lld, N=%d, max_batch=%d, group=%lld)", (long long)frames, N, max_batch,
+        return set_error(LDPC_ERR_ARG, "block_plan(frames=%lld, N=%d, max_batch=%d, group=%lld)", (long long)frames, N, max_batch,
                     (long long)group);
     const ldpc::GroupBlocks g = ldpc::plan_group_blocks((uintptr_t)base, frames, N, max_batch, group);
     out[0] = g.s0; out[1] = g.s1; out[2] = g.b0; out[3] = g.b1; out[4] = g.body_end; out[5] = g.whole_by_cpu ? 1 : 0;
@@ -2054,7 +1985,7 @@ int ldpc_host_locked_ranges(int64_t *live, int64_t *stale)
 
 int ldpc_decoder_set_timing(ldpc_decoder *d, int enable)
 {
-    if (!d) return fail(LDPC_ERR_ARG, "decoder is NULL");
+    if (!d) return set_error(LDPC_ERR_ARG, "decoder is NULL");
     if (!d->shards.empty()) {
         for (ldpc_decoder *sh : d->shards) {
             const int rc = ldpc_decoder_set_timing(sh, enable);
@@ -2063,8 +1994,8 @@ int ldpc_decoder_set_timing(ldpc_decoder *d, int enable)
         return LDPC_OK;
     }
     if (d->have_last) {   /* events of earlier calls may still be pending */
-        HIP_TRY(hipSetDevice(d->cfg.device));
-        HIP_TRY(hipEventSynchronize(d->ev_end));
+        LDPC_HIP_TRY(hipSetDevice(d->cfg.device));
+        LDPC_HIP_TRY(hipEventSynchronize(d->ev_end));
     }
     d->timing_every = enable > 0 ? enable : 0;
     d->timing_calls = 0;
@@ -2075,9 +2006,9 @@ int ldpc_decoder_set_timing(ldpc_decoder *d, int enable)
 
 int ldpc_decoder_stats(ldpc_decoder *d, ldpc_decode_stats *st)
 {
-    if (!d || !st) return fail(LDPC_ERR_ARG, "decoder/stats is NULL");
+    if (!d || !st) return set_error(LDPC_ERR_ARG, "decoder/stats is NULL");
     memset(st, 0, sizeof *st);
-    if (!d->have_last) return fail(LDPC_ERR_STATE, "no decode call to report on");
+    if (!d->have_last) return set_error(LDPC_ERR_STATE, "no decode call to report on");
     if (!d->shards.empty()) {
         /* the devices ran side by side: counts add up, times and iteration numbers take the maximum.
          * Each device's counts cover all launch groups of its range, its times the last group. */
@@ -2097,13 +2028,13 @@ int ldpc_decoder_stats(ldpc_decoder *d, ldpc_decode_stats *st)
         }
         return LDPC_OK;
     }
-    HIP_TRY(hipSetDevice(d->cfg.device));
-    HIP_TRY(hipEventSynchronize(d->ev_end));
+    LDPC_HIP_TRY(hipSetDevice(d->cfg.device));
+    LDPC_HIP_TRY(hipEventSynchronize(d->ev_end));
     st->iterations_launched = d->last_iterations;
     st->frames = d->last_frames;
-    HIP_TRY(hipEventElapsedTime(&st->ms_total, d->ev_begin, d->ev_end));
+    LDPC_HIP_TRY(hipEventElapsedTime(&st->ms_total, d->ev_begin, d->ev_end));
     int32_t summary[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpy(summary, d->summary.p, sizeof summary, hipMemcpyDeviceToHost));
+    LDPC_HIP_TRY(hipMemcpy(summary, d->summary.p, sizeof summary, hipMemcpyDeviceToHost));
     st->batch_time = summary[0];
     st->frames_converged = summary[1];
     /* frame-rounds the message kernels really worked on (tiles that were finished when a round began leave
@@ -2115,7 +2046,7 @@ int ldpc_decoder_stats(ldpc_decoder *d, ldpc_decode_stats *st)
                                              : (int64_t)d->last_iterations * d->last_tiles * d->F;
         for (const ldpc_decoder *p = d->handed_to; p; p = p->handed_to) {      /* the child, and whom it handed over to */
             int32_t cs[4] = {0, 0, 0, 0};
-            HIP_TRY(hipMemcpy(cs, p->summary.p, sizeof cs, hipMemcpyDeviceToHost));
+            LDPC_HIP_TRY(hipMemcpy(cs, p->summary.p, sizeof cs, hipMemcpyDeviceToHost));
             st->frame_rounds += (int64_t)cs[2] * p->F;
         }
     }
@@ -2128,7 +2059,7 @@ int ldpc_decoder_stats(ldpc_decoder *d, ldpc_decode_stats *st)
     }
     for (size_t i = 0; i < d->spans_used; ++i) {
         float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, d->spans[i].a, d->spans[i].b));
+        LDPC_HIP_TRY(hipEventElapsedTime(&ms, d->spans[i].a, d->spans[i].b));
         const int kind = d->spans[i].kind;
         if (kind == 0 || kind == 4 || kind == 5) { st->ms_check += ms; ++st->launches_check; }
         else if (kind == 1 || kind == 2 || kind == 6) { st->ms_var += ms; ++st->launches_var; }
@@ -2139,12 +2070,12 @@ int ldpc_decoder_stats(ldpc_decoder *d, ldpc_decode_stats *st)
 
 int ldpc_decoder_kernel_times(ldpc_decoder *d, ldpc_kernel_time *out, int32_t capacity, int32_t *count)
 {
-    if (!d || !out || !count || capacity <= 0) return fail(LDPC_ERR_ARG, "bad arguments");
+    if (!d || !out || !count || capacity <= 0) return set_error(LDPC_ERR_ARG, "bad arguments");
     *count = 0;
     if (!d->shards.empty()) return ldpc_decoder_kernel_times(d->shards[0], out, capacity, count);
-    if (!d->have_last) return fail(LDPC_ERR_STATE, "no decode call to report on");
-    HIP_TRY(hipSetDevice(d->cfg.device));
-    HIP_TRY(hipEventSynchronize(d->ev_end));
+    if (!d->have_last) return set_error(LDPC_ERR_STATE, "no decode call to report on");
+    LDPC_HIP_TRY(hipSetDevice(d->cfg.device));
+    LDPC_HIP_TRY(hipEventSynchronize(d->ev_end));
     const char *phase_name[] = {"check_kernel", "var_kernel", d->ms_corr ? "layer_corr_kernel" : "layer_kernel", "other",
                                 d->tune_link_narrow == 2 ? "check_link_half_kernel"
                                 : d->tune_link_narrow ? "check_link_narrow_kernel" : "check_link_kernel"};
@@ -2157,7 +2088,7 @@ int ldpc_decoder_kernel_times(ldpc_decoder *d, ldpc_kernel_time *out, int32_t ca
     for (size_t i = 0; i < d->spans_used; ++i) {
         const TimedSpan &sp = d->spans[i];
         float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, sp.a, sp.b));
+        LDPC_HIP_TRY(hipEventElapsedTime(&ms, sp.a, sp.b));
         const int phase = (sp.kind == 4 || sp.kind == 5) ? 0 : (sp.kind == 6 ? 1 : sp.kind);   /* check / variable node */
         char name[64];
         if (sp.kind == 3) snprintf(name, sizeof name, "other");
@@ -2194,7 +2125,7 @@ int ldpc_decoder_kernel_times(ldpc_decoder *d, ldpc_kernel_time *out, int32_t ca
 
 int ldpc_decoder_link_form(ldpc_decoder *d, int32_t *form, int32_t *calibrated, float ms[3])
 {
-    if (!d) return fail(LDPC_ERR_ARG, "decoder is NULL");
+    if (!d) return set_error(LDPC_ERR_ARG, "decoder is NULL");
     if (!d->shards.empty()) return ldpc_decoder_link_form(d->shards[0], form, calibrated, ms);
     bool linked = false;
     for (auto &rc : d->row_classes) linked = linked || rc.linked;
@@ -2206,7 +2137,7 @@ int ldpc_decoder_link_form(ldpc_decoder *d, int32_t *form, int32_t *calibrated, 
 
 int ldpc_decoder_placement(ldpc_decoder *d, int32_t *candidates, int32_t *kept, float ms[16])
 {
-    if (!d) return fail(LDPC_ERR_ARG, "decoder is NULL");
+    if (!d) return set_error(LDPC_ERR_ARG, "decoder is NULL");
     if (!d->shards.empty()) return ldpc_decoder_placement(d->shards[0], candidates, kept, ms);
     if (candidates) *candidates = d->place_candidates;
     if (kept) *kept = d->place_kept;
@@ -2216,7 +2147,7 @@ int ldpc_decoder_placement(ldpc_decoder *d, int32_t *candidates, int32_t *kept, 
 
 int ldpc_decoder_array_addresses(ldpc_decoder *d, uint64_t out[4])
 {
-    if (!d || !out) return fail(LDPC_ERR_ARG, "decoder/out is NULL");
+    if (!d || !out) return set_error(LDPC_ERR_ARG, "decoder/out is NULL");
     if (!d->shards.empty()) return ldpc_decoder_array_addresses(d->shards[0], out);
     out[0] = (uint64_t)(uintptr_t)d->Q.p; out[1] = (uint64_t)(uintptr_t)d->R.p;
     out[2] = (uint64_t)(uintptr_t)d->chan.p; out[3] = (uint64_t)(uintptr_t)d->hard.p;
@@ -2225,69 +2156,69 @@ int ldpc_decoder_array_addresses(ldpc_decoder *d, uint64_t out[4])
 
 int ldpc_decoder_set_tap(ldpc_decoder *d, int32_t iter)
 {
-    if (!d) return fail(LDPC_ERR_ARG, "decoder is NULL");
-    if (iter < 0) return fail(LDPC_ERR_ARG, "iter < 0");
-    if (!d->shards.empty()) return fail(LDPC_ERR_STATE, "debug taps need a single-device handle");
+    if (!d) return set_error(LDPC_ERR_ARG, "decoder is NULL");
+    if (iter < 0) return set_error(LDPC_ERR_ARG, "iter < 0");
+    if (!d->shards.empty()) return set_error(LDPC_ERR_STATE, "debug taps need a single-device handle");
     d->tap_iter = iter;
     return LDPC_OK;
 }
 
 int ldpc_decoder_dump(ldpc_decoder *d, int32_t which, float *host_out, int64_t count)
 {
-    if (!d || !host_out) return fail(LDPC_ERR_ARG, "decoder/host_out is NULL");
-    if (!d->shards.empty()) return fail(LDPC_ERR_STATE, "debug taps need a single-device handle");
-    if (!d->have_last) return fail(LDPC_ERR_STATE, "no decode call to dump");
-    HIP_TRY(hipSetDevice(d->cfg.device));
+    if (!d || !host_out) return set_error(LDPC_ERR_ARG, "decoder/host_out is NULL");
+    if (!d->shards.empty()) return set_error(LDPC_ERR_STATE, "debug taps need a single-device handle");
+    if (!d->have_last) return set_error(LDPC_ERR_STATE, "no decode call to dump");
+    LDPC_HIP_TRY(hipSetDevice(d->cfg.device));
     wait_for_own_work(d);
     const int64_t frames = d->last_frames;
     const int V = d->V, F = d->F;
     const int tiles = (int)((frames + F - 1) / F);
     if (d->use_fused && d->cfg.algo == LDPC_ALGO_SP) {
-        if (!d->fused.dump_p) return fail(LDPC_ERR_STATE, "fused dump needs set_tap() before the decode");
+        if (!d->fused.dump_p.p) return set_error(LDPC_ERR_STATE, "fused dump needs set_tap() before the decode");
         const int64_t per = (which == 0 || which == 1) ? d->E : d->N;
-        if (which < 0 || which > 3 || count != frames * per) return fail(LDPC_ERR_ARG, "bad `which`/count");
+        if (which < 0 || which > 3 || count != frames * per) return set_error(LDPC_ERR_ARG, "bad `which`/count");
         if (which == 3) {
             std::vector<uint8_t> b((size_t)count);
-            HIP_TRY(hipMemcpy(b.data(), d->fused.dump_b, (size_t)count, hipMemcpyDeviceToHost));
+            LDPC_HIP_TRY(hipMemcpy(b.data(), d->fused.dump_b.p, (size_t)count, hipMemcpyDeviceToHost));
             for (int64_t i = 0; i < count; ++i) host_out[i] = (float)b[i];
             return LDPC_OK;
         }
-        const float *src = which == 0 ? d->fused.dump_r : (which == 1 ? d->fused.dump_q : d->fused.dump_p);
-        HIP_TRY(hipMemcpy(host_out, src, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+        const float *src = which == 0 ? d->fused.dump_r.p : (which == 1 ? d->fused.dump_q.p : d->fused.dump_p.p);
+        LDPC_HIP_TRY(hipMemcpy(host_out, src, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
         return LDPC_OK;
     }
     if (d->use_fused) {
-        const float *dump_r = d->use_ldsp ? d->ldsp.dump_r : d->fused.dump_r;
-        const float *dump_p = d->use_ldsp ? d->ldsp.dump_p : d->fused.dump_p;
+        const float *dump_r = d->use_ldsp ? d->ldsp.dump_r.p : d->fused.dump_r.p;
+        const float *dump_p = d->use_ldsp ? d->ldsp.dump_p.p : d->fused.dump_p.p;
         const float *src = which == 0 ? dump_r : (which == 2 ? dump_p : nullptr);
         const int64_t per = which == 0 ? d->E : d->N;
         if (which == 3) {           /* hard bits = P < 0 */
-            if (!dump_p || count != frames * d->N) return fail(LDPC_ERR_ARG, "fused dump needs set_tap() and count = frames*N");
-            HIP_TRY(hipMemcpy(host_out, dump_p, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+            if (!dump_p || count != frames * d->N) return set_error(LDPC_ERR_ARG, "fused dump needs set_tap() and count = frames*N");
+            LDPC_HIP_TRY(hipMemcpy(host_out, dump_p, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
             const bool notpos = d->cfg.algo == LDPC_ALGO_MS;      /* MS chain: bit = !(p > 0) */
             for (int64_t i = 0; i < count; ++i)
                 host_out[i] = (notpos ? !(host_out[i] > 0.0f) : (host_out[i] < 0.0f)) ? 1.0f : 0.0f;
             return LDPC_OK;
         }
-        if (!src || count != frames * per) return fail(LDPC_ERR_ARG, "fused dump: set_tap() first; which in {0,2,3}");
-        HIP_TRY(hipMemcpy(host_out, src, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+        if (!src || count != frames * per) return set_error(LDPC_ERR_ARG, "fused dump: set_tap() first; which in {0,2,3}");
+        LDPC_HIP_TRY(hipMemcpy(host_out, src, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
         return LDPC_OK;
     }
     if (d->cfg.algo == LDPC_ALGO_LAYERED || d->cfg.algo == LDPC_ALGO_LAYERED_HOST) {
         hipError_t e = ldpc::layered_dump(&d->layered, which, host_out, count, frames, d->hard.p,
                                           d->h_cols.data());
-        if (e == hipErrorInvalidValue) return fail(LDPC_ERR_ARG, "bad `which`/count for layered dump");
-        if (e != hipSuccess) return fail(LDPC_ERR_HIP, "layered dump: %s", hipGetErrorString(e));
+        if (e == hipErrorInvalidValue) return set_error(LDPC_ERR_ARG, "bad `which`/count for layered dump");
+        if (e != hipSuccess) return set_error(LDPC_ERR_HIP, "layered dump: %s", hipGetErrorString(e));
         return LDPC_OK;
     }
     if (which == 0 || which == 1 || which == 2) {
         const int64_t per = (which == 2) ? d->N : d->E;
-        if (count != frames * per) return fail(LDPC_ERR_ARG, "count must be frames*%lld", (long long)per);
+        if (count != frames * per) return set_error(LDPC_ERR_ARG, "count must be frames*%lld", (long long)per);
         const uint8_t *src = which == 0 ? d->R.p : (which == 1 ? d->Q.p : d->chan.p);
         const size_t esz = (size_t)d->msg_size;
         std::vector<uint8_t> tile((size_t)per * F * esz);
         for (int t = 0; t < tiles; ++t) {
-            HIP_TRY(hipMemcpy(tile.data(), src + (size_t)t * per * F * esz, tile.size(), hipMemcpyDeviceToHost));
+            LDPC_HIP_TRY(hipMemcpy(tile.data(), src + (size_t)t * per * F * esz, tile.size(), hipMemcpyDeviceToHost));
             for (int fi = 0; fi < F; ++fi) {
                 const int64_t f = (int64_t)t * F + fi;
                 if (f >= frames) break;
@@ -2306,9 +2237,9 @@ int ldpc_decoder_dump(ldpc_decoder *d, int32_t which, float *host_out, int64_t c
         return LDPC_OK;
     }
     if (which == 3) {
-        if (count != frames * d->N) return fail(LDPC_ERR_ARG, "count must be frames*N");
+        if (count != frames * d->N) return set_error(LDPC_ERR_ARG, "count must be frames*N");
         std::vector<uint64_t> w((size_t)tiles * d->N * V);
-        HIP_TRY(hipMemcpy(w.data(), d->hard.p, w.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        LDPC_HIP_TRY(hipMemcpy(w.data(), d->hard.p, w.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
         for (int64_t f = 0; f < frames; ++f) {
             const int64_t t = f / F;
             const int fi = (int)(f % F);
@@ -2318,156 +2249,7 @@ int ldpc_decoder_dump(ldpc_decoder *d, int32_t which, float *host_out, int64_t c
         }
         return LDPC_OK;
     }
-    return fail(LDPC_ERR_ARG, "unknown `which` %d", which);
-}
-
-int ldpc_awgn_device(float *llr_dev, int64_t frames, int32_t N, const uint8_t *bits_dev, float sd,
-                     uint64_t seed, int64_t first_frame, int32_t device, void *stream)
-{
-    if (!llr_dev) return fail(LDPC_ERR_ARG, "llr_dev is NULL");
-    if (frames < 0 || N <= 0 || first_frame < 0) return fail(LDPC_ERR_ARG, "frames=%lld, N=%d, first_frame=%lld",
-                                                             (long long)frames, N, (long long)first_frame);
-    if (!(sd >= 0.0f)) return fail(LDPC_ERR_ARG, "sd must be >= 0");
-    if (frames == 0) return LDPC_OK;
-    HIP_TRY(hipSetDevice(device));
-    const int32_t groups = (N + 3) / 4;
-    const int64_t threads = frames * groups;
-    const int64_t blocks = (threads + 255) / 256;
-    if (blocks > 0x7fffffffLL) return fail(LDPC_ERR_ARG, "too many samples for one call");
-    ldpc::awgn_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(llr_dev, bits_dev, frames, N, groups, sd,
-                                                                         seed, first_frame);
-    HIP_TRY(hipGetLastError());
-    return LDPC_OK;
-}
-
-int ldpc_count_errors_device(const uint8_t *out_dev, const uint8_t *ref_dev, int64_t frames,
-                             int64_t bytes_per_frame, int64_t errors[3], int32_t device, void *stream)
-{
-    if (!out_dev || !errors) return fail(LDPC_ERR_ARG, "out_dev/errors is NULL");
-    if (frames < 0 || bytes_per_frame <= 0 || frames > 0x7fffffffLL) return fail(LDPC_ERR_ARG, "bad frames/bytes_per_frame");
-    errors[0] = errors[1] = errors[2] = 0;
-    if (frames == 0) return LDPC_OK;
-    HIP_TRY(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
-    unsigned long long *totals = nullptr;
-    HIP_TRY(hipMalloc((void **)&totals, 3 * sizeof(unsigned long long)));
-    hipError_t e = hipMemsetAsync(totals, 0, 3 * sizeof(unsigned long long), s);
-    if (e == hipSuccess) {
-        ldpc::count_errors_kernel<<<(unsigned)frames, 256, 0, s>>>(out_dev, ref_dev, frames, bytes_per_frame, totals);
-        e = hipGetLastError();
-    }
-    unsigned long long h[3] = {0, 0, 0};
-    if (e == hipSuccess) e = hipMemcpyAsync(h, totals, sizeof h, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(totals);
-    if (e != hipSuccess) return fail(LDPC_ERR_HIP, "count_errors: %s", hipGetErrorString(e));
-    for (int i = 0; i < 3; ++i) errors[i] = (int64_t)h[i];
-    return LDPC_OK;
-}
-
-/* ---- measurement aid: what this box's HBM sustains right now (a float4 copy: the figure the
- *      microarchitecture guide quotes as achievable, 6.3 of 8.0 TB/s), with the default cache policy
- *      and with the non-temporal one the streaming kernels use; the better of the two ------------ */
-
-int ldpc_hbm_probe_device(int32_t device, int64_t bytes, int32_t reps, double *copy_gbs, double *by_policy)
-{
-    if (!copy_gbs) return fail(LDPC_ERR_ARG, "copy_gbs is NULL");
-    *copy_gbs = 0.0;
-    if (by_policy) by_policy[0] = by_policy[1] = 0.0;
-    if (bytes < (1 << 20) || bytes > ((int64_t)16 << 30) || reps <= 0 || reps > 1000)
-        return fail(LDPC_ERR_ARG, "probe: bytes in [1 MiB, 16 GiB], reps in [1, 1000]");
-    HIP_TRY(hipSetDevice(device));
-    const size_t n4 = (size_t)bytes / sizeof(ldpc::vf4);
-    ldpc::vf4 *src = nullptr, *dst = nullptr;
-    hipStream_t s = nullptr;
-    hipEvent_t a = nullptr, b = nullptr;
-    hipError_t e = hipMalloc((void **)&src, n4 * sizeof(ldpc::vf4));
-    if (e == hipSuccess) e = hipMalloc((void **)&dst, n4 * sizeof(ldpc::vf4));
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreate(&a);
-    if (e == hipSuccess) e = hipEventCreate(&b);
-    if (e == hipSuccess) e = hipMemsetAsync(src, 0x3c, n4 * sizeof(ldpc::vf4), s);
-    float best_ms[2] = {0.0f, 0.0f};                             /* default policy, non-temporal */
-    if (e == hipSuccess) {
-        const unsigned grid = (unsigned)std::min<size_t>((n4 + 1023) / 1024, 256 * 64);
-        hbm_probe_copy_kernel<false><<<grid, 256, 0, s>>>(src, dst, n4);        /* warm-up */
-        for (int r = 0; r < 2 * reps && e == hipSuccess; ++r) {
-            e = hipEventRecord(a, s);
-            if (r & 1) hbm_probe_copy_kernel<true><<<grid, 256, 0, s>>>(src, dst, n4);
-            else hbm_probe_copy_kernel<false><<<grid, 256, 0, s>>>(src, dst, n4);
-            if (e == hipSuccess) e = hipEventRecord(b, s);
-            if (e == hipSuccess) e = hipEventSynchronize(b);
-            float ms = 0.0f;
-            if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-            if (e == hipSuccess && (best_ms[r & 1] == 0.0f || ms < best_ms[r & 1])) best_ms[r & 1] = ms;
-        }
-    }
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-    if (s) (void)hipStreamDestroy(s);
-    if (src) (void)hipFree(src);
-    if (dst) (void)hipFree(dst);
-    if (e != hipSuccess) return fail(LDPC_ERR_HIP, "hbm probe: %s", hipGetErrorString(e));
-    for (int k = 0; k < 2; ++k) {
-        const double gbs = best_ms[k] > 0.0f ? 2.0 * (double)(n4 * sizeof(ldpc::vf4)) / (best_ms[k] * 1e-3) / 1e9 : 0.0;
-        if (by_policy) by_policy[k] = gbs;
-        if (gbs > *copy_gbs) *copy_gbs = gbs;
-    }
-    return LDPC_OK;
-}
-
-/* The same non-temporal copy, back to back for `milliseconds`: what the box sustains (its memory throttles
- * under load at times: a burst of a few launches does not see that). */
-int ldpc_hbm_sustained_device(int32_t device, int64_t bytes, int32_t milliseconds, double *copy_gbs)
-{
-    if (!copy_gbs) return fail(LDPC_ERR_ARG, "copy_gbs is NULL");
-    *copy_gbs = 0.0;
-    if (bytes < (1 << 20) || bytes > ((int64_t)16 << 30) || milliseconds < 1 || milliseconds > 10000)
-        return fail(LDPC_ERR_ARG, "sustained probe: bytes in [1 MiB, 16 GiB], milliseconds in [1, 10000]");
-    HIP_TRY(hipSetDevice(device));
-    const size_t n4 = (size_t)bytes / sizeof(ldpc::vf4);
-    ldpc::vf4 *src = nullptr, *dst = nullptr;
-    hipStream_t s = nullptr;
-    hipEvent_t a = nullptr, b = nullptr;
-    hipError_t e = hipMalloc((void **)&src, n4 * sizeof(ldpc::vf4));
-    if (e == hipSuccess) e = hipMalloc((void **)&dst, n4 * sizeof(ldpc::vf4));
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreate(&a);
-    if (e == hipSuccess) e = hipEventCreate(&b);
-    if (e == hipSuccess) e = hipMemsetAsync(src, 0x3c, n4 * sizeof(ldpc::vf4), s);
-    const unsigned grid = (unsigned)std::min<size_t>((n4 + 1023) / 1024, 256 * 64);
-    /* one launch's time from a short burst, then a third of the time untimed and two thirds timed */
-    float one_ms = 0.0f;
-    if (e == hipSuccess) {
-        hbm_probe_copy_kernel<true><<<grid, 256, 0, s>>>(src, dst, n4);
-        e = hipEventRecord(a, s);
-        for (int r = 0; r < 4; ++r) hbm_probe_copy_kernel<true><<<grid, 256, 0, s>>>(src, dst, n4);
-        if (e == hipSuccess) e = hipEventRecord(b, s);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(&one_ms, a, b);
-        one_ms /= 4.0f;
-    }
-    int timed = 0;
-    float ms = 0.0f;
-    if (e == hipSuccess && one_ms > 0.0f) {
-        const int total = std::max(6, std::min(200000, (int)((float)milliseconds / one_ms)));
-        const int lead = total / 3;
-        timed = total - lead;
-        for (int r = 0; r < lead; ++r) hbm_probe_copy_kernel<true><<<grid, 256, 0, s>>>(src, dst, n4);
-        e = hipEventRecord(a, s);
-        for (int r = 0; r < timed; ++r) hbm_probe_copy_kernel<true><<<grid, 256, 0, s>>>(src, dst, n4);
-        if (e == hipSuccess) e = hipEventRecord(b, s);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-    }
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-    if (s) (void)hipStreamDestroy(s);
-    if (src) (void)hipFree(src);
-    if (dst) (void)hipFree(dst);
-    if (e != hipSuccess) return fail(LDPC_ERR_HIP, "hbm sustained probe: %s", hipGetErrorString(e));
-    if (ms > 0.0f) *copy_gbs = 2.0 * (double)(n4 * sizeof(ldpc::vf4)) * timed / (ms * 1e-3) / 1e9;
-    return LDPC_OK;
+    return set_error(LDPC_ERR_ARG, "unknown `which` %d", which);
 }
 
 }  /* extern "C" */

@@ -546,10 +546,10 @@ void flood_ldsp_packed_corr_kernel(const LdspArgs a, const int G, const MsCorr c
 struct LdspPlan {
     bool eligible = false;
     int32_t z = 0, layers = 0, N = 0, E = 0, M = 0, nb = 0, lds_cols = 0, ext_cols = 0;
-    int32_t *hdr = nullptr, *pack = nullptr, *col_slot = nullptr, *layer_e0 = nullptr;   /* device */
-    uint4 *recs = nullptr;
-    uint32_t *zf = nullptr;
-    float *dump_p = nullptr, *dump_r = nullptr;
+    DevBuf<int32_t> hdr, pack, col_slot, layer_e0;
+    DevBuf<uint4> recs;
+    DevBuf<uint32_t> zf;
+    DevBuf<float> dump_p, dump_r;       /* made by the first decode with a tap set */
     int64_t dump_frames = 0;
     int flood = 0;                      /* 0 layered kernels; flood_ldsp_kernel with 1: the MS chain's arithmetic (DecodeMS /
                                            DecodeCPU), 2: the fused reference kernel's (DecodeMSCL) */
@@ -559,14 +559,6 @@ struct LdspPlan {
     MsCorr mc{1.0f, 0.0f};
     size_t lds_bytes = 0;
 };
-
-inline void ldsp_plan_destroy(LdspPlan *pl)
-{
-    for (void *p : {(void *)pl->hdr, (void *)pl->pack, (void *)pl->col_slot, (void *)pl->layer_e0, (void *)pl->recs,
-                    (void *)pl->zf, (void *)pl->dump_p, (void *)pl->dump_r})
-        if (p) (void)hipFree(p);
-    *pl = LdspPlan();
-}
 
 /* the plan builder and the launcher reference every kernel above: compiled by engine_ldsp.hip only
  * (LDPC_ENGINE_LDSP); the host driver calls engine_ldsp_plan_create / engine_ldsp_run */
@@ -644,13 +636,8 @@ inline hipError_t ldsp_plan_create(LdspPlan *pl, int32_t M, int32_t N, int64_t E
     pl->lds_cols = lds_cols; pl->ext_cols = ext_cols; pl->lds_bytes = lds_bytes;
     pl->maxw = mw <= 8 ? 8 : 16;
     pl->block = 64 * mw;
-    auto up = [](int32_t **dst, const std::vector<int32_t> &v) {
-        hipError_t e = hipMalloc((void **)dst, v.size() * sizeof(int32_t));
-        if (e != hipSuccess) return e;
-        return hipMemcpy(*dst, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    };
     hipError_t e;
-    if ((e = up(&pl->hdr, hdr)) || (e = up(&pl->pack, pack)) || (e = up(&pl->col_slot, slot)) || (e = up(&pl->layer_e0, e0)))
+    if ((e = pl->hdr.upload(hdr)) || (e = pl->pack.upload(pack)) || (e = pl->col_slot.upload(slot)) || (e = pl->layer_e0.upload(e0)))
         return e;
     const void *k = flood ? (pl->wg_frames > 1 ? (flood == 1 ? (const void *)flood_ldsp_packed_kernel<true> : (const void *)flood_ldsp_packed_kernel<false>)
                                                : (const void *)flood_ldsp_kernel_for(mw <= 8 ? 8 : 16, flood))
@@ -679,8 +666,8 @@ inline hipError_t ldsp_plan_create(LdspPlan *pl, int32_t M, int32_t N, int64_t E
     pl->grid = (int32_t)std::min<int64_t>((std::max<int64_t>(max_batch, 1) + pl->wg_frames - 1) / pl->wg_frames, (int64_t)per_cu * cus);
     if (tune.ldsp_grid) pl->grid = std::max(1, std::min(pl->grid, tune.ldsp_grid));
     /* + 1024 (the largest workgroup): lanes beyond the last row request records too (never used) */
-    if ((e = hipMalloc((void **)&pl->recs, ((size_t)pl->grid * pl->wg_frames * M + 1024) * sizeof(uint4)))) return e;
-    if ((e = hipMalloc((void **)&pl->zf, ((size_t)pl->grid * pl->wg_frames * M + 1024) * sizeof(uint32_t)))) return e;
+    if ((e = pl->recs.alloc((size_t)pl->grid * pl->wg_frames * M + 1024))) return e;
+    if ((e = pl->zf.alloc((size_t)pl->grid * pl->wg_frames * M + 1024))) return e;
     pl->eligible = true;
     return hipSuccess;
 }
@@ -692,15 +679,12 @@ inline hipError_t ldsp_run(LdspPlan *pl, const FusedRun &r, hipStream_t s, int32
     if ((e = hipMemsetAsync(r.summary, 0, 2 * sizeof(int32_t), s))) return e;
     const int rounds = r.tap_iter ? (r.tap_iter < r.max_iter ? r.tap_iter : r.max_iter) : r.max_iter;
     if (r.tap_iter && pl->dump_frames < r.frames) {
-        if (pl->dump_p) (void)hipFree(pl->dump_p);
-        if (pl->dump_r) (void)hipFree(pl->dump_r);
-        pl->dump_p = pl->dump_r = nullptr;
-        if ((e = hipMalloc((void **)&pl->dump_p, (size_t)r.frames * pl->N * sizeof(float)))) return e;
-        if ((e = hipMalloc((void **)&pl->dump_r, (size_t)r.frames * pl->E * sizeof(float)))) return e;
+        if ((e = pl->dump_p.alloc((size_t)r.frames * pl->N))) return e;
+        if ((e = pl->dump_r.alloc((size_t)r.frames * pl->E))) return e;
         pl->dump_frames = r.frames;
     }
-    LdspArgs a{r.llr_dev, r.out_dev, r.iters_dev, r.summary, r.tap_iter ? pl->dump_p : nullptr,
-               r.tap_iter ? pl->dump_r : nullptr, pl->recs, pl->zf, pl->hdr, pl->pack, pl->col_slot, pl->layer_e0,
+    LdspArgs a{r.llr_dev, r.out_dev, r.iters_dev, r.summary, r.tap_iter ? pl->dump_p.p : nullptr,
+               r.tap_iter ? pl->dump_r.p : nullptr, pl->recs.p, pl->zf.p, pl->hdr.p, pl->pack.p, pl->col_slot.p, pl->layer_e0.p,
                r.frames, r.out_dev ? r.out_bytes : 0, pl->N, pl->E, r.K, pl->z, pl->layers, pl->nb, pl->lds_cols,
                r.max_iter, rounds, r.early_term};
     const unsigned grid = (unsigned)std::min<int64_t>((r.frames + pl->wg_frames - 1) / pl->wg_frames, pl->grid);

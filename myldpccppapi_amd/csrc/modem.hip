@@ -9,20 +9,14 @@
 #include <cmath>
 
 #include "../../include/ldpc_hip.h"
-#include "graph.hpp"
+#include "hip_host.hpp"
 #include "modem_kernels.hpp"
 
 using ldpc::set_error;
+using ldpc::frame_grid;
+using ldpc::ranges_overlap;
 
 namespace {
-
-#define MODEM_HIP_TRY(expr)                                                                     \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return set_error(LDPC_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                             __FILE__, __LINE__);                                               \
-    } while (0)
 
 int norm_of(int32_t Qm) { return Qm == 2 ? 2 : Qm == 4 ? 10 : Qm == 6 ? 42 : Qm == 8 ? 170 : 1; }
 
@@ -61,22 +55,9 @@ int make_map(const ldpc_modem_spec *s, int32_t E, ldpc::ModemMap *m)
 
 inline int32_t host_position(const ldpc::ModemMap &m, int32_t i, int32_t j) { return m.interleave ? i * m.S + j : j * m.Qm + i; }
 
-bool overlap(const void *p, int64_t p_bytes, const void *q, int64_t q_bytes)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + (uintptr_t)q_bytes && b < a + (uintptr_t)p_bytes;
-}
-
-/* grid.y: the kernels stride over the frames (as the rate-matching kernels do) */
-const int64_t kModemTargetBlocks = 16384;
-unsigned frame_grid(int64_t frames, unsigned grid_x)
-{
-    return (unsigned)std::min<int64_t>(std::min<int64_t>(frames, 65535), std::max<int64_t>(1, kModemTargetBlocks / grid_x));
-}
-
 int check_transmit(const ldpc::ModemMap &m, int32_t tx_format, int64_t frames, float sd, int64_t first_frame, int64_t sym_floats)
 {
-    if (tx_format != LDPC_CODE_PACKED && tx_format != LDPC_CODE_BITS) return set_error(LDPC_ERR_ARG, "unknown tx_format %d", tx_format);
+    if (int rc = ldpc::known_code_format(tx_format, "tx_format")) return rc;
     if (tx_format == LDPC_CODE_PACKED && m.E % 8) return set_error(LDPC_ERR_ARG, "tx_format LDPC_CODE_PACKED needs E %% 8 == 0 (E = %d)", m.E);
     if (frames < 0) return set_error(LDPC_ERR_ARG, "frames = %lld is negative", (long long)frames);
     if (first_frame < 0) return set_error(LDPC_ERR_ARG, "first_frame = %lld is negative", (long long)first_frame);
@@ -96,7 +77,7 @@ int launch_transmit(const ldpc::ModemMap &m, const uint8_t *tx, int32_t tx_forma
     const dim3 grid(gx, frame_grid(frames, gx));
     if (tx_format == LDPC_CODE_PACKED) modem_tx_kernel<1><<<grid, kModemBlock, 0, s>>>(m, tx, frames, sd, seed, first_frame, sym);
     else modem_tx_kernel<0><<<grid, kModemBlock, 0, s>>>(m, tx, frames, sd, seed, first_frame, sym);
-    MODEM_HIP_TRY(hipGetLastError());
+    LDPC_HIP_TRY(hipGetLastError());
     return LDPC_OK;
 }
 
@@ -112,26 +93,9 @@ int launch_demap(const ldpc::ModemMap &m, const float *sym, int64_t frames, floa
     case 6: modem_demap_kernel<6><<<grid, kModemBlock, 0, s>>>(m, sym, frames, rx); break;
     default: modem_demap_kernel<8><<<grid, kModemBlock, 0, s>>>(m, sym, frames, rx); break;
     }
-    MODEM_HIP_TRY(hipGetLastError());
+    LDPC_HIP_TRY(hipGetLastError());
     return LDPC_OK;
 }
-
-int use_device(int32_t device)
-{
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-        return set_error(LDPC_ERR_HIP, "no usable HIP device (the modem stage has no CPU fallback)");
-    if (device < 0 || device >= count) return set_error(LDPC_ERR_ARG, "device %d of %d", device, count);
-    MODEM_HIP_TRY(hipSetDevice(device));
-    return LDPC_OK;
-}
-
-struct Scratch {
-    void *p = nullptr;
-    ~Scratch() { if (p) (void)hipFree(p); }
-};
-
-const int64_t kHostChunkBytes = (int64_t)64 << 20;   /* host-buffer calls: device scratch per array */
 
 }  // namespace
 
@@ -189,10 +153,10 @@ int ldpc_modem_transmit_device(const ldpc_modem_spec *spec, const uint8_t *tx_de
     if (int rc = make_map(spec, E, &m)) return rc;
     if (int rc = check_transmit(m, tx_format, frames, sd, first_frame, sym_floats)) return rc;
     if (!tx_dev || !sym_dev) return set_error(LDPC_ERR_ARG, "tx_dev/sym_dev is NULL");
-    if (overlap(tx_dev, ldpc_code_bytes(E, frames, tx_format), sym_dev, frames * (int64_t)m.row * 4))
+    if (ranges_overlap(tx_dev, ldpc_code_bytes(E, frames, tx_format), sym_dev, frames * (int64_t)m.row * 4))
         return set_error(LDPC_ERR_ARG, "tx_dev and sym_dev overlap");
     if (frames == 0) return LDPC_OK;
-    MODEM_HIP_TRY(hipSetDevice(device));
+    LDPC_HIP_TRY(hipSetDevice(device));
     return launch_transmit(m, tx_dev, tx_format, frames, sd, seed, first_frame, sym_dev, (hipStream_t)stream);
 }
 
@@ -203,10 +167,10 @@ int ldpc_modem_demap_device(const ldpc_modem_spec *spec, const float *sym_dev, i
     if (int rc = make_map(spec, E, &m)) return rc;
     if (frames < 0) return set_error(LDPC_ERR_ARG, "frames = %lld is negative", (long long)frames);
     if (!sym_dev || !rx_dev) return set_error(LDPC_ERR_ARG, "sym_dev/rx_dev is NULL");
-    if (overlap(sym_dev, frames * (int64_t)m.row * 4, rx_dev, frames * (int64_t)E * 4))
+    if (ranges_overlap(sym_dev, frames * (int64_t)m.row * 4, rx_dev, frames * (int64_t)E * 4))
         return set_error(LDPC_ERR_ARG, "sym_dev and rx_dev overlap");
     if (frames == 0) return LDPC_OK;
-    MODEM_HIP_TRY(hipSetDevice(device));
+    LDPC_HIP_TRY(hipSetDevice(device));
     return launch_demap(m, sym_dev, frames, rx_dev, (hipStream_t)stream);
 }
 
@@ -217,22 +181,15 @@ int ldpc_modem_transmit(const ldpc_modem_spec *spec, const uint8_t *tx_host, int
     if (int rc = make_map(spec, E, &m)) return rc;
     if (int rc = check_transmit(m, tx_format, frames, sd, first_frame, sym_floats)) return rc;
     if (!tx_host || !sym_host) return set_error(LDPC_ERR_ARG, "tx_host/sym_host is NULL");
-    if (overlap(tx_host, ldpc_code_bytes(E, frames, tx_format), sym_host, frames * (int64_t)m.row * 4))
+    if (ranges_overlap(tx_host, ldpc_code_bytes(E, frames, tx_format), sym_host, frames * (int64_t)m.row * 4))
         return set_error(LDPC_ERR_ARG, "tx_host and sym_host overlap");
     if (frames == 0) return LDPC_OK;
-    if (int rc = use_device(device)) return rc;
+    if (int rc = ldpc::use_device(device, "the modem stage")) return rc;
     const int64_t in_row = tx_format == LDPC_CODE_PACKED ? E / 8 : E, out_row = (int64_t)m.row * 4;
-    const int64_t chunk = std::min<int64_t>(frames, std::max<int64_t>(1, kHostChunkBytes / std::max(in_row, out_row)));
-    Scratch in, out;
-    MODEM_HIP_TRY(hipMalloc(&in.p, (size_t)(chunk * in_row)));
-    MODEM_HIP_TRY(hipMalloc(&out.p, (size_t)(chunk * out_row)));
-    for (int64_t f0 = 0; f0 < frames; f0 += chunk) {
-        const int64_t n = std::min(chunk, frames - f0);
-        MODEM_HIP_TRY(hipMemcpy(in.p, tx_host + f0 * in_row, (size_t)(n * in_row), hipMemcpyHostToDevice));
-        if (int rc = launch_transmit(m, (const uint8_t *)in.p, tx_format, n, sd, seed, first_frame + f0, (float *)out.p, nullptr)) return rc;
-        MODEM_HIP_TRY(hipMemcpy(sym_host + f0 * m.row, out.p, (size_t)(n * out_row), hipMemcpyDeviceToHost));
-    }
-    return LDPC_OK;
+    return ldpc::host_chunks(frames, {{(void *)tx_host, in_row, true, false}, {sym_host, out_row, false, true}},
+                             [&](int64_t n, int64_t f0, void *const *dev) {
+                                 return launch_transmit(m, (const uint8_t *)dev[0], tx_format, n, sd, seed, first_frame + f0, (float *)dev[1], nullptr);
+                             });
 }
 
 int ldpc_modem_demap(const ldpc_modem_spec *spec, const float *sym_host, int64_t frames, int32_t E, float *rx_host, int32_t device)
@@ -241,22 +198,15 @@ int ldpc_modem_demap(const ldpc_modem_spec *spec, const float *sym_host, int64_t
     if (int rc = make_map(spec, E, &m)) return rc;
     if (frames < 0) return set_error(LDPC_ERR_ARG, "frames = %lld is negative", (long long)frames);
     if (!sym_host || !rx_host) return set_error(LDPC_ERR_ARG, "sym_host/rx_host is NULL");
-    if (overlap(sym_host, frames * (int64_t)m.row * 4, rx_host, frames * (int64_t)E * 4))
+    if (ranges_overlap(sym_host, frames * (int64_t)m.row * 4, rx_host, frames * (int64_t)E * 4))
         return set_error(LDPC_ERR_ARG, "sym_host and rx_host overlap");
     if (frames == 0) return LDPC_OK;
-    if (int rc = use_device(device)) return rc;
+    if (int rc = ldpc::use_device(device, "the modem stage")) return rc;
     const int64_t in_row = (int64_t)m.row * 4, out_row = (int64_t)E * 4;
-    const int64_t chunk = std::min<int64_t>(frames, std::max<int64_t>(1, kHostChunkBytes / std::max(in_row, out_row)));
-    Scratch in, out;
-    MODEM_HIP_TRY(hipMalloc(&in.p, (size_t)(chunk * in_row)));
-    MODEM_HIP_TRY(hipMalloc(&out.p, (size_t)(chunk * out_row)));
-    for (int64_t f0 = 0; f0 < frames; f0 += chunk) {
-        const int64_t n = std::min(chunk, frames - f0);
-        MODEM_HIP_TRY(hipMemcpy(in.p, sym_host + f0 * m.row, (size_t)(n * in_row), hipMemcpyHostToDevice));
-        if (int rc = launch_demap(m, (const float *)in.p, n, (float *)out.p, nullptr)) return rc;
-        MODEM_HIP_TRY(hipMemcpy(rx_host + f0 * E, out.p, (size_t)(n * out_row), hipMemcpyDeviceToHost));
-    }
-    return LDPC_OK;
+    return ldpc::host_chunks(frames, {{(void *)sym_host, in_row, true, false}, {rx_host, out_row, false, true}},
+                             [&](int64_t n, int64_t, void *const *dev) {
+                                 return launch_demap(m, (const float *)dev[0], n, (float *)dev[1], nullptr);
+                             });
 }
 
 }  // extern "C"

@@ -9,20 +9,13 @@
 #include <cmath>
 
 #include "../../include/ldpc_hip.h"
-#include "graph.hpp"
+#include "hip_host.hpp"
 #include "ratematch_kernels.hpp"
 
 using ldpc::set_error;
+using ldpc::frame_grid;
 
 namespace {
-
-#define RATE_HIP_TRY(expr)                                                                      \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return set_error(LDPC_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                             __FILE__, __LINE__);                                               \
-    } while (0)
 
 /* the spec alone: fills the fields of the map that do not depend on the transmission */
 int check_spec(const ldpc_rate_spec *s, ldpc::RateMap *m)
@@ -69,24 +62,10 @@ inline int32_t host_index(const ldpc::RateMap &m, int64_t e)
     return (int32_t)(m.P + rank + (rank >= m.lo - m.P ? m.hi - m.lo : 0));
 }
 
-int known_format(int32_t f, const char *what)
-{
-    if (f != LDPC_CODE_PACKED && f != LDPC_CODE_BITS) return set_error(LDPC_ERR_ARG, "unknown %s %d", what, f);
-    return LDPC_OK;
-}
-
-/* grid.y: the kernels stride over the frames, so that a lane's index arithmetic serves many frames and the grid is a
- * few rounds of resident workgroups instead of one small workgroup per frame and tile */
-const int64_t kRateTargetBlocks = 16384;     /* 8 resident workgroups of 256 on each of 256 CUs, eight rounds */
-unsigned frame_grid(int64_t frames, unsigned grid_x)
-{
-    return (unsigned)std::min<int64_t>(std::min<int64_t>(frames, 65535), std::max<int64_t>(1, kRateTargetBlocks / grid_x));
-}
-
 int check_match(const ldpc::RateMap &m, int32_t code_format, int32_t tx_format)
 {
-    if (int rc = known_format(code_format, "code_format")) return rc;
-    if (int rc = known_format(tx_format, "tx_format")) return rc;
+    if (int rc = ldpc::known_code_format(code_format, "code_format")) return rc;
+    if (int rc = ldpc::known_code_format(tx_format, "tx_format")) return rc;
     if (code_format == LDPC_CODE_PACKED && m.N % 8) return set_error(LDPC_ERR_ARG, "code_format LDPC_CODE_PACKED needs N %% 8 == 0 (N = %d)", m.N);
     if (tx_format == LDPC_CODE_PACKED && m.E % 8) return set_error(LDPC_ERR_ARG, "tx_format LDPC_CODE_PACKED needs E %% 8 == 0 (E = %d)", m.E);
     return LDPC_OK;
@@ -107,7 +86,7 @@ int launch_match(const ldpc::RateMap &m, const uint8_t *code, int32_t code_forma
         if (tx_format == LDPC_CODE_PACKED) rate_match_kernel<0, 1><<<grid, kRateBlock, 0, s>>>(m, code, code_bytes, frames, tx);
         else rate_match_kernel<0, 0><<<grid, kRateBlock, 0, s>>>(m, code, code_bytes, frames, tx);
     }
-    RATE_HIP_TRY(hipGetLastError());
+    LDPC_HIP_TRY(hipGetLastError());
     return LDPC_OK;
 }
 
@@ -118,7 +97,7 @@ int launch_recover(const ldpc::RateMap &m, const float *rx, int64_t frames, floa
     const unsigned gx = (unsigned)((m.N + per - 1) / per);
     const dim3 grid(gx, frame_grid(frames, gx));
     rate_recover_kernel<<<grid, kRateBlock, 0, s>>>(m, rx, frames, soft, accumulate, y);
-    RATE_HIP_TRY(hipGetLastError());
+    LDPC_HIP_TRY(hipGetLastError());
     return LDPC_OK;
 }
 
@@ -129,22 +108,12 @@ int check_recover_flags(bool have_soft, bool have_y, int32_t accumulate)
     return LDPC_OK;
 }
 
-int use_device(int32_t device)
+/* soft and y of a recover call must not alias (the same address counts even when no frame is written) */
+bool soft_y_alias(const ldpc::RateMap &m, int64_t frames, const float *soft, const float *y)
 {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-        return set_error(LDPC_ERR_HIP, "no usable HIP device (rate matching has no CPU fallback)");
-    if (device < 0 || device >= count) return set_error(LDPC_ERR_ARG, "device %d of %d", device, count);
-    RATE_HIP_TRY(hipSetDevice(device));
-    return LDPC_OK;
+    const int64_t span = frames * (int64_t)m.N * (int64_t)sizeof(float);
+    return soft && y && (soft == y || ldpc::ranges_overlap(soft, span, y, span));
 }
-
-struct Scratch {
-    void *p = nullptr;
-    ~Scratch() { if (p) (void)hipFree(p); }
-};
-
-const int64_t kHostChunkBytes = (int64_t)64 << 20;   /* host-buffer calls: device scratch per array */
 
 }  // namespace
 
@@ -191,7 +160,7 @@ int ldpc_rate_match_device(const ldpc_rate_spec *spec, const uint8_t *code_dev, 
         return set_error(LDPC_ERR_ARG, "tx_bytes = %lld, %lld frames of E = %d need %lld", (long long)tx_bytes, (long long)frames, E,
                          (long long)ldpc_code_bytes(E, frames, tx_format));
     if (frames == 0) return LDPC_OK;
-    RATE_HIP_TRY(hipSetDevice(device));
+    LDPC_HIP_TRY(hipSetDevice(device));
     return launch_match(m, code_dev, code_format, frames, tx_dev, tx_format, (hipStream_t)stream);
 }
 
@@ -203,12 +172,9 @@ int ldpc_rate_recover_device(const ldpc_rate_spec *spec, const float *rx_dev, in
     if (int rc = check_recover_flags(soft_dev != nullptr, y_dev != nullptr, accumulate)) return rc;
     if (!rx_dev) return set_error(LDPC_ERR_ARG, "rx_dev is NULL");
     if (frames < 0) return set_error(LDPC_ERR_ARG, "frames = %lld is negative", (long long)frames);
-    if (soft_dev && y_dev) {
-        const uintptr_t a = (uintptr_t)soft_dev, b = (uintptr_t)y_dev, span = (uintptr_t)frames * (uintptr_t)m.N * sizeof(float);
-        if (a == b || (a < b + span && b < a + span)) return set_error(LDPC_ERR_ARG, "soft_dev and y_dev overlap: they must not alias");
-    }
+    if (soft_y_alias(m, frames, soft_dev, y_dev)) return set_error(LDPC_ERR_ARG, "soft_dev and y_dev overlap: they must not alias");
     if (frames == 0) return LDPC_OK;
-    RATE_HIP_TRY(hipSetDevice(device));
+    LDPC_HIP_TRY(hipSetDevice(device));
     return launch_recover(m, rx_dev, frames, soft_dev, accumulate, y_dev, (hipStream_t)stream);
 }
 
@@ -224,20 +190,13 @@ int ldpc_rate_match(const ldpc_rate_spec *spec, const uint8_t *code_host, int32_
         return set_error(LDPC_ERR_ARG, "tx_bytes = %lld, %lld frames of E = %d need %lld", (long long)tx_bytes, (long long)frames, E,
                          (long long)ldpc_code_bytes(E, frames, tx_format));
     if (frames == 0) return LDPC_OK;
-    if (int rc = use_device(device)) return rc;
+    if (int rc = ldpc::use_device(device, "rate matching")) return rc;
     const int64_t in_row = code_format == LDPC_CODE_PACKED ? m.N / 8 : m.N;
     const int64_t out_row = tx_format == LDPC_CODE_PACKED ? E / 8 : E;
-    const int64_t chunk = std::min<int64_t>(frames, std::max<int64_t>(1, kHostChunkBytes / std::max(in_row, out_row)));
-    Scratch in, out;
-    RATE_HIP_TRY(hipMalloc(&in.p, (size_t)(chunk * in_row)));
-    RATE_HIP_TRY(hipMalloc(&out.p, (size_t)(chunk * out_row)));
-    for (int64_t f0 = 0; f0 < frames; f0 += chunk) {
-        const int64_t n = std::min(chunk, frames - f0);
-        RATE_HIP_TRY(hipMemcpy(in.p, code_host + f0 * in_row, (size_t)(n * in_row), hipMemcpyHostToDevice));
-        if (int rc = launch_match(m, (const uint8_t *)in.p, code_format, n, (uint8_t *)out.p, tx_format, nullptr)) return rc;
-        RATE_HIP_TRY(hipMemcpy(tx_host + f0 * out_row, out.p, (size_t)(n * out_row), hipMemcpyDeviceToHost));
-    }
-    return LDPC_OK;
+    return ldpc::host_chunks(frames, {{(void *)code_host, in_row, true, false}, {tx_host, out_row, false, true}},
+                             [&](int64_t n, int64_t, void *const *dev) {
+                                 return launch_match(m, (const uint8_t *)dev[0], code_format, n, (uint8_t *)dev[1], tx_format, nullptr);
+                             });
 }
 
 int ldpc_rate_recover(const ldpc_rate_spec *spec, const float *rx_host, int64_t frames, int32_t k0, int32_t E, float *soft_host,
@@ -248,27 +207,14 @@ int ldpc_rate_recover(const ldpc_rate_spec *spec, const float *rx_host, int64_t 
     if (int rc = check_recover_flags(soft_host != nullptr, y_host != nullptr, accumulate)) return rc;
     if (!rx_host) return set_error(LDPC_ERR_ARG, "rx_host is NULL");
     if (frames < 0) return set_error(LDPC_ERR_ARG, "frames = %lld is negative", (long long)frames);
-    if (soft_host && y_host) {
-        const uintptr_t a = (uintptr_t)soft_host, b = (uintptr_t)y_host, span = (uintptr_t)frames * (uintptr_t)m.N * sizeof(float);
-        if (a == b || (a < b + span && b < a + span)) return set_error(LDPC_ERR_ARG, "soft_host and y_host overlap: they must not alias");
-    }
+    if (soft_y_alias(m, frames, soft_host, y_host)) return set_error(LDPC_ERR_ARG, "soft_host and y_host overlap: they must not alias");
     if (frames == 0) return LDPC_OK;
-    if (int rc = use_device(device)) return rc;
+    if (int rc = ldpc::use_device(device, "rate matching")) return rc;
     const int64_t rx_row = (int64_t)E * sizeof(float), n_row = (int64_t)m.N * sizeof(float);
-    const int64_t chunk = std::min<int64_t>(frames, std::max<int64_t>(1, kHostChunkBytes / std::max(rx_row, n_row)));
-    Scratch rx, soft, y;
-    RATE_HIP_TRY(hipMalloc(&rx.p, (size_t)(chunk * rx_row)));
-    if (soft_host) RATE_HIP_TRY(hipMalloc(&soft.p, (size_t)(chunk * n_row)));
-    if (y_host) RATE_HIP_TRY(hipMalloc(&y.p, (size_t)(chunk * n_row)));
-    for (int64_t f0 = 0; f0 < frames; f0 += chunk) {
-        const int64_t n = std::min(chunk, frames - f0);
-        RATE_HIP_TRY(hipMemcpy(rx.p, rx_host + f0 * E, (size_t)(n * rx_row), hipMemcpyHostToDevice));
-        if (accumulate) RATE_HIP_TRY(hipMemcpy(soft.p, soft_host + f0 * m.N, (size_t)(n * n_row), hipMemcpyHostToDevice));
-        if (int rc = launch_recover(m, (const float *)rx.p, n, (float *)soft.p, accumulate, (float *)y.p, nullptr)) return rc;
-        if (soft_host) RATE_HIP_TRY(hipMemcpy(soft_host + f0 * m.N, soft.p, (size_t)(n * n_row), hipMemcpyDeviceToHost));
-        if (y_host) RATE_HIP_TRY(hipMemcpy(y_host + f0 * m.N, y.p, (size_t)(n * n_row), hipMemcpyDeviceToHost));
-    }
-    return LDPC_OK;
+    return ldpc::host_chunks(frames, {{(void *)rx_host, rx_row, true, false}, {soft_host, n_row, accumulate != 0, true}, {y_host, n_row, false, true}},
+                             [&](int64_t n, int64_t, void *const *dev) {
+                                 return launch_recover(m, (const float *)dev[0], n, (float *)dev[1], accumulate, (float *)dev[2], nullptr);
+                             });
 }
 
 }  // extern "C"
