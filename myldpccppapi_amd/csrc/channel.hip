@@ -36,26 +36,20 @@ __global__ __launch_bounds__(256) void hbm_probe_copy_kernel(const ldpc::vf4 *__
 
 /* what the two probes share: the two arrays (the source filled), a stream and two events */
 struct ProbeRig {
+    ldpc::Stream stream;                /* before the arrays and events: they go first */
     ldpc::DevBuf<ldpc::vf4> src, dst;
     size_t n4 = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t a = nullptr, b = nullptr;
+    ldpc::Event a, b;
     hipError_t open(int64_t bytes)
     {
         n4 = (size_t)bytes / sizeof(ldpc::vf4);
         hipError_t e = src.alloc(n4);
         if (e == hipSuccess) e = dst.alloc(n4);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreate(&a);
-        if (e == hipSuccess) e = hipEventCreate(&b);
-        if (e == hipSuccess) e = hipMemsetAsync(src.p, 0x3c, n4 * sizeof(ldpc::vf4), s);
+        if (e == hipSuccess) e = stream.create();
+        if (e == hipSuccess) e = a.create();
+        if (e == hipSuccess) e = b.create();
+        if (e == hipSuccess) e = hipMemsetAsync(src.p, 0x3c, n4 * sizeof(ldpc::vf4), stream.s);
         return e;
-    }
-    ~ProbeRig()
-    {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-        if (s) (void)hipStreamDestroy(s);
     }
 };
 
@@ -122,8 +116,8 @@ int ldpc_hbm_probe_device(int32_t device, int64_t bytes, int32_t reps, double *c
     hipError_t e = rig.open(bytes);
     const size_t n4 = rig.n4;
     ldpc::vf4 *const src = rig.src.p, *const dst = rig.dst.p;
-    const hipStream_t s = rig.s;
-    const hipEvent_t a = rig.a, b = rig.b;
+    const hipStream_t s = rig.stream.s;
+    const hipEvent_t a = rig.a.e, b = rig.b.e;
     float best_ms[2] = {0.0f, 0.0f};                             /* default policy, non-temporal */
     if (e == hipSuccess) {
         const unsigned grid = (unsigned)std::min<size_t>((n4 + 1023) / 1024, 256 * 64);
@@ -161,8 +155,8 @@ int ldpc_hbm_sustained_device(int32_t device, int64_t bytes, int32_t millisecond
     hipError_t e = rig.open(bytes);
     const size_t n4 = rig.n4;
     ldpc::vf4 *const src = rig.src.p, *const dst = rig.dst.p;
-    const hipStream_t s = rig.s;
-    const hipEvent_t a = rig.a, b = rig.b;
+    const hipStream_t s = rig.stream.s;
+    const hipEvent_t a = rig.a.e, b = rig.b.e;
     const unsigned grid = (unsigned)std::min<size_t>((n4 + 1023) / 1024, 256 * 64);
     /* one launch's time from a short burst, then a third of the time untimed and two thirds timed */
     float one_ms = 0.0f;

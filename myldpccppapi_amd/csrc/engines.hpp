@@ -1,8 +1,8 @@
 /*
- * engines.hpp -- the entry points of the one-launch and layered engines that instantiate kernels,
- * compiled in translation units of their own (engine_ldsp.hip, engine_fused.hip, engine_layered.hip)
- * so that the library builds in parallel.  The host driver calls these instead of the inline
- * functions of the kernel headers; plan structs and everything without kernels stay in the headers.
+ * engines.hpp -- the entry points of the engines that instantiate kernels, compiled in translation units of
+ * their own (engine_ldsp.hip, engine_fused.hip, engine_layered.hip, engine_flood.hip) so that the library
+ * builds in parallel.  The host driver calls these instead of the inline functions of the kernel headers;
+ * plan structs and everything without kernels stay in the headers.
  */
 #pragma once
 
@@ -12,6 +12,9 @@
 #include <vector>
 
 #include "tune.hpp"
+
+struct ldpc_decoder;
+struct ldpc_graph;
 
 namespace ldpc {
 
@@ -27,5 +30,12 @@ hipError_t engine_ldsp_plan_create(LdspPlan *pl, int32_t M, int32_t N, int64_t E
 hipError_t engine_ldsp_run(LdspPlan *pl, const FusedRun &r, hipStream_t s, int32_t *launched);
 hipError_t engine_fused_run(FusedPlan *pl, const FusedRun &r, hipStream_t s, int32_t *launched);
 hipError_t engine_layered_run(LayeredPlan *pl, const LayeredRun &r, hipStream_t s, int32_t *launched);
+
+/* The streaming flooding engine works on the handle (decoder.hpp: ldpc_decoder::flood) and returns LDPC_* codes with
+ * the message set.  setup: message arrays of TF frames, work lists, kernel tables, launch plan and, for a decoder that
+ * is no hand-over child (top_level), link calibration and placement search. */
+int engine_flood_setup(ldpc_decoder *d, const ldpc_graph *g, size_t TF, bool top_level);
+int engine_flood_run(ldpc_decoder *d, const float *llr_dev, int64_t frames, uint8_t *out_dev, int64_t out_bytes,
+                     int32_t *iters_dev, hipStream_t s);
 
 }  // namespace ldpc

@@ -1,7 +1,7 @@
 /*
  * flood_tables.hpp -- the kernel tables of the streaming flooding decoders, filled per arithmetic in
  * translation units of their own (flood_sp.hip, flood_ms.hip, flood_ms16.hip, flood_msc*.hip) so that the library
- * builds in parallel: the host driver (ldpc_hip.hip) only sees function pointers.
+ * builds in parallel: the flooding engine (engine_flood.hip) only sees function pointers.
  */
 #pragma once
 

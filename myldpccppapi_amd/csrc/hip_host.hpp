@@ -1,7 +1,8 @@
 /*
  * hip_host.hpp -- the host scaffolding every translation unit of libldpc_hip.so shares: the setter of the calling
- * thread's ldpc_last_error() message, the one HIP error macro, the one owner of device memory (DevBuf), and the small
- * helpers of the handle-less stage entry points (device selection, argument checks, grid sizing, the host-buffer loop).
+ * thread's ldpc_last_error() message (and its two accessors), the one HIP error macro, the owners of the HIP resources
+ * (DevBuf: device memory, HostBuf: pinned host memory, Event, Stream), and the small helpers of the handle-less stage
+ * entry points (device selection, argument checks, grid sizing, the host-buffer loop).
  */
 #pragma once
 
@@ -10,6 +11,7 @@
 
 #include <algorithm>
 #include <initializer_list>
+#include <string>
 #include <vector>
 
 #include "../../include/ldpc_hip.h"
@@ -18,6 +20,10 @@ namespace ldpc {
 
 /* stores the formatted message for ldpc_last_error() and returns `code` (ldpc_hip.hip) */
 int set_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+/* the calling thread's message, and putting a saved one back: a worker thread's text crosses to the thread that waited
+ * for it, and a call's first error survives its clean-up (ldpc_hip.hip) */
+std::string last_error_text();
+void restore_error(const std::string &text);
 
 #define LDPC_HIP_TRY(expr)                                                                             \
     do {                                                                                               \
@@ -53,6 +59,8 @@ template <typename T> struct DevBuf {
         if (e != hipSuccess || h.empty()) return e;
         return hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
     }
+    /* made by the first caller that needs it: nothing happens when it is there already */
+    hipError_t ensure(size_t count) { return p ? hipSuccess : alloc(count); }
     void release()
     {
         if (p) (void)hipFree(p);
@@ -60,6 +68,95 @@ template <typename T> struct DevBuf {
         n = 0;
     }
     ~DevBuf() { release(); }
+};
+
+/* pinned host memory with an owner */
+template <typename T> struct HostBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    HostBuf() = default;
+    HostBuf(const HostBuf &) = delete;
+    HostBuf &operator=(const HostBuf &) = delete;
+    HostBuf(HostBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    HostBuf &operator=(HostBuf &&o) noexcept
+    {
+        if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
+        return *this;
+    }
+    hipError_t alloc(size_t count)
+    {
+        release();
+        if (!count) return hipSuccess;
+        const hipError_t e = hipHostMalloc((void **)&p, count * sizeof(T), hipHostMallocDefault);
+        if (e != hipSuccess) p = nullptr;
+        else n = count;
+        return e;
+    }
+    hipError_t ensure(size_t count) { return p ? hipSuccess : alloc(count); }
+    void release()
+    {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        n = 0;
+    }
+    ~HostBuf() { release(); }
+};
+
+/* an event with an owner; create(false): hipEventDisableTiming (an ordering mark only) */
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    Event &operator=(Event &&o) noexcept
+    {
+        if (this != &o) { release(); e = o.e; o.e = nullptr; }
+        return *this;
+    }
+    hipError_t create(bool timed = true)
+    {
+        release();
+        const hipError_t r = timed ? hipEventCreate(&e) : hipEventCreateWithFlags(&e, hipEventDisableTiming);
+        if (r != hipSuccess) e = nullptr;
+        return r;
+    }
+    hipError_t ensure(bool timed = true) { return e ? hipSuccess : create(timed); }
+    void release()
+    {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    ~Event() { release(); }
+};
+
+/* a non-blocking stream with an owner.  The destructor does not wait: whoever owns memory or events used on the stream
+ * drains it first (decoder.hpp: ~ldpc_decoder) */
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    Stream(Stream &&o) noexcept : s(o.s) { o.s = nullptr; }
+    Stream &operator=(Stream &&o) noexcept
+    {
+        if (this != &o) { release(); s = o.s; o.s = nullptr; }
+        return *this;
+    }
+    hipError_t create()
+    {
+        release();
+        const hipError_t r = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+        if (r != hipSuccess) s = nullptr;
+        return r;
+    }
+    hipError_t ensure() { return s ? hipSuccess : create(); }
+    void release()
+    {
+        if (s) (void)hipStreamDestroy(s);
+        s = nullptr;
+    }
+    ~Stream() { release(); }
 };
 
 /* makes `device` current after checking that it exists; `what` names the stage in "... has no CPU fallback" */

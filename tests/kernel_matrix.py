@@ -49,7 +49,7 @@ def degree_maps(rows, cols, M, N):
 
 def linkable_rows(rows, cols, M, N):
     """Per row degree: how many rows share a degree-2 column with the next row of the same degree, the
-    column's first edge in the first row (what build_classes in ldpc_hip.hip may fuse into the check kernel)."""
+    column's first edge in the first row (what build_classes in engine_flood.hip may fuse into the check kernel)."""
     rows, cols = np.asarray(rows), np.asarray(cols)
     rd = np.bincount(rows, minlength=M)
     cd = np.bincount(cols, minlength=N)

@@ -287,6 +287,51 @@ def test_ms_fused_refuses_bit_packing_of_ragged_frames(built):
         assert e.value.code == 4
 
 
+def test_creation_that_fails_late_frees_what_it_took(built):
+    """A config that is refused only after the handle has allocated its common arrays: LDPC_ALGO_MS_FUSED on the
+    (648, 324) code with one circulant no longer cyclic (two of its rows trade their columns).  32 such creations must
+    not cost device memory: the free memory falls by less than one handle's common arrays (S, worked out from the
+    shapes below), where a leak would cost 32 S.  The device then still decodes: a valid decoder of the same graph
+    against the oracle."""
+    torch = _torch()
+    cd = ac.code("w648")
+    rows, cols, M, N, K, z = np.array(cd["rows"]), np.array(cd["cols"]), cd["M"], cd["N"], cd["K"], cd["z"]
+    e0 = int(np.nonzero(rows == 0)[0][0])
+    e1 = int([e for e in np.nonzero(rows == 1)[0] if cols[e] // z == cols[e0] // z][0])
+    cols[e0], cols[e1] = cols[e1], cols[e0]
+    order = np.lexsort((cols, rows))
+    rows, cols = rows[order], cols[order]
+    g = L.Graph(rows, cols, M, N)
+    B, max_iter, V = 262144, 100, 4
+    F = 64 * V
+    T = (B + F - 1) // F
+    # hard [T][N][V] words, failw [max_iter + 2][T][V] words, done [T][V] words, iters [T * F] int32
+    S = 8 * T * N * V + 8 * (max_iter + 2) * T * V + 8 * T * V + 4 * T * F
+    assert 20 * 2 ** 20 < S < 64 * 2 ** 20
+
+    def refused():
+        with pytest.raises(L.LdpcError) as e:
+            L.Decoder(g, K, max_batch=B, algo="ms_fused", max_iter=max_iter, layer_rows=z, frames_per_lane=V)
+        assert e.value.code == 4 and "quasi-cyclic" in str(e.value)
+
+    refused()                               # what the runtime sets up once per process is not counted
+    _sync()
+    before, _ = torch.cuda.mem_get_info()
+    for _ in range(32):
+        refused()
+    _sync()
+    after, _ = torch.cuda.mem_get_info()
+    print("free device memory: %d -> %d bytes (S = %d)" % (before, after, S))
+    assert before - after < S, (before, after, S)
+
+    y = ac.mix_channel(N, 64, 0.55, 0.95, seed=648)
+    ref = oracle.decode(oracle.Graph(rows, cols, M, N, K), y, "ms", max_iter=ac.MAXIT)
+    dec = L.Decoder(g, K, max_batch=64, algo="ms", max_iter=ac.MAXIT)
+    out, iters = dec.decode(y)
+    dec.close()
+    assert np.array_equal(out, ref["out"]) and np.array_equal(iters, ref["iters"])
+
+
 # --------------------------------------------------------------------------- call sequences on one handle
 
 def _sequence(c, calls):

@@ -62,7 +62,7 @@ def test_device_list_handle_equals_single_device(built, algo):
 @pytest.mark.parametrize("pack", [L.PACK_BYTES, L.PACK_BITS])
 def test_device_list_with_frames_not_byte_aligned(built, pack):
     """(648, 324): K % 8 = 4, so a frame's first byte is (frame*K)/8 per launch group -- shard
-    boundaries are chosen where that stays exact (ldpc_hip.hip: shard_unit), and three devices
+    boundaries are chosen where that stays exact (host_path.hip: shard_unit), and three devices
     sharing the GPU must reproduce the single-device bytes in both packings."""
     g, og, K, M, z = _graph(codes.RATE_1_2, 648)
     B = 301

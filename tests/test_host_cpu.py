@@ -462,3 +462,19 @@ def test_worker_threads_and_lock_registry_unit(built, tmp_path):
                            "-L/opt/rocm/lib", "-lamdhip64", "-lpthread", "-Wl,-rpath,/opt/rocm/lib"])
     p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0 and p.stdout.strip().endswith("ok"), p.stdout + p.stderr
+
+
+def test_resource_owners_unit_under_host_sanitizers(built, tmp_path):
+    """csrc/hip_host.hpp: the owners of pinned memory, events and streams (and DevBuf's make-if-absent) in a
+    stand-alone program whose host code is built with the address and undefined-behaviour sanitizers: moves,
+    release twice, make-if-absent twice, destruction of a never-created owner.  The program runs with every device
+    hidden, so each create fails and must leave its owner empty."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "hip_holders_test")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-std=c++17", "-O1", "-g",
+                           "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
+                           os.path.join(root, "tests", "cpp", "hip_holders_test.cpp"), "-o", exe])
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
+    assert p.returncode == 0 and p.stdout.strip().endswith("ok"), p.stdout + p.stderr
+    assert "5 refused" in p.stdout, p.stdout

@@ -15,9 +15,11 @@ def remarks(src):
     return subprocess.run(cmd, cwd=root, capture_output=True, text=True).stderr
 
 
-# the library's translation units (csrc/Makefile: HIP_OBJS)
-with ThreadPoolExecutor(7) as ex:
-    out = "\n".join(ex.map(remarks, ["ldpc_hip.hip", "flood_sp.hip", "flood_ms.hip", "flood_ms16.hip", "engine_ldsp.hip", "engine_fused.hip", "engine_layered.hip"]))
+# the library's translation units: HIP_OBJS of csrc/Makefile, continuation lines included
+objs = re.search(r"^HIP_OBJS\s*:=((?:.*\\\n)*.*)$", open(os.path.join(root, "Makefile")).read(), re.M).group(1)
+units = [u + ".hip" for u in re.findall(r"build/(\w+)\.o", objs)]
+with ThreadPoolExecutor(8) as ex:
+    out = "\n".join(ex.map(remarks, units))
 pat = re.compile(sys.argv[1]) if len(sys.argv) > 1 else None
 cur = None
 rows = []
