@@ -34,6 +34,8 @@
  *   - setRateMatch(): puncturing, filler bits and a circular-buffer transmission of E bits per frame around
  *     encode() / decode() (the "rate matching" section of ldpc_hip.h).
  *   - setModulation(): test() sends QPSK / 16- / 64- / 256-QAM symbols through the "modem" section of ldpc_hip.h.
+ *   - setTransportBlock(): every frame carries payload bits plus a CRC ("transport block" section of ldpc_hip.h), which
+ *     decode() checks: crcPassed() / lastCrcFailures().
  */
 #ifndef MYLDPC_H_
 #define MYLDPC_H_
@@ -119,6 +121,18 @@ public:
      * ldpc_modem_demap).  DecodeSP reads values of very unequal reliability then: setLlrScale(2 / (rate * rate)).
      * Off by default: without this call every byte is as in the reference.  Returns 0 or an ldpc_status. */
     int setModulation(int Qm, bool interleave = true);
+    /* Transport blocks (ldpc_hip.h, "transport block"), one code block each: a frame carries payloadBits payload bits
+     * (a multiple of 8) followed by their CRC -- crcBits 0, 16 or 24 (CRC24A); -1 = the rule of TS 38.212: 24 above 3824
+     * payload bits, else 16 -- and zero filler bits up to K; payloadBits + crc <= K.  Then encode() reads payloadBits / 8
+     * source bytes per frame, decode() writes payloadBits / 8 bytes per frame and checks every frame's CRC, srcLength
+     * counts payload bytes in both, and getCodeSize / getPriorCodeLength / getPostCodeLength follow.  lastCrcFailures()
+     * and crcPassed(frame) report the check of the last decode().  Composes with setEncodeOnDevice, setRateMatch and
+     * setModulation; a caller who does not want the fillers [payloadBits + crc, K) sent passes them to setRateMatch.
+     * Runs on the GPU `setDevice` names (ldpc_tb_attach / ldpc_tb_check).  Off by default: without this call every byte and
+     * length is as in the reference.  Before encode() and decode().  Returns 0 or an ldpc_status. */
+    int setTransportBlock(int payloadBits, int crcBits = -1);
+    int lastCrcFailures() const { return crcFailures; }
+    bool crcPassed(int frame) const { return frame >= 0 && (size_t)frame < crcOk.size() && crcOk[(size_t)frame] != 0; }
     int lastIterations() const { return lastTime; }             /* the reference's "Time=" */
     const char *lastError() const { return err.c_str(); }
     int getNonZeros() const { return nonZeros; }
@@ -160,6 +174,11 @@ private:
     int rmE = 0, rmK0 = 0;           /* setRateMatch(); rmE = 0: off */
     ldpc_rate_spec rmSpec = {};
     ldpc_modem_spec modSpec = {};    /* setModulation(); Qm = 0: off */
+    ldpc_tb_spec tbSpec = {};        /* setTransportBlock(); A = 0: off */
+    std::vector<unsigned char> crcOk;/* per frame of the last decode() */
+    int crcFailures = 0;
+    int frameCount(int kBytes) const { return (kBytes + (ldpcK / 8) - 1) / (ldpcK / 8); }   /* frames of K/8-byte rows */
+    int encodeSource(char *srcCode, char *priorCode, int srcLength);
     int encodeFrames(char *srcCode, char *priorCode, int srcLength);
     ldpc_encoder *encoder = nullptr; /* forEncoder() with encodeOnDevice */
     int makeGraph();

@@ -509,6 +509,66 @@ int ldpc_modem_transmit(const ldpc_modem_spec *spec, const uint8_t *tx_host, int
                         uint64_t seed, int64_t first_frame, float *sym_host, int64_t sym_floats, int32_t device);
 int ldpc_modem_demap(const ldpc_modem_spec *spec, const float *sym_host, int64_t frames, int32_t E, float *rx_host, int32_t device);
 
+/* ---- transport block: CRC attachment, segmentation into code blocks and filler bits in front of ldpc_encode_device; the
+ *      CRC checks and the reassembly behind ldpc_decode_device (TS 38.212 sections 5.1 and 5.2.2), for data that stays in
+ *      HBM.  The reference has no counterpart: it pushes K raw bits per frame and compares with the bytes it sent.
+ * Bit order: the project's, LSB first -- bit i of a row is bit i % 8 of byte i / 8.
+ * CRC (TS 38.212 section 5.1): g24A = 0x1864CFB, g24B = 0x1800063, g16 = 0x11021.  For bits a_0 .. a_(n-1) the parity
+ *   p_0 .. p_(L-1) makes a_0 x^(n+L-1) + ... + a_(n-1) x^L + p_0 x^(L-1) + ... + p_(L-1) divisible by g: register zero, no
+ *   reflection, no final XOR; the parity follows the data, p_0 first.  The nine ASCII bytes "123456789", each taken MSB
+ *   first, give 0xCDE703 (24A), 0x23EF52 (24B) and 0x31C3 (16), p_0 being the top bit of the value.
+ * Spec: plain parameters -- no handle, no device state.
+ *       B = A + tb_crc,  B % C == 0,  S = B / C,  Kp = S + cb_crc <= K
+ *   The stream of a transport block is its A payload bits followed by the tb_crc parity bits of those A bits (24: CRC24A).
+ *   Code block c takes stream bits [c S, (c + 1) S) -- S % 8 need not be 0, a code block may start in the middle of a
+ *   byte --, then the cb_crc parity bits of those S bits (CRC24B), then zeros: the filler bits [Kp, K) of every frame,
+ *   known zeros, the filler_lo / filler_hi a caller passes to ldpc_rate_spec.
+ *   ldpc_tb_spec_init applies the rule of section 5.2.2 with the code's K in place of Kcb: tb_crc = A > 3824 ? 24 : 16;
+ *   B <= K: C = 1, cb_crc = 0; otherwise cb_crc = 24 and C = ceil(B / (K - 24)).  If B % C != 0 afterwards the spec is
+ *   left as computed and the other calls refuse it.
+ * ldpc_tb_layout (host only): out = {B, S, Kp, filler_lo = Kp, filler_hi = K, C}.
+ * ldpc_crc_bits (host only): the CRC of the first nbits bits of a byte row, by long division.
+ * ldpc_tb_attach_device: payload_dev holds tbs rows of A/8 bytes, src_dev receives tbs * C rows of K/8 bytes -- what
+ *   ldpc_encode_device takes as src_dev with frames = tbs * C.  Frame t C + c is code block c of transport block t; every
+ *   byte of every row is written.  src_bytes < tbs * C * K/8 is LDPC_ERR_ARG.
+ * ldpc_tb_check_device: dec_dev holds tbs * C rows of K/8 bytes, as a decoder writes them with LDPC_PACK_BYTES.  The three
+ *   outputs are nullable, at least one must be given.
+ *       cb_ok_dev[f] = 1 if cb_crc == 0 or the first Kp bits of frame f leave remainder zero, else 0
+ *       payload_dev  = the first A bits of the reassembled stream, tbs rows of A/8 bytes
+ *       tb_ok_dev[t] = 1 if (tb_crc == 0 or the B reassembled bits leave remainder zero) and all C code blocks are ok
+ *   Decoded filler bits are ignored.
+ * ldpc_tb_tally_device: blocks, as ldpc_count_errors_device does; ref_dev NULL = all zero.  counts[0] = transport blocks
+ *   with tb_ok == 0, [1] = blocks whose bytes_per_tb payload bytes differ from the reference, [2] = blocks that differ
+ *   although tb_ok == 1 (undetected errors), [3] = blocks with tb_ok == 0 although the payload is equal (the damage is in
+ *   parity bits only).
+ * The *_device calls enqueue on `stream` (a hipStream_t, NULL = default stream), return without waiting and allocate
+ *   nothing; byte buffers may have any alignment; nothing outside the stated sizes is read or written; overlapping input
+ *   and output is LDPC_ERR_ARG; a refused call has enqueued nothing; tbs == 0 enqueues nothing.  ldpc_tb_attach /
+ *   ldpc_tb_check take host buffers, block, and run the same kernels over chunks of whole transport blocks.  There is no
+ *   CPU path.  Every argument error is LDPC_ERR_ARG with a message that names the field. */
+enum ldpc_crc_kind { LDPC_CRC16 = 16, LDPC_CRC24A = 24, LDPC_CRC24B = 25 };
+typedef struct ldpc_tb_spec {
+    uint32_t struct_size;          /* = sizeof(ldpc_tb_spec); ABI guard                                                 */
+    int32_t  A;                    /* payload bits per transport block; A % 8 == 0, A >= 8                              */
+    int32_t  tb_crc;               /* CRC on the transport block: 0, 16 or 24 (CRC24A)                                  */
+    int32_t  C;                    /* code blocks per transport block, >= 1                                             */
+    int32_t  cb_crc;               /* CRC on each code block: 0 or 24 (CRC24B)                                          */
+    int32_t  K;                    /* information bits of the code; K % 8 == 0                                          */
+} ldpc_tb_spec;
+void ldpc_tb_spec_init(ldpc_tb_spec *spec, int32_t A, int32_t K);
+int ldpc_tb_layout(const ldpc_tb_spec *spec, int32_t out[6]);
+int ldpc_crc_bits(int32_t kind, const uint8_t *bytes, int64_t nbits, uint32_t *crc);
+int ldpc_tb_attach_device(const ldpc_tb_spec *spec, const uint8_t *payload_dev, int64_t tbs, uint8_t *src_dev, int64_t src_bytes,
+                          int32_t device, void *stream);
+int ldpc_tb_check_device(const ldpc_tb_spec *spec, const uint8_t *dec_dev, int64_t tbs, uint8_t *payload_dev, uint8_t *cb_ok_dev,
+                         uint8_t *tb_ok_dev, int32_t device, void *stream);
+int ldpc_tb_tally_device(const uint8_t *tb_ok_dev, const uint8_t *payload_dev, const uint8_t *ref_dev, int64_t tbs,
+                         int64_t bytes_per_tb, int64_t counts[4], int32_t device, void *stream);
+int ldpc_tb_attach(const ldpc_tb_spec *spec, const uint8_t *payload_host, int64_t tbs, uint8_t *src_host, int64_t src_bytes,
+                   int32_t device);
+int ldpc_tb_check(const ldpc_tb_spec *spec, const uint8_t *dec_host, int64_t tbs, uint8_t *payload_host, uint8_t *cb_ok_host,
+                  uint8_t *tb_ok_host, int32_t device);
+
 /* ---- measurement aid: the rate a plain float4 copy of `bytes` bytes (read + write counted)
  *      sustains on `device` right now, best of `reps` launches each with the default cache policy
  *      and with non-temporal loads and stores (the streaming kernels' policy), HIP-event timed on

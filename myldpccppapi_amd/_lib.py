@@ -68,6 +68,12 @@ class ModemSpec(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("Qm", ctypes.c_int32), ("interleave", ctypes.c_int32)]
 
 
+class TbSpec(ctypes.Structure):
+    """Mirror of `ldpc_tb_spec`."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("A", ctypes.c_int32), ("tb_crc", ctypes.c_int32), ("C", ctypes.c_int32),
+                ("cb_crc", ctypes.c_int32), ("K", ctypes.c_int32)]
+
+
 #: every symbol include/ldpc_hip.h declares
 EXPORTS = (
     "ldpc_abi_version", "ldpc_last_error", "ldpc_device_count", "ldpc_graph_create",
@@ -81,6 +87,8 @@ EXPORTS = (
     "ldpc_rate_match", "ldpc_rate_recover",
     "ldpc_modem_spec_init", "ldpc_modem_symbol_floats", "ldpc_modem_index", "ldpc_modem_points", "ldpc_modem_transmit_device",
     "ldpc_modem_demap_device", "ldpc_modem_transmit", "ldpc_modem_demap",
+    "ldpc_tb_spec_init", "ldpc_tb_layout", "ldpc_crc_bits", "ldpc_tb_attach_device", "ldpc_tb_check_device", "ldpc_tb_tally_device",
+    "ldpc_tb_attach", "ldpc_tb_check",
 )
 
 
@@ -172,6 +180,16 @@ def load():
     L.ldpc_modem_transmit.argtypes = [msp, vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_uint64,
                                       ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int32]
     L.ldpc_modem_demap.argtypes = [msp, vp, ctypes.c_int64, ctypes.c_int32, vp, ctypes.c_int32]
+    tsp = ctypes.POINTER(TbSpec)
+    L.ldpc_tb_spec_init.argtypes = [tsp, ctypes.c_int32, ctypes.c_int32]
+    L.ldpc_tb_spec_init.restype = None
+    L.ldpc_tb_layout.argtypes = [tsp, i32p]
+    L.ldpc_crc_bits.argtypes = [ctypes.c_int32, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint32)]
+    L.ldpc_tb_attach_device.argtypes = [tsp, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int32, vp]
+    L.ldpc_tb_check_device.argtypes = [tsp, vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int32, vp]
+    L.ldpc_tb_tally_device.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int64, i64p, ctypes.c_int32, vp]
+    L.ldpc_tb_attach.argtypes = [tsp, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int32]
+    L.ldpc_tb_check.argtypes = [tsp, vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int32]
     _lib = L
     return L
 

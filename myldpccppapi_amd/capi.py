@@ -1,4 +1,5 @@
-"""Thin Python objects over the C ABI (include/ldpc_hip.h): Graph, Decoder, Encoder, RateMatcher and Modem.
+"""Thin Python objects over the C ABI (include/ldpc_hip.h): Graph, Decoder, Encoder, RateMatcher, Modem and
+TransportBlock.
 
 Host-side plumbing only -- every decode runs in the HIP kernels of
 libldpc_hip.so.  numpy arrays are passed as host pointers, integers (e.g. a
@@ -461,3 +462,77 @@ class Modem:
         rx = np.zeros((sym.shape[0], int(E)), np.float32)
         _lib.check(_lib.load().ldpc_modem_demap(ctypes.byref(self.spec), sym.ctypes.data, sym.shape[0], int(E), rx.ctypes.data, self.device))
         return rx
+
+
+CRC_KINDS = {"16": 16, "24a": 24, "24b": 25}               # enum ldpc_crc_kind
+
+
+class TransportBlock:
+    """The transport-block stage in front of Encoder.encode_device and behind Decoder.decode_device (ldpc_tb_*,
+    include/ldpc_hip.h): a CRC on the A payload bits (tb_crc 0, 16 or 24 = CRC24A), segmentation into C code blocks that
+    each carry CRC24B (cb_crc 0 or 24), zero filler bits up to the code's K; at the receiver the CRC checks and the
+    reassembly.  C, tb_crc, cb_crc: None = the rule of ldpc_tb_spec_init (TS 38.212 section 5.2.2 with K for Kcb).
+    Frame t * C + c is code block c of transport block t.  A plain parameter set: no handle."""
+
+    def __init__(self, A, K, C=None, tb_crc=None, cb_crc=None, device=0):
+        L = _lib.load()
+        self.spec = _lib.TbSpec()
+        L.ldpc_tb_spec_init(ctypes.byref(self.spec), int(A), int(K))
+        for name, v in (("C", C), ("tb_crc", tb_crc), ("cb_crc", cb_crc)):
+            if v is not None:
+                setattr(self.spec, name, int(v))
+        self.device = int(device)
+        self.B, self.S, self.Kp, self.filler_lo, self.filler_hi, self.C = self.layout()      # an unusable spec fails here
+        self.A, self.K, self.tb_crc, self.cb_crc = self.spec.A, self.spec.K, self.spec.tb_crc, self.spec.cb_crc
+
+    def layout(self):
+        """(B, S, Kp, filler_lo, filler_hi, C): stream bits, bits per code block, bits in front of the fillers [Kp, K)."""
+        out = (ctypes.c_int32 * 6)()
+        _lib.check(_lib.load().ldpc_tb_layout(ctypes.byref(self.spec), out))
+        return tuple(int(v) for v in out)
+
+    @staticmethod
+    def crc_bits(kind, data, nbits=None):
+        """CRC of the first `nbits` bits (default: all) of a uint8 row in the project's bit order; kind: 16, 24 (24A),
+        25 (24B) or "16" / "24a" / "24b".  Host arithmetic only."""
+        data = np.ascontiguousarray(data, np.uint8).reshape(-1)
+        n = data.size * 8 if nbits is None else int(nbits)
+        assert n <= data.size * 8
+        crc = ctypes.c_uint32()
+        _lib.check(_lib.load().ldpc_crc_bits(CRC_KINDS.get(kind, kind), data.ctypes.data if data.size else None, n, ctypes.byref(crc)))
+        return crc.value
+
+    # -- buffers already in HBM (integers, e.g. a torch tensor's data_ptr()); enqueued on `stream`, no wait --------
+    def attach_device(self, payload_ptr, tbs, src_ptr, src_nbytes, stream=None):
+        _lib.check(_lib.load().ldpc_tb_attach_device(ctypes.byref(self.spec), payload_ptr, int(tbs), src_ptr, int(src_nbytes),
+                                                     self.device, stream))
+
+    def check_device(self, dec_ptr, tbs, payload_ptr=None, cb_ok_ptr=None, tb_ok_ptr=None, stream=None):
+        _lib.check(_lib.load().ldpc_tb_check_device(ctypes.byref(self.spec), dec_ptr, int(tbs), payload_ptr, cb_ok_ptr, tb_ok_ptr,
+                                                    self.device, stream))
+
+    def tally_device(self, tb_ok_ptr, payload_ptr, ref_ptr, tbs, stream=None):
+        """Blocks.  (failed, wrong, undetected, parity_only) over `tbs` transport blocks of A/8 payload bytes."""
+        counts = (ctypes.c_int64 * 4)()
+        _lib.check(_lib.load().ldpc_tb_tally_device(tb_ok_ptr, payload_ptr, ref_ptr, int(tbs), self.A // 8, counts, self.device, stream))
+        return tuple(int(v) for v in counts)
+
+    # -- host buffers (numpy); blocking ---------------------------------------------------------------------------
+    def attach(self, payload):
+        """payload: uint8 [tbs, A/8] -> uint8 [tbs * C, K/8], the source rows of the encoder."""
+        payload = np.ascontiguousarray(payload, np.uint8).reshape(-1, self.A // 8)
+        tbs = payload.shape[0]
+        src = np.zeros((tbs * self.C, self.K // 8), np.uint8)
+        _lib.check(_lib.load().ldpc_tb_attach(ctypes.byref(self.spec), payload.ctypes.data, tbs, src.ctypes.data, src.size, self.device))
+        return src
+
+    def check(self, dec):
+        """dec: uint8 [tbs * C, K/8] -> (payload uint8 [tbs, A/8], cb_ok uint8 [tbs * C], tb_ok uint8 [tbs])."""
+        dec = np.ascontiguousarray(dec, np.uint8).reshape(-1, self.K // 8)
+        assert dec.shape[0] % self.C == 0
+        tbs = dec.shape[0] // self.C
+        payload = np.zeros((tbs, self.A // 8), np.uint8)
+        cb_ok, tb_ok = np.zeros(tbs * self.C, np.uint8), np.zeros(tbs, np.uint8)
+        _lib.check(_lib.load().ldpc_tb_check(ctypes.byref(self.spec), dec.ctypes.data, tbs, payload.ctypes.data, cb_ok.ctypes.data,
+                                             tb_ok.ctypes.data, self.device))
+        return payload, cb_ok, tb_ok

@@ -77,7 +77,8 @@ int Coder::initCheckMatrix()
 /* Length helpers, MyLdpc.cpp:620-631; with setRateMatch(): E transmitted bits per frame take the place of the N code bits. */
 int Coder::getPriorCodeLength(int srcLength) { return getCodeSize(srcLength) * ((rmE ? rmE : ldpcN) / 8); }
 int Coder::getPostCodeLength(int srcLength) { return getCodeSize(srcLength) * (rmE ? rmE : ldpcN); }
-int Coder::getCodeSize(int srcLength) { return (srcLength + (ldpcK / 8) - 1) / (ldpcK / 8); }
+/* with setTransportBlock(): srcLength counts payload bytes, A / 8 per frame */
+int Coder::getCodeSize(int srcLength) { return tbSpec.A ? (srcLength + tbSpec.A / 8 - 1) / (tbSpec.A / 8) : frameCount(srcLength); }
 
 /* ----------------------------------------------------------------- encoder */
 
@@ -119,6 +120,22 @@ int Coder::setModulation(int Qm, bool interleave)
     const int bits = rmE ? rmE : ldpcN;
     if (ldpc_modem_symbol_floats(&spec, bits) == 0) return fail(LDPC_ERR_ARG, std::string("setModulation: ") + ldpc_last_error());
     modSpec = spec;
+    return LDPC_SUCCESS;
+}
+
+/* Transport blocks of one code block each (the "transport block" section of ldpc_hip.h) around encode() and decode() */
+int Coder::setTransportBlock(int payloadBits, int crcBits)
+{
+    ldpc_tb_spec spec;
+    ldpc_tb_spec_init(&spec, payloadBits, ldpcK);
+    if (crcBits >= 0) spec.tb_crc = crcBits;
+    spec.C = 1;
+    spec.cb_crc = 0;
+    int32_t lay[6];
+    if (int rc = ldpc_tb_layout(&spec, lay)) return fail(rc, std::string("setTransportBlock: ") + ldpc_last_error());
+    tbSpec = spec;
+    crcOk.clear();
+    crcFailures = 0;
     return LDPC_SUCCESS;
 }
 
@@ -202,9 +219,22 @@ int Coder::encode(char *srcCode, char *priorCode, int srcLength)
 {
     if (!isEncoder) return fail(LDPC_ERR_STATE, "encode: call forEncoder() first");
     if (!srcCode || !priorCode || srcLength <= 0) return fail(LDPC_ERR_ARG, "encode: bad arguments");
+    if (!tbSpec.A) return encodeSource(srcCode, priorCode, srcLength);
+    /* payload (the last frame zero-padded) -> K / 8 source bytes per frame: payload, CRC, zero fillers */
+    const int frames = getCodeSize(srcLength);
+    std::vector<char> payload((size_t)frames * (tbSpec.A / 8), 0), source((size_t)frames * (ldpcK / 8));
+    memcpy(payload.data(), srcCode, (size_t)srcLength);
+    if (int rc = ldpc_tb_attach(&tbSpec, (const uint8_t *)payload.data(), frames, (uint8_t *)source.data(), (int64_t)source.size(), device))
+        return fail(rc, ldpc_last_error());
+    return encodeSource(source.data(), priorCode, (int)source.size());
+}
+
+/* srcLength bytes of K / 8 per frame */
+int Coder::encodeSource(char *srcCode, char *priorCode, int srcLength)
+{
     if (!rmE) return encodeFrames(srcCode, priorCode, srcLength);
     /* the mother codewords go to a buffer of their own, the caller receives E / 8 bytes per frame */
-    const int frames = getCodeSize(srcLength);
+    const int frames = frameCount(srcLength);
     std::vector<char> mother((size_t)frames * (ldpcN / 8));
     if (int rc = encodeFrames(srcCode, mother.data(), srcLength)) return rc;
     const int rc = ldpc_rate_match(&rmSpec, (const uint8_t *)mother.data(), LDPC_CODE_PACKED, frames, rmK0, rmE,
@@ -216,7 +246,7 @@ int Coder::encode(char *srcCode, char *priorCode, int srcLength)
 int Coder::encodeFrames(char *srcCode, char *priorCode, int srcLength)
 {
     if (encodeOnDevice && encoder) {
-        int rc = ldpc_encode(encoder, (const uint8_t *)srcCode, srcLength, (uint8_t *)priorCode, (int64_t)getCodeSize(srcLength) * (ldpcN / 8));
+        int rc = ldpc_encode(encoder, (const uint8_t *)srcCode, srcLength, (uint8_t *)priorCode, (int64_t)frameCount(srcLength) * (ldpcN / 8));
         return rc ? fail(rc, ldpc_last_error()) : LDPC_SUCCESS;
     }
     /* frames [0, last]: frame `offset` starts at byte offset*K/8 and is the last one once (offset+1)*K/8 >= srcLength
@@ -429,6 +459,15 @@ int Coder::decode(float *postCode, char *srcCode, int srcLength, enum decodeType
     if (!isDecoder) return fail(LDPC_ERR_STATE, "decode: call forDecoder() first");
     if (!postCode || !srcCode || srcLength <= 0) return fail(LDPC_ERR_ARG, "decode: bad arguments");
     const int codeSize = getCodeSize(srcLength);
+    /* with setTransportBlock() the decoders write whole frames of K / 8 bytes to a buffer of their own */
+    char *const payloadOut = srcCode;
+    const int payloadLength = srcLength;
+    std::vector<char> decoded;
+    if (tbSpec.A) {
+        decoded.resize((size_t)codeSize * (ldpcK / 8));
+        srcCode = decoded.data();
+        srcLength = (int)decoded.size();
+    }
     ldpc_decoder *d = nullptr;
     if (deType == DecodeCPU) {
         /* decodeCPU, MyLdpc.cpp:684-784: one pass over the whole stream, bit-offset packing */
@@ -466,6 +505,15 @@ int Coder::decode(float *postCode, char *srcCode, int srcLength, enum decodeType
     if (rc) return fail(rc, ldpc_last_error());
     ldpc_decode_stats st;
     if (ldpc_decoder_stats(d, &st) == LDPC_OK) lastTime = st.batch_time;
+    if (tbSpec.A) {
+        std::vector<char> payload((size_t)codeSize * (tbSpec.A / 8));
+        crcOk.assign((size_t)codeSize, 0);
+        rc = ldpc_tb_check(&tbSpec, (const uint8_t *)decoded.data(), codeSize, (uint8_t *)payload.data(), nullptr, crcOk.data(), device);
+        if (rc) return fail(rc, ldpc_last_error());
+        memcpy(payloadOut, payload.data(), (size_t)payloadLength);
+        crcFailures = 0;
+        for (unsigned char ok : crcOk) crcFailures += !ok;
+    }
     return LDPC_SUCCESS;
 }
 

@@ -193,7 +193,7 @@ inline unsigned frame_grid(int64_t frames, unsigned grid_x)
 /* The host-buffer form of a handle-less stage: the frames pass through device scratch in chunks of at most
  * kHostChunkBytes per array; per chunk the `in` arrays are copied up, launch(frames_in_chunk, first_frame, dev) runs on
  * the null stream and the `out` arrays are copied back, all in the order of `arrays`.  dev[i] belongs to the i-th array
- * and is null where that array's host pointer is (array absent). */
+ * and is null where that array's host pointer is (array absent).  At most four arrays. */
 const int64_t kHostChunkBytes = (int64_t)64 << 20;
 struct HostArray {
     void *host;
@@ -205,8 +205,8 @@ template <typename Launch> int host_chunks(int64_t frames, std::initializer_list
     int64_t widest = 1;
     for (const HostArray &a : arrays) widest = std::max(widest, a.row);
     const int64_t chunk = std::min<int64_t>(frames, std::max<int64_t>(1, kHostChunkBytes / widest));
-    DevBuf<uint8_t> buf[3];
-    void *dev[3] = {nullptr, nullptr, nullptr};
+    DevBuf<uint8_t> buf[4];
+    void *dev[4] = {nullptr, nullptr, nullptr, nullptr};
     int i = 0;
     for (const HostArray &a : arrays) {
         if (a.host) {

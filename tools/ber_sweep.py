@@ -9,7 +9,8 @@ reference counts differing BYTES (Test.cpp:105-110); this prints byte errors too
 
     python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N>] [--algo sp|ms|layered]
                               [--payload zero|random] [--rate-match P,FLO,FHI,E[,K0]] [--erasure-llr X]
-                              [--modulation bpsk|qpsk|qam16|qam64|qam256] [--no-interleave] [--snr=1.0,1.5,...]  (write --snr=-0.5,0 for a list that starts with a minus) [--frames 4096] [--iters 50]
+                              [--modulation bpsk|qpsk|qam16|qam64|qam256] [--no-interleave] [--transport-block A[,C]]
+                              [--snr=1.0,1.5,...]  (write --snr=-0.5,0 for a list that starts with a minus) [--frames 4096] [--iters 50]
 --rate-match: code bits [0, P) punctured, [FLO, FHI) filler bits (known zeros; multiples of 8, inside the information part),
 E bits per frame sent from circular-buffer position K0 (default 0): ldpc_rate_match_device between the encoder and the
 channel, ldpc_rate_recover_device between the channel and the decoder -- the whole chain stays in HBM.  --erasure-llr 1e-6
@@ -21,6 +22,13 @@ Eb/N0 = Es/N0 / (bits per symbol x rate).  --no-interleave switches the bit inte
 the decoder's llr_scale follows the noise, 2 / sd^2 per point (and the fillers read min(10, 80 / llr_scale)), unless
 --llr-scale is given.  From 16-QAM up use --payload random: the all-zero codeword sends one corner point only, and the
 bits of a QAM symbol are not equally protected.
+--transport-block A[,C] (with --payload random): the random bytes are transport blocks of A payload bits; ldpc_tb_attach_device
+in front of the encoder adds the transport block's CRC, cuts it into C code blocks with CRC24B each (C omitted: the rule of
+ldpc_tb_spec_init) and fills up to K with zeros; ldpc_tb_check_device and ldpc_tb_tally_device behind the decoder judge the
+blocks as a receiver does, without the bytes that were sent (include/ldpc_hip.h, "transport block").  --frames must be a
+multiple of C.  Every point also prints the block error rate (blocks whose payload is wrong), the blocks whose CRCs failed
+(detected), the wrong blocks whose CRCs passed (undetected) and the right blocks whose CRCs failed (parity only).  The
+fillers [Kp, K) are sent unless --rate-match names them.
 The DVB-S2 / BG1 codes are PROFILE SURROGATES (codes.py): the numbers are not the standards'."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -47,7 +55,10 @@ ap.add_argument("--erasure-llr", type=float, default=0.0, help="decoder input at
 ap.add_argument("--modulation", choices=("bpsk", "qpsk", "qam16", "qam64", "qam256"), default=None,
                 help="send symbols through ldpc_modem_transmit_device + ldpc_modem_demap_device instead of ldpc_awgn_device")
 ap.add_argument("--no-interleave", action="store_true", help="with --modulation: no bit interleaver")
+ap.add_argument("--transport-block", default=None, metavar="A[,C]",
+                help="with --payload random: A payload bits per transport block, C code blocks (default: the rule of ldpc_tb_spec_init)")
 args = ap.parse_args()
+assert not args.transport_block or args.payload == "random", "--transport-block needs --payload random"
 assert args.modulation or not args.no_interleave, "--no-interleave needs --modulation"
 QM = {None: 0, "bpsk": 1, "qpsk": 2, "qam16": 4, "qam64": 6, "qam256": 8}[args.modulation]
 matched = bool(QM) and args.algo == "sp" and args.llr_scale is None       # llr_scale = 2 / sd^2 per SNR point
@@ -92,6 +103,16 @@ if args.payload == "random":
     code = torch.empty((B, N), dtype=torch.uint8, device="cuda")
     gen = torch.Generator(device="cuda")
     gen.manual_seed(args.seed)
+tb = pay = back = cb_ok = tb_ok = None
+if args.transport_block:
+    tbv = [int(x) for x in args.transport_block.split(",")]
+    tb = L.TransportBlock(tbv[0], K, C=tbv[1] if len(tbv) > 1 else None)
+    assert B % tb.C == 0, "--frames must be a multiple of the %d code blocks of a transport block" % tb.C
+    TBS = B // tb.C
+    pay = torch.empty((TBS, tb.A // 8), dtype=torch.uint8, device="cuda")
+    back = torch.empty_like(pay)
+    cb_ok = torch.empty(B, dtype=torch.uint8, device="cuda")
+    tb_ok = torch.empty(TBS, dtype=torch.uint8, device="cuda")
 rm = tx = rx = None
 rate = K / N
 if args.rate_match:
@@ -99,6 +120,8 @@ if args.rate_match:
     P, FLO, FHI, E = rmv[:4]
     K0 = rmv[4] if len(rmv) > 4 else 0
     assert FLO % 8 == 0 and FHI % 8 == 0 and FLO <= FHI <= K, "--rate-match: FLO and FHI are multiples of 8 inside the information part"
+    assert tb is None or FLO == FHI or (tb.filler_lo <= FLO and FHI <= tb.filler_hi), \
+        "--rate-match: with --transport-block the fillers lie inside [%d, %d)" % (tb.filler_lo if tb else 0, tb.filler_hi if tb else 0)
     rm = L.RateMatcher(N, punctured=P, filler=(FLO, FHI), erasure_llr=args.erasure_llr)
     rx = torch.empty((B, E), dtype=torch.float32, device="cuda")
     if enc is not None:
@@ -118,9 +141,13 @@ def channel_batch(first, sd, seed):
     """Channel values of one batch into y; with a random payload: fresh source bytes -> code bits -> BPSK + noise."""
     stream = torch.cuda.current_stream().cuda_stream
     if enc is not None:
-        src.random_(0, 256, generator=gen)
-        if rm is not None:
-            src.view(B, K // 8)[:, FLO // 8:FHI // 8] = 0          # filler bits are known zeros
+        if tb is not None:
+            pay.random_(0, 256, generator=gen)
+            tb.attach_device(pay.data_ptr(), TBS, src.data_ptr(), src.numel(), stream)   # payload, CRCs, zero fillers
+        else:
+            src.random_(0, 256, generator=gen)
+            if rm is not None:
+                src.view(B, K // 8)[:, FLO // 8:FHI // 8] = 0      # filler bits are known zeros
         enc.encode_device(src.data_ptr(), src.numel(), B, code.data_ptr(), code.numel(), "bits", stream)
     if rm is None:
         if md is None:
@@ -159,6 +186,9 @@ def point_decoder(sd):
 if rm is not None:
     print("rate matching: punctured=%d fillers=[%d,%d) E=%d k0=%d erasure_llr=%g effective rate (K - fillers)/E = %.4f" % (
         P, FLO, FHI, E, K0, args.erasure_llr, rate))
+if tb is not None:
+    print("transport block: A=%d tb_crc=%d C=%d cb_crc=%d, %d bits per code block, Kp=%d of K=%d, %d blocks per batch" % (
+        tb.A, tb.tb_crc, tb.C, tb.cb_crc, tb.S, tb.Kp, K, TBS))
 if md is not None:
     print("modulation: %s (%d bits per symbol) interleave=%d llr_scale=%s" % (
         args.modulation, QM, md.spec.interleave, "2/sd^2 per point" if matched else "%g" % (8.0 if args.llr_scale is None else args.llr_scale)))
@@ -176,6 +206,7 @@ for snr in points:
     sd = 10.0 ** (-snr / 20.0)
     point_decoder(sd)
     tot = [0, 0, 0]
+    blocks = [0, 0, 0, 0]
     it_sum, conv = 0.0, 0
     t0 = time.perf_counter()
     for b in range(args.batches):
@@ -183,6 +214,9 @@ for snr in points:
         dec.decode_device(y.data_ptr(), B, out.data_ptr(), out.numel(), it.data_ptr(), None)
         e = channel.count_errors_device(out, src, B)
         tot = [t + x for t, x in zip(tot, e)]
+        if tb is not None:
+            tb.check_device(out.data_ptr(), TBS, back.data_ptr(), cb_ok.data_ptr(), tb_ok.data_ptr(), None)
+            blocks = [t + x for t, x in zip(blocks, tb.tally_device(tb_ok.data_ptr(), back.data_ptr(), pay.data_ptr(), TBS, None))]
         it_sum += float(it.float().sum())
         conv += dec.stats()["frames_converged"]
     dt = time.perf_counter() - t0
@@ -195,4 +229,8 @@ for snr in points:
         es_n0 = 1.0 / (2.0 * sd * sd)
         res.update({"es_n0_db": round(10.0 * np.log10(es_n0), 3), "eb_n0_db": round(10.0 * np.log10(es_n0 / (QM * rate)), 3),
                     "llr_scale": round(2.0 / (sd * sd), 3) if matched else (8.0 if args.llr_scale is None else args.llr_scale)})
+    if tb is not None:
+        n = TBS * args.batches
+        res.update({"blocks": n, "bler": blocks[1] / n, "blocks_crc_failed": blocks[0], "blocks_undetected": blocks[2],
+                    "blocks_parity_only": blocks[3]})
     print(json.dumps(res), flush=True)
