@@ -114,8 +114,10 @@ typedef struct ldpc_decoder_config {
     int32_t frames_per_lane;/* tuning: 0 = auto, else 1, 2 or 4 (tile = 64*frames_per_lane) */
     int32_t poll_interval;  /* early_term: host checks "all frames done" every this many
                                iterations (0 = never; finished tiles still skip on device).
-                               With polling on, the last <= 512 running frames of a multi-tile
-                               batch are handed to a small child decoder (tail compaction)   */
+                               With polling on, the last running frames of a multi-tile batch
+                               (at most a quarter of it, and <= 1024 frames for max_batch >=
+                               4096, <= 512 otherwise) are handed to a small child decoder
+                               (tail compaction)                                              */
     /* ---- tuning (was reserved[8]): 0 = automatic everywhere.  Kernel selection and launch
      *      shapes only -- results never depend on these (the parity tests run the alternatives
      *      against each other).  The library reads NO environment variables. ---------------- */
@@ -125,7 +127,8 @@ typedef struct ldpc_decoder_config {
     int32_t tune_link_rows;     /* rows per wave of the column-fused check kernel (default 16; 4 for a
                                    single tile); -1 = column-local fusion off                     */
     int32_t tune_compact;       /* tail compaction: hand over when <= this many frames still run
-                                   (default and maximum 512); -1 = off                            */
+                                   (default and maximum: 1024 for max_batch >= 4096, 512
+                                   otherwise); -1 = off                                           */
     int32_t tune_ldsp_grid;     /* record kernels (ldsp_kernels.hpp): persistent workgroups        */
     int32_t tune_ldsp_shape;    /* workgroups per CU | waves per workgroup << 8                    */
     int32_t tune_place;         /* streaming flooding decoders: fresh allocations tried for the check->variable and for
