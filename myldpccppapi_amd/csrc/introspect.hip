@@ -109,9 +109,11 @@ int ldpc_decoder_kernel_times(ldpc_decoder *d, ldpc_kernel_time *out, int32_t ca
     if (!d->tm.have_last) return set_error(LDPC_ERR_STATE, "no decode call to report on");
     LDPC_HIP_TRY(hipSetDevice(d->cfg.device));
     LDPC_HIP_TRY(hipEventSynchronize(d->tm.ev_end.e));
+    /* the half form exists for tiles of 256 frames only: below that the launch takes the narrow kernel (enqueue_check_phase) */
+    const int link_form = (d->flood.link_form == 2 && d->V != 4) ? 1 : d->flood.link_form;
     const char *phase_name[] = {"check_kernel", "var_kernel", d->ms_corr ? "layer_corr_kernel" : "layer_kernel", "other",
-                                d->flood.link_form == 2 ? "check_link_half_kernel"
-                                : d->flood.link_form ? "check_link_narrow_kernel" : "check_link_kernel"};
+                                link_form == 2 ? "check_link_half_kernel"
+                                : link_form ? "check_link_narrow_kernel" : "check_link_kernel"};
     static const char *algo_name_f32[] = {"sp", "ms", "layered", "ms_fused", "layered_host"};
     static const char *algo_name_f16[] = {"sp16", "ms16", "layered16", "ms_fused16", "layered_host16"};
     static const char *algo_name_corr_f32[] = {"sp", "msc", "layered", "ms_fused", "layered_host"};  /* kAlgoMSC */

@@ -121,7 +121,8 @@ def ira_code(d, n_link, extra, info_col_deg=3, seed=1):
 
 # One entry per tuning key of capi.TUNE_FIELDS / capi.TUNE_INTS: the tuning dict of a case the kernel-matrix
 # module runs, and the test that runs it.  Keys that other modules already cover name that test instead
-# ("tune": None).
+# ("tune": None).  The forms of the column-fused check kernel (link_*) run in fp32 and sum-product there; with fp16
+# messages, plain and corrected, tests/test_gpu_fp16.py::test_fp16_column_fused_forms runs them all again.
 _KM = "test_gpu_kernel_matrix"
 TUNE_CASES = {
     "fused": dict(tune={"fused": True, "ldsp": False}, test=_KM + "::test_one_launch_kernels_on_qc_shapes"),

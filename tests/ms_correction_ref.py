@@ -12,14 +12,16 @@ where they are stored, and so is the corrected magnitude where the check->variab
 
 Each decoder returns dict(out=packed bytes, iters=int32[frames], hard=uint8[frames, N], r_tap=float32[frames, E]
 or None, hard_tap=uint8[frames, N] (the hard bits at iteration tap_iter) or None, and for layered undefined=uint8[frames]: a row none of whose |q| is <= 1000 -- the oracle's "undefined
-frame", where the reference reads an uninitialised index)."""
+frame", where the reference reads an uninitialised index).  flood_ms also returns q_tap=float32[frames, E] or None: the
+variable->check messages after round tap_iter, NaN-filled for the frames that had stopped by then (the oracle's taps["q"])."""
 import numpy as np
 
 F32 = np.float32
 
 
 def _f16(x):
-    return x.astype(np.float16).astype(F32)
+    with np.errstate(over="ignore"):                        # |x| >= 65520 rounds to infinity: that is the definition
+        return x.astype(np.float16).astype(F32)
 
 
 def _corr(m, scale, offset, f16=False):
@@ -27,8 +29,8 @@ def _corr(m, scale, offset, f16=False):
     if scale == 0 and offset == 0:
         return m
     a = F32(scale if scale != 0 else 1.0)
-    r = np.maximum(m - F32(offset), F32(0)) * a
-    return _f16(r) if f16 else r.astype(F32)
+    r = (np.maximum(m - F32(offset), F32(0)) * a).astype(F32)
+    return _f16(r) if f16 else r
 
 
 class Code:
@@ -88,6 +90,7 @@ def _check_ms(code, Q, scale, offset, f16):
     Qx = np.concatenate([Q, np.full((frames, 1), np.inf, F32)], axis=1)
     x = Qx[:, code.row_edges]                               # [F, M, dmax]
     a = np.abs(x)
+    a = np.where(np.isnan(a), F32(np.inf), a)               # fminf skips a NaN message (its sign test x < 0 is false)
     idx = np.argmin(a, axis=2)
     m1 = np.minimum(np.take_along_axis(a, idx[..., None], 2)[..., 0], F32(1000))
     a2 = a.copy()
@@ -105,19 +108,34 @@ def _check_ms(code, Q, scale, offset, f16):
     return R[:, :code.E]
 
 
-def flood_ms(code, y, max_iter, scale=0.0, offset=0.0, f16=False, tap_iter=0, pack_mode=0):
-    """oracle_decode_ms with the correction."""
+def flood_ms(code, y, max_iter, scale=0.0, offset=0.0, f16=False, tap_iter=0, pack_mode=0, raw_cols=None):
+    """oracle_decode_ms with the correction.
+
+    raw_cols (bool [N], fp16 with a correction only) is no part of the definition: it is the model of a WRONG kernel
+    for tests/test_fp16_cpu.py.  The marked columns see the corrected check->variable messages as they are before
+    their rounding to binary16 -- what a column-fused check kernel would compute if it rounded R only where it
+    stores it, since the fused columns' R stay in registers.  Every stored R (the tap included) is still rounded."""
     y = np.ascontiguousarray(y, F32).reshape(-1, code.N)
     frames = y.shape[0]
+    with np.errstate(invalid="ignore"):                     # inf - inf and NaN inputs are part of what is defined
+        return _flood_ms(code, y, frames, max_iter, scale, offset, f16, tap_iter, pack_mode, raw_cols)
+
+
+def _flood_ms(code, y, frames, max_iter, scale, offset, f16, tap_iter, pack_mode, raw_cols):
     yf = _f16(y) if f16 else y.copy()
     Q = yf[:, code.cols].copy()
     hard = np.zeros((frames, code.N), np.uint8)
     iters = np.zeros(frames, np.int32)
     r_tap = np.full((frames, code.E), np.nan, F32) if tap_iter else None
+    q_tap = np.full((frames, code.E), np.nan, F32) if tap_iter else None
     hard_tap = np.zeros((frames, code.N), np.uint8) if tap_iter else None
+    raw_edges = None if raw_cols is None else np.asarray(raw_cols, bool)[code.cols]
     A = np.arange(frames)
     for t in range(1, max_iter + 1):
         R = _check_ms(code, Q[A], scale, offset, f16)
+        R_stored = R
+        if raw_edges is not None:
+            R = np.where(raw_edges[None, :], _check_ms(code, Q[A], scale, offset, False), R)
         Rx = np.concatenate([R, np.full((len(A), 1), -0.0, F32)], axis=1)
         P = yf[A].copy()
         for k in range(code.col_edges.shape[1]):             # ascending edge id along every column
@@ -127,7 +145,7 @@ def flood_ms(code, y, max_iter, scale=0.0, offset=0.0, f16=False, tap_iter=0, pa
         ok = code.syndrome_ok(h)
         iters[A] = t
         if tap_iter == t:
-            r_tap[A] = R
+            r_tap[A] = R_stored
             hard_tap[A] = h
         if t == max_iter:
             break
@@ -137,7 +155,9 @@ def flood_ms(code, y, max_iter, scale=0.0, offset=0.0, f16=False, tap_iter=0, pa
             break
         Qn = P[:, code.cols] - R
         Q[A] = _f16(Qn) if f16 else Qn
-    return dict(out=code.pack(hard, pack_mode), iters=iters, hard=hard, r_tap=r_tap, hard_tap=hard_tap)
+        if tap_iter == t:
+            q_tap[A] = Q[A]
+    return dict(out=code.pack(hard, pack_mode), iters=iters, hard=hard, r_tap=r_tap, q_tap=q_tap, hard_tap=hard_tap)
 
 
 def _cl_sign(x):

@@ -10,6 +10,7 @@ import pytest
 import oracle
 import myldpccppapi_amd as L
 from myldpccppapi_amd import _lib, channel, codes
+import fp16_cases as fc
 from ms_correction_ref import Code, flood_ms, layered_ms
 from util import golden_files, load_golden, wimax_oracle_graph
 
@@ -80,6 +81,43 @@ def test_restatement_equals_oracle_on_random_qc_codes(case):
     ref = layered_ms(code, y, z, 12)
     _same(ref, want, "layered %s" % (case,))
     assert np.array_equal(ref["undefined"], want["undefined"]) and want["undefined"][5]
+
+
+def _same_taps(ref, want, what):
+    """R on the frames that reached the tapped round, Q on those that went on: bit patterns, NaN where the oracle has NaN
+    (a frame that had stopped, or a NaN message)"""
+    run_r, run_q = fc.tap_frames(want["iters"])
+    assert run_q.size > 0, what
+    assert fc.same_floats(ref["r_tap"][run_r], want["taps"]["r"][run_r]), what + ": R tap"
+    assert fc.same_floats(ref["q_tap"][run_q], want["taps"]["q"][run_q]), what + ": Q tap"
+    stopped = np.nonzero(want["iters"] <= fc.TAP)[0]
+    assert np.isnan(ref["q_tap"][stopped]).all() and np.isnan(want["taps"]["q"][stopped]).all(), what
+
+
+@pytest.mark.parametrize("f16", [False, True], ids=["f32", "f16"])
+@pytest.mark.parametrize("name", ["wimax", "ira3", "ira7", "ira16"])
+def test_restatement_equals_oracle_on_degenerate_frames_and_q_tap(name, f16):
+    """scale = offset = 0: the overlay of fp16_cases.py (zeros, values around binary16's largest number, infinities, NaN,
+    binary16 subnormals and ties, -0) and the variable->check tap.  The NaN frame is where a restatement that takes argmin
+    over |q| differs from the oracle's fminf chain, which skips a NaN."""
+    c = fc.wimax() if name == "wimax" else fc.staircase(int(name[3:]), "ride")
+    y = fc.overlay(channel.awgn_frames(c["N"], 0, fc.DEGENERATE_FRAMES, 0.7, seed=21))
+    assert np.isnan(y[7]).sum() == 5
+    want = oracle.decode(c["og"], y, "ms", max_iter=fc.DEGENERATE_MAXIT, tap_iter=fc.TAP, msg_f16=f16)
+    ref = flood_ms(c["code"], y, fc.DEGENERATE_MAXIT, f16=f16, tap_iter=fc.TAP)
+    _same(ref, want, "%s f16=%s" % (name, f16))
+    _same_taps(ref, want, "%s f16=%s" % (name, f16))
+    assert want["iters"][7] > fc.TAP                        # the NaN frame runs on: its Q tap is compared
+
+
+@pytest.mark.parametrize("f16", [False, True], ids=["f32", "f16"])
+@pytest.mark.parametrize("d", fc.DEGREES)
+def test_restatement_q_tap_equals_oracle_on_staircase_codes(d, f16):
+    c = fc.staircase(d, "ride")
+    want = oracle.decode(c["og"], c["y"], "ms", max_iter=fc.MAXIT, tap_iter=fc.TAP, msg_f16=f16)
+    ref = flood_ms(c["code"], c["y"], fc.MAXIT, f16=f16, tap_iter=fc.TAP)
+    _same(ref, want, "d=%d f16=%s" % (d, f16))
+    _same_taps(ref, want, "d=%d f16=%s" % (d, f16))
 
 
 def test_hand_computed_row():
