@@ -8,7 +8,7 @@
 
 #include "../../include/ldpc_hip.h"
 #include "channel_kernels.hpp"
-#include "flood_kernels.hpp"   /* ldpc::vf4 */
+#include "flood_common.hpp"    /* ldpc::vf4 */
 #include "hip_host.hpp"
 
 using ldpc::set_error;

@@ -39,6 +39,12 @@ template <typename Fn> inline int dispatch_v(int V, Fn &&fn)
                   : V == 2 ? fn(std::integral_constant<int, 2>{}) : fn(std::integral_constant<int, 4>{});
 }
 
+/* the run-time message size (4: float, 2: fp16 storage) as a type: fn(T{}) */
+template <typename Fn> inline void dispatch_msg(int64_t msg_size, Fn &&fn)
+{
+    if (msg_size == 2) fn(_Float16{}); else fn(float{});
+}
+
 struct RowClass {
     int degree = 0;
     int count = 0;
@@ -48,7 +54,7 @@ struct RowClass {
      * the next list row when both fall in one wave's chunk of link_rpw rows */
     DevBuf<int32_t> link_col, link_pos;
     int linked = 0;          /* number of fused columns */
-    /* guided chunks (flood_kernels.hpp: LinkArgs): n_big chunks of link_rpw rows, then chunks of small_rows */
+    /* guided chunks (flood_link.hpp: LinkArgs): n_big chunks of link_rpw rows, then chunks of small_rows */
     int n_big = 0, small_rows = 1;
 };
 struct ColClass {
@@ -102,13 +108,13 @@ struct FloodPlan {
     int place_candidates = 0, place_kept = 0;
     float place_ms[16] = {};            /* the original pair, then up to 7 fresh R and 7 fresh Q allocations */
 
-    /* device-side tail (flood_kernels.hpp: TailRef, tail_gather_kernel): TO overflow tiles follow the T
+    /* device-side tail (flood_common.hpp: TailRef, flood_handover.hpp: tail_gather_kernel): TO overflow tiles follow the T
      * tiles of max_batch in every array (TA = T + TO allocated) */
     bool tail_enabled = false;
     int TO = 0, TA = 0;
     DevBuf<int32_t> tail_state, tail_map, running;
 
-    /* tail compaction (flood_kernels.hpp): a V = 1, one-tile decoder that takes over the last running
+    /* tail compaction (flood_handover.hpp): a V = 1, one-tile decoder that takes over the last running
      * frames of a polled, early-terminating decode */
     std::unique_ptr<ldpc_decoder> child;
     DevBuf<int32_t> cmap;               /* [child_capacity] frame indices handed to the child */

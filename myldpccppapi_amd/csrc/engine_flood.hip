@@ -15,7 +15,8 @@
  * then pack.
  *
  * The message kernels themselves are instantiated per arithmetic in flood_sp / flood_ms / flood_ms16 / flood_msc*
- * (flood_tables.hpp); the bookkeeping kernels of a round (flood_kernels.hpp) are instantiated here.  Declared in
+ * (flood_tables.hpp); the bookkeeping kernels of a round (flood_round.hpp) and of the hand-over (flood_handover.hpp)
+ * are instantiated here.  Declared in
  * engines.hpp like the other engines; unlike them it works on the handle (decoder.hpp), because it needs the stream,
  * the timing spans and the tail-compaction child.
  */
@@ -25,7 +26,8 @@
 #include <map>
 #include <vector>
 
-#include "flood_kernels.hpp"
+#include "flood_round.hpp"
+#include "flood_handover.hpp"
 #include "decoder.hpp"
 #include "graph.hpp"
 
@@ -65,7 +67,7 @@ __global__ void summary_kernel(const int32_t *iters, const uint64_t *done, const
     if ((ok >> l) & 1ull) atomicAdd(&summary[1], 1);
 }
 
-/* grid of a flooding launch: (tiles, blocks) -- flood_kernels.hpp: grid_pos() -- when the blocks fit gridDim.y */
+/* grid of a flooding launch: (tiles, blocks) -- flood_common.hpp: grid_pos() -- when the blocks fit gridDim.y */
 static inline dim3 flood_grid(const ldpc_decoder *d, unsigned blocks, unsigned tiles, int32_t *tiles_first, bool linked = false)
 {
     /* tune_tiles_first: 0 automatic = the column-fused check launch only (-8 % there; the variable-node
@@ -74,6 +76,20 @@ static inline dim3 flood_grid(const ldpc_decoder *d, unsigned blocks, unsigned t
     const bool want = d->tune.tiles_first == 1 || (d->tune.tiles_first == 0 && linked);
     *tiles_first = (blocks <= 65535u && want) ? 1 : 0;
     return *tiles_first ? dim3(tiles, blocks) : dim3(blocks, tiles);
+}
+
+/* The arguments every check launch of round `it` shares: the message arrays, the frozen frames, the min-sum
+ * correction, the Q slots, the tail and -- where round 1 reads q = y (first_round_from_chan; never the column-fused
+ * launch) -- the channel array by column.  e0 / n_rows / degree: the class of a launch of its own (a bucket launch
+ * takes them from its table). */
+static ldpc::CheckArgs check_args(const ldpc_decoder *d, const ldpc::TailRef &tr, int rows_per_wave, bool from_chan,
+                                  const int32_t *e0 = nullptr, int n_rows = 0, int degree = 0)
+{
+    ldpc::CheckArgs a{d->flood.Q.p, d->flood.R.p, e0, d->done.p, d->E, n_rows, rows_per_wave, degree, d->ms_scale, tr};
+    a.ms_offset = d->ms_offset;
+    a.qpos = d->flood.qpos.p;
+    if (from_chan) { a.first_chan = d->flood.chan.p; a.edge_col = d->edge_col.p; a.N = d->N; }
+    return a;
 }
 
 template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t frames,
@@ -87,6 +103,7 @@ template <int V> int enqueue_check_phase(ldpc_decoder *d, hipStream_t s, int til
 {
     using namespace ldpc;
     const int64_t msz = d->flood.msg_size;
+    const bool from_chan = it == 1 && d->flood.first_round_from_chan;      /* CheckArgs::first_chan */
     for (auto &rc : d->flood.row_classes) {
         if (!rc.linked) continue;
         /* algorithmic bytes: the fused columns' messages and channel values count as in the
@@ -98,13 +115,10 @@ template <int V> int enqueue_check_phase(ldpc_decoder *d, hipStream_t s, int til
                            msz * ((int64_t)rc.degree * rc.count + rc.linked +
                                   ((int64_t)rc.degree * rc.count - 2 * rc.linked) +
                                   (it < max_iter ? 2 * rc.linked : 0) + 2 * d->flood.extra_edges) * frames));
-        CheckArgs a{d->flood.Q.p, d->flood.R.p, rc.e0.p, d->done.p, d->E, rc.count, 1, rc.degree, d->ms_scale, tr};
-        a.ms_offset = d->ms_offset;
-        a.qpos = d->flood.qpos.p;
+        CheckArgs a = check_args(d, tr, d->flood.link_rpw, false, rc.e0.p, rc.count, rc.degree);
         LinkArgs lk{rc.link_col.p, rc.link_pos.p, d->flood.chan.p, d->flood.Q.p, d->hard.p, d->N,
                     (it < max_iter) ? 1 : 0, d->tm.tap_iter ? 1 : 0, d->flood.extra_e0.p, d->flood.extra_deg.p, d->flood.n_extra, 0,
                     rc.n_big, rc.small_rows};
-        a.rows_per_wave = d->flood.link_rpw;
         const int variant = (d->flood.link_form == 2 && !d->flood.fns.link_half[rc.degree]) ? 1 : d->flood.link_form;
         const int waves = link_chunk_count(d->flood.link_rpw, rc.n_big, rc.small_rows, rc.count) * (variant == 1 ? V : variant == 2 ? V / 2 : 1);
         lk.link_blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
@@ -118,10 +132,7 @@ template <int V> int enqueue_check_phase(ldpc_decoder *d, hipStream_t s, int til
         int64_t edges = 0;
         for (int i : g.members) edges += (int64_t)d->flood.row_classes[i].degree * d->flood.row_classes[i].count;
         LDPC_HIP_TRY(span_begin(d, s, 5, g.hi, 2 * msz * edges * frames, -1, g.lo));
-        CheckArgs a{d->flood.Q.p, d->flood.R.p, nullptr, d->done.p, d->E, 0, (d->tune.rows_per_wave ? d->tune.rows_per_wave : 2) * (fat ? kIdleFat : 1), 0, d->ms_scale, tr};
-        a.ms_offset = d->ms_offset;
-        a.qpos = d->flood.qpos.p;
-        if (it == 1 && d->flood.first_round_from_chan) { a.first_chan = d->flood.chan.p; a.edge_col = d->edge_col.p; a.N = d->N; }
+        CheckArgs a = check_args(d, tr, (d->tune.rows_per_wave ? d->tune.rows_per_wave : 2) * (fat ? kIdleFat : 1), from_chan);
         const dim3 grid = flood_grid(d, fat ? g.blocks_fat : g.blocks, tiles, &a.tiles_first);
         d->flood.fns.check_group[g.bucket]<<<grid, kBlock, 0, s>>>(a, fat ? g.table_fat.p : g.table.p, (int)g.members.size());
         LDPC_HIP_TRY(span_end(d, s));
@@ -129,14 +140,10 @@ template <int V> int enqueue_check_phase(ldpc_decoder *d, hipStream_t s, int til
     for (int ci : d->flood.check_solo) {
         RowClass &rc = d->flood.row_classes[ci];
         LDPC_HIP_TRY(span_begin(d, s, 0, rc.degree, 2 * msz * rc.degree * rc.count * frames));
-        CheckArgs a{d->flood.Q.p, d->flood.R.p, rc.e0.p, d->done.p, d->E, rc.count, 1, rc.degree, d->ms_scale, tr};
-        a.ms_offset = d->ms_offset;
-        a.qpos = d->flood.qpos.p;
-        if (it == 1 && d->flood.first_round_from_chan) { a.first_chan = d->flood.chan.p; a.edge_col = d->edge_col.p; a.N = d->N; }
         const int slotk = rc.degree <= d->flood.fns.max_check_unrolled ? rc.degree : 0;
         const bool narrow = slotk && (!d->flood.check_wide || rc.degree > kMaxUnrolledDegree);
         const int rpw = (d->tune.rows_per_wave ? d->tune.rows_per_wave : (narrow ? 2 : 1)) * (fat ? kIdleFat : 1);
-        a.rows_per_wave = rpw;
+        CheckArgs a = check_args(d, tr, rpw, from_chan, rc.e0.p, rc.count, rc.degree);
         const int waves = ((rc.count + rpw - 1) / rpw) * (narrow ? V : 1);
         const dim3 grid = flood_grid(d, (waves + kWavesPerBlock - 1) / kWavesPerBlock, tiles, &a.tiles_first);
         (narrow ? d->flood.fns.check : d->flood.fns.check_wide)[slotk]<<<grid, kBlock, 0, s>>>(a);
@@ -202,23 +209,19 @@ template <int V> int compact_and_finish(ldpc_decoder *d, int64_t frames, int cou
     /* many frames: one coalesced pass over the parent's rows through LDS; few: one sector per value */
     const bool rowwise = count >= 128;
     const int ptiles = (int)((frames + 64 * V - 1) / (64 * V));
-    if (d->flood.msg_size == 2) {
+    dispatch_msg(d->flood.msg_size, [&](auto t) {
+        using T = decltype(t);
+        const T *pq = (const T *)d->flood.Q.p, *pc = (const T *)d->flood.chan.p;
+        T *cq = (T *)c->flood.Q.p, *cc = (T *)c->flood.chan.p;
         if (rowwise) {
-            compact_gather_rows_kernel<V, _Float16><<<(unsigned)((d->E + gather_rows_per_block<_Float16>() - 1) / gather_rows_per_block<_Float16>()), kBlock, 0, s>>>((const _Float16 *)d->flood.Q.p, (_Float16 *)c->flood.Q.p, d->flood.cmap.p, count, d->E, ptiles, cf, d->flood.qpos.p, c->flood.qpos.p);
-            compact_gather_rows_kernel<V, _Float16><<<(unsigned)((d->N + gather_rows_per_block<_Float16>() - 1) / gather_rows_per_block<_Float16>()), kBlock, 0, s>>>((const _Float16 *)d->flood.chan.p, (_Float16 *)c->flood.chan.p, d->flood.cmap.p, count, d->N, ptiles, cf);
+            constexpr int rpb = gather_rows_per_block<T>();
+            compact_gather_rows_kernel<V, T><<<(unsigned)((d->E + rpb - 1) / rpb), kBlock, 0, s>>>(pq, cq, d->flood.cmap.p, count, d->E, ptiles, cf, d->flood.qpos.p, c->flood.qpos.p);
+            compact_gather_rows_kernel<V, T><<<(unsigned)((d->N + rpb - 1) / rpb), kBlock, 0, s>>>(pc, cc, d->flood.cmap.p, count, d->N, ptiles, cf);
         } else {
-            compact_gather_kernel<V, _Float16><<<ge, kBlock, 0, s>>>((const _Float16 *)d->flood.Q.p, (_Float16 *)c->flood.Q.p, d->flood.cmap.p, count, d->E, cf, d->flood.qpos.p, c->flood.qpos.p);
-            compact_gather_kernel<V, _Float16><<<gn, kBlock, 0, s>>>((const _Float16 *)d->flood.chan.p, (_Float16 *)c->flood.chan.p, d->flood.cmap.p, count, d->N, cf);
+            compact_gather_kernel<V, T><<<ge, kBlock, 0, s>>>(pq, cq, d->flood.cmap.p, count, d->E, cf, d->flood.qpos.p, c->flood.qpos.p);
+            compact_gather_kernel<V, T><<<gn, kBlock, 0, s>>>(pc, cc, d->flood.cmap.p, count, d->N, cf);
         }
-    } else {
-        if (rowwise) {
-            compact_gather_rows_kernel<V, float><<<(unsigned)((d->E + gather_rows_per_block<float>() - 1) / gather_rows_per_block<float>()), kBlock, 0, s>>>((const float *)d->flood.Q.p, (float *)c->flood.Q.p, d->flood.cmap.p, count, d->E, ptiles, cf, d->flood.qpos.p, c->flood.qpos.p);
-            compact_gather_rows_kernel<V, float><<<(unsigned)((d->N + gather_rows_per_block<float>() - 1) / gather_rows_per_block<float>()), kBlock, 0, s>>>((const float *)d->flood.chan.p, (float *)c->flood.chan.p, d->flood.cmap.p, count, d->N, ptiles, cf);
-        } else {
-            compact_gather_kernel<V, float><<<ge, kBlock, 0, s>>>((const float *)d->flood.Q.p, (float *)c->flood.Q.p, d->flood.cmap.p, count, d->E, cf, d->flood.qpos.p, c->flood.qpos.p);
-            compact_gather_kernel<V, float><<<gn, kBlock, 0, s>>>((const float *)d->flood.chan.p, (float *)c->flood.chan.p, d->flood.cmap.p, count, d->N, cf);
-        }
-    }
+    });
     /* the hard bits travel only where the next decision can depend on the previous one: the sum-product rule keeps the old
      * bit on a tie or a NaN (decodeCL.c:78-82); min-sum decides every bit anew in every round (bit = !(p > 0), :161-165) */
     LDPC_HIP_TRY(hipMemsetAsync(c->hard.p, 0, (size_t)ct * d->N * cv * sizeof(uint64_t), s));
@@ -342,8 +345,7 @@ template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t
                  * below the threshold after this round (decided by the kernel; usually it just returns) */
                 ta.iter = it;
                 const unsigned tg = (unsigned)std::min<int64_t>(1024, d->E + 2 * (int64_t)d->N);
-                if (d->flood.msg_size == 2) tail_gather_kernel<V, _Float16><<<tg, kBlock, 0, s>>>(ta);
-                else tail_gather_kernel<V, float><<<tg, kBlock, 0, s>>>(ta);
+                dispatch_msg(d->flood.msg_size, [&](auto t) { tail_gather_kernel<V, decltype(t)><<<tg, kBlock, 0, s>>>(ta); });
             }
             LDPC_HIP_TRY(span_end(d, s));
             if (poll) {
@@ -634,10 +636,7 @@ template <int V> int calibrate_link(ldpc_decoder *d)
     hipError_t err = hipSuccess;
     for (int rep = 0; rep < 4 && err == hipSuccess; ++rep) {
         for (int nar = 0; nar < candidates && err == hipSuccess; ++nar) {
-            CheckArgs a{d->flood.Q.p, d->flood.R.p, rc.e0.p, d->done.p, d->E, rc.count, d->flood.link_rpw, rc.degree, d->ms_scale,
-                        TailRef{nullptr, 0, 0}};
-            a.ms_offset = d->ms_offset;
-            a.qpos = d->flood.qpos.p;
+            CheckArgs a = check_args(d, TailRef{nullptr, 0, 0}, d->flood.link_rpw, false, rc.e0.p, rc.count, rc.degree);
             LinkArgs lk{rc.link_col.p, rc.link_pos.p, d->flood.chan.p, d->flood.Q.p, d->hard.p, d->N, 1, 0, nullptr, nullptr, 0, 0,
                         rc.n_big, rc.small_rows};
             const int waves = link_chunk_count(d->flood.link_rpw, rc.n_big, rc.small_rows, rc.count) * (nar == 1 ? V : nar == 2 ? V / 2 : 1);

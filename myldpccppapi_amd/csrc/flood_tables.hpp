@@ -12,7 +12,7 @@ namespace ldpc {
 using CheckFn = void (*)(const CheckArgs);
 using VarFn = void (*)(const VarArgs);
 using LinkFn = void (*)(const CheckArgs, const LinkArgs);
-/* group launches (several degree classes of a bucket in one launch, flood_kernels.hpp) */
+/* group launches (several degree classes of a bucket in one launch: flood_check.hpp, flood_var.hpp) */
 using CheckGroupFn = void (*)(const CheckArgs, const GroupClass *, int);
 using VarGroupFn = void (*)(const VarArgs, const GroupClass *, int);
 using InitFn = void (*)(const InitArgs);

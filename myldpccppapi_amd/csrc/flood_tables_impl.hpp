@@ -65,7 +65,7 @@ template <int ALGO, int V, typename T> void fill_v(FloodFns *f)
     constexpr int DM = kMaxUnrolledDegree;
     FloodTable<ALGO, V, T, DM>::fill(f->check, f->check_wide, f->var);
     LinkTable<ALGO, V, T, DM>::fill(f->link, f->link_narrow, f->link_deep, f->link_half);
-    /* fp16 messages in tiles of 256 frames: two values per lane (flood_kernels.hpp: check_group_kernel) */
+    /* fp16 messages in tiles of 256 frames: two values per lane (flood_check.hpp: check_group_kernel) */
     constexpr int GW = (sizeof(T) == 2 && V == 4) ? 2 : 1;
     f->check_group_width = GW;
     f->check_group[0] = check_group_kernel<ALGO, V, T, 1, 8, GW>;

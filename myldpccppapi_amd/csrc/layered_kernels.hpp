@@ -67,7 +67,7 @@ __global__ __launch_bounds__(kBlock) void layer_kernel(const LayerArgs a)
     const MsCorr corr{1.0f, 0.0f};
 #include "layer_kernel.inc"
 }
-/* Normalized / offset min-sum (LayeredPlan::corr): the row's two candidates b, c go through ms_corr (flood_kernels.hpp)
+/* Normalized / offset min-sum (LayeredPlan::corr): the row's two candidates b, c go through ms_corr (flood_common.hpp)
  * before the sign and the per-edge selection -- two operations per row, not per edge. */
 template <int D, int V>
 __global__ __launch_bounds__(kBlock) void layer_corr_kernel(const LayerArgs a, const MsCorr corr)

@@ -177,27 +177,43 @@ LINK_FORMS = {"default": {}, "narrow_off": {"link_narrow": False}, "narrow": {"l
               "half": {"link_half": True}, "deep": {"link_deep": True}, "rows_5": {"link_rows": 5}}
 
 
+def _link_kernel_name(form, V):
+    """The name the timing report gives the form asked for; None where the decoder chooses (V = 1 takes narrow, above
+    that the creation-time calibration picks).  The deep form reports as narrow; half exists at V = 4 only."""
+    if form == "narrow_off":
+        return "check_link_kernel<"
+    if form == "half" and V == 4:
+        return "check_link_half_kernel<"
+    if form in ("narrow", "deep", "half"):
+        return "check_link_narrow_kernel<"
+    return "check_link_narrow_kernel<" if V == 1 else None
+
+
 @pytest.mark.parametrize("d", [3, 9, 16])
 def test_column_fused_forms(built, ira_codes, d):
     """IRA codes with the linked class at degree d: with <= 64 unlinked rows they ride along in the column-fused
     launch (only check_link_* in phase 0); with more they get launches of their own.  Every form against the
-    oracle, V = 1 and 4: bytes, iteration counts, R and Q after two rounds."""
+    oracle, V = 1, 2 and 4 (V = 2: the 32-bit mask fields of the narrow forms): bytes, iteration counts, all N hard
+    bits (the staircase columns are parity columns: their bits never reach the bytes), R and Q after two rounds.
+    Then sum-product through every form: its variable node keeps the previous bit on a tie or NaN, in every form's
+    own mask handling, and the fixture holds frames that run all 25 iterations."""
     for kind in ("ride", "own"):
         c = ira_codes[d, kind]
         B, want = c["y"].shape[0], c["want"]
         for form, tune in (LINK_FORMS.items() if kind == "ride" else [("default", {})]):
-            for V in (1, 4):
+            for V in (1, 2, 4):
                 what = (d, kind, form, V)
                 dec = L.Decoder(c["g"], c["K"], max_batch=B, algo="ms", max_iter=25, frames_per_lane=V, tune=tune)
                 dec.set_timing(True)
                 out, iters = dec.decode(c["y"])
                 assert np.array_equal(out, want["out"]) and np.array_equal(iters, want["iters"]), what
+                assert np.array_equal(dec.dump(3, B).astype(np.uint8), want["hard"]), what
                 kt = dec.kernel_times()
                 dec.set_timing(False)
                 phase0 = {k["name"] for k in kt if k["phase"] == 0}
                 assert any(n.startswith("check_link") and n.endswith(",%d,%d>" % (d, V)) for n in phase0), (what, phase0)
                 if kind == "ride":
-                    assert all(n.startswith("check_link") for n in phase0), (what, phase0)
+                    assert all(n.startswith(_link_kernel_name(form, V) or "check_link") for n in phase0), (what, phase0)
                 else:
                     assert any(n.startswith("check_group_kernel<ms,") or n.startswith("check_kernel<ms,20,")
                                for n in phase0), (what, phase0)
@@ -208,12 +224,22 @@ def test_column_fused_forms(built, ira_codes, d):
                 assert np.array_equal(dec.dump(0, B)[run_r], want["taps"]["r"][run_r]), what
                 assert np.array_equal(dec.dump(1, B)[run_q], want["taps"]["q"][run_q], equal_nan=True), what
                 dec.close()
-        if kind == "ride":               # sum-product through the same launch
-            for V in (1, 4):
-                dec = L.Decoder(c["g"], c["K"], max_batch=B, algo="sp", max_iter=25, frames_per_lane=V)
-                out, iters = dec.decode(c["y"])
-                assert np.array_equal(out, c["want_sp"]["out"]) and np.array_equal(iters, c["want_sp"]["iters"]), (d, "sp", V)
-                dec.close()
+        if kind == "ride":               # sum-product through the same launch, every form
+            want_sp = c["want_sp"]
+            assert (want_sp["iters"] == 25).any(), (d, "no sum-product frame runs all 25 iterations")
+            for form, tune in LINK_FORMS.items():
+                for V in (1, 2, 4):
+                    what = (d, "sp", form, V)
+                    dec = L.Decoder(c["g"], c["K"], max_batch=B, algo="sp", max_iter=25, frames_per_lane=V, tune=tune)
+                    dec.set_timing(True)
+                    out, iters = dec.decode(c["y"])
+                    phase0 = {k["name"] for k in dec.kernel_times() if k["phase"] == 0}
+                    dec.set_timing(False)
+                    assert np.array_equal(out, want_sp["out"]) and np.array_equal(iters, want_sp["iters"]), what
+                    assert np.array_equal(dec.dump(3, B).astype(np.uint8), want_sp["hard"]), what
+                    assert phase0 and all(n.startswith(_link_kernel_name(form, V) or "check_link")
+                                          and n.endswith(",%d,%d>" % (d, V)) for n in phase0), (what, phase0)
+                    dec.close()
 
 
 # --------------------------------------------------------------------------- one-launch kernels on QC shapes
