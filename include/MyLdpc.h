@@ -131,6 +131,18 @@ public:
      * Runs on the GPU `setDevice` names (ldpc_tb_attach / ldpc_tb_check).  Off by default: without this call every byte and
      * length is as in the reference.  Before encode() and decode().  Returns 0 or an ldpc_status. */
     int setTransportBlock(int payloadBits, int crcBits = -1);
+    /* CRC-aided early termination (ldpc_hip.h: crc_kind / crc_bits): with setTransportBlock() every frame carries a CRC,
+     * and a frame then also stops in the first round in which its payload and CRC bits pass it -- usually a round before
+     * its syndrome is clean.  Needs setTransportBlock() with crcBits != 0 first (LDPC_ERR_STATE otherwise).  DecodeSP,
+     * DecodeMS, DecodeCPU and DecodeTDMPCL take it, and DecodeTDMP where it runs the layered schedule of DecodeTDMPCL; on
+     * DecodeMSCL, and on DecodeTDMP where it follows the reference's host-layered path, addDecodeType fails while it is
+     * on, as with setMinSumCorrection (both reproduce reference kernels).  The decoders then run the streaming kernels.
+     * lastCrcStops(): frames of the last decode() that stopped in a round in which their syndrome was not clean.  A frame
+     * stopped with wrong bits that pass the CRC is the undetected error crcPassed() cannot see either; its chance grows
+     * with the rounds tested (ldpc_hip.h).  Off by default: without this call every byte is as without it.  Before
+     * addDecodeType().  Returns 0 or an ldpc_status. */
+    int setCrcEarlyStop(bool on);
+    long long lastCrcStops() const { return crcStops; }
     int lastCrcFailures() const { return crcFailures; }
     bool crcPassed(int frame) const { return frame >= 0 && (size_t)frame < crcOk.size() && crcOk[(size_t)frame] != 0; }
     int lastIterations() const { return lastTime; }             /* the reference's "Time=" */
@@ -177,6 +189,9 @@ private:
     ldpc_tb_spec tbSpec = {};        /* setTransportBlock(); A = 0: off */
     std::vector<unsigned char> crcOk;/* per frame of the last decode() */
     int crcFailures = 0;
+    bool crcEarlyStop = false;       /* setCrcEarlyStop() */
+    long long crcStops = 0;
+    int applyCrcEarlyStop(ldpc_decoder_config &cfg);
     int frameCount(int kBytes) const { return (kBytes + (ldpcK / 8) - 1) / (ldpcK / 8); }   /* frames of K/8-byte rows */
     int encodeSource(char *srcCode, char *priorCode, int srcLength);
     int encodeFrames(char *srcCode, char *priorCode, int srcLength);

@@ -164,6 +164,30 @@ typedef struct ldpc_decoder_config {
      *      LDPC_ERR_UNSUPPORTED).  NaN, inf or a value out of range: LDPC_ERR_ARG. ----------------------------- */
     float ms_scale;             /* alpha: 0 = off (factor 1), else 0 < alpha <= 1                            */
     float ms_offset;            /* beta: 0 = off, else 0 < beta < 1000                                        */
+    /* ---- CRC-aided early termination (appended; a struct_size of offsetof(ldpc_decoder_config, crc_kind), the size
+     *      before these fields, is accepted and means off).  A receiver whose frames carry a CRC (ldpc_tb_frame_crc) can
+     *      stop a frame as soon as its information bits pass it, usually a round before the syndrome is clean: parity
+     *      and punctured columns converge last.  With crc_kind != 0, after the variable-node phase of round i = 1, 2, ...
+     *      (layered: after the last layer) has produced the hard bits b_i(f, .) of every running frame f:
+     *          clean_i(f): the syndrome of b_i(f, .) is zero                                   (the rule without a CRC)
+     *          crc_i(f):   b_i(f, 0 .. crc_bits-1) leave remainder zero under the polynomial of crc_kind, conventions of
+     *                      ldpc_crc_bits: zero register, no reflection, bit 0 first
+     *      a running frame freezes at the first i with clean_i(f) OR crc_i(f): iters[f] = i, its output is b_i.  A frame
+     *      that never freezes gets iters = max_iter and the last round's bits, as without a CRC.  frames_converged counts
+     *      frames frozen by either rule; ldpc_decoder_crc_stops those frozen in a round where clean_i was false.
+     *      Needs early_term = 1 (LDPC_ERR_ARG otherwise, as for an unknown kind or crc_bits out of range).
+     *      Streaming kernels only: LDPC_ALGO_SP and LDPC_ALGO_MS (fp32 and LDPC_MSG_F16, with or without ms_scale /
+     *      ms_offset) and LDPC_ALGO_LAYERED with one launch per layer; one more launch per round (crc_term_kernel).
+     *      LDPC_ALGO_MS_FUSED and LDPC_ALGO_LAYERED_HOST reproduce reference kernels: LDPC_ERR_UNSUPPORTED.  The
+     *      LDS-resident one-launch kernels and the record kernels do not carry the rule and are not selected (forcing
+     *      them, LDPC_TUNE_ON(FUSED) or LDPC_TUNE_ON(LDSP): LDPC_ERR_UNSUPPORTED).
+     *      Two facts.  An all-zero prefix passes every one of these CRCs; that is harmless, it is the all-zero payload
+     *      (padding frames are born frozen and are never counted).  And every round tested is one more chance in 2^16 or
+     *      2^24 that wrong bits pass: a frame stopped that way is the same undetected error ldpc_tb_check_device would
+     *      report, so the undetected-error rate of a transport block can grow by up to the number of rounds tested. --- */
+    int32_t crc_kind;           /* 0 = off, else enum ldpc_crc_kind: LDPC_CRC16, LDPC_CRC24A, LDPC_CRC24B             */
+    int32_t crc_bits;           /* the CRC covers hard bits [0, crc_bits) of every frame, parity included:
+                                   24 < crc_bits <= K (16 < for LDPC_CRC16)                                           */
 } ldpc_decoder_config;
 
 /* two-bit fields of tune_flags: LDPC_TUNE_ON(f) forces the choice on, LDPC_TUNE_OFF(f) off */
@@ -229,7 +253,16 @@ int ldpc_graph_info(const ldpc_graph *g, int32_t *M, int32_t *N, int64_t *E, int
 
 /* ---- decoder: replaces Coder::forDecoder's device setup + addDecodeType,
  *      MyLdpc.cpp:226-305, 307-552 -------------------------------------------- */
-void ldpc_decoder_config_init(ldpc_decoder_config *cfg); /* reference defaults */
+/* Reference defaults.  The caller says how large its struct is, so that the call never writes behind it:
+ * ldpc_decoder_config_init_sized fills the first struct_size bytes -- one of the three sizes ldpc_decoder_create accepts:
+ * offsetof(ms_scale), offsetof(crc_kind), sizeof -- and stores struct_size itself; any other size is LDPC_ERR_ARG and
+ * nothing is written.  The exported function ldpc_decoder_config_init is what callers built against the header before
+ * crc_kind / crc_bits call with their shorter struct: it fills offsetof(ldpc_decoder_config, crc_kind) bytes and stores
+ * that as struct_size (CRC off).  Code compiled against THIS header gets its own struct's size through the macro below,
+ * so `ldpc_decoder_config_init(&cfg)` keeps meaning "all of cfg, struct_size = sizeof cfg". */
+void ldpc_decoder_config_init(ldpc_decoder_config *cfg);
+int ldpc_decoder_config_init_sized(ldpc_decoder_config *cfg, uint32_t struct_size);
+#define ldpc_decoder_config_init(cfg) ((void)ldpc_decoder_config_init_sized((cfg), (uint32_t)sizeof(ldpc_decoder_config)))
 int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg, ldpc_decoder **out);
 /* The reference uses devices[0] of its context only (MyLdpc.cpp:226-235).  Here one handle may
  * span several HIP devices: ldpc_decode() cuts the caller's frame stream into n_devices contiguous
@@ -292,6 +325,11 @@ int64_t ldpc_out_bytes(int32_t K, int64_t frames, int32_t pack_mode);
  * gathered since timing was enabled); blocks until that call has finished. */
 int ldpc_decoder_set_timing(ldpc_decoder *d, int enable);
 int ldpc_decoder_stats(ldpc_decoder *d, ldpc_decode_stats *stats);
+/* CRC-aided early termination (crc_kind != 0): *frames = frames of the last call that froze in a round in which their
+ * syndrome was not clean -- stopped by the CRC alone.  Summed over the launch groups of an ldpc_decode() call, the
+ * decoders the stragglers were handed to and the devices of a multi-device handle; 0 with crc_kind = 0.  Blocks until
+ * the call has finished, as ldpc_decoder_stats does. */
+int ldpc_decoder_crc_stops(ldpc_decoder *d, int64_t *frames);
 
 /* One line per distinct kernel launched since timing was enabled. */
 typedef struct ldpc_kernel_time {
@@ -561,6 +599,13 @@ typedef struct ldpc_tb_spec {
 void ldpc_tb_spec_init(ldpc_tb_spec *spec, int32_t A, int32_t K);
 int ldpc_tb_layout(const ldpc_tb_spec *spec, int32_t out[6]);
 int ldpc_crc_bits(int32_t kind, const uint8_t *bytes, int64_t nbits, uint32_t *crc);
+/* Host only.  ldpc_crc_weights: w[n], n < nbits, is the ldpc_crc_bits of the unit vector e_n of nbits bits; the CRC is
+ *   linear, so the XOR of the weights of a row's set bits is the row's CRC (what the decoders' CRC test computes).
+ * ldpc_tb_frame_crc: the CRC every FRAME of a spec carries, as the decoder config's (crc_kind, crc_bits):
+ *   cb_crc == 24: (LDPC_CRC24B, Kp); C == 1 with tb_crc 16 or 24: (LDPC_CRC16 or LDPC_CRC24A, Kp); otherwise LDPC_ERR_ARG
+ *   -- the frames have no CRC of their own (the transport block's CRC spans several frames, or there is none). */
+int ldpc_crc_weights(int32_t kind, int32_t nbits, uint32_t *w);
+int ldpc_tb_frame_crc(const ldpc_tb_spec *spec, int32_t *kind, int32_t *bits);
 int ldpc_tb_attach_device(const ldpc_tb_spec *spec, const uint8_t *payload_dev, int64_t tbs, uint8_t *src_dev, int64_t src_bytes,
                           int32_t device, void *stream);
 int ldpc_tb_check_device(const ldpc_tb_spec *spec, const uint8_t *dec_dev, int64_t tbs, uint8_t *payload_dev, uint8_t *cb_ok_dev,

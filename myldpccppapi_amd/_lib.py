@@ -39,6 +39,13 @@ class DecoderConfig(ctypes.Structure):
                 ("ms_scale", ctypes.c_float), ("ms_offset", ctypes.c_float)]
 
 
+class DecoderConfigCrc(DecoderConfig):
+    """The whole of `ldpc_decoder_config`: DecoderConfig is the struct as it was before crc_kind / crc_bits (a size the
+    library still accepts, CRC off, and the one ldpc_decoder_config_init fills); this one has the two fields behind it and
+    is initialised with ldpc_decoder_config_init_sized(cfg, sizeof)."""
+    _fields_ = [("crc_kind", ctypes.c_int32), ("crc_bits", ctypes.c_int32)]
+
+
 class DecodeStats(ctypes.Structure):
     """Mirror of `ldpc_decode_stats`."""
     _fields_ = [("iterations_launched", ctypes.c_int32), ("batch_time", ctypes.c_int32),
@@ -89,6 +96,7 @@ EXPORTS = (
     "ldpc_modem_demap_device", "ldpc_modem_transmit", "ldpc_modem_demap",
     "ldpc_tb_spec_init", "ldpc_tb_layout", "ldpc_crc_bits", "ldpc_tb_attach_device", "ldpc_tb_check_device", "ldpc_tb_tally_device",
     "ldpc_tb_attach", "ldpc_tb_check",
+    "ldpc_decoder_crc_stops", "ldpc_crc_weights", "ldpc_tb_frame_crc", "ldpc_decoder_config_init_sized",
 )
 
 
@@ -121,6 +129,7 @@ def load():
     L.ldpc_graph_info.argtypes = [vp, i32p, i32p, i64p, i32p, i32p]
     L.ldpc_decoder_config_init.argtypes = [ctypes.POINTER(DecoderConfig)]
     L.ldpc_decoder_config_init.restype = None
+    L.ldpc_decoder_config_init_sized.argtypes = [ctypes.POINTER(DecoderConfig), ctypes.c_uint32]
     L.ldpc_decoder_create.argtypes = [vp, ctypes.POINTER(DecoderConfig), ctypes.POINTER(vp)]
     L.ldpc_decoder_create_multi.argtypes = [vp, ctypes.POINTER(DecoderConfig), i32p, ctypes.c_int32,
                                             ctypes.POINTER(vp)]
@@ -190,6 +199,9 @@ def load():
     L.ldpc_tb_tally_device.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int64, i64p, ctypes.c_int32, vp]
     L.ldpc_tb_attach.argtypes = [tsp, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int32]
     L.ldpc_tb_check.argtypes = [tsp, vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int32]
+    L.ldpc_decoder_crc_stops.argtypes = [vp, i64p]
+    L.ldpc_crc_weights.argtypes = [ctypes.c_int32, ctypes.c_int32, vp]
+    L.ldpc_tb_frame_crc.argtypes = [tsp, i32p, i32p]
     _lib = L
     return L
 

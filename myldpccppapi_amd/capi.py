@@ -178,10 +178,10 @@ class Decoder:
     def __init__(self, graph, K, max_batch, algo="sp", max_iter=40, llr_scale=8.0, early_term=True,
                  device=0, layer_rows=0, pack_mode=PACK_BYTES, frames_per_lane=0, poll_interval=0,
                  msg_dtype=MSG_F32, tune=None, devices=None, host_input="auto", host_copy_threads=0,
-                 ms_scale=0.0, ms_offset=0.0):
+                 ms_scale=0.0, ms_offset=0.0, crc_kind=0, crc_bits=0):
         L = _lib.load()
-        cfg = DecoderConfig()
-        L.ldpc_decoder_config_init(ctypes.byref(cfg))
+        cfg = _lib.DecoderConfigCrc()
+        _lib.check(L.ldpc_decoder_config_init_sized(ctypes.byref(cfg), ctypes.sizeof(cfg)))
         cfg.K, cfg.max_batch = int(K), int(max_batch)
         cfg.algo = ALGOS[algo] if isinstance(algo, str) else int(algo)
         cfg.msg_dtype = {"f32": MSG_F32, "f16": MSG_F16}.get(msg_dtype, msg_dtype)
@@ -195,6 +195,9 @@ class Decoder:
         cfg.host_copy_threads = int(host_copy_threads)
         # normalized / offset min-sum, algo "ms" / "layered": R = fmaxf(min - ms_offset, 0) * ms_scale (0 = off)
         cfg.ms_scale, cfg.ms_offset = float(ms_scale), float(ms_offset)
+        # CRC-aided early termination: a frame also stops once its first crc_bits hard bits pass the CRC (0 = off;
+        # kind 16, 24 (24A), 25 (24B) or "16" / "24a" / "24b"; TransportBlock.frame_crc() gives both)
+        cfg.crc_kind, cfg.crc_bits = int(CRC_KINDS.get(crc_kind, crc_kind)), int(crc_bits)
         self.cfg = cfg
         self.graph = graph
         self.K, self.N, self.E = int(K), graph.N, graph.E
@@ -232,6 +235,12 @@ class Decoder:
         st = DecodeStats()
         _lib.check(_lib.load().ldpc_decoder_stats(self._h, ctypes.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
+
+    def crc_stops(self):
+        """Frames of the last call stopped by the CRC in a round in which their syndrome was not clean."""
+        n = ctypes.c_int64(0)
+        _lib.check(_lib.load().ldpc_decoder_crc_stops(self._h, ctypes.byref(n)))
+        return n.value
 
     def kernel_times(self):
         """Per-kernel HIP-event times gathered since set_timing(True)."""
@@ -501,6 +510,21 @@ class TransportBlock:
         crc = ctypes.c_uint32()
         _lib.check(_lib.load().ldpc_crc_bits(CRC_KINDS.get(kind, kind), data.ctypes.data if data.size else None, n, ctypes.byref(crc)))
         return crc.value
+
+    @staticmethod
+    def crc_weights(kind, nbits):
+        """uint32 [nbits]: entry n is the CRC of the unit vector e_n of nbits bits (ldpc_crc_weights); the XOR of the
+        weights of a row's set bits is the row's CRC.  Host arithmetic only."""
+        w = np.zeros(max(int(nbits), 0), np.uint32)
+        _lib.check(_lib.load().ldpc_crc_weights(CRC_KINDS.get(kind, kind), int(nbits), w.ctypes.data if w.size else None))
+        return w
+
+    def frame_crc(self):
+        """(crc_kind, crc_bits) of the CRC every frame carries, for Decoder(crc_kind=, crc_bits=): CRC24B over Kp bits
+        with a code-block CRC, the transport block's CRC when C = 1; LdpcError code 1 when the frames have none."""
+        kind, bits = ctypes.c_int32(0), ctypes.c_int32(0)
+        _lib.check(_lib.load().ldpc_tb_frame_crc(ctypes.byref(self.spec), ctypes.byref(kind), ctypes.byref(bits)))
+        return kind.value, bits.value
 
     # -- buffers already in HBM (integers, e.g. a torch tensor's data_ptr()); enqueued on `stream`, no wait --------
     def attach_device(self, payload_ptr, tbs, src_ptr, src_nbytes, stream=None):

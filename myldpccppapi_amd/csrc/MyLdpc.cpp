@@ -139,6 +139,28 @@ int Coder::setTransportBlock(int payloadBits, int crcBits)
     return LDPC_SUCCESS;
 }
 
+/* CRC-aided early termination of the decoders addDecodeType makes from here on */
+int Coder::setCrcEarlyStop(bool on)
+{
+    if (!on) { crcEarlyStop = false; return LDPC_SUCCESS; }
+    if (!tbSpec.A) return fail(LDPC_ERR_STATE, "setCrcEarlyStop: call setTransportBlock() first: without it the frames carry no CRC");
+    int32_t kind = 0, bits = 0;
+    if (int rc = ldpc_tb_frame_crc(&tbSpec, &kind, &bits)) return fail(rc, std::string("setCrcEarlyStop: setTransportBlock() with crcBits = 0: ") + ldpc_last_error());
+    crcEarlyStop = true;
+    return LDPC_SUCCESS;
+}
+
+/* the two config fields of a decoder made while setCrcEarlyStop is on */
+int Coder::applyCrcEarlyStop(ldpc_decoder_config &cfg)
+{
+    if (!crcEarlyStop) return LDPC_SUCCESS;
+    int32_t kind = 0, bits = 0;
+    if (int rc = ldpc_tb_frame_crc(&tbSpec, &kind, &bits)) return fail(rc, std::string("setCrcEarlyStop: ") + ldpc_last_error());
+    cfg.crc_kind = kind;
+    cfg.crc_bits = bits;
+    return LDPC_SUCCESS;
+}
+
 int Coder::makeGraph()
 {
     if (graph) return LDPC_SUCCESS;
@@ -445,6 +467,15 @@ int Coder::addDecodeType(enum decodeType deType)
                         "this code and takes no min-sum correction (setMinSumCorrection); DecodeTDMPCL does");
         if (cfg.algo != LDPC_ALGO_SP) { cfg.ms_scale = msScale; cfg.ms_offset = msOffset; }   /* DecodeSP: ignored */
     }
+    if (crcEarlyStop) {
+        if (cfg.algo == LDPC_ALGO_MS_FUSED)
+            return fail(LDPC_ERR_UNSUPPORTED, "addDecodeType: DecodeMSCL reproduces the reference's fused min-sum "
+                        "kernel, which stops on the syndrome alone (setCrcEarlyStop)");
+        if (cfg.algo == LDPC_ALGO_LAYERED_HOST)
+            return fail(LDPC_ERR_UNSUPPORTED, "addDecodeType: DecodeTDMP follows the reference's host-layered path on "
+                        "this code, which stops on the syndrome alone (setCrcEarlyStop); DecodeTDMPCL takes the CRC");
+        if (int rc = applyCrcEarlyStop(cfg)) return rc;
+    }
     ldpc_decoder *d = nullptr;
     int rc = makeDecoder(cfg, &d);
     if (rc) return fail(rc, ldpc_last_error());
@@ -481,6 +512,7 @@ int Coder::decode(float *postCode, char *srcCode, int srcLength, enum decodeType
             cfg.layer_rows = z;                              /* circulant size: lets the record / one-launch kernels apply
                                                                 (with a correction: the record kernel or the streaming ones) */
             cfg.ms_scale = msScale; cfg.ms_offset = msOffset;
+            if (int rc = applyCrcEarlyStop(cfg)) return rc;
             int rc = makeDecoder(cfg, &d);
             if (rc) return fail(rc, ldpc_last_error());
             decoders[(int)DecodeCPU] = d;
@@ -505,6 +537,8 @@ int Coder::decode(float *postCode, char *srcCode, int srcLength, enum decodeType
     if (rc) return fail(rc, ldpc_last_error());
     ldpc_decode_stats st;
     if (ldpc_decoder_stats(d, &st) == LDPC_OK) lastTime = st.batch_time;
+    int64_t stops = 0;
+    crcStops = ldpc_decoder_crc_stops(d, &stops) == LDPC_OK ? (long long)stops : 0;
     if (tbSpec.A) {
         std::vector<char> payload((size_t)codeSize * (tbSpec.A / 8));
         crcOk.assign((size_t)codeSize, 0);

@@ -160,7 +160,7 @@ struct HostSlot {
 };
 struct RingChunk { HostBuf<uint8_t> h; Event ev; bool used = false; };
 /* counts of the last ldpc_decode() call over ALL its launch groups (ldpc_decoder_stats) */
-struct CallCounts { bool valid = false; int32_t iterations = 0, batch_time = 0; int64_t frames = 0, converged = 0, frame_rounds = 0; };
+struct CallCounts { bool valid = false; int32_t iterations = 0, batch_time = 0; int64_t frames = 0, converged = 0, frame_rounds = 0, crc_stops = 0; };
 
 struct HostPath {
     Stream copy_stream;                 /* declared before the slots and the ring: their events and memory go first */
@@ -222,7 +222,9 @@ struct ldpc_decoder {
     ldpc::DevBuf<int32_t> row_ptr, edge_col, col_ptr, col_edge;
     ldpc::DevBuf<uint64_t> hard, failw, done;
     ldpc::DevBuf<int32_t> iters, active;
-    ldpc::DevBuf<int32_t> summary;      /* [4]: max iters, converged count, tile-rounds that did work (early termination) */
+    ldpc::DevBuf<int32_t> summary;      /* [4]: max iters, converged count, tile-rounds that did work (early termination),
+                                           frames stopped by the CRC alone (cfg.crc_kind) */
+    ldpc::DevBuf<uint32_t> crc_w;       /* cfg.crc_kind != 0: [crc_bits] column weights of crc_term_kernel (crc_term_host.hpp) */
 
     ldpc::LayeredPlan layered;          /* LDPC_ALGO_LAYERED, streaming (one launch per layer) */
     ldpc::FusedPlan fused;              /* LDPC_ALGO_LAYERED, short QC codes: whole decode in LDS */

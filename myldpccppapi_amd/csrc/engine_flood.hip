@@ -10,6 +10,7 @@
  *   check_i    : R_i = check(Q_{i-1})
  *   var_i      : bits_i = hard(R_i) (frozen frames keep theirs); Q_i = var(R_i)
  *   syndrome_i : fail_i = any parity check of bits_i odd          } early_term only
+ *   crc_i      : (cfg.crc_kind) fail_i &= ~(CRC of bits_i passes)  } (crc_term_kernels.hpp)
  *   state_i    : frames with clean bits_i freeze, iters = i        } (and after the last round)
  *   tail_i     : (asynchronous callers) hand the last running frames over to the overflow tiles
  * then pack.
@@ -28,6 +29,7 @@
 
 #include "flood_round.hpp"
 #include "flood_handover.hpp"
+#include "crc_term_kernels.hpp"
 #include "decoder.hpp"
 #include "graph.hpp"
 
@@ -331,6 +333,12 @@ template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t
                             d->flood.syn_xcd ? tiles : 0, rbk, tr};
             dim3 sgrid = d->flood.syn_xcd ? dim3(8 * rbk * ((tiles + 7) / 8)) : dim3(rbk, tiles);
             syndrome_kernel<V><<<sgrid, kBlock, 0, s>>>(sa);
+            if (d->cfg.crc_kind) {
+                /* frames whose information bits pass the CRC count as clean from here on; those the syndrome had not
+                 * passed go into summary[3] */
+                CrcTermArgs ca{d->hard.p, fw, d->done.p, d->crc_w.p, d->summary.p + 3, d->N, d->cfg.crc_bits, tr};
+                crc_term_kernel<V><<<dim3((unsigned)tiles, V), 64 * crc_term_waves(d->cfg.crc_bits), 0, s>>>(ca);
+            }
             StateArgs st{d->done.p, fw, d->iters.p, nullptr, frames, it, max_iter, 1, tr, use_tail ? d->flood.running.p : nullptr,
                          d->summary.p + 2};
             const bool poll = freeze && it < rounds && d->cfg.poll_interval > 0 && !d->host.suppress_poll &&

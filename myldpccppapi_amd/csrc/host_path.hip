@@ -162,6 +162,10 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
             counts.frame_rounds += d->cfg.early_term ? (int64_t)sl.h_sum.p[2] * d->F : (int64_t)sl.g_iterations * sl.g_tiles * d->F;
             for (int c = 0; c < sl.g_children; ++c) counts.frame_rounds += (int64_t)sl.h_sum.p[4 * (c + 1) + 2] * sl.g_child_f[c];
         }
+        if (d->cfg.crc_kind) {       /* frames stopped by the CRC alone: this decoder's and those of the hand-over chain */
+            counts.crc_stops += sl.h_sum.p[3];
+            for (int c = 0; c < sl.g_children; ++c) counts.crc_stops += sl.h_sum.p[4 * (c + 1) + 3];
+        }
         return LDPC_OK;
     };
     int rc = LDPC_OK;

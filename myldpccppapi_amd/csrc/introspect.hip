@@ -101,6 +101,37 @@ int ldpc_decoder_stats(ldpc_decoder *d, ldpc_decode_stats *st)
     return LDPC_OK;
 }
 
+int ldpc_decoder_crc_stops(ldpc_decoder *d, int64_t *frames)
+{
+    if (!d || !frames) return set_error(LDPC_ERR_ARG, "decoder/frames is NULL");
+    *frames = 0;
+    if (!d->tm.have_last) return set_error(LDPC_ERR_STATE, "no decode call to report on");
+    if (!d->shards.empty()) {
+        for (ldpc_decoder *sh : d->shards) {
+            if (!sh->tm.have_last) continue;
+            int64_t one = 0;
+            const int rc = ldpc_decoder_crc_stops(sh, &one);
+            if (rc) return rc;
+            *frames += one;
+        }
+        return LDPC_OK;
+    }
+    if (!d->cfg.crc_kind) return LDPC_OK;
+    LDPC_HIP_TRY(hipSetDevice(d->cfg.device));
+    LDPC_HIP_TRY(hipEventSynchronize(d->tm.ev_end.e));
+    if (d->host.call.valid) {            /* a host-buffer call of several launch groups */
+        *frames = d->host.call.crc_stops;
+        return LDPC_OK;
+    }
+    /* summary[3] of this decoder and of those its stragglers were handed to, as frame_rounds sums summary[2] */
+    for (const ldpc_decoder *p = d; p; p = p->flood.handed_to) {
+        int32_t cs[4] = {0, 0, 0, 0};
+        LDPC_HIP_TRY(hipMemcpy(cs, p->summary.p, sizeof cs, hipMemcpyDeviceToHost));
+        *frames += cs[3];
+    }
+    return LDPC_OK;
+}
+
 int ldpc_decoder_kernel_times(ldpc_decoder *d, ldpc_kernel_time *out, int32_t capacity, int32_t *count)
 {
     if (!d || !out || !count || capacity <= 0) return set_error(LDPC_ERR_ARG, "bad arguments");

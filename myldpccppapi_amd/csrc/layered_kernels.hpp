@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "flood_kernels.hpp"
+#include "crc_term_kernels.hpp"
 #include "hip_host.hpp"
 
 namespace ldpc {
@@ -228,6 +229,9 @@ struct LayeredRun {
     int32_t *iters;
     const int32_t *row_ptr, *edge_col;
     int32_t *summary;
+    /* CRC-aided early termination (ldpc_decoder_config::crc_kind): column weights and covered bits, 0 = off */
+    const uint32_t *crc_w = nullptr;
+    int32_t crc_bits = 0;
 };
 
 /* The launching code instantiates every kernel above: only the translation unit that defines
@@ -276,7 +280,7 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
     const int rounds = r.tap_iter ? (r.tap_iter < r.max_iter ? r.tap_iter : r.max_iter) : r.max_iter;
     hipError_t e;
     if ((e = hipMemsetAsync(r.failw, 0, (size_t)(r.max_iter + 2) * slot * sizeof(uint64_t), s))) return e;
-    if ((e = hipMemsetAsync(r.summary, 0, 2 * sizeof(int32_t), s))) return e;
+    if ((e = hipMemsetAsync(r.summary, 0, (r.crc_bits ? 4 : 2) * sizeof(int32_t), s))) return e;
     if ((e = hipMemsetAsync(pl->R.p, 0, (size_t)tiles * F * (size_t)pl->E * sizeof(float), s))) return e;
     {
         LayeredInitArgs ia{r.llr_dev, pl->P.p, r.hard, r.frames, pl->N, pl->host_arith};
@@ -310,6 +314,10 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
         SyndromeArgs sa{r.row_ptr, r.edge_col, r.hard, fw, r.done, pl->M, pl->N, 0, 0};
         dim3 sgrid((pl->M + kBlock - 1) / kBlock, tiles);
         syndrome_kernel<V><<<sgrid, kBlock, 0, s>>>(sa);
+        if (r.crc_bits) {       /* frames whose information bits pass the CRC count as clean (crc_term_kernels.hpp) */
+            CrcTermArgs ca{r.hard, fw, r.done, r.crc_w, r.summary + 3, pl->N, r.crc_bits, TailRef{nullptr, 0, 0}};
+            crc_term_kernel<V><<<dim3((unsigned)tiles, V), 64 * crc_term_waves(r.crc_bits), 0, s>>>(ca);
+        }
         StateArgs st{r.done, fw, r.iters, nullptr, r.frames, it, r.max_iter, 1};
         state_kernel<V><<<tiles, 64, 0, s>>>(st);
     }

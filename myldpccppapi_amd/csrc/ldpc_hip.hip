@@ -26,6 +26,7 @@
 
 #include "decoder.hpp"
 #include "graph.hpp"
+#include "crc_term_host.hpp"
 
 using ldpc::set_error;
 
@@ -154,11 +155,16 @@ int ldpc_graph_info(const ldpc_graph *g, int32_t *M, int32_t *N, int64_t *E, int
     return LDPC_OK;
 }
 
-void ldpc_decoder_config_init(ldpc_decoder_config *cfg)
+int ldpc_decoder_config_init_sized(ldpc_decoder_config *cfg, uint32_t struct_size)
 {
-    if (!cfg) return;
-    memset(cfg, 0, sizeof *cfg);
-    cfg->struct_size = sizeof *cfg;
+    if (!cfg) return set_error(LDPC_ERR_ARG, "config is NULL");
+    if (struct_size != sizeof(ldpc_decoder_config) && struct_size != offsetof(ldpc_decoder_config, crc_kind) &&
+        struct_size != offsetof(ldpc_decoder_config, ms_scale))
+        return set_error(LDPC_ERR_ARG, "config struct_size %u is none of %zu, %zu, %zu (ABI mismatch)", struct_size,
+                    sizeof(ldpc_decoder_config), offsetof(ldpc_decoder_config, crc_kind), offsetof(ldpc_decoder_config, ms_scale));
+    /* every field that has a non-zero default lies in front of ms_scale */
+    memset(cfg, 0, struct_size);
+    cfg->struct_size = struct_size;
     cfg->max_batch = 1;
     cfg->algo = LDPC_ALGO_SP;
     cfg->msg_dtype = LDPC_MSG_F32;
@@ -166,16 +172,26 @@ void ldpc_decoder_config_init(ldpc_decoder_config *cfg)
     cfg->llr_scale = 8.0f;    /* decodeCL.c:9 */
     cfg->early_term = 1;
     cfg->pack_mode = LDPC_PACK_BYTES;
+    return LDPC_OK;
 }
 
-/* The caller's config as the current struct: callers built against the header before ms_scale / ms_offset pass
- * the shorter struct, of which only struct_size bytes are read; the fields it lacks are 0 (off). */
+/* the symbol callers built against the header before crc_kind / crc_bits call with their shorter struct (the header's
+ * macro of the same name sends callers of this header to the function above with their own size) */
+#undef ldpc_decoder_config_init
+void ldpc_decoder_config_init(ldpc_decoder_config *cfg)
+{
+    (void)ldpc_decoder_config_init_sized(cfg, (uint32_t)offsetof(ldpc_decoder_config, crc_kind));
+}
+
+/* The caller's config as the current struct: callers built against the header before ms_scale / ms_offset, or before
+ * crc_kind / crc_bits, pass a shorter struct, of which only struct_size bytes are read; the fields it lacks are 0 (off). */
 static int config_in(const ldpc_decoder_config *cfg, ldpc_decoder_config *full)
 {
     constexpr size_t kSizeBeforeMsCorr = offsetof(ldpc_decoder_config, ms_scale);
-    if (cfg->struct_size != sizeof(ldpc_decoder_config) && cfg->struct_size != kSizeBeforeMsCorr)
-        return set_error(LDPC_ERR_ARG, "config struct_size %u is neither %zu nor %zu (ABI mismatch)", cfg->struct_size,
-                    sizeof(ldpc_decoder_config), kSizeBeforeMsCorr);
+    constexpr size_t kSizeBeforeCrc = offsetof(ldpc_decoder_config, crc_kind);
+    if (cfg->struct_size != sizeof(ldpc_decoder_config) && cfg->struct_size != kSizeBeforeCrc && cfg->struct_size != kSizeBeforeMsCorr)
+        return set_error(LDPC_ERR_ARG, "config struct_size %u is none of %zu, %zu, %zu (ABI mismatch)", cfg->struct_size,
+                    sizeof(ldpc_decoder_config), kSizeBeforeCrc, kSizeBeforeMsCorr);
     memset(full, 0, sizeof *full);
     memcpy(full, cfg, cfg->struct_size);
     full->struct_size = sizeof *full;
@@ -224,6 +240,19 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         return set_error(LDPC_ERR_UNSUPPORTED, "fp16 messages are built for flooding min-sum only "
                     "(the probability-domain SP needs fp32 range; layered: not yet)");
     if (!ldpc::tune_valid(*cfg)) return set_error(LDPC_ERR_ARG, "tuning / streams config fields out of range");
+    /* CRC-aided early termination: the streaming kernels carry the rule (crc_term_kernel), nothing else does */
+    const bool crc_term = cfg->crc_kind != 0;
+    {
+        char msg[256];
+        if (ldpc::crc_term_check(cfg->crc_kind, cfg->crc_bits, cfg->K, cfg->early_term, msg, sizeof msg)) return set_error(LDPC_ERR_ARG, "%s", msg);
+        if (crc_term && (cfg->algo == LDPC_ALGO_MS_FUSED || cfg->algo == LDPC_ALGO_LAYERED_HOST))
+            return set_error(LDPC_ERR_UNSUPPORTED, "crc_kind: LDPC_ALGO_MS_FUSED and LDPC_ALGO_LAYERED_HOST reproduce reference kernels, which "
+                        "stop on the syndrome alone; LDPC_ALGO_SP, LDPC_ALGO_MS and LDPC_ALGO_LAYERED carry the CRC rule");
+        const ldpc::Tune t = ldpc::tune_from_config(*cfg);
+        if (crc_term && (ldpc::tune_forced_on(t.fused) || ldpc::tune_forced_on(t.ldsp)))
+            return set_error(LDPC_ERR_UNSUPPORTED, "crc_kind: the LDS-resident one-launch kernels and the record kernels (LDPC_TUNE_FUSED / "
+                        "LDPC_TUNE_LDSP forced on) do not carry the CRC rule; the streaming kernels do");
+    }
 
     int ndev = 0;
     LDPC_HIP_TRY(hipGetDeviceCount(&ndev));
@@ -279,6 +308,11 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     LDPC_HIP_TRY(d->iters.alloc(TF));
     LDPC_HIP_TRY(d->active.alloc(1));
     LDPC_HIP_TRY(d->summary.alloc(4));
+    if (crc_term) {
+        std::vector<uint32_t> w((size_t)cfg->crc_bits);
+        ldpc::crc_term_weights(cfg->crc_kind, cfg->crc_bits, w.data());
+        LDPC_HIP_TRY(d->crc_w.upload(w));
+    }
 
     if (cfg->algo == LDPC_ALGO_MS_FUSED) {
         if (cfg->pack_mode != LDPC_PACK_BYTES && cfg->K % 8)
@@ -312,7 +346,7 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         if (d->ms_corr && ldpc::tune_forced_on(tune.fused) && ldpc::tune_forced_off(tune.ldsp))
             return set_error(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset: the LDS-resident layered kernel (LDPC_TUNE_FUSED on, "
                         "LDPC_TUNE_LDSP off) carries no correction; the record or the streaming kernels do");
-        if (!ldpc::tune_forced_off(tune.fused) && (cfg->pack_mode == LDPC_PACK_BYTES || cfg->K % 8 == 0)) {
+        if (!crc_term && !ldpc::tune_forced_off(tune.fused) && (cfg->pack_mode == LDPC_PACK_BYTES || cfg->K % 8 == 0)) {
             if (!d->ms_corr) {
                 LDPC_HIP_TRY(ldpc::fused_plan_create(&d->fused, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows));
                 d->use_fused = d->fused.eligible;
@@ -353,7 +387,7 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         if (d->ms_corr && ldpc::tune_forced_on(tune.fused) && ldpc::tune_forced_off(tune.ldsp))
             return set_error(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset: the LDS-resident flooding kernel (LDPC_TUNE_FUSED on, "
                         "LDPC_TUNE_LDSP off) carries no correction; the record or the streaming kernels do");
-        if (cfg->msg_dtype == LDPC_MSG_F32 && cfg->layer_rows > 0 && cfg->frames_per_lane == 0 &&
+        if (!crc_term && cfg->msg_dtype == LDPC_MSG_F32 && cfg->layer_rows > 0 && cfg->frames_per_lane == 0 &&
             (cfg->pack_mode == LDPC_PACK_BYTES || cfg->K % 8 == 0)) {
             const bool small = (int64_t)cfg->max_batch * g->E <= (int64_t)1 << 23;
             if (!d->ms_corr && ldpc::tune_pick(tune.fused, small)) {
@@ -538,6 +572,7 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
         run.early_term = d->cfg.early_term; run.pack_mode = d->cfg.pack_mode;
         run.hard = d->hard.p; run.failw = d->failw.p; run.done = d->done.p; run.iters = d->iters.p;
         run.row_ptr = d->row_ptr.p; run.edge_col = d->edge_col.p; run.summary = d->summary.p;
+        run.crc_w = d->crc_w.p; run.crc_bits = d->cfg.crc_kind ? d->cfg.crc_bits : 0;
         hipError_t e = ldpc::engine_layered_run(&d->layered, run, s, &d->last_iterations);
         rc = (e == hipSuccess) ? LDPC_OK
                                : set_error(LDPC_ERR_HIP, "layered decode: %s", hipGetErrorString(e));

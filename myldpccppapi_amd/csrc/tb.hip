@@ -7,6 +7,7 @@
 #include "../../include/ldpc_hip.h"
 #include "hip_host.hpp"
 #include "tb_host.hpp"
+#include "crc_term_host.hpp"
 #include "tb_kernels.hpp"
 
 using ldpc::set_error;
@@ -112,6 +113,24 @@ int ldpc_crc_bits(int32_t kind, const uint8_t *bytes, int64_t nbits, uint32_t *c
     if (nbits < 0) return set_error(LDPC_ERR_ARG, "nbits = %lld is negative", (long long)nbits);
     if (!crc || (!bytes && nbits > 0)) return set_error(LDPC_ERR_ARG, "bytes/crc is NULL");
     *crc = ldpc::tb_crc_bits(g, L, bytes, nbits);
+    return LDPC_OK;
+}
+
+int ldpc_crc_weights(int32_t kind, int32_t nbits, uint32_t *w)
+{
+    uint32_t g;
+    int L;
+    if (!ldpc::tb_crc_poly(kind, &g, &L)) return set_error(LDPC_ERR_ARG, "kind = %d is none of 16, 24 (CRC24A), 25 (CRC24B)", kind);
+    if (nbits < 0) return set_error(LDPC_ERR_ARG, "nbits = %d is negative", nbits);
+    if (!w && nbits > 0) return set_error(LDPC_ERR_ARG, "w is NULL");
+    ldpc::crc_term_weights(kind, nbits, w);
+    return LDPC_OK;
+}
+
+int ldpc_tb_frame_crc(const ldpc_tb_spec *spec, int32_t *kind, int32_t *bits)
+{
+    char msg[200];
+    if (ldpc::tb_frame_crc(spec, kind, bits, msg, sizeof msg)) return set_error(LDPC_ERR_ARG, "%s", msg);
     return LDPC_OK;
 }
 

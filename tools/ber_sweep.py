@@ -9,7 +9,8 @@ reference counts differing BYTES (Test.cpp:105-110); this prints byte errors too
 
     python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N>] [--algo sp|ms|layered]
                               [--payload zero|random] [--rate-match P,FLO,FHI,E[,K0]] [--erasure-llr X]
-                              [--modulation bpsk|qpsk|qam16|qam64|qam256] [--no-interleave] [--transport-block A[,C]]
+                              [--modulation bpsk|qpsk|qam16|qam64|qam256] [--no-interleave] [--transport-block A[,C]] [--crc-stop]
+                              [--msg-dtype f32|f16]
                               [--snr=1.0,1.5,...]  (write --snr=-0.5,0 for a list that starts with a minus) [--frames 4096] [--iters 50]
 --rate-match: code bits [0, P) punctured, [FLO, FHI) filler bits (known zeros; multiples of 8, inside the information part),
 E bits per frame sent from circular-buffer position K0 (default 0): ldpc_rate_match_device between the encoder and the
@@ -29,6 +30,10 @@ blocks as a receiver does, without the bytes that were sent (include/ldpc_hip.h,
 multiple of C.  Every point also prints the block error rate (blocks whose payload is wrong), the blocks whose CRCs failed
 (detected), the wrong blocks whose CRCs passed (undetected) and the right blocks whose CRCs failed (parity only).  The
 fillers [Kp, K) are sent unless --rate-match names them.
+--crc-stop (with --transport-block whose frames carry a CRC of their own: C = 1, or C > 1 with CRC24B): the decoder also stops
+a frame in the first round in which its first Kp bits pass that CRC (include/ldpc_hip.h: crc_kind / crc_bits; the streaming
+kernels then run).  Every point of a --transport-block run prints crc_stops, the frames stopped in a round in which their
+syndrome was not clean (0 without --crc-stop), next to the block counts -- blocks_undetected is where a false pass would show.
 The DVB-S2 / BG1 codes are PROFILE SURROGATES (codes.py): the numbers are not the standards'."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -57,8 +62,11 @@ ap.add_argument("--modulation", choices=("bpsk", "qpsk", "qam16", "qam64", "qam2
 ap.add_argument("--no-interleave", action="store_true", help="with --modulation: no bit interleaver")
 ap.add_argument("--transport-block", default=None, metavar="A[,C]",
                 help="with --payload random: A payload bits per transport block, C code blocks (default: the rule of ldpc_tb_spec_init)")
+ap.add_argument("--msg-dtype", choices=("f32", "f16"), default="f32", help="message storage (f16: --algo ms only)")
+ap.add_argument("--crc-stop", action="store_true", help="with --transport-block: frames also stop once their CRC passes")
 args = ap.parse_args()
 assert not args.transport_block or args.payload == "random", "--transport-block needs --payload random"
+assert args.transport_block or not args.crc_stop, "--crc-stop needs --transport-block"
 assert args.modulation or not args.no_interleave, "--no-interleave needs --modulation"
 QM = {None: 0, "bpsk": 1, "qpsk": 2, "qam16": 4, "qam64": 6, "qam256": 8}[args.modulation]
 matched = bool(QM) and args.algo == "sp" and args.llr_scale is None       # llr_scale = 2 / sd^2 per SNR point
@@ -82,11 +90,17 @@ else:
 M = N - K
 g = L.Graph(rows, cols, M, N)
 B = args.frames
+tb = None
+if args.transport_block:
+    tbv = [int(x) for x in args.transport_block.split(",")]
+    tb = L.TransportBlock(tbv[0], K, C=tbv[1] if len(tbv) > 1 else None)
+crc_kind, crc_bits = tb.frame_crc() if args.crc_stop else (0, 0)
 
 
 def make_decoder(llr_scale):
     return L.Decoder(g, K, max_batch=B, algo=args.algo, max_iter=args.iters, llr_scale=llr_scale,
-                     layer_rows=layer, poll_interval=2, ms_scale=args.ms_scale, ms_offset=args.ms_offset)
+                     layer_rows=layer, poll_interval=2, ms_scale=args.ms_scale, ms_offset=args.ms_offset,
+                     crc_kind=crc_kind, crc_bits=crc_bits, msg_dtype=args.msg_dtype)
 
 
 dec = None if matched else make_decoder(8.0 if args.llr_scale is None else args.llr_scale)
@@ -103,10 +117,8 @@ if args.payload == "random":
     code = torch.empty((B, N), dtype=torch.uint8, device="cuda")
     gen = torch.Generator(device="cuda")
     gen.manual_seed(args.seed)
-tb = pay = back = cb_ok = tb_ok = None
-if args.transport_block:
-    tbv = [int(x) for x in args.transport_block.split(",")]
-    tb = L.TransportBlock(tbv[0], K, C=tbv[1] if len(tbv) > 1 else None)
+pay = back = cb_ok = tb_ok = None
+if tb is not None:
     assert B % tb.C == 0, "--frames must be a multiple of the %d code blocks of a transport block" % tb.C
     TBS = B // tb.C
     pay = torch.empty((TBS, tb.A // 8), dtype=torch.uint8, device="cuda")
@@ -192,6 +204,8 @@ if tb is not None:
 if md is not None:
     print("modulation: %s (%d bits per symbol) interleave=%d llr_scale=%s" % (
         args.modulation, QM, md.spec.interleave, "2/sd^2 per point" if matched else "%g" % (8.0 if args.llr_scale is None else args.llr_scale)))
+if args.crc_stop:
+    print("crc stop: crc_kind=%d over the first %d bits of every frame" % (crc_kind, crc_bits))
 print("code=%s algo=%s payload=%s ms_scale=%g ms_offset=%g frames=%d x %d max_iter=%d (info bits per point: %d)" % (
     args.code, args.algo, args.payload, args.ms_scale, args.ms_offset, B, args.batches, args.iters, B * K * args.batches))
 points = [float(x) for x in args.snr.split(",")]
@@ -207,7 +221,7 @@ for snr in points:
     point_decoder(sd)
     tot = [0, 0, 0]
     blocks = [0, 0, 0, 0]
-    it_sum, conv = 0.0, 0
+    it_sum, conv, stops, rounds, dec_ms = 0.0, 0, 0, 0, 0.0
     t0 = time.perf_counter()
     for b in range(args.batches):
         channel_batch(b * B, sd, args.seed)
@@ -218,12 +232,17 @@ for snr in points:
             tb.check_device(out.data_ptr(), TBS, back.data_ptr(), cb_ok.data_ptr(), tb_ok.data_ptr(), None)
             blocks = [t + x for t, x in zip(blocks, tb.tally_device(tb_ok.data_ptr(), back.data_ptr(), pay.data_ptr(), TBS, None))]
         it_sum += float(it.float().sum())
-        conv += dec.stats()["frames_converged"]
+        st = dec.stats()
+        conv += st["frames_converged"]
+        rounds += st["frame_rounds"]
+        dec_ms += st["ms_total"]
+        if tb is not None:
+            stops += dec.crc_stops()
     dt = time.perf_counter() - t0
     frames = B * args.batches
     res = {"snr_db": snr, "sd": round(sd, 4), "ber": tot[0] / (frames * K), "bit_errors": tot[0],
            "byte_errors": tot[1], "fer": tot[2] / frames, "avg_iters": round(it_sum / frames, 2),
-           "frames_converged": conv, "frames": frames,
+           "frames_converged": conv, "frames": frames, "frame_rounds": rounds, "decode_ms_per_batch": round(dec_ms / args.batches, 3),
            "end_to_end_Mbit_s": round(frames * K / dt / 1e6, 1)}
     if md is not None:
         es_n0 = 1.0 / (2.0 * sd * sd)
@@ -232,5 +251,5 @@ for snr in points:
     if tb is not None:
         n = TBS * args.batches
         res.update({"blocks": n, "bler": blocks[1] / n, "blocks_crc_failed": blocks[0], "blocks_undetected": blocks[2],
-                    "blocks_parity_only": blocks[3]})
+                    "blocks_parity_only": blocks[3], "crc_stops": stops})
     print(json.dumps(res), flush=True)
