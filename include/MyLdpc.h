@@ -69,6 +69,12 @@ public:
     int encode(char *srcCode, char *priorCode, int srcLength);
     /* postCode: getPostCodeLength(srcLength) floats; srcCode: srcLength bytes out */
     int decode(float *postCode, char *srcCode, int srcLength, enum decodeType deType);
+    /* decode() with soft output (ldpc_hip.h: ldpc_decode_soft): soft takes N floats per frame over the MOTHER code --
+     * also under setRateMatch(), where postCode holds E per frame --, per frame the posterior of the round the frame
+     * stopped in (kind LDPC_SOFT_POSTERIOR: positive <-> bit 0, its sign is the decoded bit) or that minus the channel
+     * value the decoder read (LDPC_SOFT_EXTRINSIC).  Everything else as decode(), the transport-block check included.
+     * DecodeSP returns LDPC_ERR_UNSUPPORTED with lastError() set: sum-product has no usable soft value. */
+    int decodeSoft(float *postCode, char *srcCode, int srcLength, enum decodeType deType, float *soft, int kind = LDPC_SOFT_POSTERIOR);
 
     /* BPSK + AWGN of standard deviation `rate` on libc rand() (MyLdpc.cpp:1061-1105) */
     int test(char *priorCode, float *postCode, int priorCodeLength, float rate);
@@ -157,6 +163,7 @@ public:
 private:
     int initCheckMatrix();
     int encodeOnce(const char *src, char *code, int srcLength);
+    int decodeFrames(float *postCode, char *srcCode, int srcLength, enum decodeType deType, float *soft, int kind);
     int fail(int code, const std::string &msg);
 
     int times;

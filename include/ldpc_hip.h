@@ -316,6 +316,42 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
 
 int64_t ldpc_out_bytes(int32_t K, int64_t frames, int32_t pack_mode);
 
+/* ---- soft output: the decode above plus one fp32 value per frame and code bit --------------------------------
+ * The rule, per frame.  Let i_f = iters[f] be the round in which frame f froze (its syndrome first was clean, or its
+ * CRC passed), or max_iter; with early_term = 0 it is max_iter for every frame.  Then
+ *   LDPC_SOFT_POSTERIOR:  soft[f * N + n] = p_{i_f}(f, n), the fp32 posterior bit n of the frame's output was decided
+ *     from, in the units of the channel values, positive <-> bit 0:
+ *       LDPC_ALGO_MS, every form (fp32, LDPC_MSG_F16, ms_scale / ms_offset): p = y_n + R_e1 + R_e2 + ... in fp32, one add
+ *         at a time, R = the check->variable messages of round i_f on the column's edges in ascending edge id; y_n is the
+ *         channel value as the decoder read it (rounded to fp16 with LDPC_MSG_F16).  This is the very sum the variable
+ *         node forms for the hard decision.
+ *       LDPC_ALGO_LAYERED, LDPC_ALGO_LAYERED_HOST, LDPC_ALGO_MS_FUSED: P[n] after the last layer (MS_FUSED: after the
+ *         posterior update) of round i_f.
+ *   LDPC_SOFT_EXTRINSIC:  soft = p - y_n, one fp32 subtraction, the same y_n.
+ * Consequence: wherever the posterior is finite and not zero, its sign is the output bit.
+ * The value is that of round i_f and no later one: a frozen frame's messages keep evolving unread inside the streaming
+ * decoders, so it is caught when the frame freezes (0 ulp against the CPU oracle's `post` tap of that round).
+ *
+ * LDPC_ALGO_SP has no soft output (LDPC_ERR_UNSUPPORTED): the reference's sum-product runs in the probability domain in
+ * fp32, and its normalised posterior (f0 - f1) / (f0 + f1) carries nothing by the time a frame stops -- on the
+ * BG1-profile test code (N = 1088, 64 frames, llr_scale 8) it is exactly +-1 on 68210 of 69632 values at 3.0 dB, and 0/0
+ * on 20690 of them at 1.5 dB.
+ *
+ * ldpc_decode_soft_device follows ldpc_decode_device in everything the two share (out_dev and iters_dev stay nullable).
+ *   soft_dev:    soft_floats floats, 4-byte aligned and no more; exactly frames * N are written, nothing else -- not the
+ *                rows behind them, not for the padding frames of a ragged tile.  Must not overlap llr_dev.
+ *   LDPC_ERR_ARG (nothing enqueued): soft_dev NULL, soft_floats < frames * N, an unknown soft_kind, an overlap with
+ *                llr_dev.  LDPC_ERR_STATE: a debug tap is set.  LDPC_ERR_UNSUPPORTED: LDPC_ALGO_SP, on any engine.
+ * It works on whichever engine the handle was created with, through both hand-overs of the stragglers, and leaves
+ * nothing behind: the plain entry points launch and move exactly what they did before and after a soft call.
+ * ldpc_decode_soft: the same on host buffers, as ldpc_decode (launch groups, device lists); soft_host holds
+ * frames * N floats.  The handle's first soft call allocates the staging buffers for it. */
+enum ldpc_soft_kind { LDPC_SOFT_POSTERIOR = 1, LDPC_SOFT_EXTRINSIC = 2 };
+int ldpc_decode_soft_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, uint8_t *out_dev, int64_t out_bytes,
+                            int32_t *iters_dev, float *soft_dev, int64_t soft_floats, int32_t soft_kind, void *stream);
+int ldpc_decode_soft(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t *out_host, int64_t out_bytes,
+                     int32_t *iters, float *soft_host, int64_t soft_floats, int32_t soft_kind);
+
 /* Per-kernel HIP-event timing of subsequent decode calls (two event records per
  * launch on the decode stream; off by default).  enable = 1: every call; enable = k > 1:
  * every k-th ldpc_decode_device call, starting with the next one (the events cost about 2 %

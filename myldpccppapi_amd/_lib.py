@@ -97,6 +97,7 @@ EXPORTS = (
     "ldpc_tb_spec_init", "ldpc_tb_layout", "ldpc_crc_bits", "ldpc_tb_attach_device", "ldpc_tb_check_device", "ldpc_tb_tally_device",
     "ldpc_tb_attach", "ldpc_tb_check",
     "ldpc_decoder_crc_stops", "ldpc_crc_weights", "ldpc_tb_frame_crc", "ldpc_decoder_config_init_sized",
+    "ldpc_decode_soft_device", "ldpc_decode_soft",
 )
 
 
@@ -137,6 +138,8 @@ def load():
     L.ldpc_decoder_destroy.argtypes = [vp]
     L.ldpc_decode.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp]
     L.ldpc_decode_device.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp]
+    L.ldpc_decode_soft.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, ctypes.c_int32]
+    L.ldpc_decode_soft_device.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, ctypes.c_int32, vp]
     L.ldpc_out_bytes.argtypes = [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]
     L.ldpc_out_bytes.restype = ctypes.c_int64
     L.ldpc_decoder_set_timing.argtypes = [vp, ctypes.c_int]

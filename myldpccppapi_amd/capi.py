@@ -19,6 +19,8 @@ CODE_PACKED, CODE_BITS = 0, 1                              # enum ldpc_code_form
 CODE_FORMATS = {"packed": CODE_PACKED, "bits": CODE_BITS}
 PARITY_KINDS = {1: "dual_diagonal", 2: "staircase"}        # enum ldpc_parity_kind
 HOST_INPUT = {"auto": 0, "staged": 1, "lock_pages": 2}     # enum ldpc_host_input
+SOFT_POSTERIOR, SOFT_EXTRINSIC = 1, 2                      # enum ldpc_soft_kind
+SOFT_KINDS = {"posterior": SOFT_POSTERIOR, "extrinsic": SOFT_EXTRINSIC}
 ALGOS = {"sp": ALGO_SP, "ms": ALGO_MS, "layered": ALGO_LAYERED, "ms_fused": ALGO_MS_FUSED,
          "layered_host": ALGO_LAYERED_HOST}
 
@@ -210,22 +212,36 @@ class Decoder:
                                                    ctypes.byref(self._h)))
 
     # -- host buffers (the reference's Coder::decode signature) -------------
-    def decode(self, llr, want_iters=True):
-        """llr: float32 [frames, N] (numpy).  Returns (bytes uint8, iters int32)."""
+    def decode(self, llr, want_iters=True, soft=None):
+        """llr: float32 [frames, N] (numpy).  Returns (bytes uint8, iters int32); with soft="posterior" or "extrinsic"
+        (ldpc_decode_soft) a third value, float32 [frames, N]: per frame the posterior of the round it stopped in, or
+        that minus the channel value."""
         L = _lib.load()
         llr = np.ascontiguousarray(llr, np.float32).reshape(-1, self.N)
         frames = llr.shape[0]
         out = np.zeros(out_bytes(self.K, frames, self.cfg.pack_mode), np.uint8)
         iters = np.zeros(frames, np.int32)
-        _lib.check(L.ldpc_decode(self._h, llr.ctypes.data, frames, out.ctypes.data, out.size,
-                                 iters.ctypes.data if want_iters else None))
-        return out, iters
+        if soft is None:
+            _lib.check(L.ldpc_decode(self._h, llr.ctypes.data, frames, out.ctypes.data, out.size,
+                                     iters.ctypes.data if want_iters else None))
+            return out, iters
+        vals = np.zeros((frames, self.N), np.float32)
+        _lib.check(L.ldpc_decode_soft(self._h, llr.ctypes.data, frames, out.ctypes.data, out.size,
+                                      iters.ctypes.data if want_iters else None, vals.ctypes.data, vals.size,
+                                      SOFT_KINDS.get(soft, soft)))
+        return out, iters, vals
 
     # -- buffers already in HBM ----------------------------------------------
-    def decode_device(self, llr_ptr, frames, out_ptr, out_nbytes, iters_ptr=None, stream=None):
-        """ldpc_decode_device: out_ptr None = iteration counts and stats() only; iters_ptr None = bytes only."""
-        _lib.check(_lib.load().ldpc_decode_device(self._h, llr_ptr, frames, out_ptr, out_nbytes,
-                                                  iters_ptr, stream))
+    def decode_device(self, llr_ptr, frames, out_ptr, out_nbytes, iters_ptr=None, stream=None, soft_ptr=None, soft_floats=0,
+                      soft="posterior"):
+        """ldpc_decode_device: out_ptr None = iteration counts and stats() only; iters_ptr None = bytes only.
+        soft_ptr: ldpc_decode_soft_device -- soft_floats >= frames * N float32 values of kind `soft` are written there."""
+        if soft_ptr is None and not soft_floats:
+            _lib.check(_lib.load().ldpc_decode_device(self._h, llr_ptr, frames, out_ptr, out_nbytes,
+                                                      iters_ptr, stream))
+        else:
+            _lib.check(_lib.load().ldpc_decode_soft_device(self._h, llr_ptr, frames, out_ptr, out_nbytes, iters_ptr, soft_ptr,
+                                                           int(soft_floats), SOFT_KINDS.get(soft, soft), stream))
 
     def set_timing(self, enable=True):
         """True / 1: time every launch of every call; k > 1: of every k-th decode_device call; False: off."""

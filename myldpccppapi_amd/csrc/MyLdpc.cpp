@@ -487,6 +487,22 @@ int Coder::addDecodeType(enum decodeType deType)
  * ldpc_decode.  srcLength bytes are written. */
 int Coder::decode(float *postCode, char *srcCode, int srcLength, enum decodeType deType)
 {
+    return decodeFrames(postCode, srcCode, srcLength, deType, nullptr, 0);
+}
+
+int Coder::decodeSoft(float *postCode, char *srcCode, int srcLength, enum decodeType deType, float *soft, int kind)
+{
+    if (!soft) return fail(LDPC_ERR_ARG, "decodeSoft: soft is NULL");
+    if (kind != LDPC_SOFT_POSTERIOR && kind != LDPC_SOFT_EXTRINSIC) return fail(LDPC_ERR_ARG, "decodeSoft: unknown kind");
+    if (deType == DecodeSP)
+        return fail(LDPC_ERR_UNSUPPORTED, "decodeSoft: DecodeSP works in the probability domain, where the posterior has "
+                    "saturated by the time a frame stops; the min-sum decode types carry soft output");
+    return decodeFrames(postCode, srcCode, srcLength, deType, soft, kind);
+}
+
+/* soft != nullptr: ldpc_decode_soft, N floats per frame of the mother code */
+int Coder::decodeFrames(float *postCode, char *srcCode, int srcLength, enum decodeType deType, float *soft, int kind)
+{
     if (!isDecoder) return fail(LDPC_ERR_STATE, "decode: call forDecoder() first");
     if (!postCode || !srcCode || srcLength <= 0) return fail(LDPC_ERR_ARG, "decode: bad arguments");
     const int codeSize = getCodeSize(srcLength);
@@ -533,7 +549,8 @@ int Coder::decode(float *postCode, char *srcCode, int srcLength, enum decodeType
         if (rm) return fail(rm, ldpc_last_error());
         postCode = recovered.data();
     }
-    int rc = ldpc_decode(d, postCode, codeSize, (uint8_t *)srcCode, srcLength, nullptr);
+    int rc = soft ? ldpc_decode_soft(d, postCode, codeSize, (uint8_t *)srcCode, srcLength, nullptr, soft, (int64_t)codeSize * ldpcN, kind)
+                  : ldpc_decode(d, postCode, codeSize, (uint8_t *)srcCode, srcLength, nullptr);
     if (rc) return fail(rc, ldpc_last_error());
     ldpc_decode_stats st;
     if (ldpc_decoder_stats(d, &st) == LDPC_OK) lastTime = st.batch_time;

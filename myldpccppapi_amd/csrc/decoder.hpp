@@ -125,6 +125,8 @@ struct FloodPlan {
     bool is_child = false;
     ldpc_decoder *handed_to = nullptr;  /* the decoder (child, or the child's child) that finished the last call's stragglers */
     HostBuf<int32_t> h_active;          /* pinned: the polled "frames still running" word */
+    DevBuf<int32_t> soft_map;           /* a child: [max_batch] its slots as frames of the soft call's batch; made by the first
+                                           hand-over of a soft call (soft_kernels.hpp: soft_map_kernel) */
 
     /* Rounds beyond the previous call's iteration count are probably idle: they are launched with
      * kIdleFat times as many rows / columns per wave, i.e. that many times fewer workgroups (an idle
@@ -148,7 +150,9 @@ struct HostSlot {
     DevBuf<int32_t> iters;
     HostBuf<uint8_t> h_out;             /* pinned: D2H completes without blocking the host */
     HostBuf<int32_t> h_iters;
-    HostBuf<uint8_t> h_head;            /* pinned, kStageBytes: a whole small group, or a large group's bytes before
+    DevBuf<float> soft;                 /* soft output, [max_batch][N]: both made by the handle's first ldpc_decode_soft */
+    HostBuf<float> h_soft;
+    HostBuf<uint8_t> h_head;           /* pinned, kStageBytes: a whole small group, or a large group's bytes before
                                            its first page boundary and (last group) after its last one */
     Event h2d_done, all_done;
     bool busy = false;
@@ -185,7 +189,8 @@ struct HostPath {
 
 struct TimedSpan {
     Event a, b;
-    int kind = 0;       /* 0 check, 1 var, 2 layer, 3 other, 4 check with column-local fusion, 5 check group, 6 var group */
+    int kind = 0;       /* 0 check, 1 var, 2 layer, 3 other, 4 check with column-local fusion, 5 check group, 6 var group,
+                           7 soft_settle_kernel (soft output) */
     int degree = 0;     /* groups: the bucket's highest degree */
     int64_t bytes = 0;  /* algorithmic bytes of the launch in the two-kernel formulation (16 E + 4 N in total) */
     int64_t moved = 0;  /* bytes this kernel's own loads and stores move (less when columns are fused in) */
@@ -203,6 +208,14 @@ struct Timing {
     hipStream_t last_stream = nullptr;
     bool have_last = false;
     int32_t tap_iter = 0;
+};
+
+/* Soft output of the call being enqueued (ldpc_decode_soft_device sets it around the plain entry point and clears it
+ * again: nothing of it outlives the call).  dst == nullptr: a plain call. */
+struct SoftReq {
+    float *dst = nullptr;               /* [frames][N] the caller's device buffer */
+    int32_t kind = 0;                   /* LDPC_SOFT_POSTERIOR / LDPC_SOFT_EXTRINSIC */
+    const int32_t *fmap = nullptr;      /* a hand-over child: its slots as frames of the caller's batch (FloodPlan::soft_map) */
 };
 
 }  // namespace ldpc
@@ -243,6 +256,7 @@ struct ldpc_decoder {
     ldpc::FloodPlan flood;
     ldpc::HostPath host;
     ldpc::Timing tm;
+    ldpc::SoftReq soft;
 
     /* a handle over several devices (ldpc_decoder_create_multi): one single-device decoder per entry
      * of the device list, and one persistent host thread per entry that runs its frame range; this

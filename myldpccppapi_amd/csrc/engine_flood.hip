@@ -11,6 +11,7 @@
  *   var_i      : bits_i = hard(R_i) (frozen frames keep theirs); Q_i = var(R_i)
  *   syndrome_i : fail_i = any parity check of bits_i odd          } early_term only
  *   crc_i      : (cfg.crc_kind) fail_i &= ~(CRC of bits_i passes)  } (crc_term_kernels.hpp)
+ *   soft_i     : (soft calls) the frames that settle in round i leave y + sum R_i in the caller's buffer (soft_kernels.hpp)
  *   state_i    : frames with clean bits_i freeze, iters = i        } (and after the last round)
  *   tail_i     : (asynchronous callers) hand the last running frames over to the overflow tiles
  * then pack.
@@ -30,6 +31,7 @@
 #include "flood_round.hpp"
 #include "flood_handover.hpp"
 #include "crc_term_kernels.hpp"
+#include "soft_kernels.hpp"
 #include "decoder.hpp"
 #include "graph.hpp"
 
@@ -118,8 +120,10 @@ template <int V> int enqueue_check_phase(ldpc_decoder *d, hipStream_t s, int til
                                   ((int64_t)rc.degree * rc.count - 2 * rc.linked) +
                                   (it < max_iter ? 2 * rc.linked : 0) + 2 * d->flood.extra_edges) * frames));
         CheckArgs a = check_args(d, tr, d->flood.link_rpw, false, rc.e0.p, rc.count, rc.degree);
+        /* soft output reads the fused columns' R like a tap does: stored in every round a frame can settle in */
+        const bool soft_reads = d->soft.dst && (d->cfg.early_term || it == max_iter);
         LinkArgs lk{rc.link_col.p, rc.link_pos.p, d->flood.chan.p, d->flood.Q.p, d->hard.p, d->N,
-                    (it < max_iter) ? 1 : 0, d->tm.tap_iter ? 1 : 0, d->flood.extra_e0.p, d->flood.extra_deg.p, d->flood.n_extra, 0,
+                    (it < max_iter) ? 1 : 0, (d->tm.tap_iter || soft_reads) ? 1 : 0, d->flood.extra_e0.p, d->flood.extra_deg.p, d->flood.n_extra, 0,
                     rc.n_big, rc.small_rows};
         const int variant = (d->flood.link_form == 2 && !d->flood.fns.link_half[rc.degree]) ? 1 : d->flood.link_form;
         const int waves = link_chunk_count(d->flood.link_rpw, rc.n_big, rc.small_rows, rc.count) * (variant == 1 ? V : variant == 2 ? V / 2 : 1);
@@ -189,6 +193,23 @@ template <int V> int enqueue_var_phase(ldpc_decoder *d, hipStream_t s, int tiles
     return LDPC_OK;
 }
 
+/* soft_i of a soft call (soft_kernels.hpp), between the CRC test and state_i: the frames that settle in this round --
+ * running and passed by `fail`, or every running frame where fail is nullptr (the last round launched) -- leave
+ * y + sum R (or that minus y) in the caller's buffer.  Min-sum only: the entry point refuses sum-product. */
+template <int V> int enqueue_soft(ldpc_decoder *d, hipStream_t s, int tiles, int64_t frames, const uint64_t *fail,
+                                  const ldpc::TailRef &tr)
+{
+    using namespace ldpc;
+    /* priced as if every frame settled here: channel value and column messages in, one float out */
+    LDPC_HIP_TRY(span_begin(d, s, 7, 0, ((int64_t)d->flood.msg_size * (d->E + d->N) + 4 * (int64_t)d->N) * frames));
+    SoftArgs a{d->flood.chan.p, d->flood.R.p, d->col_ptr.p, d->col_edge.p, d->done.p, fail, d->soft.dst, nullptr,
+               d->soft.fmap, d->flood.tail_map.p, d->E, frames, d->N, d->soft.kind == LDPC_SOFT_EXTRINSIC ? 1 : 0, tr};
+    const dim3 grid((unsigned)((d->N + kInitCols - 1) / kInitCols), (unsigned)tiles);
+    dispatch_msg(d->flood.msg_size, [&](auto t) { soft_settle_kernel<V, decltype(t)><<<grid, kBlock, 0, s>>>(a); });
+    LDPC_HIP_TRY(span_end(d, s));
+    return LDPC_OK;
+}
+
 /* Hand the `count` frames that are still running after round `it` over to the child decoder, let it
  * finish them (rounds it+1 ...), and bring their bits, iteration counts and converged flags back. */
 template <int V> int compact_and_finish(ldpc_decoder *d, int64_t frames, int count, int it, hipStream_t s)
@@ -237,7 +258,16 @@ template <int V> int compact_and_finish(ldpc_decoder *d, int64_t frames, int cou
     LDPC_HIP_TRY(hipGetLastError());
     c->tm.timing = false;
     c->tm.tap_iter = 0;
+    c->soft = SoftReq{};
+    if (d->soft.dst) {
+        /* the child runs soft_i in its own rounds and addresses the caller's frames: its slots through cmap, and through
+         * this decoder's own map where it is a child itself */
+        LDPC_HIP_TRY(c->flood.soft_map.ensure((size_t)c->cfg.max_batch));
+        soft_map_kernel<0><<<(unsigned)((count + kBlock - 1) / kBlock), kBlock, 0, s>>>(c->flood.soft_map.p, d->flood.cmap.p, d->soft.fmap, count);
+        c->soft = SoftReq{d->soft.dst, d->soft.kind, c->flood.soft_map.p};
+    }
     const int rc = dispatch_v(cv, [&](auto v) { return run_flooding<decltype(v)::value>(c, nullptr, count, nullptr, 0, nullptr, s, it + 1); });
+    c->soft = SoftReq{};
     if (rc) return rc;
     d->flood.handed_to = c;
     /* the bits back: every parent word collects its moved frames' bits (no atomics; the per-bit atomic scatter of
@@ -338,6 +368,15 @@ template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t
                  * passed go into summary[3] */
                 CrcTermArgs ca{d->hard.p, fw, d->done.p, d->crc_w.p, d->summary.p + 3, d->N, d->cfg.crc_bits, tr};
                 crc_term_kernel<V><<<dim3((unsigned)tiles, V), 64 * crc_term_waves(d->cfg.crc_bits), 0, s>>>(ca);
+            }
+            if (d->soft.dst) {
+                /* soft_i: `done` still holds the frames frozen before this round and fw this round's verdict, so
+                 * ~done & ~fw settle here; in the last round launched every running frame does.  Before state_i and
+                 * tail_i: a hand-over marks every batch tile finished, which is not "settled". */
+                LDPC_HIP_TRY(span_end(d, s));
+                const int rcs = enqueue_soft<V>(d, s, tiles, frames, (freeze && it < rounds) ? fw : nullptr, tr);
+                if (rcs) return rcs;
+                LDPC_HIP_TRY(span_begin(d, s, 3));
             }
             StateArgs st{d->done.p, fw, d->iters.p, nullptr, frames, it, max_iter, 1, tr, use_tail ? d->flood.running.p : nullptr,
                          d->summary.p + 2};

@@ -838,7 +838,19 @@ struct FusedRun {
     float llr_scale;
     int32_t loop_rows;  /* tuning: run-time row loops instead of the unrolled widths */
     int32_t no_pack;    /* tuning: one frame per wave also for circulants of <= 32 rows */
+    float *soft = nullptr;  /* soft output (ldpc_decode_soft_device): the caller's [frames][N] buffer takes the place of the
+                               tap's dump_p -- every kernel stores a frame's posterior there when the frame stops */
+    int32_t soft_extrinsic = 0;     /* ... and one pass afterwards turns it into posterior - channel value */
 };
+
+/* soft output, extrinsic kind: soft = p - y over the caller's two frame-major buffers (soft_kernels.hpp) */
+inline hipError_t fused_soft_finish(const FusedRun &r, int32_t N, hipStream_t s)
+{
+    if (!r.soft || !r.soft_extrinsic) return hipSuccess;
+    const int64_t count = r.frames * (int64_t)N;
+    soft_extrinsic_kernel<0><<<(unsigned)((count + kBlock - 1) / kBlock), kBlock, 0, s>>>(r.soft, r.llr_dev, count);
+    return hipGetLastError();
+}
 
 /* instantiates every kernel above: compiled by engine_fused.hip only (LDPC_ENGINE_FUSED) */
 #ifdef LDPC_ENGINE_FUSED
@@ -854,7 +866,7 @@ inline hipError_t fused_run(FusedPlan *pl, const FusedRun &r, hipStream_t s, int
         if ((e = pl->dump_b.alloc((size_t)r.frames * pl->N))) return e;
         pl->dump_frames = r.frames;
     }
-    FusedArgs a{r.llr_dev, r.out_dev, r.iters_dev, r.summary, r.tap_iter ? pl->dump_p.p : nullptr,
+    FusedArgs a{r.llr_dev, r.out_dev, r.iters_dev, r.summary, r.soft ? r.soft : (r.tap_iter ? pl->dump_p.p : nullptr),
                 r.tap_iter ? pl->dump_r.p : nullptr, nullptr, r.tap_iter ? pl->dump_q.p : nullptr,
                 r.tap_iter ? pl->dump_b.p : nullptr, r.llr_scale, pl->layer_ptr.p, pl->ent_bc.p, pl->ent_sh.p,
                 pl->layer_e0.p, pl->ent_pack.p, pl->pack_w, pl->bcol_ptr.p, pl->bcol_e0.p, pl->bcol_sh.p, r.frames, r.out_dev ? r.out_bytes : 0, pl->N, pl->E, r.K, pl->z, pl->layers,
@@ -918,7 +930,8 @@ inline hipError_t fused_run(FusedPlan *pl, const FusedRun &r, hipStream_t s, int
 #undef LDPC_FUSED_BY_MW
 #undef LDPC_FUSED_LAUNCH
     *launched = rounds;
-    return hipGetLastError();
+    if ((e = hipGetLastError())) return e;
+    return fused_soft_finish(r, pl->N, s);
 }
 
 #endif  /* LDPC_ENGINE_FUSED */

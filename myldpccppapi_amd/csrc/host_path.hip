@@ -104,7 +104,7 @@ hipError_t staged_copy(ldpc_decoder *d, uint8_t *dst, const uint8_t *src, size_t
 /* ldpc_decode on ONE device; `mode` was decided once per ldpc_decode call, before any thread of a device
  * list has touched the buffer. */
 int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t *out_host,
-                int64_t out_bytes, int32_t *iters, InputMode mode)
+                int64_t out_bytes, int32_t *iters, InputMode mode, float *soft_host = nullptr, int32_t soft_kind = 0)
 {
     const int64_t total = ldpc_out_bytes(d->cfg.K, frames, d->cfg.pack_mode);
     LDPC_HIP_TRY(hipSetDevice(d->cfg.device));
@@ -134,6 +134,10 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
         LDPC_HIP_TRY(sl.iters.ensure((size_t)Bmax));
         LDPC_HIP_TRY(sl.h_out.ensure((size_t)stage_out));
         LDPC_HIP_TRY(sl.h_iters.ensure((size_t)Bmax));
+        if (soft_host) {        /* soft output: made by the handle's first soft call */
+            LDPC_HIP_TRY(sl.soft.ensure((size_t)Bmax * d->N));
+            LDPC_HIP_TRY(sl.h_soft.ensure((size_t)Bmax * d->N));
+        }
         LDPC_HIP_TRY(sl.h_head.ensure(kStageBytes));
         LDPC_HIP_TRY(sl.h_sum.ensure(16));
         LDPC_HIP_TRY(sl.h2d_done.ensure(false));
@@ -153,6 +157,7 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
         LDPC_HIP_TRY(hipEventSynchronize(sl.all_done.e));
         if (sl.copy_bytes > 0) memcpy(out_host + sl.dst, sl.h_out.p, (size_t)sl.copy_bytes);
         if (iters) memcpy(iters + sl.off, sl.h_iters.p, (size_t)sl.n * sizeof(int32_t));
+        if (soft_host) memcpy(soft_host + (size_t)sl.off * d->N, sl.h_soft.p, (size_t)sl.n * d->N * sizeof(float));
         /* the call's counts: sums over its groups, maxima for the iteration numbers (as ldpc_decoder_stats forms them) */
         counts.frames += sl.n;
         counts.converged += sl.h_sum.p[1];
@@ -259,7 +264,11 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
         hipError_t e = hipStreamWaitEvent(d->stream.s, sl.h2d_done.e, 0);
         if (e != hipSuccess) { rc = set_error(LDPC_ERR_HIP, "host-to-device staging: %s", hipGetErrorString(e)); break; }
         const int64_t chunk_bytes = ldpc_out_bytes(d->cfg.K, n, d->cfg.pack_mode);
-        rc = ldpc_decode_device(d, sl.llr.p, n, sl.out.p, chunk_bytes, iters ? sl.iters.p : nullptr, d->stream.s);
+        if (soft_host)
+            rc = ldpc_decode_soft_device(d, sl.llr.p, n, sl.out.p, chunk_bytes, iters ? sl.iters.p : nullptr, sl.soft.p,
+                                         n * (int64_t)d->N, soft_kind, d->stream.s);
+        else
+            rc = ldpc_decode_device(d, sl.llr.p, n, sl.out.p, chunk_bytes, iters ? sl.iters.p : nullptr, d->stream.s);
         if (rc) break;
         LDPC_STAMP("decode enqueued", k);
         /* byte offset of this group's first frame: (off*K)/8 in both packings */
@@ -270,6 +279,8 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
             e = hipMemcpyAsync(sl.h_out.p, sl.out.p, (size_t)sl.copy_bytes, hipMemcpyDeviceToHost, d->stream.s);
         if (e == hipSuccess && iters)
             e = hipMemcpyAsync(sl.h_iters.p, sl.iters.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, d->stream.s);
+        if (e == hipSuccess && soft_host)
+            e = hipMemcpyAsync(sl.h_soft.p, sl.soft.p, (size_t)n * d->N * sizeof(float), hipMemcpyDeviceToHost, d->stream.s);
         sl.g_iterations = d->last_iterations; sl.g_tiles = d->last_tiles; sl.g_children = 0;
         if (e == hipSuccess) e = hipMemcpyAsync(sl.h_sum.p, d->summary.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, d->stream.s);
         for (const ldpc_decoder *p = d->flood.handed_to; p && sl.g_children < 3 && e == hipSuccess; p = p->flood.handed_to) {
@@ -334,12 +345,9 @@ int32_t shard_unit(const ldpc_decoder_config &cfg, int64_t frames)
     return (int32_t)std::min<int64_t>(u, 0x7fffffff);
 }
 
-}  // namespace
-
-extern "C" {
-
-int ldpc_decode(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t *out_host,
-                int64_t out_bytes, int32_t *iters)
+/* ldpc_decode (soft_host == nullptr) and ldpc_decode_soft: one device, or the frame ranges of a device list */
+int decode_entry(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t *out_host, int64_t out_bytes, int32_t *iters,
+                 float *soft_host, int32_t soft_kind)
 {
     if (!d) return set_error(LDPC_ERR_ARG, "decoder is NULL");
     if (frames < 0) return set_error(LDPC_ERR_ARG, "frames < 0");
@@ -348,7 +356,7 @@ int ldpc_decode(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
     if (out_bytes < 0) return set_error(LDPC_ERR_ARG, "out_bytes < 0");
     /* asked once, before any thread touches the buffer */
     const InputMode mode = resolve_input_mode(d->cfg, llr_host, (size_t)frames * d->N * sizeof(float));
-    if (d->shards.empty()) return decode_host(d, llr_host, frames, out_host, out_bytes, iters, mode);
+    if (d->shards.empty()) return decode_host(d, llr_host, frames, out_host, out_bytes, iters, mode, soft_host, soft_kind);
 
     /* several devices: each entry's own host thread decodes a contiguous frame range */
     const int n = (int)d->shards.size();
@@ -368,9 +376,9 @@ int ldpc_decode(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
         const int64_t lo_i = lo[i], cnt = hi[i] - lo[i];
         const int64_t obytes = std::min(room, ldpc_out_bytes(d->cfg.K, cnt, d->cfg.pack_mode));
         const int32_t N = d->N;
-        jobs[i].fn = [sh, llr_host, out_host, iters, lo_i, cnt, base, obytes, N, mode]() -> int {
+        jobs[i].fn = [sh, llr_host, out_host, iters, lo_i, cnt, base, obytes, N, mode, soft_host, soft_kind]() -> int {
             return decode_host(sh, llr_host + (size_t)lo_i * N, cnt, out_host + base, obytes,
-                               iters ? iters + lo_i : nullptr, mode);
+                               iters ? iters + lo_i : nullptr, mode, soft_host ? soft_host + (size_t)lo_i * N : nullptr, soft_kind);
         };
         d->shard_workers[i]->submit(&jobs[i]);
     }
@@ -384,6 +392,33 @@ int ldpc_decode(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
     d->tm.have_last = true;
     d->last_frames = frames;
     return LDPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ldpc_decode(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t *out_host,
+                int64_t out_bytes, int32_t *iters)
+{
+    return decode_entry(d, llr_host, frames, out_host, out_bytes, iters, nullptr, 0);
+}
+
+int ldpc_decode_soft(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t *out_host, int64_t out_bytes,
+                     int32_t *iters, float *soft_host, int64_t soft_floats, int32_t soft_kind)
+{
+    if (!d) return set_error(LDPC_ERR_ARG, "decoder is NULL");
+    /* what ldpc_decode_soft_device refuses, before any launch group is staged */
+    if (soft_kind != LDPC_SOFT_POSTERIOR && soft_kind != LDPC_SOFT_EXTRINSIC)
+        return set_error(LDPC_ERR_ARG, "unknown soft_kind %d", soft_kind);
+    if (d->cfg.algo == LDPC_ALGO_SP)
+        return set_error(LDPC_ERR_UNSUPPORTED, "soft output: LDPC_ALGO_SP has no usable soft value (include/ldpc_hip.h); "
+                    "the min-sum algorithms carry it");
+    if (d->tm.tap_iter) return set_error(LDPC_ERR_STATE, "soft output while a debug tap is set");
+    if (frames > 0 && !soft_host) return set_error(LDPC_ERR_ARG, "soft is NULL");
+    if (frames > 0 && soft_floats < frames * (int64_t)d->N)
+        return set_error(LDPC_ERR_ARG, "soft_floats=%lld < %lld", (long long)soft_floats, (long long)(frames * (int64_t)d->N));
+    return decode_entry(d, llr_host, frames, out_host, out_bytes, iters, soft_host, soft_kind);
 }
 
 int ldpc_host_block_plan(uint64_t base, int64_t frames, int32_t N, int32_t max_batch, int64_t group, uint64_t out[6])

@@ -32,6 +32,7 @@
 
 #include "flood_kernels.hpp"
 #include "crc_term_kernels.hpp"
+#include "soft_kernels.hpp"
 #include "hip_host.hpp"
 
 namespace ldpc {
@@ -232,6 +233,9 @@ struct LayeredRun {
     /* CRC-aided early termination (ldpc_decoder_config::crc_kind): column weights and covered bits, 0 = off */
     const uint32_t *crc_w = nullptr;
     int32_t crc_bits = 0;
+    /* soft output (ldpc_decode_soft_device): the caller's [frames][N] buffer, nullptr = a plain call; extrinsic: P - y */
+    float *soft = nullptr;
+    int32_t soft_extrinsic = 0;
 };
 
 /* The launching code instantiates every kernel above: only the translation unit that defines
@@ -317,6 +321,16 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
         if (r.crc_bits) {       /* frames whose information bits pass the CRC count as clean (crc_term_kernels.hpp) */
             CrcTermArgs ca{r.hard, fw, r.done, r.crc_w, r.summary + 3, pl->N, r.crc_bits, TailRef{nullptr, 0, 0}};
             crc_term_kernel<V><<<dim3((unsigned)tiles, V), 64 * crc_term_waves(r.crc_bits), 0, s>>>(ca);
+        }
+        if (r.soft) {
+            /* soft_i (soft_kernels.hpp): `done` still holds the frames frozen before this round and fw this round's
+             * verdict; the frames that settle now leave P -- the posterior after the round's last layer, which later
+             * rounds overwrite -- in the caller's buffer.  In the last round launched every running frame settles. */
+            SoftArgs so{pl->P.p, nullptr, nullptr, nullptr, r.done, (r.early_term && it < rounds) ? fw : nullptr, r.soft,
+                        r.llr_dev, nullptr, nullptr, pl->E, r.frames, pl->N, r.soft_extrinsic, TailRef{nullptr, 0, 0}};
+            if (r.span_begin && (e = r.span_begin(r.span_ctx, s, /*soft_settle_kernel*/ 7, 0,(int64_t)8 * pl->N * r.frames))) return e;
+            soft_settle_kernel<V, float><<<dim3((unsigned)((pl->N + kInitCols - 1) / kInitCols), (unsigned)tiles), kBlock, 0, s>>>(so);
+            if (r.span_end && (e = r.span_end(r.span_ctx, s))) return e;
         }
         StateArgs st{r.done, fw, r.iters, nullptr, r.frames, it, r.max_iter, 1};
         state_kernel<V><<<tiles, 64, 0, s>>>(st);

@@ -553,6 +553,8 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
                            d->cfg.algo == LDPC_ALGO_MS_FUSED ? 1 : (d->cfg.algo == LDPC_ALGO_MS ? 2 : (d->cfg.algo == LDPC_ALGO_SP ? 3 : 0)),
                            d->cfg.llr_scale, ldpc::tune_pick(d->tune.fused_loop, false) ? 1 : 0,
                            ldpc::tune_pick(d->tune.fused_pack, true) ? 0 : 1};
+        run.soft = d->soft.dst;
+        run.soft_extrinsic = d->soft.kind == LDPC_SOFT_EXTRINSIC ? 1 : 0;
         hipError_t e = ldpc::span_begin(d, s, 2, 0, (int64_t)frames * (4 * d->N + d->cfg.K / 8));
         if (e == hipSuccess)
             e = d->use_ldsp ? ldpc::engine_ldsp_run(&d->ldsp, run, s, &d->last_iterations)
@@ -573,6 +575,7 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
         run.hard = d->hard.p; run.failw = d->failw.p; run.done = d->done.p; run.iters = d->iters.p;
         run.row_ptr = d->row_ptr.p; run.edge_col = d->edge_col.p; run.summary = d->summary.p;
         run.crc_w = d->crc_w.p; run.crc_bits = d->cfg.crc_kind ? d->cfg.crc_bits : 0;
+        run.soft = d->soft.dst; run.soft_extrinsic = d->soft.kind == LDPC_SOFT_EXTRINSIC ? 1 : 0;
         hipError_t e = ldpc::engine_layered_run(&d->layered, run, s, &d->last_iterations);
         rc = (e == hipSuccess) ? LDPC_OK
                                : set_error(LDPC_ERR_HIP, "layered decode: %s", hipGetErrorString(e));
@@ -583,6 +586,38 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
     LDPC_HIP_TRY(hipEventRecord(d->tm.ev_end.e, s));
     d->tm.have_last = true;
     return LDPC_OK;
+}
+
+int ldpc_decode_soft_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, uint8_t *out_dev, int64_t out_bytes,
+                            int32_t *iters_dev, float *soft_dev, int64_t soft_floats, int32_t soft_kind, void *stream)
+{
+    if (!d) return set_error(LDPC_ERR_ARG, "decoder is NULL");
+    if (!d->shards.empty())
+        return set_error(LDPC_ERR_STATE, "a multi-device handle decodes host buffers only (ldpc_decode_soft): device "
+                    "pointers belong to one device");
+    if (soft_kind != LDPC_SOFT_POSTERIOR && soft_kind != LDPC_SOFT_EXTRINSIC)
+        return set_error(LDPC_ERR_ARG, "unknown soft_kind %d", soft_kind);
+    if (d->cfg.algo == LDPC_ALGO_SP)
+        return set_error(LDPC_ERR_UNSUPPORTED, "soft output: LDPC_ALGO_SP works in the probability domain in fp32, where the "
+                    "posterior saturates to exactly +-1 on nearly every bit of a frame that converges and is 0/0 on frames "
+                    "that do not; the min-sum algorithms (MS, MS_FUSED, LAYERED, LAYERED_HOST) carry it");
+    if (d->tm.tap_iter)
+        return set_error(LDPC_ERR_STATE, "soft output while a debug tap is set (ldpc_decoder_set_tap(d, 0) clears it)");
+    if (frames < 0 || frames > d->cfg.max_batch)
+        return set_error(LDPC_ERR_ARG, "frames=%lld outside [0, max_batch=%d]", (long long)frames, d->cfg.max_batch);
+    if (frames > 0) {
+        if (!soft_dev) return set_error(LDPC_ERR_ARG, "soft is NULL");
+        if (reinterpret_cast<uintptr_t>(soft_dev) & 3) return set_error(LDPC_ERR_ARG, "soft is not 4-byte aligned");
+        const int64_t need = frames * (int64_t)d->N;
+        if (soft_floats < need) return set_error(LDPC_ERR_ARG, "soft_floats=%lld < %lld", (long long)soft_floats, (long long)need);
+        if (llr_dev && soft_dev < llr_dev + need && llr_dev < soft_dev + need)
+            return set_error(LDPC_ERR_ARG, "soft overlaps llr: the channel values are read while soft values are written");
+    }
+    /* the plain entry point does the rest; the request lives on the handle for exactly this call */
+    d->soft = ldpc::SoftReq{frames > 0 ? soft_dev : nullptr, soft_kind, nullptr};
+    const int rc = ldpc_decode_device(d, llr_dev, frames, out_dev, out_bytes, iters_dev, stream);
+    d->soft = ldpc::SoftReq{};
+    return rc;
 }
 
 }  /* extern "C" */

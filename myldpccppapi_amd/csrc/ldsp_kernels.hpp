@@ -683,7 +683,7 @@ inline hipError_t ldsp_run(LdspPlan *pl, const FusedRun &r, hipStream_t s, int32
         if ((e = pl->dump_r.alloc((size_t)r.frames * pl->E))) return e;
         pl->dump_frames = r.frames;
     }
-    LdspArgs a{r.llr_dev, r.out_dev, r.iters_dev, r.summary, r.tap_iter ? pl->dump_p.p : nullptr,
+    LdspArgs a{r.llr_dev, r.out_dev, r.iters_dev, r.summary, r.soft ? r.soft : (r.tap_iter ? pl->dump_p.p : nullptr),
                r.tap_iter ? pl->dump_r.p : nullptr, pl->recs.p, pl->zf.p, pl->hdr.p, pl->pack.p, pl->col_slot.p, pl->layer_e0.p,
                r.frames, r.out_dev ? r.out_bytes : 0, pl->N, pl->E, r.K, pl->z, pl->layers, pl->nb, pl->lds_cols,
                r.max_iter, rounds, r.early_term};
@@ -699,7 +699,8 @@ inline hipError_t ldsp_run(LdspPlan *pl, const FusedRun &r, hipStream_t s, int32
     else if (pl->wg_frames > 1) layered_ldsp_packed_kernel<0><<<grid, 64, pl->lds_bytes, s>>>(a, pl->wg_frames);
     else ldsp_kernel_for(pl->maxw)<<<grid, pl->block, pl->lds_bytes, s>>>(a);
     *launched = rounds;
-    return hipGetLastError();
+    if ((e = hipGetLastError())) return e;
+    return fused_soft_finish(r, pl->N, s);
 }
 
 #endif  /* LDPC_ENGINE_LDSP */

@@ -10,7 +10,7 @@ reference counts differing BYTES (Test.cpp:105-110); this prints byte errors too
     python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N>] [--algo sp|ms|layered]
                               [--payload zero|random] [--rate-match P,FLO,FHI,E[,K0]] [--erasure-llr X]
                               [--modulation bpsk|qpsk|qam16|qam64|qam256] [--no-interleave] [--transport-block A[,C]] [--crc-stop]
-                              [--msg-dtype f32|f16]
+                              [--msg-dtype f32|f16] [--soft-check]
                               [--snr=1.0,1.5,...]  (write --snr=-0.5,0 for a list that starts with a minus) [--frames 4096] [--iters 50]
 --rate-match: code bits [0, P) punctured, [FLO, FHI) filler bits (known zeros; multiples of 8, inside the information part),
 E bits per frame sent from circular-buffer position K0 (default 0): ldpc_rate_match_device between the encoder and the
@@ -34,6 +34,9 @@ fillers [Kp, K) are sent unless --rate-match names them.
 a frame in the first round in which its first Kp bits pass that CRC (include/ldpc_hip.h: crc_kind / crc_bits; the streaming
 kernels then run).  Every point of a --transport-block run prints crc_stops, the frames stopped in a round in which their
 syndrome was not clean (0 without --crc-stop), next to the block counts -- blocks_undetected is where a false pass would show.
+--soft-check (not with --algo sp): every batch is decoded a second time through ldpc_decode_soft_device; every point prints
+soft_checked, the posteriors of the K output bits that are finite and not zero, soft_sign_disagreements, those whose sign is
+not the output bit, and soft_bytes_differ against the plain call -- the last two must be 0, the run fails otherwise.
 The DVB-S2 / BG1 codes are PROFILE SURROGATES (codes.py): the numbers are not the standards'."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -64,7 +67,11 @@ ap.add_argument("--transport-block", default=None, metavar="A[,C]",
                 help="with --payload random: A payload bits per transport block, C code blocks (default: the rule of ldpc_tb_spec_init)")
 ap.add_argument("--msg-dtype", choices=("f32", "f16"), default="f32", help="message storage (f16: --algo ms only)")
 ap.add_argument("--crc-stop", action="store_true", help="with --transport-block: frames also stop once their CRC passes")
+ap.add_argument("--soft-check", action="store_true",
+                help="every batch is decoded once more with soft output (not --algo sp): prints the finite non-zero posteriors whose sign "
+                     "disagrees with the output bit -- must be 0")
 args = ap.parse_args()
+assert not (args.soft_check and args.algo == "sp"), "--soft-check: sum-product has no soft output (include/ldpc_hip.h)"
 assert not args.transport_block or args.payload == "random", "--transport-block needs --payload random"
 assert args.transport_block or not args.crc_stop, "--crc-stop needs --transport-block"
 assert args.modulation or not args.no_interleave, "--no-interleave needs --modulation"
@@ -195,6 +202,25 @@ def point_decoder(sd):
     dec = make_decoder(scale)
 
 
+soft = out2 = shifts = None
+if args.soft_check:
+    assert K % 8 == 0, "--soft-check compares whole bytes per frame: K % 8 must be 0"
+    soft = torch.empty((B, N), dtype=torch.float32, device="cuda")
+    out2 = torch.empty_like(out)
+    shifts = torch.arange(8, dtype=torch.int32, device="cuda")
+
+
+def soft_check():
+    """The batch in y once more through ldpc_decode_soft_device: (posteriors of the K output bits that are finite and not
+    zero, those among them whose sign is not the output bit, bytes that differ from the plain call's)."""
+    dec.decode_device(y.data_ptr(), B, out2.data_ptr(), out2.numel(), None, None, soft_ptr=soft.data_ptr(), soft_floats=soft.numel(),
+                      soft="posterior")
+    bits = ((out2.view(B, K // 8).to(torch.int32)[:, :, None] >> shifts) & 1).reshape(B, K)
+    p = soft[:, :K]
+    ok = torch.isfinite(p) & (p != 0)
+    return int(ok.sum()), int((ok & ((p < 0) != (bits != 0))).sum()), int((out2 != out).sum())
+
+
 if rm is not None:
     print("rate matching: punctured=%d fillers=[%d,%d) E=%d k0=%d erasure_llr=%g effective rate (K - fillers)/E = %.4f" % (
         P, FLO, FHI, E, K0, args.erasure_llr, rate))
@@ -222,6 +248,7 @@ for snr in points:
     tot = [0, 0, 0]
     blocks = [0, 0, 0, 0]
     it_sum, conv, stops, rounds, dec_ms = 0.0, 0, 0, 0, 0.0
+    soft_tot = [0, 0, 0]
     t0 = time.perf_counter()
     for b in range(args.batches):
         channel_batch(b * B, sd, args.seed)
@@ -238,6 +265,8 @@ for snr in points:
         dec_ms += st["ms_total"]
         if tb is not None:
             stops += dec.crc_stops()
+        if args.soft_check:
+            soft_tot = [t + x for t, x in zip(soft_tot, soft_check())]
     dt = time.perf_counter() - t0
     frames = B * args.batches
     res = {"snr_db": snr, "sd": round(sd, 4), "ber": tot[0] / (frames * K), "bit_errors": tot[0],
@@ -252,4 +281,7 @@ for snr in points:
         n = TBS * args.batches
         res.update({"blocks": n, "bler": blocks[1] / n, "blocks_crc_failed": blocks[0], "blocks_undetected": blocks[2],
                     "blocks_parity_only": blocks[3], "crc_stops": stops})
+    if args.soft_check:
+        res.update({"soft_checked": soft_tot[0], "soft_sign_disagreements": soft_tot[1], "soft_bytes_differ": soft_tot[2]})
     print(json.dumps(res), flush=True)
+    assert soft_tot[1] == 0 and soft_tot[2] == 0, "soft output disagrees with the decoded bytes"
