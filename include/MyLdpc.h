@@ -103,6 +103,12 @@ public:
      * path (every row of one weight) it fails in addDecodeType while a correction is set, as DecodeMSCL always
      * does (both reproduce reference kernels).  (0, 0) = off.  Before addDecodeType(). */
     void setMinSumCorrection(float scale, float offset) { msScale = scale; msOffset = offset; }
+    /* How the decoders addDecodeType makes from here on store their messages (include/ldpc_hip.h: enum ldpc_msg_dtype):
+     * LDPC_MSG_F32 (the default, the reference's arithmetic), LDPC_MSG_F16 or LDPC_MSG_F8 (one E4M3 byte per message).
+     * DecodeMS and DecodeCPU take all three and give the bytes of the C ABI decoder with that msg_dtype; with any other
+     * decode type a type other than LDPC_MSG_F32 makes addDecodeType fail as ldpc_decoder_create does
+     * (LDPC_ERR_UNSUPPORTED; an unknown value: LDPC_ERR_ARG).  Before addDecodeType(). */
+    void setMessageType(int msgDtype) { msgType = msgDtype; }
     /* encode() on the GPU `setDevice` names (ldpc_encode, include/ldpc_hip.h) instead of the host: same bytes.
      * forEncoder() then creates the device encoder and skips the host precompute, so it also serves the seed whose
      * parity part the host solves by dense elimination only (rate_3_4_b: any N, where the host path stops at
@@ -172,6 +178,7 @@ private:
     std::vector<int> devices;        /* setDevices(); empty: `device` alone */
     int hostInput = 0;               /* setHostInput() */
     float msScale = 0.0f, msOffset = 0.0f; /* setMinSumCorrection() */
+    int msgType = 0;                 /* setMessageType(): LDPC_MSG_F32 */
     int makeDecoder(const ldpc_decoder_config &cfg, ldpc_decoder **out);
     const signed char *hSeed;
     int seedRowLength;

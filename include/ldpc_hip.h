@@ -72,7 +72,21 @@ enum ldpc_algo {
                               fp32, one launch per layer                                    */
 };
 
-enum ldpc_msg_dtype { LDPC_MSG_F32 = 0, LDPC_MSG_F16 = 1 };
+/* How the streaming flooding min-sum decoder (LDPC_ALGO_MS) stores its messages; the arithmetic is fp32 in one
+ * operation order for all three.  F16 and F8 are this library's own definitions (the reference is fp32 only) and are
+ * LDPC_ERR_UNSUPPORTED with every other algorithm; the one-launch and record kernels are fp32 and are never selected
+ * for them (F8 with LDPC_TUNE_FUSED / LDPC_TUNE_LDSP forced on: LDPC_ERR_UNSUPPORTED).  An unknown value: LDPC_ERR_ARG.
+ *   LDPC_MSG_F16: channel values and variable->check messages are rounded to binary16 (nearest even) where they are
+ *     stored, a corrected check->variable magnitude (ms_scale / ms_offset) where it is produced.
+ *   LDPC_MSG_F8: one byte per message, OCP E4M3 ("e4m3fn": 1-4-3, bias 7, subnormals down to 2^-9, no infinities).
+ *     s8(x) for fp32 x: NaN stays NaN; anything else is clamped to [-448, 448] and then rounded to the nearest E4M3
+ *     value, ties to the even code, the sign of zero kept (so 464, 1000 and +inf give 448, 2^-10 gives 0, 1.5 * 2^-10
+ *     gives 2^-9, -1e-8 gives -0).  Loads widen exactly.  s8 is applied to the channel values where they are stored
+ *     (y8 = s8(y); round 1 reads them as Q), to the variable->check messages where they are stored, and to the
+ *     check->variable message where it is PRODUCED, in registers too: corrected, s8(fmaxf(m - ms_offset, 0) * ms_scale);
+ *     plain, every |q| is an E4M3 value already and only the start value 1000 is affected, which reads 448.  The
+ *     posterior -- hard decision and soft output alike -- is y8 + R_e1 + R_e2 + ... in fp32, ascending edge id. */
+enum ldpc_msg_dtype { LDPC_MSG_F32 = 0, LDPC_MSG_F16 = 1, LDPC_MSG_F8 = 2 };
 
 /* ldpc_decode() and the caller's input buffer (the reference copies it with a blocking
  * enqueueWriteBuffer, MyLdpc.cpp:796 / :988).

@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import DecoderConfig, DecodeStats, LdpcError  # noqa: F401
 
 ALGO_SP, ALGO_MS, ALGO_LAYERED, ALGO_MS_FUSED, ALGO_LAYERED_HOST = 0, 1, 2, 3, 4
-MSG_F32, MSG_F16 = 0, 1
+MSG_F32, MSG_F16, MSG_F8 = 0, 1, 2
 PACK_BYTES, PACK_BITS = 0, 1
 CODE_PACKED, CODE_BITS = 0, 1                              # enum ldpc_code_format
 CODE_FORMATS = {"packed": CODE_PACKED, "bits": CODE_BITS}
@@ -186,7 +186,7 @@ class Decoder:
         _lib.check(L.ldpc_decoder_config_init_sized(ctypes.byref(cfg), ctypes.sizeof(cfg)))
         cfg.K, cfg.max_batch = int(K), int(max_batch)
         cfg.algo = ALGOS[algo] if isinstance(algo, str) else int(algo)
-        cfg.msg_dtype = {"f32": MSG_F32, "f16": MSG_F16}.get(msg_dtype, msg_dtype)
+        cfg.msg_dtype = {"f32": MSG_F32, "f16": MSG_F16, "f8": MSG_F8}.get(msg_dtype, msg_dtype)
         cfg.max_iter, cfg.llr_scale = int(max_iter), float(llr_scale)
         cfg.early_term, cfg.device, cfg.layer_rows = int(bool(early_term)), int(device), int(layer_rows)
         cfg.pack_mode, cfg.frames_per_lane, cfg.poll_interval = int(pack_mode), int(frames_per_lane), int(poll_interval)

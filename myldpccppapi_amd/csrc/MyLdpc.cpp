@@ -444,6 +444,7 @@ int Coder::addDecodeType(enum decodeType deType)
     cfg.poll_interval = 4;
     cfg.pack_mode = LDPC_PACK_BYTES;
     cfg.layer_rows = z;
+    cfg.msg_dtype = msgType;                           /* setMessageType(): ldpc_decoder_create refuses what it does not carry */
     cfg.algo = (deType == DecodeSP) ? LDPC_ALGO_SP : (deType == DecodeMS) ? LDPC_ALGO_MS
                : (deType == DecodeMSCL) ? LDPC_ALGO_MS_FUSED : LDPC_ALGO_LAYERED;
     if (deType == DecodeTDMP) {
@@ -528,6 +529,7 @@ int Coder::decodeFrames(float *postCode, char *srcCode, int srcLength, enum deco
             cfg.layer_rows = z;                              /* circulant size: lets the record / one-launch kernels apply
                                                                 (with a correction: the record kernel or the streaming ones) */
             cfg.ms_scale = msScale; cfg.ms_offset = msOffset;
+            cfg.msg_dtype = msgType;
             if (int rc = applyCrcEarlyStop(cfg)) return rc;
             int rc = makeDecoder(cfg, &d);
             if (rc) return fail(rc, ldpc_last_error());

@@ -39,10 +39,10 @@ template <typename Fn> inline int dispatch_v(int V, Fn &&fn)
                   : V == 2 ? fn(std::integral_constant<int, 2>{}) : fn(std::integral_constant<int, 4>{});
 }
 
-/* the run-time message size (4: float, 2: fp16 storage) as a type: fn(T{}) */
+/* the run-time message size (4: float, 2: fp16 storage, 1: fp8 storage) as a type: fn(T{}) */
 template <typename Fn> inline void dispatch_msg(int64_t msg_size, Fn &&fn)
 {
-    if (msg_size == 2) fn(_Float16{}); else fn(float{});
+    if (msg_size == 1) fn(f8{}); else if (msg_size == 2) fn(_Float16{}); else fn(float{});
 }
 
 struct RowClass {
@@ -80,7 +80,7 @@ constexpr int kIdleFat = LDPC_IDLE_FAT;
  * creation-time measurements chose.  A handle that runs a layered or a one-launch kernel leaves all of it empty. */
 struct FloodPlan {
     DevBuf<uint8_t> chan, Q, R;         /* message arrays: msg_size bytes per element */
-    int msg_size = 4;                   /* 4 = fp32, 2 = fp16 (LDPC_MSG_F16) */
+    int msg_size = 4;                   /* 4 = fp32, 2 = fp16 (LDPC_MSG_F16), 1 = fp8 E4M3 (LDPC_MSG_F8) */
     /* Q in writer order (CheckArgs::qpos): slot of every edge, and col_edge with slots in place of edge ids (init_kernel) */
     DevBuf<int32_t> qpos, col_qedge;
     std::vector<int32_t> h_qpos;

@@ -16,7 +16,7 @@
  *   tail_i     : (asynchronous callers) hand the last running frames over to the overflow tiles
  * then pack.
  *
- * The message kernels themselves are instantiated per arithmetic in flood_sp / flood_ms / flood_ms16 / flood_msc*
+ * The message kernels themselves are instantiated per arithmetic in flood_sp / flood_ms* / flood_msc*
  * (flood_tables.hpp); the bookkeeping kernels of a round (flood_round.hpp) and of the hand-over (flood_handover.hpp)
  * are instantiated here.  Declared in
  * engines.hpp like the other engines; unlike them it works on the handle (decoder.hpp), because it needs the stream,
@@ -638,15 +638,17 @@ int plan_launches(ldpc_decoder *d)
 int setup_flooding(ldpc_decoder *d, const ldpc_graph *g, size_t TF)
 {
     const ldpc_decoder_config *cfg = &d->cfg;
-    d->flood.msg_size = cfg->msg_dtype == LDPC_MSG_F16 ? 2 : 4;
+    d->flood.msg_size = cfg->msg_dtype == LDPC_MSG_F8 ? 1 : cfg->msg_dtype == LDPC_MSG_F16 ? 2 : 4;
     LDPC_HIP_TRY(d->flood.chan.alloc(TF * d->N * d->flood.msg_size));
     LDPC_HIP_TRY(d->flood.Q.alloc(TF * (size_t)d->E * d->flood.msg_size));
     LDPC_HIP_TRY(d->flood.R.alloc(TF * (size_t)d->E * d->flood.msg_size));
     int rc = build_classes(d, g);
     if (rc) return rc;
-    /* the kernels live in flood_sp.hip / flood_ms.hip / flood_ms16.hip / flood_msc*.hip (flood_tables.hpp) */
+    /* the kernels live in flood_sp.hip / flood_ms*.hip / flood_msc*.hip (flood_tables.hpp) */
     ldpc::FloodFns *fns = &d->flood.fns;
     if (cfg->algo == LDPC_ALGO_SP) ldpc::fill_flood_sp(d->V, fns);
+    else if (d->ms_corr && cfg->msg_dtype == LDPC_MSG_F8) ldpc::fill_flood_msc8(d->V, fns);
+    else if (cfg->msg_dtype == LDPC_MSG_F8) ldpc::fill_flood_ms8(d->V, fns);
     else if (d->ms_corr && cfg->msg_dtype == LDPC_MSG_F16) ldpc::fill_flood_msc16(d->V, fns);
     else if (d->ms_corr) ldpc::fill_flood_msc(d->V, fns);
     else if (cfg->msg_dtype == LDPC_MSG_F16) ldpc::fill_flood_ms16(d->V, fns);
@@ -680,9 +682,13 @@ template <int V> int calibrate_link(ldpc_decoder *d)
     LDPC_HIP_TRY(ev[1].create());
     float best[3] = {1e30f, 1e30f, 1e30f};
     const int candidates = d->flood.fns.link_half[rc.degree] ? 3 : 2;
+    /* fp8 messages: the narrow form moves one byte per lane (64 B per wave-instruction) and is no candidate; wide
+     * and, at V = 4, half are */
+    const bool skip_narrow = d->flood.msg_size == 1;
     hipError_t err = hipSuccess;
     for (int rep = 0; rep < 4 && err == hipSuccess; ++rep) {
         for (int nar = 0; nar < candidates && err == hipSuccess; ++nar) {
+            if (nar == 1 && skip_narrow) continue;
             CheckArgs a = check_args(d, TailRef{nullptr, 0, 0}, d->flood.link_rpw, false, rc.e0.p, rc.count, rc.degree);
             LinkArgs lk{rc.link_col.p, rc.link_pos.p, d->flood.chan.p, d->flood.Q.p, d->hard.p, d->N, 1, 0, nullptr, nullptr, 0, 0,
                         rc.n_big, rc.small_rows};

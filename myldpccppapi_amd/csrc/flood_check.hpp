@@ -38,7 +38,7 @@ __device__ __forceinline__ void check_sp(const float (&x)[D][V], float (&out)[D]
 /* Min-sum, decodeCL.c:132-146: sign = XOR of (x_j < 0) over j != k, magnitude =
  * fmin chain over |x_j| starting at 1000.  min is exact and order-free, so the
  * two-smallest form gives the same floats; NaNs are skipped as fmin skips them.
- * CORR: the candidates go through ms_corr<T> first. */
+ * CORR: the candidates go through ms_corr<T> first; plain: through MsgStart<T> (fp8: the start value reads 448). */
 template <int D, int V, bool CORR = false, typename T = float>
 __device__ __forceinline__ void check_ms(const float (&x)[D][V], float (&out)[D][V], MsCorr c = MsCorr{1.0f, 0.0f})
 {
@@ -55,6 +55,7 @@ __device__ __forceinline__ void check_ms(const float (&x)[D][V], float (&out)[D]
             else if (a < m2) { m2 = a; }
         }
         if (CORR) { m1 = ms_corr<T>(m1, c); m2 = ms_corr<T>(m2, c); }
+        else { m1 = MsgStart<T>::of(m1); m2 = MsgStart<T>::of(m2); }
 #pragma unroll
         for (int k = 0; k < D; ++k) {
             const float b = (k == idx) ? m2 : m1;
@@ -69,7 +70,7 @@ template <int ALGO, int D, int W, typename T>
 __device__ __forceinline__ void check_node(const float (&x)[D][W], float (&out)[D][W], const MsCorr &c)
 {
     if (ALGO == kAlgoSP) check_sp<D, W>(x, out);
-    else if (ALGO == kAlgoMS) check_ms<D, W>(x, out);
+    else if (ALGO == kAlgoMS) check_ms<D, W, false, T>(x, out);
     else check_ms<D, W, true, T>(x, out, c);
 }
 
@@ -156,6 +157,9 @@ __device__ __forceinline__ void check_row_generic(const T *Qu, unsigned lane_off
         if (ALGO == kAlgoMSC) {
 #pragma unroll
             for (int v = 0; v < V; ++v) { m1[v] = ms_corr<T>(m1[v], c); m2[v] = ms_corr<T>(m2[v], c); }
+        } else {
+#pragma unroll
+            for (int v = 0; v < V; ++v) { m1[v] = MsgStart<T>::of(m1[v]); m2[v] = MsgStart<T>::of(m2[v]); }
         }
         for (int k = 0; k < D; ++k) {
             float xk[V], o[V];
@@ -224,7 +228,7 @@ template <int ALGO, int V, typename T, int DLO, int W> struct CheckDispatch<ALGO
 /* degrees DLO..DHI; W values per lane (V / W consecutive waves cover a row's segment).  W = 1: narrow waves,
  * the form of all fp32 kernels (256 B per wave-instruction).  fp16 messages at V = 4 use W = 2: with one
  * 2-byte value per lane a wave-instruction moves 128 B and the degree-30 rows of the rate-9/10 code ran at
- * 5.0 TB/s against 6.0 for the fp32 narrow form. */
+ * 5.0 TB/s against 6.0 for the fp32 narrow form.  fp8 messages use W = V: a dword per lane at V = 4. */
 template <int ALGO, int V, typename T, int DLO, int DHI, int W = 1>
 __global__ __launch_bounds__(kBlock) void check_group_kernel(const CheckArgs a, const GroupClass *__restrict__ cls, int n_classes)
 {

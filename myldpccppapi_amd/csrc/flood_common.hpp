@@ -107,6 +107,80 @@ template <> __device__ __forceinline__ void vstore<4>(hf *p, const float (&s)[4]
     st_stream(reinterpret_cast<vh4 *>(p), t);
 }
 
+/* fp8 message storage (msg_dtype = LDPC_MSG_F8): one OCP E4M3 byte per message (1-4-3, bias 7, subnormals down to
+ * 2^-9, no infinities), arithmetic in fp32.  Loads widen exactly.  Stores apply s8 (include/ldpc_hip.h): NaN stays
+ * NaN, everything else is clamped to [-448, 448] and rounded to nearest, ties to even, the sign of zero kept.  The
+ * clamp is ours, in fp32, in front of the conversion instruction: what v_cvt_pk_fp8_f32 does out of range depends
+ * on the wave's mode bits and is not relied on.  fminf / fmaxf drop a NaN, hence the select behind the clamp.
+ * A struct, so that the overloads below are told apart from plain bytes; (f8)0 is the byte 0x00 = +0, which is what the
+ * hand-over kernels (flood_handover.hpp) fill unused slots with. */
+struct f8 {
+    uint8_t bits;
+    f8() = default;
+    __host__ __device__ constexpr explicit f8(int) : bits(0) {}
+};
+static_assert(sizeof(f8) == 1, "one byte per message");
+
+constexpr float kF8Max = 448.0f;
+__device__ __forceinline__ float f8_clamp(float x)
+{
+    const float c = fminf(fmaxf(x, -kF8Max), kF8Max);
+    return x != x ? x : c;
+}
+/* two values as E4M3 into the low (hi = false) or high half of a dword, the other half kept from `old` */
+__device__ __forceinline__ int f8_pack2(float a, float b, int old, bool hi)
+{
+    return hi ? __builtin_amdgcn_cvt_pk_fp8_f32(f8_clamp(a), f8_clamp(b), old, true)
+              : __builtin_amdgcn_cvt_pk_fp8_f32(f8_clamp(a), f8_clamp(b), old, false);
+}
+/* s8 as a float: the value a message has once it is stored */
+__device__ __forceinline__ float f8_round(float x)
+{
+    return __builtin_amdgcn_cvt_f32_fp8(f8_pack2(x, x, 0, false), 0);
+}
+
+template <int V> __device__ __forceinline__ void vload(float (&d)[V], const f8 *p);
+template <> __device__ __forceinline__ void vload<1>(float (&d)[1], const f8 *p)
+{
+    d[0] = __builtin_amdgcn_cvt_f32_fp8((int)ld_stream(reinterpret_cast<const uint8_t *>(p)), 0);
+}
+template <> __device__ __forceinline__ void vload<2>(float (&d)[2], const f8 *p)
+{
+    const int w = (int)ld_stream(reinterpret_cast<const uint16_t *>(p));
+    d[0] = __builtin_amdgcn_cvt_f32_fp8(w, 0); d[1] = __builtin_amdgcn_cvt_f32_fp8(w, 1);
+}
+template <> __device__ __forceinline__ void vload<4>(float (&d)[4], const f8 *p)
+{
+    const int w = (int)ld_stream(reinterpret_cast<const uint32_t *>(p));
+    d[0] = __builtin_amdgcn_cvt_f32_fp8(w, 0); d[1] = __builtin_amdgcn_cvt_f32_fp8(w, 1);
+    d[2] = __builtin_amdgcn_cvt_f32_fp8(w, 2); d[3] = __builtin_amdgcn_cvt_f32_fp8(w, 3);
+}
+template <int V> __device__ __forceinline__ void vstore(f8 *p, const float (&s)[V]);
+template <> __device__ __forceinline__ void vstore<1>(f8 *p, const float (&s)[1])
+{
+    st_stream(reinterpret_cast<uint8_t *>(p), (uint8_t)f8_pack2(s[0], s[0], 0, false));
+}
+template <> __device__ __forceinline__ void vstore<2>(f8 *p, const float (&s)[2])
+{
+    st_stream(reinterpret_cast<uint16_t *>(p), (uint16_t)f8_pack2(s[0], s[1], 0, false));
+}
+template <> __device__ __forceinline__ void vstore<4>(f8 *p, const float (&s)[4])
+{
+    const int lo = f8_pack2(s[0], s[1], 0, false);
+    st_stream(reinterpret_cast<uint32_t *>(p), (uint32_t)f8_pack2(s[2], s[3], lo, true));
+}
+
+/* a check->variable magnitude as its storage type holds it, applied where the message is produced: the column-fused
+ * kernels keep some R in registers without ever storing them */
+template <typename T> struct MsgRound;
+template <> struct MsgRound<float> { static __device__ __forceinline__ float of(float r) { return r; } };
+template <> struct MsgRound<hf> { static __device__ __forceinline__ float of(float r) { return (float)(hf)r; } };
+template <> struct MsgRound<f8> { static __device__ __forceinline__ float of(float r) { return f8_round(r); } };
+/* plain min-sum: a row's magnitude candidates are |q| of stored messages -- values of T already -- or the start value
+ * 1000, which no E4M3 value reaches: it reads 448 */
+template <typename T> struct MsgStart { static __device__ __forceinline__ float of(float m) { return m; } };
+template <> struct MsgStart<f8> { static __device__ __forceinline__ float of(float m) { return fminf(m, kF8Max); } };
+
 __device__ __forceinline__ int wave_id_in_block()
 {
     return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -145,7 +219,7 @@ template <int V> __device__ __forceinline__ int tile_select(const TailRef &t, co
 }
 
 struct CheckArgs {
-    const void *__restrict__ Q;          /* [T][E][F] variable->check (float or fp16) */
+    const void *__restrict__ Q;          /* [T][E][F] variable->check (float, fp16 or fp8) */
     void *__restrict__ R;                /* [T][E][F] check->variable          */
     const int32_t *__restrict__ cls_e0;  /* [n_rows] first edge id of each row of this degree class */
     const uint64_t *__restrict__ done;   /* [T][V] frozen frames                */
@@ -199,22 +273,22 @@ __device__ __forceinline__ GridPos grid_pos(int tiles_first)
 
 /* Normalized / offset min-sum (LDPC_ALGO_MS / LAYERED with ms_scale or ms_offset set): each of a row's
  * two magnitude candidates m becomes fmaxf(m - beta, 0) * alpha, fp32, once per row and frame, before the
- * per-edge selection and sign.  With fp16 messages the result is rounded to fp16 right here, where R is
- * produced: alpha * m is generally no binary16 value (+-min always was), and the column-fused kernels keep
- * some R in registers without ever storing them. */
+ * per-edge selection and sign.  With fp16 or fp8 messages the result is rounded to the storage type right here,
+ * where R is produced (MsgRound): alpha * m is generally no binary16 / E4M3 value (+-min always was), and the
+ * column-fused kernels keep some R in registers without ever storing them. */
 struct MsCorr {
     float scale, offset;
 };
 template <typename T> __device__ __forceinline__ float ms_corr(float m, const MsCorr &c)
 {
     const float r = fmaxf(m - c.offset, 0.0f) * c.scale;
-    return sizeof(T) == 2 ? (float)(hf)r : r;
+    return MsgRound<T>::of(r);
 }
 
 __device__ __forceinline__ MsCorr ms_corr_of(const CheckArgs &a) { return MsCorr{a.ms_scale, a.ms_offset}; }
 
 struct VarArgs {
-    const void *__restrict__ R;           /* [T][E][F] (float or fp16) */
+    const void *__restrict__ R;           /* [T][E][F] (float, fp16 or fp8) */
     void *__restrict__ Q;                 /* [T][E][F] */
     const void *__restrict__ chan;        /* [T][N][F] SP: exp(scale*y); MS: y */
     uint64_t *hard;                       /* [T][N][V] read-modify-write */

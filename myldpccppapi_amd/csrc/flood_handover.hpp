@@ -63,8 +63,9 @@ __global__ __launch_bounds__(kBlock) void compact_gather_kernel(const T *__restr
 constexpr int kGatherChunk = 4096;      /* elements staged at a time (16 KB of fp32) */
 /* rows a block walks, the next one's loads in flight: 2-byte rows (8 KB for 4096 frames) left the memory pipe idle with one row
  * per block (3.6 -> 4.9 TB/s with eight); 4-byte rows have enough in flight with one row per block and LOSE with eight (650 -> 880 us
- * for the headline code's 3.7 GB: the block's serial stage / pick phases then stand in the way) */
-template <typename T> constexpr int gather_rows_per_block() { return sizeof(T) == 2 ? 8 : 1; }
+ * for the headline code's 3.7 GB: the block's serial stage / pick phases then stand in the way);
+ * 1-byte rows (4 KB for 4096 frames) walk eight rows like the 2-byte ones (not measured on their own) */
+template <typename T> constexpr int gather_rows_per_block() { return sizeof(T) < 4 ? 8 : 1; }
 template <int V, typename T>
 __global__ __launch_bounds__(kBlock) void compact_gather_rows_kernel(const T *__restrict__ src, T *__restrict__ dst,
                                                                      const int32_t *__restrict__ map, int32_t count,
@@ -74,7 +75,8 @@ __global__ __launch_bounds__(kBlock) void compact_gather_rows_kernel(const T *__
 {
     constexpr int F = 64 * V;
     constexpr int TPC = kGatherChunk / F;               /* parent tiles per chunk */
-    constexpr int VEC = 16 / (int)sizeof(T);            /* 16 bytes per lane (a tile's row segment is F * sizeof(T) >= 128 bytes, 16-byte aligned) */
+    constexpr int VEC = 16 / (int)sizeof(T);            /* 16 bytes per lane (a tile's row segment is F * sizeof(T) >= 64 bytes -- fp8 at V = 1 --, 16-byte aligned) */
+    static_assert(F % VEC == 0 && kGatherChunk % (kBlock * VEC) == 0, "whole 16-byte vectors per segment and per pass");
     constexpr int NV = kGatherChunk / (kBlock * VEC);   /* 16-byte vectors a thread stages per chunk */
     __shared__ __attribute__((aligned(16))) T stage[kGatherChunk];
     const int cslots = ((count + cf - 1) / cf) * cf;    /* child slots in use (whole child tiles) */

@@ -1,7 +1,7 @@
 /*
  * flood_tables_impl.hpp -- instantiates every streaming flooding kernel of ONE arithmetic
  * (algorithm + message type) for V = 1, 2, 4 and hands out the function pointers.  Included by
- * flood_sp.hip / flood_ms.hip / flood_ms16.hip only.
+ * flood_sp.hip / flood_ms*.hip / flood_msc*.hip only.
  */
 #pragma once
 
@@ -65,8 +65,9 @@ template <int ALGO, int V, typename T> void fill_v(FloodFns *f)
     constexpr int DM = kMaxUnrolledDegree;
     FloodTable<ALGO, V, T, DM>::fill(f->check, f->check_wide, f->var);
     LinkTable<ALGO, V, T, DM>::fill(f->link, f->link_narrow, f->link_deep, f->link_half);
-    /* fp16 messages in tiles of 256 frames: two values per lane (flood_check.hpp: check_group_kernel) */
-    constexpr int GW = (sizeof(T) == 2 && V == 4) ? 2 : 1;
+    /* fp16 messages in tiles of 256 frames: two values per lane; fp8 messages: V values, a dword at V = 4
+     * (flood_check.hpp: check_group_kernel) */
+    constexpr int GW = sizeof(T) == 1 ? V : (sizeof(T) == 2 && V == 4) ? 2 : 1;
     f->check_group_width = GW;
     f->check_group[0] = check_group_kernel<ALGO, V, T, 1, 8, GW>;
     f->check_group[1] = check_group_kernel<ALGO, V, T, 9, 16, GW>;

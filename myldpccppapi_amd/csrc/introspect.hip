@@ -149,8 +149,11 @@ int ldpc_decoder_kernel_times(ldpc_decoder *d, ldpc_kernel_time *out, int32_t ca
     static const char *algo_name_f16[] = {"sp16", "ms16", "layered16", "ms_fused16", "layered_host16"};
     static const char *algo_name_corr_f32[] = {"sp", "msc", "layered", "ms_fused", "layered_host"};  /* kAlgoMSC */
     static const char *algo_name_corr_f16[] = {"sp16", "msc16", "layered16", "ms_fused16", "layered_host16"};
-    const char **algo_name = d->ms_corr ? (d->flood.msg_size == 2 ? algo_name_corr_f16 : algo_name_corr_f32)
-                                        : (d->flood.msg_size == 2 ? algo_name_f16 : algo_name_f32);
+    static const char *algo_name_f8[] = {"sp8", "ms8", "layered8", "ms_fused8", "layered_host8"};
+    static const char *algo_name_corr_f8[] = {"sp8", "msc8", "layered8", "ms_fused8", "layered_host8"};
+    const int msz = d->flood.msg_size;
+    const char **algo_name = d->ms_corr ? (msz == 1 ? algo_name_corr_f8 : msz == 2 ? algo_name_corr_f16 : algo_name_corr_f32)
+                                        : (msz == 1 ? algo_name_f8 : msz == 2 ? algo_name_f16 : algo_name_f32);
     for (size_t i = 0; i < d->tm.spans_used; ++i) {
         const ldpc::TimedSpan &sp = d->tm.spans[i];
         float ms = 0;
@@ -230,6 +233,22 @@ int ldpc_decoder_set_tap(ldpc_decoder *d, int32_t iter)
     return LDPC_OK;
 }
 
+/* an OCP E4M3 byte (1-4-3, bias 7, no infinities, S.1111.111 = NaN) as the float it stands for: exact */
+static float e4m3_widen(uint8_t b)
+{
+    const uint32_t sign = (uint32_t)(b & 0x80) << 24, e = (b >> 3) & 15, m = b & 7;
+    uint32_t bits;
+    if (e == 15 && m == 7) bits = 0x7fc00000u;
+    else if (e == 0) {
+        const float sub = (float)m * 0.001953125f;              /* m * 2^-9 */
+        memcpy(&bits, &sub, 4);
+    } else bits = ((e + 120) << 23) | (m << 20);                /* exponent e - 7 + 127 */
+    bits |= sign;
+    float out;
+    memcpy(&out, &bits, 4);
+    return out;
+}
+
 int ldpc_decoder_dump(ldpc_decoder *d, int32_t which, float *host_out, int64_t count)
 {
     if (!d || !host_out) return set_error(LDPC_ERR_ARG, "decoder/host_out is NULL");
@@ -293,10 +312,12 @@ int ldpc_decoder_dump(ldpc_decoder *d, int32_t which, float *host_out, int64_t c
                     const size_t ir = (which == 1 && !d->flood.h_qpos.empty()) ? (size_t)d->flood.h_qpos[(size_t)i] : (size_t)i;   /* Q: slot of edge i */
                     if (esz == 4) {
                         memcpy(&host_out[f * per + i], &tile[(ir * F + fi) * 4], 4);
-                    } else {
+                    } else if (esz == 2) {
                         _Float16 h;
                         memcpy(&h, &tile[(ir * F + fi) * 2], 2);
                         host_out[f * per + i] = (float)h;
+                    } else {
+                        host_out[f * per + i] = e4m3_widen(tile[ir * F + fi]);
                     }
                 }
             }

@@ -43,6 +43,8 @@ int pick_frames_per_lane(const ldpc_decoder_config &cfg, int32_t max_row_deg, in
      * holds a whole row (P and R) per lane. */
     int deg = cfg.algo == LDPC_ALGO_LAYERED ? max_row_deg : max_col_deg;
     if (cfg.algo == LDPC_ALGO_MS) deg = (deg + 1) / 2;   /* min-sum variable nodes need half the registers */
+    /* fp8 messages: 4 values are one dword per lane, the least a lane should move -- from one full tile on */
+    if (cfg.msg_dtype == LDPC_MSG_F8 && cfg.max_batch >= 256 && deg <= 8) return 4;
     if (cfg.max_batch >= 1024 && deg <= 8) return 4;
     if (cfg.max_batch >= 256 && deg <= ldpc::kMaxUnrolledDegree) return 2;
     return 1;
@@ -234,12 +236,21 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     if (cfg->frames_per_lane != 0 && cfg->frames_per_lane != 1 && cfg->frames_per_lane != 2 &&
         cfg->frames_per_lane != 4)
         return set_error(LDPC_ERR_ARG, "frames_per_lane must be 0, 1, 2 or 4");
-    if (cfg->msg_dtype != LDPC_MSG_F32 && cfg->msg_dtype != LDPC_MSG_F16)
+    if (cfg->msg_dtype != LDPC_MSG_F32 && cfg->msg_dtype != LDPC_MSG_F16 && cfg->msg_dtype != LDPC_MSG_F8)
         return set_error(LDPC_ERR_ARG, "unknown msg_dtype %d", cfg->msg_dtype);
+    if (cfg->msg_dtype == LDPC_MSG_F8 && cfg->algo != LDPC_ALGO_MS)
+        return set_error(LDPC_ERR_UNSUPPORTED, "fp8 messages are built for flooding min-sum only "
+                    "(the probability-domain SP needs fp32 range; the layered and reference-reproducing decoders are fp32)");
     if (cfg->msg_dtype == LDPC_MSG_F16 && cfg->algo != LDPC_ALGO_MS)
         return set_error(LDPC_ERR_UNSUPPORTED, "fp16 messages are built for flooding min-sum only "
                     "(the probability-domain SP needs fp32 range; layered: not yet)");
     if (!ldpc::tune_valid(*cfg)) return set_error(LDPC_ERR_ARG, "tuning / streams config fields out of range");
+    if (cfg->msg_dtype == LDPC_MSG_F8) {
+        const ldpc::Tune t = ldpc::tune_from_config(*cfg);
+        if (ldpc::tune_forced_on(t.fused) || ldpc::tune_forced_on(t.ldsp))
+            return set_error(LDPC_ERR_UNSUPPORTED, "fp8 messages: the LDS-resident one-launch kernels and the record kernels (LDPC_TUNE_FUSED / "
+                        "LDPC_TUNE_LDSP forced on) are fp32; the streaming kernels carry the fp8 rule");
+    }
     /* CRC-aided early termination: the streaming kernels carry the rule (crc_term_kernel), nothing else does */
     const bool crc_term = cfg->crc_kind != 0;
     {
@@ -271,8 +282,13 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     d->h_cols = g->cols;
     const ldpc::Tune tune = d->tune = ldpc::tune_from_config(*cfg);
     d->flood.syn_xcd = ldpc::tune_pick(tune.syn_xcd, true);
-    d->flood.check_wide = ldpc::tune_pick(tune.check_wide, false);
-    d->flood.link_form = ldpc::tune_pick(tune.link_half, false) ? 2 : (ldpc::tune_pick(tune.link_narrow, true) ? 1 : 0);
+    /* fp8 messages: the forms that move a dword per lane at V = 4 are the automatic choice -- check kernels in wide waves
+     * where every row has one (degree <= kMaxUnrolledDegree; above, the bucket launches, V values per lane), the
+     * column-fused kernel wide unless the creation-time measurement prefers the half form.  The narrow forms move one
+     * byte per lane; the tuning fields still select them, results never depend on the choice. */
+    const bool f8 = cfg->msg_dtype == LDPC_MSG_F8;
+    d->flood.check_wide = ldpc::tune_pick(tune.check_wide, f8 && g->max_row_deg <= ldpc::kMaxUnrolledDegree);
+    d->flood.link_form = ldpc::tune_pick(tune.link_half, false) ? 2 : (ldpc::tune_pick(tune.link_narrow, !f8 || ldpc::tune_forced_on(tune.link_deep)) ? 1 : 0);   /* deep is a narrow form */
     d->flood.link_deep = ldpc::tune_pick(tune.link_deep, false);
     if (tune.link_rows) d->flood.link_rpw = tune.link_rows < 0 ? 0 : tune.link_rows;
     LDPC_HIP_TRY(hipDeviceGetAttribute(&d->flood.cus, hipDeviceAttributeMultiprocessorCount, cfg->device));

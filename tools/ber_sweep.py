@@ -10,7 +10,7 @@ reference counts differing BYTES (Test.cpp:105-110); this prints byte errors too
     python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N>] [--algo sp|ms|layered]
                               [--payload zero|random] [--rate-match P,FLO,FHI,E[,K0]] [--erasure-llr X]
                               [--modulation bpsk|qpsk|qam16|qam64|qam256] [--no-interleave] [--transport-block A[,C]] [--crc-stop]
-                              [--msg-dtype f32|f16] [--soft-check]
+                              [--msg-dtype f32|f16|f8] [--soft-check]
                               [--snr=1.0,1.5,...]  (write --snr=-0.5,0 for a list that starts with a minus) [--frames 4096] [--iters 50]
 --rate-match: code bits [0, P) punctured, [FLO, FHI) filler bits (known zeros; multiples of 8, inside the information part),
 E bits per frame sent from circular-buffer position K0 (default 0): ldpc_rate_match_device between the encoder and the
@@ -65,7 +65,7 @@ ap.add_argument("--modulation", choices=("bpsk", "qpsk", "qam16", "qam64", "qam2
 ap.add_argument("--no-interleave", action="store_true", help="with --modulation: no bit interleaver")
 ap.add_argument("--transport-block", default=None, metavar="A[,C]",
                 help="with --payload random: A payload bits per transport block, C code blocks (default: the rule of ldpc_tb_spec_init)")
-ap.add_argument("--msg-dtype", choices=("f32", "f16"), default="f32", help="message storage (f16: --algo ms only)")
+ap.add_argument("--msg-dtype", choices=("f32", "f16", "f8"), default="f32", help="message storage (f16, f8: --algo ms only)")
 ap.add_argument("--crc-stop", action="store_true", help="with --transport-block: frames also stop once their CRC passes")
 ap.add_argument("--soft-check", action="store_true",
                 help="every batch is decoded once more with soft output (not --algo sp): prints the finite non-zero posteriors whose sign "
