@@ -64,17 +64,48 @@ enum ldpc_algo {
                               decodeOnceMS (DecodeMSCL, decodeCL.c:432-567): short
                               quasi-cyclic codes only, whole decode in LDS; the reference
                               hard-codes max_iter = 120 there                            */
-    LDPC_ALGO_LAYERED_HOST = 4 /* layered min-sum as the reference's HOST drives it (DecodeTDMP,
+    LDPC_ALGO_LAYERED_HOST = 4,/* layered min-sum as the reference's HOST drives it (DecodeTDMP,
                               MyLdpc.cpp:889-976 over decodeCL.c:203-300): check node of the MS
                               kernel chain, three-way hard decision once per iteration.  The
                               reference mis-sizes its layers unless every row of H has the same
                               weight (MyLdpc.cpp:907,958): any other H is LDPC_ERR_UNSUPPORTED.
                               fp32, one launch per layer                                    */
+    LDPC_ALGO_BP = 5       /* flooding sum-product in the LOG domain (box-plus check node): this library's own
+                              definition, below; streaming kernels, fp32 or LDPC_MSG_F16 messages              */
 };
+
+/* LDPC_ALGO_BP, bit for bit.  The reference's sum-product (LDPC_ALGO_SP) works on probabilities in fp32 and saturates at
+ * practical SNRs; this is the same algorithm on log-likelihood ratios, which does not, with a one-line stand-in for the
+ * exact correction term.  It is min-sum's variable node with another check node.  Every operation is fp32, one at a
+ * time, no contraction.
+ *   Channel:      chan[n] = llr_scale * y[n], one multiply (rounded to binary16 with LDPC_MSG_F16).  It is the y_n of the
+ *                 posterior and of the soft-output rule.  exp(llr_scale * y) is SP's likelihood ratio, so llr_scale * y is
+ *                 the LLR: for BPSK +-1 in noise of standard deviation sd, llr_scale = 2 / sd^2.  Padding frames read
+ *                 y = 1.  llr_scale NaN, inf or <= 0: LDPC_ERR_ARG.
+ *   Row inputs:   x_0 .. x_{D-1}, the variable->check messages of the row in ascending edge id, are read as
+ *                     a_j = fminf(|x_j|, 1000.0f),  s_j = (x_j < 0),  t_j = s_j ? -a_j : a_j
+ *                 so NaN reads +1000 (fminf drops it, its sign is +), -0 reads +0 and +-inf read +-1000 (min-sum's start
+ *                 value).
+ *   Correction:   c(x) = fmaxf(0.6931472f - 0.25f * x, 0.0f)       (the float nearest ln 2, 0x3F317218)
+ *   Box-plus:     m = fminf(|u|, |v|),  S = |u| + |v|,  D = fabsf(|u| - |v|),
+ *                 g = fmaxf((m + c(S)) - c(D), 0.0f),  u [+] v = ((u < 0) != (v < 0)) ? -g : g
+ *                 It is bitwise commutative and |u [+] v| <= min(|u|, |v|); it is NOT associative, so the association is
+ *                 part of the definition:
+ *   Row, D >= 3:  forward  f_0 = t_0,          f_j = f_{j-1} [+] t_j   for j = 1 .. D-2
+ *                 backward b_{D-1} = t_{D-1},  b_j = t_j [+] b_{j+1}   for j = D-2 .. 1
+ *                 out_0 = b_1,  out_{D-1} = f_{D-2},  out_k = f_{k-1} [+] b_{k+1} otherwise.
+ *   Short rows:   D = 2: out_0 = t_1, out_1 = t_0.  D = 1: out_0 = +1000.0f.
+ *   Rounding:     R_k = out_k, with LDPC_MSG_F16 rounded to binary16 where it is PRODUCED (in registers too).
+ *   Everything else is LDPC_ALGO_MS's: the posterior chan + R_e1 + R_e2 + ... in ascending edge id, bit = !(P > 0),
+ *   Q = P - R rounded where stored, freezing, iters, the CRC rule, both soft kinds.  With c == 0 the definition is
+ *   flooding min-sum.
+ * It always runs the streaming flooding engine: layer_rows is accepted and ignored for the choice, the one-launch and
+ * record kernels are never selected (LDPC_TUNE_ON(FUSED) or LDPC_TUNE_ON(LDSP): LDPC_ERR_UNSUPPORTED), as are
+ * LDPC_MSG_F8 and a non-zero ms_scale / ms_offset (there is no minimum to correct). */
 
 /* How the streaming flooding min-sum decoder (LDPC_ALGO_MS) stores its messages; the arithmetic is fp32 in one
  * operation order for all three.  F16 and F8 are this library's own definitions (the reference is fp32 only) and are
- * LDPC_ERR_UNSUPPORTED with every other algorithm; the one-launch and record kernels are fp32 and are never selected
+ * LDPC_ERR_UNSUPPORTED with every other algorithm -- except that LDPC_ALGO_BP takes F16 (not F8); the one-launch and record kernels are fp32 and are never selected
  * for them (F8 with LDPC_TUNE_FUSED / LDPC_TUNE_LDSP forced on: LDPC_ERR_UNSUPPORTED).  An unknown value: LDPC_ERR_ARG.
  *   LDPC_MSG_F16: channel values and variable->check messages are rounded to binary16 (nearest even) where they are
  *     stored, a corrected check->variable magnitude (ms_scale / ms_offset) where it is produced.
@@ -118,7 +149,8 @@ typedef struct ldpc_decoder_config {
     int32_t algo;           /* enum ldpc_algo                                              */
     int32_t msg_dtype;      /* enum ldpc_msg_dtype                                         */
     int32_t max_iter;       /* `times`, MyLdpc.cpp:24 (reference: 40)                      */
-    float llr_scale;        /* SP only: q = exp(llr_scale*y)..., decodeCL.c:9 (reference: 8) */
+    float llr_scale;        /* SP: q = exp(llr_scale*y)..., decodeCL.c:9 (reference: 8); BP: chan = llr_scale * y, the
+                               LLR (> 0 and finite, else LDPC_ERR_ARG); ignored by the min-sum algorithms  */
     int32_t early_term;     /* 1: frames freeze when their syndrome is clean (reference
                                behaviour, decodeCL.c:27,48-49); 0: always run max_iter      */
     int32_t device;         /* HIP device ordinal                                          */
@@ -172,7 +204,8 @@ typedef struct ldpc_decoder_config {
      *      rounded to fp16 where it is produced.  ms_offset is in the units of the channel values passed to
      *      ldpc_decode (with the reference's convention, BPSK +-1 plus noise: units of y, not of LLRs): offset
      *      min-sum depends on the scale of the input, normalized min-sum does not.
-     *      LDPC_ALGO_MS and LDPC_ALGO_LAYERED only (others: LDPC_ERR_UNSUPPORTED when either is non-zero).  The
+     *      LDPC_ALGO_MS and LDPC_ALGO_LAYERED only (others, LDPC_ALGO_BP among them: LDPC_ERR_UNSUPPORTED when either is
+     *      non-zero).  The
      *      record kernels and the streaming kernels carry the correction; the LDS-resident one-launch kernels do
      *      not and are not selected (forcing them, LDPC_TUNE_ON(FUSED) with LDPC_TUNE_OFF(LDSP):
      *      LDPC_ERR_UNSUPPORTED).  NaN, inf or a value out of range: LDPC_ERR_ARG. ----------------------------- */
@@ -190,8 +223,8 @@ typedef struct ldpc_decoder_config {
      *      that never freezes gets iters = max_iter and the last round's bits, as without a CRC.  frames_converged counts
      *      frames frozen by either rule; ldpc_decoder_crc_stops those frozen in a round where clean_i was false.
      *      Needs early_term = 1 (LDPC_ERR_ARG otherwise, as for an unknown kind or crc_bits out of range).
-     *      Streaming kernels only: LDPC_ALGO_SP and LDPC_ALGO_MS (fp32 and LDPC_MSG_F16, with or without ms_scale /
-     *      ms_offset) and LDPC_ALGO_LAYERED with one launch per layer; one more launch per round (crc_term_kernel).
+     *      Streaming kernels only: LDPC_ALGO_SP, LDPC_ALGO_MS (fp32 and LDPC_MSG_F16, with or without ms_scale /
+     *      ms_offset), LDPC_ALGO_BP (fp32 and LDPC_MSG_F16) and LDPC_ALGO_LAYERED with one launch per layer; one more launch per round (crc_term_kernel).
      *      LDPC_ALGO_MS_FUSED and LDPC_ALGO_LAYERED_HOST reproduce reference kernels: LDPC_ERR_UNSUPPORTED.  The
      *      LDS-resident one-launch kernels and the record kernels do not carry the rule and are not selected (forcing
      *      them, LDPC_TUNE_ON(FUSED) or LDPC_TUNE_ON(LDSP): LDPC_ERR_UNSUPPORTED).
@@ -339,6 +372,8 @@ int64_t ldpc_out_bytes(int32_t K, int64_t frames, int32_t pack_mode);
  *         at a time, R = the check->variable messages of round i_f on the column's edges in ascending edge id; y_n is the
  *         channel value as the decoder read it (rounded to fp16 with LDPC_MSG_F16).  This is the very sum the variable
  *         node forms for the hard decision.
+ *       LDPC_ALGO_BP, fp32 and LDPC_MSG_F16: the same sum with y_n = chan[n] = llr_scale * y[n] as the decoder stored it
+ *         (one fp32 multiply, rounded to fp16 with LDPC_MSG_F16): the value is an LLR.
  *       LDPC_ALGO_LAYERED, LDPC_ALGO_LAYERED_HOST, LDPC_ALGO_MS_FUSED: P[n] after the last layer (MS_FUSED: after the
  *         posterior update) of round i_f.
  *   LDPC_SOFT_EXTRINSIC:  soft = p - y_n, one fp32 subtraction, the same y_n.
@@ -346,7 +381,8 @@ int64_t ldpc_out_bytes(int32_t K, int64_t frames, int32_t pack_mode);
  * The value is that of round i_f and no later one: a frozen frame's messages keep evolving unread inside the streaming
  * decoders, so it is caught when the frame freezes (0 ulp against the CPU oracle's `post` tap of that round).
  *
- * LDPC_ALGO_SP has no soft output (LDPC_ERR_UNSUPPORTED): the reference's sum-product runs in the probability domain in
+ * LDPC_ALGO_SP has no soft output (LDPC_ERR_UNSUPPORTED; LDPC_ALGO_BP is the sum-product that has one): the reference's
+ * sum-product runs in the probability domain in
  * fp32, and its normalised posterior (f0 - f1) / (f0 + f1) carries nothing by the time a frame stops -- on the
  * BG1-profile test code (N = 1088, 64 frames, llr_scale 8) it is exactly +-1 on 68210 of 69632 values at 3.0 dB, and 0/0
  * on 20690 of them at 1.5 dB.
@@ -420,7 +456,7 @@ int ldpc_decoder_array_addresses(ldpc_decoder *d, uint64_t out[4]);
  * its messages.  ldpc_decoder_dump then copies them out in the reference's layout
  * [frame][E] / [frame][N] (decodeCL.c: q/r at b*nonZeros+e, posteriors at b*N+n).
  * which: 0 = check->variable messages R (SP: r0-r1), 1 = variable->check
- * messages Q (SP: q0-q1), 2 = channel term (SP: exp(scale*y), MS: y; layered:
+ * messages Q (SP: q0-q1), 2 = channel term (SP: exp(scale*y), MS: y, BP: scale*y; layered:
  * posterior P), 3 = hard bits as floats 0/1 [frame][N]. */
 int ldpc_decoder_set_tap(ldpc_decoder *d, int32_t iter);
 int ldpc_decoder_dump(ldpc_decoder *d, int32_t which, float *host_out, int64_t count);
@@ -506,9 +542,9 @@ int64_t ldpc_code_bytes(int32_t N, int64_t frames, int32_t format);
  *   cannot take an exact 0: a check row's sign is the running product of its inputs (a *= tmp with the message sign
  *   taken from tmp), so one input of exactly 0 zeroes every message of its row for good, and two erased columns of
  *   EQUAL tiny magnitude cancel back to exactly 0 in the layered update.  With erased = 0 LDPC_ALGO_LAYERED fails on
- *   every frame that has a punctured column; the flooding decoders (LDPC_ALGO_SP, LDPC_ALGO_MS) handle zeros.  Small,
+ *   every frame that has a punctured column; the flooding decoders (LDPC_ALGO_SP, LDPC_ALGO_MS, LDPC_ALGO_BP) handle zeros.  Small,
  *   pairwise DISTINCT positive values repair the layered decoders completely (DESIGN.md has the figures):
- *   erasure_llr = 1e-6 is the recommended value whenever a layered decoder reads y; it is harmless for SP and MS.
+ *   erasure_llr = 1e-6 is the recommended value whenever a layered decoder reads y; it is harmless for SP, MS and BP.
  *   With LDPC_MSG_F16 messages the values collapse to a few fp16 levels and stop being distinct -- the flooding
  *   decoders, the only ones with fp16 messages, do not need the rule.  erasure_llr > 0 needs N <= 2^22 (beyond that
  *   the values are no longer pairwise distinct in fp32): LDPC_ERR_ARG.

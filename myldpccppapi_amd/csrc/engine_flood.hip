@@ -319,9 +319,9 @@ template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t
                       d->E, frames, d->N, tiles, d->T, d->flood.TO * F, std::min(d->flood.compact_threshold, d->flood.TO * F), 0, max_iter};
     }
 
-    /* min-sum whose check phase is made of the unrolled bucket / single-class kernels only: round 1 reads q = y from the
+    /* min-sum / box-plus whose check phase is made of the unrolled bucket / single-class kernels only: round 1 reads q = y from the
      * channel array and the input transpose writes no Q (CheckArgs::first_chan); not with a debug tap */
-    bool q_less = d->cfg.algo == LDPC_ALGO_MS && !resume && !d->tm.tap_iter && max_iter > 1 && d->flood.n_extra == 0;
+    bool q_less = (d->cfg.algo == LDPC_ALGO_MS || d->cfg.algo == LDPC_ALGO_BP) && !resume && !d->tm.tap_iter && max_iter > 1 && d->flood.n_extra == 0;
     for (auto &rc : d->flood.row_classes) if (rc.linked) q_less = false;
     for (int ci : d->flood.check_solo) if (d->flood.row_classes[ci].degree > d->flood.fns.max_check_unrolled) q_less = false;
     d->flood.first_round_from_chan = q_less;
@@ -644,9 +644,11 @@ int setup_flooding(ldpc_decoder *d, const ldpc_graph *g, size_t TF)
     LDPC_HIP_TRY(d->flood.R.alloc(TF * (size_t)d->E * d->flood.msg_size));
     int rc = build_classes(d, g);
     if (rc) return rc;
-    /* the kernels live in flood_sp.hip / flood_ms*.hip / flood_msc*.hip (flood_tables.hpp) */
+    /* the kernels live in flood_sp.hip / flood_ms*.hip / flood_msc*.hip / flood_bp*.hip (flood_tables.hpp) */
     ldpc::FloodFns *fns = &d->flood.fns;
     if (cfg->algo == LDPC_ALGO_SP) ldpc::fill_flood_sp(d->V, fns);
+    else if (cfg->algo == LDPC_ALGO_BP && cfg->msg_dtype == LDPC_MSG_F16) ldpc::fill_flood_bp16(d->V, fns);
+    else if (cfg->algo == LDPC_ALGO_BP) ldpc::fill_flood_bp(d->V, fns);
     else if (d->ms_corr && cfg->msg_dtype == LDPC_MSG_F8) ldpc::fill_flood_msc8(d->V, fns);
     else if (cfg->msg_dtype == LDPC_MSG_F8) ldpc::fill_flood_ms8(d->V, fns);
     else if (d->ms_corr && cfg->msg_dtype == LDPC_MSG_F16) ldpc::fill_flood_msc16(d->V, fns);

@@ -1,5 +1,5 @@
 /*
- * flood_check.hpp -- the check node of the streaming flooding decoders: check_sp / check_ms, the unrolled row
+ * flood_check.hpp -- the check node of the streaming flooding decoders: check_sp / check_ms / check_bp, the unrolled row
  * loop (check_rows), check_kernel, the run-time-degree row and kernel, the bucket launch (check_group_kernel).
  */
 #pragma once
@@ -65,11 +65,69 @@ __device__ __forceinline__ void check_ms(const float (&x)[D][V], float (&out)[D]
     }
 }
 
+/* Log-domain sum-product (LDPC_ALGO_BP, include/ldpc_hip.h has the rule bit for bit): fp32, one operation at a time.
+ * bp_clamp: a row's input as the row reads it -- |x| capped at min-sum's start value 1000, so NaN reads +1000 (fminf
+ * drops it, its sign is +), -0 reads +0, +-inf read +-1000.  From there on every value is finite. */
+__device__ __forceinline__ float bp_clamp(float x)
+{
+    const float a = fminf(__builtin_fabsf(x), 1000.0f);
+    return (x < 0.0f) ? -a : a;
+}
+/* the linear stand-in for log1p(exp(-x)): ln 2 at 0, 0 from 4 ln 2 on.  0.25f * x is exact (a power of two; where it
+ * underflows, x < 2^-124 and both forms give ln 2), so the fused multiply-add rounds the very number the definition's
+ * multiply and subtract round: same bits, one instruction less -- the fp16 check kernels are bound by these (8k) */
+__device__ __forceinline__ float bp_corr(float x) { return fmaxf(__builtin_fmaf(-0.25f, x, 0.6931472f), 0.0f); }
+/* u [+] v = sign * max(min(|u|, |v|) + c(|u| + |v|) - c(||u| - |v||), 0): bitwise commutative, not associative */
+__device__ __forceinline__ float bp_boxplus(float u, float v)
+{
+    const float au = __builtin_fabsf(u), av = __builtin_fabsf(v);
+    const float m = fminf(au, av);
+    const float s = au + av;
+    const float d = __builtin_fabsf(au - av);
+    const float g = fmaxf((m + bp_corr(s)) - bp_corr(d), 0.0f);
+    return ((u < 0.0f) != (v < 0.0f)) ? -g : g;
+}
+
+/* A row of degree D: forward chain f_j = f_{j-1} [+] t_j from the left, backward chain b_j = t_j [+] b_{j+1} from the
+ * right, out_k = f_{k-1} [+] b_{k+1} -- 3 (D - 2) box-plus operations.  The association is part of the definition.  The
+ * backward values are kept (D registers per value next to the inputs), the forward value is carried.  The result is
+ * rounded to the storage type here, where it is produced (MsgRound): the column-fused kernels keep some R in registers. */
+template <int D, int W, typename T>
+__device__ __forceinline__ void check_bp(const float (&x)[D][W], float (&out)[D][W])
+{
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        float t[D];
+#pragma unroll
+        for (int j = 0; j < D; ++j) t[j] = bp_clamp(x[j][w]);
+        if constexpr (D == 1) {
+            out[0][w] = MsgRound<T>::of(1000.0f);
+        } else if constexpr (D == 2) {
+            out[0][w] = MsgRound<T>::of(t[1]);
+            out[1][w] = MsgRound<T>::of(t[0]);
+        } else {
+            float b[D];
+            b[D - 1] = t[D - 1];
+#pragma unroll
+            for (int j = D - 2; j >= 1; --j) b[j] = bp_boxplus(t[j], b[j + 1]);
+            out[0][w] = MsgRound<T>::of(b[1]);
+            float f = t[0];
+#pragma unroll
+            for (int k = 1; k <= D - 2; ++k) {
+                out[k][w] = MsgRound<T>::of(bp_boxplus(f, b[k + 1]));
+                f = bp_boxplus(f, t[k]);
+            }
+            out[D - 1][w] = MsgRound<T>::of(f);
+        }
+    }
+}
+
 /* the check node of one row in arithmetic ALGO: W values per lane, c = the min-sum correction (kAlgoMSC only) */
 template <int ALGO, int D, int W, typename T>
 __device__ __forceinline__ void check_node(const float (&x)[D][W], float (&out)[D][W], const MsCorr &c)
 {
     if (ALGO == kAlgoSP) check_sp<D, W>(x, out);
+    else if (ALGO == kAlgoBP) check_bp<D, W, T>(x, out);
     else if (ALGO == kAlgoMS) check_ms<D, W, false, T>(x, out);
     else check_ms<D, W, true, T>(x, out, c);
 }
@@ -135,6 +193,48 @@ __device__ __forceinline__ void check_row_generic(const T *Qu, unsigned lane_off
                                                   const int32_t *__restrict__ qpos, const MsCorr &c)
 {
     constexpr size_t F = 64 * V;
+    if (ALGO == kAlgoBP) {
+        /* check_bp's association with run-time loops: the forward value is carried in registers (never through T: fp16
+         * would round it), b_{k+1} is rebuilt from the row's end for every output (L2 serves the re-reads) */
+        auto load = [&](int j, float (&t)[V]) {
+            vload<V>(t, Qu + (size_t)edge_slot(qpos, e0 + j) * F + lane_off);
+#pragma unroll
+            for (int v = 0; v < V; ++v) t[v] = bp_clamp(t[v]);
+        };
+        auto store = [&](int k, float (&o)[V]) {
+#pragma unroll
+            for (int v = 0; v < V; ++v) o[v] = MsgRound<T>::of(o[v]);
+            vstore<V>(Rt + (size_t)(e0 + k) * F, o);
+        };
+        if (D <= 0) return;
+        float f[V], b[V], t[V];
+        if (D == 1) {
+#pragma unroll
+            for (int v = 0; v < V; ++v) b[v] = 1000.0f;
+            store(0, b);
+            return;
+        }
+        load(0, f);
+        for (int k = 0; k < D - 1; ++k) {
+            /* b = b_{k+1}; f = f_{k-1} (k >= 1) */
+            load(D - 1, b);
+            for (int j = D - 2; j > k; --j) {
+                load(j, t);
+#pragma unroll
+                for (int v = 0; v < V; ++v) b[v] = bp_boxplus(t[v], b[v]);
+            }
+            if (k == 0) { store(0, b); continue; }
+            float o[V];
+#pragma unroll
+            for (int v = 0; v < V; ++v) o[v] = bp_boxplus(f[v], b[v]);
+            store(k, o);
+            load(k, t);
+#pragma unroll
+            for (int v = 0; v < V; ++v) f[v] = bp_boxplus(f[v], t[v]);
+        }
+        store(D - 1, f);
+        return;
+    }
     if (ALGO != kAlgoSP) {
         /* two passes over the row instead of one per output: min1/min2/argmin and the sign
          * parity first, then each output from its own re-read value (L2 serves the re-read) */

@@ -14,6 +14,7 @@ namespace ldpc {
 constexpr int kAlgoSP = 0;
 constexpr int kAlgoMS = 1;
 constexpr int kAlgoMSC = 2;   /* min-sum with the normalized / offset correction (check_ms, MsCorr) */
+constexpr int kAlgoBP = 3;    /* log-domain sum-product: min-sum's variable node, box-plus check node (check_bp) */
 constexpr int kCompactCapacity = 512;   /* frames a child decoder takes over (8 tiles of 64) */
 constexpr int kLastCapacity = 64;       /* ... and the last decoder of the chain: one tile */
 constexpr int kBlock = 256;          /* 4 waves */
@@ -290,7 +291,7 @@ __device__ __forceinline__ MsCorr ms_corr_of(const CheckArgs &a) { return MsCorr
 struct VarArgs {
     const void *__restrict__ R;           /* [T][E][F] (float, fp16 or fp8) */
     void *__restrict__ Q;                 /* [T][E][F] */
-    const void *__restrict__ chan;        /* [T][N][F] SP: exp(scale*y); MS: y */
+    const void *__restrict__ chan;        /* [T][N][F] SP: exp(scale*y); MS: y; BP: scale*y */
     uint64_t *hard;                       /* [T][N][V] read-modify-write */
     const uint64_t *__restrict__ done;    /* [T][V] */
     const int32_t *__restrict__ cls_col;  /* [n_cols] column ids of this degree class */

@@ -39,7 +39,7 @@
 
 /* The kernels by role; this file is the umbrella include.
  *   flood_common.hpp    stream loads and stores, tile selection, CheckArgs / VarArgs / GroupClass, Q slots, MsCorr
- *   flood_check.hpp     check_sp / check_ms / check_node, check_rows, check_kernel, generic, group
+ *   flood_check.hpp     check_sp / check_ms / check_bp / check_node, check_rows, check_kernel, generic, group
  *   flood_var.hpp       var_sp, var_columns, var_kernel, group, generic
  *   flood_link.hpp      the column-fused check kernels: wide, narrow / half, deep
  *   flood_round.hpp     init, syndrome, state, pack

@@ -78,6 +78,13 @@ __global__ __launch_bounds__(kBlock) void init_kernel(const InitArgs a)
                 const float t = ldpc_expf(a.llr_scale * y);         /* decodeCL.c:9 */
                 ch[v] = t;
                 q[v] = t / (1.0f + t) - 1.0f / (1.0f + t);          /* :10-11, as q0-q1 */
+            } else if (ALGO == kAlgoBP) {
+                /* the LLR: one fp32 multiply; fp16 storage rounds the PRODUCT at the store.  The empty asm keeps the
+                 * product a value of its own: folded into the conversion (v_fma_mixlo_f16) it is rounded once, from
+                 * the exact product, and differs from the definition in the double-rounding cases */
+                float t = a.llr_scale * y;
+                asm volatile("" : "+v"(t));
+                ch[v] = q[v] = t;
             } else {
                 ch[v] = y;                                          /* fp16 storage rounds it here */
                 q[v] = y;                                           /* :121 */

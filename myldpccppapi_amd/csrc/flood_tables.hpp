@@ -1,6 +1,6 @@
 /*
  * flood_tables.hpp -- the kernel tables of the streaming flooding decoders, filled per arithmetic in
- * translation units of their own (flood_sp.hip, flood_ms*.hip, flood_msc*.hip) so that the library
+ * translation units of their own (flood_sp.hip, flood_ms*.hip, flood_msc*.hip, flood_bp*.hip) so that the library
  * builds in parallel: the flooding engine (engine_flood.hip) only sees function pointers.
  */
 #pragma once
@@ -44,5 +44,7 @@ void fill_flood_msc(int V, FloodFns *f);     /* corrected min-sum (kAlgoMSC), fp
 void fill_flood_msc16(int V, FloodFns *f);   /* corrected min-sum, fp16 message storage     (flood_msc16.hip) */
 void fill_flood_ms8(int V, FloodFns *f);     /* min-sum, fp8 (E4M3) message storage         (flood_ms8.hip)   */
 void fill_flood_msc8(int V, FloodFns *f);    /* corrected min-sum, fp8 message storage      (flood_msc8.hip)  */
+void fill_flood_bp(int V, FloodFns *f);      /* log-domain sum-product (kAlgoBP), fp32 messages (flood_bp.hip)  */
+void fill_flood_bp16(int V, FloodFns *f);    /* log-domain sum-product, fp16 message storage    (flood_bp16.hip) */
 
 }  // namespace ldpc

@@ -1,7 +1,7 @@
 /*
  * flood_tables_impl.hpp -- instantiates every streaming flooding kernel of ONE arithmetic
  * (algorithm + message type) for V = 1, 2, 4 and hands out the function pointers.  Included by
- * flood_sp.hip / flood_ms*.hip / flood_msc*.hip only.
+ * flood_sp.hip / flood_ms*.hip / flood_msc*.hip / flood_bp*.hip only.
  */
 #pragma once
 
@@ -28,7 +28,7 @@ template <int ALGO, int V, typename T> struct FloodTable<ALGO, V, T, 0> {
     }
 };
 
-/* min-sum rows of degree 17..32: narrow unrolled kernels only */
+/* min-sum and box-plus rows of degree 17..32: narrow unrolled kernels only */
 template <int ALGO, int V, typename T, int D> struct CheckTableMS {
     static void fill(CheckFn *c, CheckFn *cw)
     {
@@ -77,7 +77,7 @@ template <int ALGO, int V, typename T> void fill_v(FloodFns *f)
     f->var_group[2] = var_group_kernel<ALGO, V, T, 9, 16>;
     f->init = init_kernel<ALGO, V, T>;
     f->max_check_unrolled = DM;
-    if (ALGO != kAlgoSP) {       /* min-sum rows of degree 17..32: narrow unrolled kernels */
+    if (ALGO != kAlgoSP) {       /* min-sum and box-plus rows of degree 17..32: narrow unrolled kernels */
         CheckTableMS<ALGO, V, T, kMaxUnrolledCheckDegreeMS>::fill(f->check, f->check_wide);
         f->check_group[2] = check_group_kernel<ALGO, V, T, 17, 24, GW>;
         f->check_group[3] = check_group_kernel<ALGO, V, T, 25, 32, GW>;

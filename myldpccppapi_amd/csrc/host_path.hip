@@ -413,7 +413,7 @@ int ldpc_decode_soft(ldpc_decoder *d, const float *llr_host, int64_t frames, uin
         return set_error(LDPC_ERR_ARG, "unknown soft_kind %d", soft_kind);
     if (d->cfg.algo == LDPC_ALGO_SP)
         return set_error(LDPC_ERR_UNSUPPORTED, "soft output: LDPC_ALGO_SP has no usable soft value (include/ldpc_hip.h); "
-                    "the min-sum algorithms carry it");
+                    "the min-sum algorithms and LDPC_ALGO_BP carry it");
     if (d->tm.tap_iter) return set_error(LDPC_ERR_STATE, "soft output while a debug tap is set");
     if (frames > 0 && !soft_host) return set_error(LDPC_ERR_ARG, "soft is NULL");
     if (frames > 0 && soft_floats < frames * (int64_t)d->N)

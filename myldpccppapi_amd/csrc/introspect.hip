@@ -145,12 +145,12 @@ int ldpc_decoder_kernel_times(ldpc_decoder *d, ldpc_kernel_time *out, int32_t ca
     const char *phase_name[] = {"check_kernel", "var_kernel", d->ms_corr ? "layer_corr_kernel" : "layer_kernel", "other",
                                 link_form == 2 ? "check_link_half_kernel"
                                 : link_form ? "check_link_narrow_kernel" : "check_link_kernel"};
-    static const char *algo_name_f32[] = {"sp", "ms", "layered", "ms_fused", "layered_host"};
-    static const char *algo_name_f16[] = {"sp16", "ms16", "layered16", "ms_fused16", "layered_host16"};
-    static const char *algo_name_corr_f32[] = {"sp", "msc", "layered", "ms_fused", "layered_host"};  /* kAlgoMSC */
-    static const char *algo_name_corr_f16[] = {"sp16", "msc16", "layered16", "ms_fused16", "layered_host16"};
-    static const char *algo_name_f8[] = {"sp8", "ms8", "layered8", "ms_fused8", "layered_host8"};
-    static const char *algo_name_corr_f8[] = {"sp8", "msc8", "layered8", "ms_fused8", "layered_host8"};
+    static const char *algo_name_f32[] = {"sp", "ms", "layered", "ms_fused", "layered_host", "bp"};
+    static const char *algo_name_f16[] = {"sp16", "ms16", "layered16", "ms_fused16", "layered_host16", "bp16"};
+    static const char *algo_name_corr_f32[] = {"sp", "msc", "layered", "ms_fused", "layered_host", "bp"};  /* kAlgoMSC; index = enum ldpc_algo */
+    static const char *algo_name_corr_f16[] = {"sp16", "msc16", "layered16", "ms_fused16", "layered_host16", "bp16"};
+    static const char *algo_name_f8[] = {"sp8", "ms8", "layered8", "ms_fused8", "layered_host8", "bp8"};
+    static const char *algo_name_corr_f8[] = {"sp8", "msc8", "layered8", "ms_fused8", "layered_host8", "bp8"};
     const int msz = d->flood.msg_size;
     const char **algo_name = d->ms_corr ? (msz == 1 ? algo_name_corr_f8 : msz == 2 ? algo_name_corr_f16 : algo_name_corr_f32)
                                         : (msz == 1 ? algo_name_f8 : msz == 2 ? algo_name_f16 : algo_name_f32);

@@ -42,7 +42,7 @@ int pick_frames_per_lane(const ldpc_decoder_config &cfg, int32_t max_row_deg, in
      * kernels run in narrow waves, so only the column degree counts there; the layered kernel
      * holds a whole row (P and R) per lane. */
     int deg = cfg.algo == LDPC_ALGO_LAYERED ? max_row_deg : max_col_deg;
-    if (cfg.algo == LDPC_ALGO_MS) deg = (deg + 1) / 2;   /* min-sum variable nodes need half the registers */
+    if (cfg.algo == LDPC_ALGO_MS || cfg.algo == LDPC_ALGO_BP) deg = (deg + 1) / 2;   /* min-sum variable nodes (BP's too) need half the registers */
     /* fp8 messages: 4 values are one dword per lane, the least a lane should move -- from one full tile on */
     if (cfg.msg_dtype == LDPC_MSG_F8 && cfg.max_batch >= 256 && deg <= 8) return 4;
     if (cfg.max_batch >= 1024 && deg <= 8) return 4;
@@ -212,7 +212,7 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     if (cfg->max_batch <= 0) return set_error(LDPC_ERR_ARG, "max_batch must be positive");
     if (cfg->max_iter <= 0 || cfg->max_iter > 100000) return set_error(LDPC_ERR_ARG, "max_iter out of range");
     if (cfg->algo != LDPC_ALGO_SP && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED &&
-        cfg->algo != LDPC_ALGO_MS_FUSED && cfg->algo != LDPC_ALGO_LAYERED_HOST)
+        cfg->algo != LDPC_ALGO_MS_FUSED && cfg->algo != LDPC_ALGO_LAYERED_HOST && cfg->algo != LDPC_ALGO_BP)
         return set_error(LDPC_ERR_ARG, "unknown algo %d", cfg->algo);
     /* comparisons written so that NaN fails them */
     if (!(cfg->ms_scale >= 0.0f && cfg->ms_scale <= 1.0f))
@@ -222,7 +222,9 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     const bool ms_corr = cfg->ms_scale != 0.0f || cfg->ms_offset != 0.0f;
     if (ms_corr && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED)
         return set_error(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset apply to LDPC_ALGO_MS and LDPC_ALGO_LAYERED only "
-                    "(SP has no minimum to correct; MS_FUSED and LAYERED_HOST reproduce reference kernels)");
+                    "(SP and BP have no minimum to correct; MS_FUSED and LAYERED_HOST reproduce reference kernels)");
+    if (cfg->algo == LDPC_ALGO_BP && !(cfg->llr_scale > 0.0f && cfg->llr_scale <= 3.402823466e38f))
+        return set_error(LDPC_ERR_ARG, "LDPC_ALGO_BP: llr_scale must be positive and finite (chan = llr_scale * y is the LLR)");
     if (cfg->algo == LDPC_ALGO_LAYERED_HOST) {
         for (int32_t m = 1; m < g->M; ++m)
             if (g->row_ptr[m + 1] - g->row_ptr[m] != g->row_ptr[1] - g->row_ptr[0])
@@ -240,11 +242,17 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         return set_error(LDPC_ERR_ARG, "unknown msg_dtype %d", cfg->msg_dtype);
     if (cfg->msg_dtype == LDPC_MSG_F8 && cfg->algo != LDPC_ALGO_MS)
         return set_error(LDPC_ERR_UNSUPPORTED, "fp8 messages are built for flooding min-sum only "
-                    "(the probability-domain SP needs fp32 range; the layered and reference-reproducing decoders are fp32)");
-    if (cfg->msg_dtype == LDPC_MSG_F16 && cfg->algo != LDPC_ALGO_MS)
-        return set_error(LDPC_ERR_UNSUPPORTED, "fp16 messages are built for flooding min-sum only "
+                    "(the probability-domain SP needs fp32 range; BP is fp32 / fp16; the layered and reference-reproducing decoders are fp32)");
+    if (cfg->msg_dtype == LDPC_MSG_F16 && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_BP)
+        return set_error(LDPC_ERR_UNSUPPORTED, "fp16 messages are built for flooding min-sum and BP only "
                     "(the probability-domain SP needs fp32 range; layered: not yet)");
     if (!ldpc::tune_valid(*cfg)) return set_error(LDPC_ERR_ARG, "tuning / streams config fields out of range");
+    if (cfg->algo == LDPC_ALGO_BP) {
+        const ldpc::Tune t = ldpc::tune_from_config(*cfg);
+        if (ldpc::tune_forced_on(t.fused) || ldpc::tune_forced_on(t.ldsp))
+            return set_error(LDPC_ERR_UNSUPPORTED, "LDPC_ALGO_BP: the LDS-resident one-launch kernels and the record kernels (LDPC_TUNE_FUSED / "
+                        "LDPC_TUNE_LDSP forced on) carry no box-plus check node; the streaming kernels do");
+    }
     if (cfg->msg_dtype == LDPC_MSG_F8) {
         const ldpc::Tune t = ldpc::tune_from_config(*cfg);
         if (ldpc::tune_forced_on(t.fused) || ldpc::tune_forced_on(t.ldsp))
@@ -258,7 +266,7 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         if (ldpc::crc_term_check(cfg->crc_kind, cfg->crc_bits, cfg->K, cfg->early_term, msg, sizeof msg)) return set_error(LDPC_ERR_ARG, "%s", msg);
         if (crc_term && (cfg->algo == LDPC_ALGO_MS_FUSED || cfg->algo == LDPC_ALGO_LAYERED_HOST))
             return set_error(LDPC_ERR_UNSUPPORTED, "crc_kind: LDPC_ALGO_MS_FUSED and LDPC_ALGO_LAYERED_HOST reproduce reference kernels, which "
-                        "stop on the syndrome alone; LDPC_ALGO_SP, LDPC_ALGO_MS and LDPC_ALGO_LAYERED carry the CRC rule");
+                        "stop on the syndrome alone; LDPC_ALGO_SP, LDPC_ALGO_MS, LDPC_ALGO_BP and LDPC_ALGO_LAYERED carry the CRC rule");
         const ldpc::Tune t = ldpc::tune_from_config(*cfg);
         if (crc_term && (ldpc::tune_forced_on(t.fused) || ldpc::tune_forced_on(t.ldsp)))
             return set_error(LDPC_ERR_UNSUPPORTED, "crc_kind: the LDS-resident one-launch kernels and the record kernels (LDPC_TUNE_FUSED / "
@@ -314,7 +322,7 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
      * LDPC_TUNE_OFF(LDPC_TUNE_DEVICE_TAIL) switches it off. */
     d->flood.TO = (ldpc::kCompactCapacity + d->F - 1) / d->F;
     d->flood.tail_enabled = cfg->early_term && cfg->poll_interval == 0 && ldpc::tune_pick(tune.device_tail, true) &&
-                      (cfg->algo == LDPC_ALGO_SP || cfg->algo == LDPC_ALGO_MS) && d->T >= 4 * d->flood.TO && t_child_depth == 0;
+                      (cfg->algo == LDPC_ALGO_SP || cfg->algo == LDPC_ALGO_MS || cfg->algo == LDPC_ALGO_BP) && d->T >= 4 * d->flood.TO && t_child_depth == 0;
     if (!d->flood.tail_enabled) d->flood.TO = 0;
     d->flood.TA = d->T + d->flood.TO;
     const size_t TF = (size_t)d->flood.TA * d->F;
@@ -403,7 +411,8 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         if (d->ms_corr && ldpc::tune_forced_on(tune.fused) && ldpc::tune_forced_off(tune.ldsp))
             return set_error(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset: the LDS-resident flooding kernel (LDPC_TUNE_FUSED on, "
                         "LDPC_TUNE_LDSP off) carries no correction; the record or the streaming kernels do");
-        if (!crc_term && cfg->msg_dtype == LDPC_MSG_F32 && cfg->layer_rows > 0 && cfg->frames_per_lane == 0 &&
+        /* LDPC_ALGO_BP: the streaming kernels always (layer_rows does not select an engine) */
+        if (cfg->algo != LDPC_ALGO_BP && !crc_term && cfg->msg_dtype == LDPC_MSG_F32 && cfg->layer_rows > 0 && cfg->frames_per_lane == 0 &&
             (cfg->pack_mode == LDPC_PACK_BYTES || cfg->K % 8 == 0)) {
             const bool small = (int64_t)cfg->max_batch * g->E <= (int64_t)1 << 23;
             if (!d->ms_corr && ldpc::tune_pick(tune.fused, small)) {
@@ -616,7 +625,7 @@ int ldpc_decode_soft_device(ldpc_decoder *d, const float *llr_dev, int64_t frame
     if (d->cfg.algo == LDPC_ALGO_SP)
         return set_error(LDPC_ERR_UNSUPPORTED, "soft output: LDPC_ALGO_SP works in the probability domain in fp32, where the "
                     "posterior saturates to exactly +-1 on nearly every bit of a frame that converges and is 0/0 on frames "
-                    "that do not; the min-sum algorithms (MS, MS_FUSED, LAYERED, LAYERED_HOST) carry it");
+                    "that do not; the min-sum algorithms (MS, MS_FUSED, LAYERED, LAYERED_HOST) and the log-domain LDPC_ALGO_BP carry it");
     if (d->tm.tap_iter)
         return set_error(LDPC_ERR_STATE, "soft output while a debug tap is set (ldpc_decoder_set_tap(d, 0) clears it)");
     if (frames < 0 || frames > d->cfg.max_batch)

@@ -7,7 +7,7 @@ b is frame b*frames + f of the seed's stream, so a point can be extended or re-r
 and errors counted by ldpc_count_errors_device; nothing crosses PCIe but the counts.  The
 reference counts differing BYTES (Test.cpp:105-110); this prints byte errors too.
 
-    python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N>] [--algo sp|ms|layered]
+    python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N>] [--algo sp|ms|layered|bp]
                               [--payload zero|random] [--rate-match P,FLO,FHI,E[,K0]] [--erasure-llr X]
                               [--modulation bpsk|qpsk|qam16|qam64|qam256] [--no-interleave] [--transport-block A[,C]] [--crc-stop]
                               [--msg-dtype f32|f16|f8] [--soft-check]
@@ -23,6 +23,8 @@ Eb/N0 = Es/N0 / (bits per symbol x rate).  --no-interleave switches the bit inte
 the decoder's llr_scale follows the noise, 2 / sd^2 per point (and the fillers read min(10, 80 / llr_scale)), unless
 --llr-scale is given.  From 16-QAM up use --payload random: the all-zero codeword sends one corner point only, and the
 bits of a QAM symbol are not equally protected.
+--algo bp (the log-domain sum-product, include/ldpc_hip.h: LDPC_ALGO_BP) reads LLRs: its llr_scale follows the noise, 2 / sd^2
+per point, with any modulation and with none, unless --llr-scale is given; --msg-dtype f16, --soft-check and --crc-stop apply.
 --transport-block A[,C] (with --payload random): the random bytes are transport blocks of A payload bits; ldpc_tb_attach_device
 in front of the encoder adds the transport block's CRC, cuts it into C code blocks with CRC24B each (C omitted: the rule of
 ldpc_tb_spec_init) and fills up to K with zeros; ldpc_tb_check_device and ldpc_tb_tally_device behind the decoder judge the
@@ -51,7 +53,7 @@ ap.add_argument("--algo", default="sp")
 ap.add_argument("--snr", default="2.5,3.0,3.5,4.0,4.5,5.0")
 ap.add_argument("--frames", type=int, default=4096)
 ap.add_argument("--iters", type=int, default=50)
-ap.add_argument("--llr-scale", type=float, default=None, help="sum-product channel scale (default 8; with --modulation: 2 / sd^2 per point)")
+ap.add_argument("--llr-scale", type=float, default=None, help="channel scale of sp and bp (sp: default 8, with --modulation 2 / sd^2 per point; bp: 2 / sd^2 per point)")
 ap.add_argument("--batches", type=int, default=1, help="batches of --frames per SNR point")
 ap.add_argument("--seed", type=int, default=20260101)
 ap.add_argument("--ms-scale", type=float, default=0.0, help="normalized min-sum factor (ms / layered; 0 = off)")
@@ -65,7 +67,7 @@ ap.add_argument("--modulation", choices=("bpsk", "qpsk", "qam16", "qam64", "qam2
 ap.add_argument("--no-interleave", action="store_true", help="with --modulation: no bit interleaver")
 ap.add_argument("--transport-block", default=None, metavar="A[,C]",
                 help="with --payload random: A payload bits per transport block, C code blocks (default: the rule of ldpc_tb_spec_init)")
-ap.add_argument("--msg-dtype", choices=("f32", "f16", "f8"), default="f32", help="message storage (f16, f8: --algo ms only)")
+ap.add_argument("--msg-dtype", choices=("f32", "f16", "f8"), default="f32", help="message storage (f16: --algo ms and bp; f8: --algo ms)")
 ap.add_argument("--crc-stop", action="store_true", help="with --transport-block: frames also stop once their CRC passes")
 ap.add_argument("--soft-check", action="store_true",
                 help="every batch is decoded once more with soft output (not --algo sp): prints the finite non-zero posteriors whose sign "
@@ -76,7 +78,8 @@ assert not args.transport_block or args.payload == "random", "--transport-block 
 assert args.transport_block or not args.crc_stop, "--crc-stop needs --transport-block"
 assert args.modulation or not args.no_interleave, "--no-interleave needs --modulation"
 QM = {None: 0, "bpsk": 1, "qpsk": 2, "qam16": 4, "qam64": 6, "qam256": 8}[args.modulation]
-matched = bool(QM) and args.algo == "sp" and args.llr_scale is None       # llr_scale = 2 / sd^2 per SNR point
+# llr_scale = 2 / sd^2 per SNR point: sp behind a demapper, bp always (its messages are LLRs)
+matched = ((bool(QM) and args.algo == "sp") or args.algo == "bp") and args.llr_scale is None
 
 layer = 0
 if args.code == "dvbs2_12":
@@ -197,7 +200,7 @@ def point_decoder(sd):
     if dec is not None:
         dec.close()
     scale = 2.0 / (sd * sd)
-    if rm is not None:
+    if rm is not None and args.algo == "sp":                         # exp(llr_scale * fill_llr) must stay finite
         rm.spec.fill_llr = min(10.0, 80.0 / scale)
     dec = make_decoder(scale)
 
@@ -277,6 +280,8 @@ for snr in points:
         es_n0 = 1.0 / (2.0 * sd * sd)
         res.update({"es_n0_db": round(10.0 * np.log10(es_n0), 3), "eb_n0_db": round(10.0 * np.log10(es_n0 / (QM * rate)), 3),
                     "llr_scale": round(2.0 / (sd * sd), 3) if matched else (8.0 if args.llr_scale is None else args.llr_scale)})
+    if md is None and args.algo == "bp":
+        res["llr_scale"] = round(2.0 / (sd * sd), 3) if matched else args.llr_scale
     if tb is not None:
         n = TBS * args.batches
         res.update({"blocks": n, "bler": blocks[1] / n, "blocks_crc_failed": blocks[0], "blocks_undetected": blocks[2],
