@@ -52,7 +52,9 @@
 enum rate_type { rate_1_2, rate_2_3_a, rate_2_3_b, rate_3_4_a, rate_3_4_b, rate_5_6 };
 
 enum decodeType { DecodeCPU, DecodeMS, DecodeSP, DecodeTDMP, DecodeTDMPCL, DecodeMSCL,
-                  DecodeBP /* not in the reference: log-domain sum-product, LDPC_ALGO_BP (include/ldpc_hip.h) */ };
+                  DecodeBP, /* not in the reference: log-domain sum-product, LDPC_ALGO_BP (include/ldpc_hip.h) */
+                  DecodeLayeredBP /* not in the reference: the layered schedule of DecodeTDMPCL (same circulant size) with
+                                     DecodeBP's check node, LDPC_ALGO_LAYERED_BP (include/ldpc_hip.h); fp32 messages only */ };
 
 const int n_b = 24;
 
@@ -75,7 +77,7 @@ public:
      * stopped in (kind LDPC_SOFT_POSTERIOR: positive <-> bit 0, its sign is the decoded bit) or that minus the channel
      * value the decoder read (LDPC_SOFT_EXTRINSIC).  Everything else as decode(), the transport-block check included.
      * DecodeSP returns LDPC_ERR_UNSUPPORTED with lastError() set: sum-product has no usable soft value in the probability
-     * domain; DecodeBP, the log-domain sum-product, gives LLRs (y_n = llrScale * y). */
+     * domain; DecodeBP and DecodeLayeredBP, the log-domain sum-products, give LLRs (y_n = llrScale * y). */
     int decodeSoft(float *postCode, char *srcCode, int srcLength, enum decodeType deType, float *soft, int kind = LDPC_SOFT_POSTERIOR);
 
     /* BPSK + AWGN of standard deviation `rate` on libc rand() (MyLdpc.cpp:1061-1105) */
@@ -87,7 +89,7 @@ public:
 
     /* ---- additions ------------------------------------------------------ */
     void setMaxIterations(int times) { this->times = times; }   /* before addDecodeType */
-    void setLlrScale(float s) { llrScale = s; }                 /* DecodeSP and DecodeBP (2 / sd^2 for BPSK in noise sd); before addDecodeType */
+    void setLlrScale(float s) { llrScale = s; }                 /* DecodeSP, DecodeBP and DecodeLayeredBP (2 / sd^2 for BPSK in noise sd); before addDecodeType */
     void setDevice(int ordinal) { device = ordinal; devices.clear(); }
     /* Several HIP devices behind one Coder (the reference opens devices[0] only, MyLdpc.cpp:235):
      * decode() then cuts the frame stream into one contiguous range per entry and decodes the
@@ -103,12 +105,12 @@ public:
      * ms_scale / ms_offset).  DecodeSP ignores it.  DecodeTDMP on a code whose rows differ in weight runs the
      * layered schedule of DecodeTDMPCL and takes the correction too; where it follows the reference's host-layered
      * path (every row of one weight) it fails in addDecodeType while a correction is set, as DecodeMSCL always
-     * does (both reproduce reference kernels), and as DecodeBP does (LDPC_ERR_UNSUPPORTED: there is no minimum to
+     * does (both reproduce reference kernels), and as DecodeBP and DecodeLayeredBP do (LDPC_ERR_UNSUPPORTED: there is no minimum to
      * correct).  (0, 0) = off.  Before addDecodeType(). */
     void setMinSumCorrection(float scale, float offset) { msScale = scale; msOffset = offset; }
     /* How the decoders addDecodeType makes from here on store their messages (include/ldpc_hip.h: enum ldpc_msg_dtype):
      * LDPC_MSG_F32 (the default, the reference's arithmetic), LDPC_MSG_F16 or LDPC_MSG_F8 (one E4M3 byte per message).
-     * DecodeMS and DecodeCPU take all three, DecodeBP takes F32 and F16, and give the bytes of the C ABI decoder with that
+     * DecodeMS and DecodeCPU take all three, DecodeBP takes F32 and F16 (DecodeLayeredBP, like every layered type, F32 only), and give the bytes of the C ABI decoder with that
      * msg_dtype; with any other decode type a type other than LDPC_MSG_F32 makes addDecodeType fail as ldpc_decoder_create does
      * (LDPC_ERR_UNSUPPORTED; an unknown value: LDPC_ERR_ARG).  Before addDecodeType(). */
     void setMessageType(int msgDtype) { msgType = msgDtype; }
@@ -123,7 +125,7 @@ public:
      * encode() writes E / 8 bytes per frame (E % 8 == 0), test() and decode() take E floats per frame, and
      * getPriorCodeLength / getPostCodeLength follow; getCodeSize is the frame count as before.  erasureLlr: what
      * decode() feeds the decoder at positions that were not received -- 0, or the distinct-value rule of ldpc_hip.h:
-     * pass 1e-6 with DecodeTDMP / DecodeTDMPCL, whose layered arithmetic cannot take an exact 0.  Host buffers go
+     * pass 1e-6 with DecodeTDMP / DecodeTDMPCL, whose layered min-sum arithmetic cannot take an exact 0 (DecodeLayeredBP can).  Host buffers go
      * through ldpc_rate_match / ldpc_rate_recover on the GPU `setDevice` names.  Off by default: without this call every
      * byte and length is as in the reference.  Before forEncoder() and forDecoder().  Returns 0 or an ldpc_status. */
     int setRateMatch(int E, int k0, int punctured = 0, int fillerLo = 0, int fillerHi = 0, float erasureLlr = 0);
@@ -149,7 +151,7 @@ public:
     /* CRC-aided early termination (ldpc_hip.h: crc_kind / crc_bits): with setTransportBlock() every frame carries a CRC,
      * and a frame then also stops in the first round in which its payload and CRC bits pass it -- usually a round before
      * its syndrome is clean.  Needs setTransportBlock() with crcBits != 0 first (LDPC_ERR_STATE otherwise).  DecodeSP,
-     * DecodeMS, DecodeCPU, DecodeBP and DecodeTDMPCL take it, and DecodeTDMP where it runs the layered schedule of DecodeTDMPCL; on
+     * DecodeMS, DecodeCPU, DecodeBP, DecodeLayeredBP and DecodeTDMPCL take it, and DecodeTDMP where it runs the layered schedule of DecodeTDMPCL; on
      * DecodeMSCL, and on DecodeTDMP where it follows the reference's host-layered path, addDecodeType fails while it is
      * on, as with setMinSumCorrection (both reproduce reference kernels).  The decoders then run the streaming kernels.
      * lastCrcStops(): frames of the last decode() that stopped in a round in which their syndrome was not clean.  A frame

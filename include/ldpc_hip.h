@@ -70,8 +70,10 @@ enum ldpc_algo {
                               reference mis-sizes its layers unless every row of H has the same
                               weight (MyLdpc.cpp:907,958): any other H is LDPC_ERR_UNSUPPORTED.
                               fp32, one launch per layer                                    */
-    LDPC_ALGO_BP = 5       /* flooding sum-product in the LOG domain (box-plus check node): this library's own
+    LDPC_ALGO_BP = 5,      /* flooding sum-product in the LOG domain (box-plus check node): this library's own
                               definition, below; streaming kernels, fp32 or LDPC_MSG_F16 messages              */
+    LDPC_ALGO_LAYERED_BP = 6 /* layered (TDMP) schedule with LDPC_ALGO_BP's box-plus check node: this library's own
+                              definition, below; the streaming layered engine, fp32, one launch per layer    */
 };
 
 /* LDPC_ALGO_BP, bit for bit.  The reference's sum-product (LDPC_ALGO_SP) works on probabilities in fp32 and saturates at
@@ -103,9 +105,34 @@ enum ldpc_algo {
  * record kernels are never selected (LDPC_TUNE_ON(FUSED) or LDPC_TUNE_ON(LDSP): LDPC_ERR_UNSUPPORTED), as are
  * LDPC_MSG_F8 and a non-zero ms_scale / ms_offset (there is no minimum to correct). */
 
+/* LDPC_ALGO_LAYERED_BP, bit for bit: the schedule and the bookkeeping of LDPC_ALGO_LAYERED with the row of LDPC_ALGO_BP.
+ * Every operation is fp32, one at a time, no contraction.
+ *   Channel:      chan[n] = llr_scale * y[n], one multiply.  Padding frames read y = 1.  llr_scale NaN, inf or <= 0:
+ *                 LDPC_ERR_ARG.
+ *   Start:        P = chan, R = 0; the initial bits are chan < 0.
+ *   Row update:   for a row of layer l with edges e0 .. e0+D-1 in ascending edge id
+ *                     q_k = P[col_k] - R_k
+ *                     out = the row of LDPC_ALGO_BP (above) applied to x_k = q_k: the clamp t_k on input, the same
+ *                           forward / backward association, D = 2 and D = 1 as there, no storage rounding
+ *                     R_k = out_k,  P[col_k] = q_k + R_k          (q_k as formed, not clamped)
+ *   Rounds:       layers in order; the rows of a layer are independent (a layer whose rows share a column is refused).
+ *   After the last layer of round i: bit = (P < 0), kept current with every write of P; syndrome, freeze rule, iters and
+ *                 the CRC rule exactly as for LDPC_ALGO_LAYERED.
+ *   Soft output:  posterior = P after the last layer of the round the frame stopped in (an LLR); extrinsic = that minus
+ *                 chan[n], where chan[n] is the fp32 product formed first, then one subtraction (never one fma).
+ *   Debug taps:   0 = R, 2 = P, 3 = bits.
+ * A row takes its sign from (x < 0) and never multiplies messages, so -- unlike LDPC_ALGO_LAYERED, whose running fp32
+ * sign product one exact 0 kills -- it takes exact zeros as the flooding decoders do (see erasure_llr below).
+ * Refusals: layer_rows is required (<= 0 or not dividing M: LDPC_ERR_ARG, as for LAYERED).  LDPC_MSG_F16 and LDPC_MSG_F8
+ * are LDPC_ERR_UNSUPPORTED (the layered engine is fp32), as is a non-zero ms_scale / ms_offset.  It always runs the
+ * streaming layered engine: the LDS-resident and record kernels are never selected (the 16-byte check record holds two
+ * minima and cannot hold D independent messages); LDPC_TUNE_ON(FUSED) or LDPC_TUNE_ON(LDSP) is LDPC_ERR_UNSUPPORTED.
+ * crc_kind, early termination on and off, both pack modes, ldpc_decode, ldpc_decode_soft and ldpc_decoder_create_multi
+ * work as for LDPC_ALGO_LAYERED. */
+
 /* How the streaming flooding min-sum decoder (LDPC_ALGO_MS) stores its messages; the arithmetic is fp32 in one
  * operation order for all three.  F16 and F8 are this library's own definitions (the reference is fp32 only) and are
- * LDPC_ERR_UNSUPPORTED with every other algorithm -- except that LDPC_ALGO_BP takes F16 (not F8); the one-launch and record kernels are fp32 and are never selected
+ * LDPC_ERR_UNSUPPORTED with every other algorithm (LDPC_ALGO_LAYERED_BP included: the layered engine is fp32) -- except that LDPC_ALGO_BP takes F16 (not F8); the one-launch and record kernels are fp32 and are never selected
  * for them (F8 with LDPC_TUNE_FUSED / LDPC_TUNE_LDSP forced on: LDPC_ERR_UNSUPPORTED).  An unknown value: LDPC_ERR_ARG.
  *   LDPC_MSG_F16: channel values and variable->check messages are rounded to binary16 (nearest even) where they are
  *     stored, a corrected check->variable magnitude (ms_scale / ms_offset) where it is produced.
@@ -154,7 +181,7 @@ typedef struct ldpc_decoder_config {
     int32_t early_term;     /* 1: frames freeze when their syndrome is clean (reference
                                behaviour, decodeCL.c:27,48-49); 0: always run max_iter      */
     int32_t device;         /* HIP device ordinal                                          */
-    int32_t layer_rows;     /* rows per layer = circulant size z.  Required for LDPC_ALGO_LAYERED / MS_FUSED; with
+    int32_t layer_rows;     /* rows per layer = circulant size z.  Required for LDPC_ALGO_LAYERED / LAYERED_BP / MS_FUSED; with
                                SP / MS it lets the one-launch kernels for quasi-cyclic codes apply (0: streaming) */
     int32_t pack_mode;      /* enum ldpc_pack_mode                                         */
     int32_t frames_per_lane;/* tuning: 0 = auto, else 1, 2 or 4 (tile = 64*frames_per_lane) */
@@ -204,7 +231,7 @@ typedef struct ldpc_decoder_config {
      *      rounded to fp16 where it is produced.  ms_offset is in the units of the channel values passed to
      *      ldpc_decode (with the reference's convention, BPSK +-1 plus noise: units of y, not of LLRs): offset
      *      min-sum depends on the scale of the input, normalized min-sum does not.
-     *      LDPC_ALGO_MS and LDPC_ALGO_LAYERED only (others, LDPC_ALGO_BP among them: LDPC_ERR_UNSUPPORTED when either is
+     *      LDPC_ALGO_MS and LDPC_ALGO_LAYERED only (others, LDPC_ALGO_BP and LDPC_ALGO_LAYERED_BP among them: LDPC_ERR_UNSUPPORTED when either is
      *      non-zero).  The
      *      record kernels and the streaming kernels carry the correction; the LDS-resident one-launch kernels do
      *      not and are not selected (forcing them, LDPC_TUNE_ON(FUSED) with LDPC_TUNE_OFF(LDSP):
@@ -224,7 +251,7 @@ typedef struct ldpc_decoder_config {
      *      frames frozen by either rule; ldpc_decoder_crc_stops those frozen in a round where clean_i was false.
      *      Needs early_term = 1 (LDPC_ERR_ARG otherwise, as for an unknown kind or crc_bits out of range).
      *      Streaming kernels only: LDPC_ALGO_SP, LDPC_ALGO_MS (fp32 and LDPC_MSG_F16, with or without ms_scale /
-     *      ms_offset), LDPC_ALGO_BP (fp32 and LDPC_MSG_F16) and LDPC_ALGO_LAYERED with one launch per layer; one more launch per round (crc_term_kernel).
+     *      ms_offset), LDPC_ALGO_BP (fp32 and LDPC_MSG_F16), and LDPC_ALGO_LAYERED and LDPC_ALGO_LAYERED_BP with one launch per layer; one more launch per round (crc_term_kernel).
      *      LDPC_ALGO_MS_FUSED and LDPC_ALGO_LAYERED_HOST reproduce reference kernels: LDPC_ERR_UNSUPPORTED.  The
      *      LDS-resident one-launch kernels and the record kernels do not carry the rule and are not selected (forcing
      *      them, LDPC_TUNE_ON(FUSED) or LDPC_TUNE_ON(LDSP): LDPC_ERR_UNSUPPORTED).
@@ -376,12 +403,14 @@ int64_t ldpc_out_bytes(int32_t K, int64_t frames, int32_t pack_mode);
  *         (one fp32 multiply, rounded to fp16 with LDPC_MSG_F16): the value is an LLR.
  *       LDPC_ALGO_LAYERED, LDPC_ALGO_LAYERED_HOST, LDPC_ALGO_MS_FUSED: P[n] after the last layer (MS_FUSED: after the
  *         posterior update) of round i_f.
+ *       LDPC_ALGO_LAYERED_BP: P[n] after the last layer of round i_f, an LLR; y_n = chan[n] = llr_scale * y[n], the fp32
+ *         product formed first (the extrinsic value is never one fma).
  *   LDPC_SOFT_EXTRINSIC:  soft = p - y_n, one fp32 subtraction, the same y_n.
  * Consequence: wherever the posterior is finite and not zero, its sign is the output bit.
  * The value is that of round i_f and no later one: a frozen frame's messages keep evolving unread inside the streaming
  * decoders, so it is caught when the frame freezes (0 ulp against the CPU oracle's `post` tap of that round).
  *
- * LDPC_ALGO_SP has no soft output (LDPC_ERR_UNSUPPORTED; LDPC_ALGO_BP is the sum-product that has one): the reference's
+ * LDPC_ALGO_SP has no soft output (LDPC_ERR_UNSUPPORTED; LDPC_ALGO_BP and LDPC_ALGO_LAYERED_BP are the sum-products that have one): the reference's
  * sum-product runs in the probability domain in
  * fp32, and its normalised posterior (f0 - f1) / (f0 + f1) carries nothing by the time a frame stops -- on the
  * BG1-profile test code (N = 1088, 64 frames, llr_scale 8) it is exactly +-1 on 68210 of 69632 values at 3.0 dB, and 0/0
@@ -538,13 +567,16 @@ int64_t ldpc_code_bytes(int32_t N, int64_t frames, int32_t format);
  *   what a decoder reads.  soft and y must not overlap.  Conventions of the channel values as for ldpc_decode:
  *   positive <-> bit 0, so a filler (a known zero) reads +fill_llr.
  * The erasure rule -- why erasure_llr exists.  A position that was never received (punctured, or not reached by a
- *   short transmission) carries no information: 0.  The layered arithmetic the project reproduces from the reference
- *   cannot take an exact 0: a check row's sign is the running product of its inputs (a *= tmp with the message sign
+ *   short transmission) carries no information: 0.  The layered MIN-SUM arithmetic the project reproduces from the
+ *   reference (LDPC_ALGO_LAYERED, LDPC_ALGO_LAYERED_HOST) cannot take an exact 0: a check row's sign is the running product of its inputs (a *= tmp with the message sign
  *   taken from tmp), so one input of exactly 0 zeroes every message of its row for good, and two erased columns of
  *   EQUAL tiny magnitude cancel back to exactly 0 in the layered update.  With erased = 0 LDPC_ALGO_LAYERED fails on
- *   every frame that has a punctured column; the flooding decoders (LDPC_ALGO_SP, LDPC_ALGO_MS, LDPC_ALGO_BP) handle zeros.  Small,
- *   pairwise DISTINCT positive values repair the layered decoders completely (DESIGN.md has the figures):
- *   erasure_llr = 1e-6 is the recommended value whenever a layered decoder reads y; it is harmless for SP, MS and BP.
+ *   every frame that has a punctured column; the flooding decoders (LDPC_ALGO_SP, LDPC_ALGO_MS, LDPC_ALGO_BP) handle zeros, and so
+ *   does LDPC_ALGO_LAYERED_BP, whose rows take their sign from (x < 0): on the 64 frames of the BG1-profile test scenario with
+ *   punctured columns and erasure_llr = 0 it gets all 64 right where LDPC_ALGO_LAYERED gets none.  Small,
+ *   pairwise DISTINCT positive values repair the layered min-sum decoders completely (DESIGN.md has the figures):
+ *   erasure_llr = 1e-6 is the recommended value whenever a layered min-sum decoder reads y; it is harmless for SP, MS, BP
+ *   and LAYERED_BP.
  *   With LDPC_MSG_F16 messages the values collapse to a few fp16 levels and stop being distinct -- the flooding
  *   decoders, the only ones with fp16 messages, do not need the rule.  erasure_llr > 0 needs N <= 2^22 (beyond that
  *   the values are no longer pairwise distinct in fp32): LDPC_ERR_ARG.

@@ -12,7 +12,7 @@ import numpy as np
 from . import _lib
 from ._lib import DecoderConfig, DecodeStats, LdpcError  # noqa: F401
 
-ALGO_SP, ALGO_MS, ALGO_LAYERED, ALGO_MS_FUSED, ALGO_LAYERED_HOST, ALGO_BP = 0, 1, 2, 3, 4, 5
+ALGO_SP, ALGO_MS, ALGO_LAYERED, ALGO_MS_FUSED, ALGO_LAYERED_HOST, ALGO_BP, ALGO_LAYERED_BP = 0, 1, 2, 3, 4, 5, 6
 MSG_F32, MSG_F16, MSG_F8 = 0, 1, 2
 PACK_BYTES, PACK_BITS = 0, 1
 CODE_PACKED, CODE_BITS = 0, 1                              # enum ldpc_code_format
@@ -22,7 +22,7 @@ HOST_INPUT = {"auto": 0, "staged": 1, "lock_pages": 2}     # enum ldpc_host_inpu
 SOFT_POSTERIOR, SOFT_EXTRINSIC = 1, 2                      # enum ldpc_soft_kind
 SOFT_KINDS = {"posterior": SOFT_POSTERIOR, "extrinsic": SOFT_EXTRINSIC}
 ALGOS = {"sp": ALGO_SP, "ms": ALGO_MS, "layered": ALGO_LAYERED, "ms_fused": ALGO_MS_FUSED,
-         "layered_host": ALGO_LAYERED_HOST, "bp": ALGO_BP}
+         "layered_host": ALGO_LAYERED_HOST, "bp": ALGO_BP, "layered_bp": ALGO_LAYERED_BP}
 
 # two-bit fields of ldpc_decoder_config.tune_flags (enum ldpc_tune_field): True forces on, False off
 TUNE_FIELDS = {"fused": 0, "ldsp": 2, "ldsp_ext": 4, "ldsp_pack": 6, "link_narrow": 8, "check_wide": 10,

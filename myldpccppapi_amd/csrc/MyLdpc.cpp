@@ -446,7 +446,8 @@ int Coder::addDecodeType(enum decodeType deType)
     cfg.layer_rows = z;
     cfg.msg_dtype = msgType;                           /* setMessageType(): ldpc_decoder_create refuses what it does not carry */
     cfg.algo = (deType == DecodeSP) ? LDPC_ALGO_SP : (deType == DecodeMS) ? LDPC_ALGO_MS
-               : (deType == DecodeMSCL) ? LDPC_ALGO_MS_FUSED : (deType == DecodeBP) ? LDPC_ALGO_BP : LDPC_ALGO_LAYERED;
+               : (deType == DecodeMSCL) ? LDPC_ALGO_MS_FUSED : (deType == DecodeBP) ? LDPC_ALGO_BP
+               : (deType == DecodeLayeredBP) ? LDPC_ALGO_LAYERED_BP : LDPC_ALGO_LAYERED;
     if (deType == DecodeTDMP) {
         /* The reference's host-layered path (MyLdpc.cpp:889-976) sizes layer l as
          * hRowRange[l + z] - hRowRange[l] (:907, :958): right only when all rows of H have one weight
@@ -466,7 +467,7 @@ int Coder::addDecodeType(enum decodeType deType)
         if (cfg.algo == LDPC_ALGO_LAYERED_HOST)
             return fail(LDPC_ERR_UNSUPPORTED, "addDecodeType: DecodeTDMP follows the reference's host-layered path on "
                         "this code and takes no min-sum correction (setMinSumCorrection); DecodeTDMPCL does");
-        if (cfg.algo != LDPC_ALGO_SP) { cfg.ms_scale = msScale; cfg.ms_offset = msOffset; }   /* DecodeSP: ignored; DecodeBP: refused by ldpc_decoder_create */
+        if (cfg.algo != LDPC_ALGO_SP) { cfg.ms_scale = msScale; cfg.ms_offset = msOffset; }   /* DecodeSP: ignored; DecodeBP, DecodeLayeredBP: refused by ldpc_decoder_create */
     }
     if (crcEarlyStop) {
         if (cfg.algo == LDPC_ALGO_MS_FUSED)
@@ -497,7 +498,7 @@ int Coder::decodeSoft(float *postCode, char *srcCode, int srcLength, enum decode
     if (kind != LDPC_SOFT_POSTERIOR && kind != LDPC_SOFT_EXTRINSIC) return fail(LDPC_ERR_ARG, "decodeSoft: unknown kind");
     if (deType == DecodeSP)
         return fail(LDPC_ERR_UNSUPPORTED, "decodeSoft: DecodeSP works in the probability domain, where the posterior has "
-                    "saturated by the time a frame stops; the min-sum decode types and DecodeBP carry soft output");
+                    "saturated by the time a frame stops; the min-sum decode types, DecodeBP and DecodeLayeredBP carry soft output");
     return decodeFrames(postCode, srcCode, srcLength, deType, soft, kind);
 }
 

@@ -239,7 +239,7 @@ struct ldpc_decoder {
                                            frames stopped by the CRC alone (cfg.crc_kind) */
     ldpc::DevBuf<uint32_t> crc_w;       /* cfg.crc_kind != 0: [crc_bits] column weights of crc_term_kernel (crc_term_host.hpp) */
 
-    ldpc::LayeredPlan layered;          /* LDPC_ALGO_LAYERED, streaming (one launch per layer) */
+    ldpc::LayeredPlan layered;          /* LDPC_ALGO_LAYERED / LAYERED_HOST / LAYERED_BP, streaming (one launch per layer) */
     ldpc::FusedPlan fused;              /* LDPC_ALGO_LAYERED, short QC codes: whole decode in LDS */
     bool use_fused = false;
     ldpc::LdspPlan ldsp;                /* LDPC_ALGO_LAYERED, mid-size QC codes: posterior in LDS, check records in cache */

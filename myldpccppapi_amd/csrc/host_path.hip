@@ -150,7 +150,8 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
     ldpc::PageLockRegistry &registry = ldpc::PageLockRegistry::instance();
     /* a finished group's bytes go from the pinned slot to the caller's buffers */
     ldpc::CallCounts counts;
-    const bool flooding_counts = !d->use_fused && d->cfg.algo != LDPC_ALGO_LAYERED && d->cfg.algo != LDPC_ALGO_LAYERED_HOST;
+    const bool flooding_counts = !d->use_fused && d->cfg.algo != LDPC_ALGO_LAYERED && d->cfg.algo != LDPC_ALGO_LAYERED_HOST &&
+                                 d->cfg.algo != LDPC_ALGO_LAYERED_BP;
     auto drain = [&](ldpc::HostSlot &sl) -> int {
         if (!sl.busy) return LDPC_OK;
         sl.busy = false;
@@ -413,7 +414,7 @@ int ldpc_decode_soft(ldpc_decoder *d, const float *llr_host, int64_t frames, uin
         return set_error(LDPC_ERR_ARG, "unknown soft_kind %d", soft_kind);
     if (d->cfg.algo == LDPC_ALGO_SP)
         return set_error(LDPC_ERR_UNSUPPORTED, "soft output: LDPC_ALGO_SP has no usable soft value (include/ldpc_hip.h); "
-                    "the min-sum algorithms and LDPC_ALGO_BP carry it");
+                    "the min-sum algorithms, LDPC_ALGO_BP and LDPC_ALGO_LAYERED_BP carry it");
     if (d->tm.tap_iter) return set_error(LDPC_ERR_STATE, "soft output while a debug tap is set");
     if (frames > 0 && !soft_host) return set_error(LDPC_ERR_ARG, "soft is NULL");
     if (frames > 0 && soft_floats < frames * (int64_t)d->N)

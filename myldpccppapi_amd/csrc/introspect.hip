@@ -74,7 +74,7 @@ int ldpc_decoder_stats(ldpc_decoder *d, ldpc_decode_stats *st)
      * at kernel entry): counted on the device with early termination, all launched rounds without; the
      * one-launch kernels (frames leave individually inside the launch) report 0 */
     st->frame_rounds = 0;
-    if (!d->use_fused && d->cfg.algo != LDPC_ALGO_LAYERED && d->cfg.algo != LDPC_ALGO_LAYERED_HOST) {
+    if (!d->use_fused && d->cfg.algo != LDPC_ALGO_LAYERED && d->cfg.algo != LDPC_ALGO_LAYERED_HOST && d->cfg.algo != LDPC_ALGO_LAYERED_BP) {
         st->frame_rounds = d->cfg.early_term ? (int64_t)summary[2] * d->F
                                              : (int64_t)d->last_iterations * d->last_tiles * d->F;
         for (const ldpc_decoder *p = d->flood.handed_to; p; p = p->flood.handed_to) {      /* the child, and whom it handed over to */
@@ -145,12 +145,12 @@ int ldpc_decoder_kernel_times(ldpc_decoder *d, ldpc_kernel_time *out, int32_t ca
     const char *phase_name[] = {"check_kernel", "var_kernel", d->ms_corr ? "layer_corr_kernel" : "layer_kernel", "other",
                                 link_form == 2 ? "check_link_half_kernel"
                                 : link_form ? "check_link_narrow_kernel" : "check_link_kernel"};
-    static const char *algo_name_f32[] = {"sp", "ms", "layered", "ms_fused", "layered_host", "bp"};
-    static const char *algo_name_f16[] = {"sp16", "ms16", "layered16", "ms_fused16", "layered_host16", "bp16"};
-    static const char *algo_name_corr_f32[] = {"sp", "msc", "layered", "ms_fused", "layered_host", "bp"};  /* kAlgoMSC; index = enum ldpc_algo */
-    static const char *algo_name_corr_f16[] = {"sp16", "msc16", "layered16", "ms_fused16", "layered_host16", "bp16"};
-    static const char *algo_name_f8[] = {"sp8", "ms8", "layered8", "ms_fused8", "layered_host8", "bp8"};
-    static const char *algo_name_corr_f8[] = {"sp8", "msc8", "layered8", "ms_fused8", "layered_host8", "bp8"};
+    static const char *algo_name_f32[] = {"sp", "ms", "layered", "ms_fused", "layered_host", "bp", "layered_bp"};
+    static const char *algo_name_f16[] = {"sp16", "ms16", "layered16", "ms_fused16", "layered_host16", "bp16", "layered_bp16"};
+    static const char *algo_name_corr_f32[] = {"sp", "msc", "layered", "ms_fused", "layered_host", "bp", "layered_bp"};  /* kAlgoMSC; index = enum ldpc_algo */
+    static const char *algo_name_corr_f16[] = {"sp16", "msc16", "layered16", "ms_fused16", "layered_host16", "bp16", "layered_bp16"};
+    static const char *algo_name_f8[] = {"sp8", "ms8", "layered8", "ms_fused8", "layered_host8", "bp8", "layered_bp8"};
+    static const char *algo_name_corr_f8[] = {"sp8", "msc8", "layered8", "ms_fused8", "layered_host8", "bp8", "layered_bp8"};
     const int msz = d->flood.msg_size;
     const char **algo_name = d->ms_corr ? (msz == 1 ? algo_name_corr_f8 : msz == 2 ? algo_name_corr_f16 : algo_name_corr_f32)
                                         : (msz == 1 ? algo_name_f8 : msz == 2 ? algo_name_f16 : algo_name_f32);
@@ -290,7 +290,7 @@ int ldpc_decoder_dump(ldpc_decoder *d, int32_t which, float *host_out, int64_t c
         LDPC_HIP_TRY(hipMemcpy(host_out, src, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
         return LDPC_OK;
     }
-    if (d->cfg.algo == LDPC_ALGO_LAYERED || d->cfg.algo == LDPC_ALGO_LAYERED_HOST) {
+    if (d->cfg.algo == LDPC_ALGO_LAYERED || d->cfg.algo == LDPC_ALGO_LAYERED_HOST || d->cfg.algo == LDPC_ALGO_LAYERED_BP) {
         hipError_t e = ldpc::layered_dump(&d->layered, which, host_out, count, frames, d->hard.p,
                                           d->h_cols.data());
         if (e == hipErrorInvalidValue) return set_error(LDPC_ERR_ARG, "bad `which`/count for layered dump");

@@ -20,6 +20,8 @@
  * segments are gathered.  16*E bytes per frame-iteration (R and P each read and
  * written once per edge).  Frozen frames keep their hard bits (bit masks), their
  * P/R keep evolving unread -- no per-lane predication in the hot loop.
+ *
+ * LDPC_ALGO_LAYERED_BP (layer_bp_kernel, below) is the same engine with the box-plus row of flood_check.hpp.
  */
 #pragma once
 
@@ -93,6 +95,24 @@ __global__ __launch_bounds__(kBlock) void layer_corr_kernel_generic(const LayerA
 #include "layer_kernel_generic.inc"
 }
 
+/* Layered log-domain sum-product (LDPC_ALGO_LAYERED_BP, include/ldpc_hip.h has the rule bit for bit): the schedule, the
+ * memory behaviour and the bookkeeping of layer_kernel with the row of LDPC_ALGO_BP (check_bp, flood_check.hpp) on
+ * x_k = q_k = P[col_k] - R_k: R_k = out_k, P[col_k] = q_k + R_k.  The row's sign comes from (x < 0), never from a
+ * product of messages, so an exact 0 does not kill a row. */
+template <int D, int V>
+__global__ __launch_bounds__(kBlock) void layer_bp_kernel(const LayerArgs a)
+{
+#include "layer_bp_kernel.inc"
+}
+
+/* Rows of any degree with run-time loops.  The update is in place, so the order matters: k ascends, the forward value
+ * f_{k-1} is carried in registers, and b_{k+1} is rebuilt from the row's end out of q_j = P[col_j] - R_j for j > k. */
+template <int V>
+__global__ __launch_bounds__(kBlock) void layer_bp_kernel_generic(const LayerArgs a)
+{
+#include "layer_bp_kernel_generic.inc"
+}
+
 /* hardDecisionTDMP, decodeCL.c:261-280, after the last layer of an iteration: P > 0 -> 0, P < 0 -> 1,
  * otherwise (0, NaN) the bit stays; frozen frames keep theirs.  One wave per column. */
 template <int V>
@@ -127,40 +147,35 @@ struct LayeredInitArgs {
     int32_t zero_bits;              /* host-layered path: bits start at 0 (the reference: undefined) */
 };
 
-/* lP = postCode (decodeCL.c:331-334), transposed into the tile layout; bits = y < 0. */
+/* lP = postCode (decodeCL.c:331-334), transposed into the tile layout; bits = y < 0.  SCALED (LDPC_ALGO_LAYERED_BP): the
+ * value is chan = scale * y, one fp32 multiply, padding frames included; the other algorithms' kernel has no multiply. */
 template <int V>
 __global__ __launch_bounds__(kBlock) void layered_init_kernel(const LayeredInitArgs a)
 {
-    constexpr int F = 64 * V;
-    constexpr int LD = F + 1;
-    __shared__ float patch[kInitCols * LD];
-    const int tile = blockIdx.y;
-    const int n0 = blockIdx.x * kInitCols;
-    {
-        const int c = threadIdx.x & (kInitCols - 1);
-        const int n = n0 + c;
-        for (int f = threadIdx.x / kInitCols; f < F; f += kBlock / kInitCols) {
-            const int64_t frame = (int64_t)tile * F + f;
-            float y = 1.0f;
-            if (frame < a.frames && n < a.N) y = a.llr[(size_t)frame * a.N + n];
-            patch[c * LD + f] = y;
-        }
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    for (int c = threadIdx.x >> 6; c < kInitCols; c += kWavesPerBlock) {
-        const int n = n0 + c;
-        if (n >= a.N) break;
-        float y[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) y[v] = patch[c * LD + lane * V + v];
-        vstore<V>(a.P + ((size_t)tile * a.N + n) * F + (size_t)lane * V, y);
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            const uint64_t w = __ballot(y[v] < 0.0f);
-            if (lane == 0) a.hard[((size_t)tile * a.N + n) * V + v] = a.zero_bits ? 0ull : w;
-        }
-    }
+    constexpr bool SCALED = false;
+    const float scale = 1.0f;
+#include "layered_init_kernel.inc"
+}
+template <int V>
+__global__ __launch_bounds__(kBlock) void layered_init_scaled_kernel(const LayeredInitArgs a, const float scale)
+{
+    constexpr bool SCALED = true;
+#include "layered_init_kernel.inc"
+}
+
+/* LDPC_ALGO_LAYERED_BP, extrinsic soft output: soft_settle_kernel leaves the posterior of every frame's stop round in the
+ * caller's buffer (each value written once); this one pass afterwards subtracts chan = scale * y -- the fp32 product
+ * formed first, then one subtraction.  The empty asm keeps the product a value of its own: contracted into an fma the
+ * difference would be rounded once, from the exact product. */
+template <int kUnused = 0>
+__global__ __launch_bounds__(kBlock) void layered_bp_extrinsic_kernel(float *__restrict__ soft, const float *__restrict__ llr,
+                                                                      const float scale, int64_t count)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= count) return;
+    float chan = scale * llr[i];
+    asm volatile("" : "+v"(chan));
+    soft[i] = soft[i] - chan;
 }
 
 /* ------------------------------------------------------------- host side */
@@ -179,6 +194,8 @@ struct LayeredPlan {
     int host_arith = 0;             /* 1: LDPC_ALGO_LAYERED_HOST (layer_kernel<.., HOST = true>) */
     int corr = 0;                   /* 1: normalized / offset min-sum (layer_corr_kernel) with these: */
     float ms_scale = 1.0f, ms_offset = 0.0f;
+    int bp = 0;                     /* 1: LDPC_ALGO_LAYERED_BP (layer_bp_kernel), chan = llr_scale * y: */
+    float llr_scale = 1.0f;
     DevBuf<float> P, R;
     std::vector<LayerGroup> groups; /* ordered by layer */
 };
@@ -255,6 +272,12 @@ template <int V, int D> struct LayerCorrTable {
 template <int V> struct LayerCorrTable<V, 0> {
     static void fill(LayerCorrFn *t) { t[0] = layer_corr_kernel_generic<V>; }
 };
+template <int V, int D> struct LayerBpTable {
+    static void fill(LayerFn *t) { t[D] = layer_bp_kernel<D, V>; LayerBpTable<V, D - 1>::fill(t); }
+};
+template <int V> struct LayerBpTable<V, 0> {
+    static void fill(LayerFn *t) { t[0] = layer_bp_kernel_generic<V>; }
+};
 
 
 template <int V> __global__ void layered_summary_kernel(const int32_t *iters, const uint64_t *done,
@@ -277,7 +300,8 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
     const size_t slot = (size_t)pl->T * V;
     LayerFn table[kMaxUnrolledLayerDegree + 1];
     LayerCorrFn corr_table[kMaxUnrolledLayerDegree + 1];
-    if (pl->host_arith) LayerTable<V, kMaxUnrolledLayerDegree, true>::fill(table);
+    if (pl->bp) LayerBpTable<V, kMaxUnrolledLayerDegree>::fill(table);
+    else if (pl->host_arith) LayerTable<V, kMaxUnrolledLayerDegree, true>::fill(table);
     else LayerTable<V, kMaxUnrolledLayerDegree>::fill(table);
     LayerCorrTable<V, kMaxUnrolledLayerDegree>::fill(corr_table);
     const MsCorr corr{pl->ms_scale, pl->ms_offset};
@@ -289,7 +313,8 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
     {
         LayeredInitArgs ia{r.llr_dev, pl->P.p, r.hard, r.frames, pl->N, pl->host_arith};
         dim3 grid((pl->N + kInitCols - 1) / kInitCols, tiles);
-        layered_init_kernel<V><<<grid, kBlock, 0, s>>>(ia);
+        if (pl->bp) layered_init_scaled_kernel<V><<<grid, kBlock, 0, s>>>(ia, pl->llr_scale);
+        else layered_init_kernel<V><<<grid, kBlock, 0, s>>>(ia);
         StateArgs st{r.done, nullptr, r.iters, nullptr, r.frames, 0, r.max_iter, 1};
         state_kernel<V><<<tiles, 64, 0, s>>>(st);
     }
@@ -327,13 +352,17 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
              * verdict; the frames that settle now leave P -- the posterior after the round's last layer, which later
              * rounds overwrite -- in the caller's buffer.  In the last round launched every running frame settles. */
             SoftArgs so{pl->P.p, nullptr, nullptr, nullptr, r.done, (r.early_term && it < rounds) ? fw : nullptr, r.soft,
-                        r.llr_dev, nullptr, nullptr, pl->E, r.frames, pl->N, r.soft_extrinsic, TailRef{nullptr, 0, 0}};
+                        r.llr_dev, nullptr, nullptr, pl->E, r.frames, pl->N, pl->bp ? 0 : r.soft_extrinsic, TailRef{nullptr, 0, 0}};
             if (r.span_begin && (e = r.span_begin(r.span_ctx, s, /*soft_settle_kernel*/ 7, 0,(int64_t)8 * pl->N * r.frames))) return e;
             soft_settle_kernel<V, float><<<dim3((unsigned)((pl->N + kInitCols - 1) / kInitCols), (unsigned)tiles), kBlock, 0, s>>>(so);
             if (r.span_end && (e = r.span_end(r.span_ctx, s))) return e;
         }
         StateArgs st{r.done, fw, r.iters, nullptr, r.frames, it, r.max_iter, 1};
         state_kernel<V><<<tiles, 64, 0, s>>>(st);
+    }
+    if (pl->bp && r.soft && r.soft_extrinsic) {     /* posterior - chan, chan = llr_scale * y (layered_bp_extrinsic_kernel) */
+        const int64_t count = r.frames * (int64_t)pl->N;
+        layered_bp_extrinsic_kernel<><<<(unsigned)((count + kBlock - 1) / kBlock), kBlock, 0, s>>>(r.soft, r.llr_dev, pl->llr_scale, count);
     }
     *launched = rounds;
     PackArgs pa{r.hard, r.out_dev, r.iters, r.iters_dev, r.frames, r.out_bytes, pl->N, r.K, r.pack_mode};

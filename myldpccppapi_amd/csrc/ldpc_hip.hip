@@ -41,7 +41,7 @@ int pick_frames_per_lane(const ldpc_decoder_config &cfg, int32_t max_row_deg, in
      * fill them and the register arrays of the unrolled kernels stay moderate.  Flooding check
      * kernels run in narrow waves, so only the column degree counts there; the layered kernel
      * holds a whole row (P and R) per lane. */
-    int deg = cfg.algo == LDPC_ALGO_LAYERED ? max_row_deg : max_col_deg;
+    int deg = (cfg.algo == LDPC_ALGO_LAYERED || cfg.algo == LDPC_ALGO_LAYERED_BP) ? max_row_deg : max_col_deg;
     if (cfg.algo == LDPC_ALGO_MS || cfg.algo == LDPC_ALGO_BP) deg = (deg + 1) / 2;   /* min-sum variable nodes (BP's too) need half the registers */
     /* fp8 messages: 4 values are one dword per lane, the least a lane should move -- from one full tile on */
     if (cfg.msg_dtype == LDPC_MSG_F8 && cfg.max_batch >= 256 && deg <= 8) return 4;
@@ -212,7 +212,8 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     if (cfg->max_batch <= 0) return set_error(LDPC_ERR_ARG, "max_batch must be positive");
     if (cfg->max_iter <= 0 || cfg->max_iter > 100000) return set_error(LDPC_ERR_ARG, "max_iter out of range");
     if (cfg->algo != LDPC_ALGO_SP && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED &&
-        cfg->algo != LDPC_ALGO_MS_FUSED && cfg->algo != LDPC_ALGO_LAYERED_HOST && cfg->algo != LDPC_ALGO_BP)
+        cfg->algo != LDPC_ALGO_MS_FUSED && cfg->algo != LDPC_ALGO_LAYERED_HOST && cfg->algo != LDPC_ALGO_BP &&
+        cfg->algo != LDPC_ALGO_LAYERED_BP)
         return set_error(LDPC_ERR_ARG, "unknown algo %d", cfg->algo);
     /* comparisons written so that NaN fails them */
     if (!(cfg->ms_scale >= 0.0f && cfg->ms_scale <= 1.0f))
@@ -222,9 +223,13 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     const bool ms_corr = cfg->ms_scale != 0.0f || cfg->ms_offset != 0.0f;
     if (ms_corr && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED)
         return set_error(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset apply to LDPC_ALGO_MS and LDPC_ALGO_LAYERED only "
-                    "(SP and BP have no minimum to correct; MS_FUSED and LAYERED_HOST reproduce reference kernels)");
-    if (cfg->algo == LDPC_ALGO_BP && !(cfg->llr_scale > 0.0f && cfg->llr_scale <= 3.402823466e38f))
-        return set_error(LDPC_ERR_ARG, "LDPC_ALGO_BP: llr_scale must be positive and finite (chan = llr_scale * y is the LLR)");
+                    "(SP, BP and LAYERED_BP have no minimum to correct; MS_FUSED and LAYERED_HOST reproduce reference kernels)");
+    const bool bp_row = cfg->algo == LDPC_ALGO_BP || cfg->algo == LDPC_ALGO_LAYERED_BP;      /* box-plus check node */
+    if (bp_row && !(cfg->llr_scale > 0.0f && cfg->llr_scale <= 3.402823466e38f))
+        return set_error(LDPC_ERR_ARG, "%s: llr_scale must be positive and finite (chan = llr_scale * y is the LLR)",
+                    cfg->algo == LDPC_ALGO_BP ? "LDPC_ALGO_BP" : "LDPC_ALGO_LAYERED_BP");
+    if (cfg->algo == LDPC_ALGO_LAYERED_BP && (cfg->layer_rows <= 0 || g->M % cfg->layer_rows))
+        return set_error(LDPC_ERR_ARG, "LDPC_ALGO_LAYERED_BP: layer_rows=%d must be positive and divide M=%d", cfg->layer_rows, g->M);
     if (cfg->algo == LDPC_ALGO_LAYERED_HOST) {
         for (int32_t m = 1; m < g->M; ++m)
             if (g->row_ptr[m + 1] - g->row_ptr[m] != g->row_ptr[1] - g->row_ptr[0])
@@ -242,15 +247,16 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         return set_error(LDPC_ERR_ARG, "unknown msg_dtype %d", cfg->msg_dtype);
     if (cfg->msg_dtype == LDPC_MSG_F8 && cfg->algo != LDPC_ALGO_MS)
         return set_error(LDPC_ERR_UNSUPPORTED, "fp8 messages are built for flooding min-sum only "
-                    "(the probability-domain SP needs fp32 range; BP is fp32 / fp16; the layered and reference-reproducing decoders are fp32)");
+                    "(the probability-domain SP needs fp32 range; BP is fp32 / fp16; the layered decoders, LAYERED_BP among them, and the "
+                    "reference-reproducing ones are fp32)");
     if (cfg->msg_dtype == LDPC_MSG_F16 && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_BP)
         return set_error(LDPC_ERR_UNSUPPORTED, "fp16 messages are built for flooding min-sum and BP only "
-                    "(the probability-domain SP needs fp32 range; layered: not yet)");
+                    "(the probability-domain SP needs fp32 range; the layered engine, LAYERED and LAYERED_BP, is fp32)");
     if (!ldpc::tune_valid(*cfg)) return set_error(LDPC_ERR_ARG, "tuning / streams config fields out of range");
-    if (cfg->algo == LDPC_ALGO_BP) {
+    if (bp_row) {
         const ldpc::Tune t = ldpc::tune_from_config(*cfg);
         if (ldpc::tune_forced_on(t.fused) || ldpc::tune_forced_on(t.ldsp))
-            return set_error(LDPC_ERR_UNSUPPORTED, "LDPC_ALGO_BP: the LDS-resident one-launch kernels and the record kernels (LDPC_TUNE_FUSED / "
+            return set_error(LDPC_ERR_UNSUPPORTED, "LDPC_ALGO_BP / LDPC_ALGO_LAYERED_BP: the LDS-resident one-launch kernels and the record kernels (LDPC_TUNE_FUSED / "
                         "LDPC_TUNE_LDSP forced on) carry no box-plus check node; the streaming kernels do");
     }
     if (cfg->msg_dtype == LDPC_MSG_F8) {
@@ -266,7 +272,7 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         if (ldpc::crc_term_check(cfg->crc_kind, cfg->crc_bits, cfg->K, cfg->early_term, msg, sizeof msg)) return set_error(LDPC_ERR_ARG, "%s", msg);
         if (crc_term && (cfg->algo == LDPC_ALGO_MS_FUSED || cfg->algo == LDPC_ALGO_LAYERED_HOST))
             return set_error(LDPC_ERR_UNSUPPORTED, "crc_kind: LDPC_ALGO_MS_FUSED and LDPC_ALGO_LAYERED_HOST reproduce reference kernels, which "
-                        "stop on the syndrome alone; LDPC_ALGO_SP, LDPC_ALGO_MS, LDPC_ALGO_BP and LDPC_ALGO_LAYERED carry the CRC rule");
+                        "stop on the syndrome alone; LDPC_ALGO_SP, LDPC_ALGO_MS, LDPC_ALGO_BP, LDPC_ALGO_LAYERED and LDPC_ALGO_LAYERED_BP carry the CRC rule");
         const ldpc::Tune t = ldpc::tune_from_config(*cfg);
         if (crc_term && (ldpc::tune_forced_on(t.fused) || ldpc::tune_forced_on(t.ldsp)))
             return set_error(LDPC_ERR_UNSUPPORTED, "crc_kind: the LDS-resident one-launch kernels and the record kernels (LDPC_TUNE_FUSED / "
@@ -356,8 +362,12 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
                             "posteriors fit in LDS");
         }
         d->use_fused = true;
-    } else if (cfg->algo == LDPC_ALGO_LAYERED_HOST) {
-        d->layered.host_arith = 1;
+    } else if (cfg->algo == LDPC_ALGO_LAYERED_HOST || cfg->algo == LDPC_ALGO_LAYERED_BP) {
+        /* the streaming layered engine always.  LAYERED_BP: the record kernels' 16-byte check record holds two minima and
+         * cannot hold a row's D independent messages, and the LDS-resident kernel carries no box-plus row */
+        d->layered.host_arith = cfg->algo == LDPC_ALGO_LAYERED_HOST;
+        d->layered.bp = cfg->algo == LDPC_ALGO_LAYERED_BP;
+        d->layered.llr_scale = cfg->llr_scale;
         int rc = ldpc::layered_plan_create(&d->layered, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows, d->T, d->V);
         if (rc == -1) return set_error(LDPC_ERR_ARG, "layer_rows=%d must divide M=%d and rows of a layer "
                                   "must not share a column", cfg->layer_rows, g->M);
@@ -586,7 +596,7 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
                             : ldpc::engine_fused_run(&d->fused, run, s, &d->last_iterations);
         if (e == hipSuccess) e = ldpc::span_end(d, s);
         rc = (e == hipSuccess) ? LDPC_OK : set_error(LDPC_ERR_HIP, "fused decode: %s", hipGetErrorString(e));
-    } else if (d->cfg.algo == LDPC_ALGO_LAYERED || d->cfg.algo == LDPC_ALGO_LAYERED_HOST) {
+    } else if (d->cfg.algo == LDPC_ALGO_LAYERED || d->cfg.algo == LDPC_ALGO_LAYERED_HOST || d->cfg.algo == LDPC_ALGO_LAYERED_BP) {
         ldpc::LayeredRun run;
         run.span_begin = [](void *c, hipStream_t st, int kind, int deg, int64_t bytes) {
             return ldpc::span_begin((ldpc_decoder *)c, st, kind, deg, bytes);
@@ -625,7 +635,7 @@ int ldpc_decode_soft_device(ldpc_decoder *d, const float *llr_dev, int64_t frame
     if (d->cfg.algo == LDPC_ALGO_SP)
         return set_error(LDPC_ERR_UNSUPPORTED, "soft output: LDPC_ALGO_SP works in the probability domain in fp32, where the "
                     "posterior saturates to exactly +-1 on nearly every bit of a frame that converges and is 0/0 on frames "
-                    "that do not; the min-sum algorithms (MS, MS_FUSED, LAYERED, LAYERED_HOST) and the log-domain LDPC_ALGO_BP carry it");
+                    "that do not; the min-sum algorithms (MS, MS_FUSED, LAYERED, LAYERED_HOST) and the log-domain LDPC_ALGO_BP / LDPC_ALGO_LAYERED_BP carry it");
     if (d->tm.tap_iter)
         return set_error(LDPC_ERR_STATE, "soft output while a debug tap is set (ldpc_decoder_set_tap(d, 0) clears it)");
     if (frames < 0 || frames > d->cfg.max_batch)

@@ -7,7 +7,7 @@ b is frame b*frames + f of the seed's stream, so a point can be extended or re-r
 and errors counted by ldpc_count_errors_device; nothing crosses PCIe but the counts.  The
 reference counts differing BYTES (Test.cpp:105-110); this prints byte errors too.
 
-    python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N>] [--algo sp|ms|layered|bp]
+    python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N>] [--algo sp|ms|layered|bp|layered_bp]
                               [--payload zero|random] [--rate-match P,FLO,FHI,E[,K0]] [--erasure-llr X]
                               [--modulation bpsk|qpsk|qam16|qam64|qam256] [--no-interleave] [--transport-block A[,C]] [--crc-stop]
                               [--msg-dtype f32|f16|f8] [--soft-check]
@@ -25,6 +25,8 @@ the decoder's llr_scale follows the noise, 2 / sd^2 per point (and the fillers r
 bits of a QAM symbol are not equally protected.
 --algo bp (the log-domain sum-product, include/ldpc_hip.h: LDPC_ALGO_BP) reads LLRs: its llr_scale follows the noise, 2 / sd^2
 per point, with any modulation and with none, unless --llr-scale is given; --msg-dtype f16, --soft-check and --crc-stop apply.
+--algo layered_bp (LDPC_ALGO_LAYERED_BP: the layered schedule with bp's check node) reads LLRs in the same way; like --algo
+layered it needs a code with a circulant size (bg1, wimax:...), it is fp32 only, and it takes exact zeros (no --erasure-llr).
 --transport-block A[,C] (with --payload random): the random bytes are transport blocks of A payload bits; ldpc_tb_attach_device
 in front of the encoder adds the transport block's CRC, cuts it into C code blocks with CRC24B each (C omitted: the rule of
 ldpc_tb_spec_init) and fills up to K with zeros; ldpc_tb_check_device and ldpc_tb_tally_device behind the decoder judge the
@@ -79,7 +81,7 @@ assert args.transport_block or not args.crc_stop, "--crc-stop needs --transport-
 assert args.modulation or not args.no_interleave, "--no-interleave needs --modulation"
 QM = {None: 0, "bpsk": 1, "qpsk": 2, "qam16": 4, "qam64": 6, "qam256": 8}[args.modulation]
 # llr_scale = 2 / sd^2 per SNR point: sp behind a demapper, bp always (its messages are LLRs)
-matched = ((bool(QM) and args.algo == "sp") or args.algo == "bp") and args.llr_scale is None
+matched = ((bool(QM) and args.algo == "sp") or args.algo in ("bp", "layered_bp")) and args.llr_scale is None
 
 layer = 0
 if args.code == "dvbs2_12":
@@ -98,6 +100,7 @@ else:
     K, M, layer = codes.wimax_dims(rate, N)
     rows, cols = codes.wimax_edges(rate, N)
 M = N - K
+assert layer or args.algo not in ("layered", "layered_bp"), "--algo %s needs the code's circulant size z: --code bg1 or wimax:<rate>:<N>" % args.algo
 g = L.Graph(rows, cols, M, N)
 B = args.frames
 tb = None
@@ -280,7 +283,7 @@ for snr in points:
         es_n0 = 1.0 / (2.0 * sd * sd)
         res.update({"es_n0_db": round(10.0 * np.log10(es_n0), 3), "eb_n0_db": round(10.0 * np.log10(es_n0 / (QM * rate)), 3),
                     "llr_scale": round(2.0 / (sd * sd), 3) if matched else (8.0 if args.llr_scale is None else args.llr_scale)})
-    if md is None and args.algo == "bp":
+    if md is None and args.algo in ("bp", "layered_bp"):
         res["llr_scale"] = round(2.0 / (sd * sd), 3) if matched else args.llr_scale
     if tb is not None:
         n = TBS * args.batches
