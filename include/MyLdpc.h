@@ -79,6 +79,14 @@ public:
      * DecodeSP returns LDPC_ERR_UNSUPPORTED with lastError() set: sum-product has no usable soft value in the probability
      * domain; DecodeBP and DecodeLayeredBP, the log-domain sum-products, give LLRs (y_n = llrScale * y). */
     int decodeSoft(float *postCode, char *srcCode, int srcLength, enum decodeType deType, float *soft, int kind = LDPC_SOFT_POSTERIOR);
+    /* decode() / decodeSoft() on channel values as receivers deliver them (ldpc_hip.h: enum ldpc_llr_type, ldpc_decode_typed):
+     * postCode holds getPostCodeLength(srcLength) elements of llrType -- LDPC_LLR_I8 (int8_t), LDPC_LLR_F16 (binary16) or
+     * LDPC_LLR_F32 (llrUnit exactly 1: the call is decode()) -- and the decoder reads y = x * llrUnit, one fp32 multiply,
+     * then does exactly what decode() does with that y.  A quarter (half) of the bytes cross the bus.  Not under
+     * setRateMatch(), whose recovery sums floats: LDPC_ERR_UNSUPPORTED. */
+    int decodeTyped(const void *postCode, int llrType, float llrUnit, char *srcCode, int srcLength, enum decodeType deType);
+    int decodeSoftTyped(const void *postCode, int llrType, float llrUnit, char *srcCode, int srcLength, enum decodeType deType,
+                        float *soft, int kind = LDPC_SOFT_POSTERIOR);
 
     /* BPSK + AWGN of standard deviation `rate` on libc rand() (MyLdpc.cpp:1061-1105) */
     int test(char *priorCode, float *postCode, int priorCodeLength, float rate);
@@ -174,7 +182,8 @@ public:
 private:
     int initCheckMatrix();
     int encodeOnce(const char *src, char *code, int srcLength);
-    int decodeFrames(float *postCode, char *srcCode, int srcLength, enum decodeType deType, float *soft, int kind);
+    int decodeFrames(const void *postCode, int llrType, float llrUnit, char *srcCode, int srcLength, enum decodeType deType,
+                     float *soft, int kind);
     int fail(int code, const std::string &msg);
 
     int times;

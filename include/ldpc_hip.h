@@ -431,6 +431,56 @@ int ldpc_decode_soft_device(ldpc_decoder *d, const float *llr_dev, int64_t frame
 int ldpc_decode_soft(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t *out_host, int64_t out_bytes,
                      int32_t *iters, float *soft_host, int64_t soft_floats, int32_t soft_kind);
 
+/* ---- typed channel values: int8 and fp16 input for every decode entry point -------------------------------------
+ * Receivers deliver int8 (sometimes fp16) soft bits; widened to fp32 on the host they cost four (two) times the bytes on
+ * every bus in front of a decoder whose first kernel rounds them to fp16 or E4M3 again.  A typed call names the element
+ * type of its channel buffer and a unit.  The rule, bit for bit: for element x[f * N + n] the decoder reads
+ *       y = (float)x * llr_unit          one fp32 multiply; the widening is exact
+ * and everything else is exactly what the handle does when ldpc_decode_device is given that y: SP forms
+ * exp(llr_scale * y), BP and LAYERED_BP form chan = llr_scale * y, min-sum stores y; with LDPC_MSG_F16 / LDPC_MSG_F8 the
+ * value is rounded where it is stored.  Two roundings, never one: the product x * llr_unit is a value of its own, never
+ * folded with llr_scale and never contracted into the conversion to fp16.  Padding frames read y = +1.0f exactly, not
+ * 1 * llr_unit.  Soft output, extrinsic kind: the y_n of the rule above is this product (BP, LAYERED_BP: llr_scale * y).
+ *   LDPC_LLR_I8:  all 256 codes are legal; -128 reads -128 * llr_unit.  Any alignment.
+ *   LDPC_LLR_F16: binary16; infinities and NaN widen as they are.  Two-byte alignment and no more (an odd address:
+ *                 LDPC_ERR_ARG).
+ *   LDPC_LLR_F32: llr_unit must be exactly 1.0f, and the call IS ldpc_decode_device / ldpc_decode.
+ *   LDPC_ERR_ARG (nothing enqueued): an unknown type; llr_unit NaN, infinite or <= 0; what the plain entry points refuse.
+ *   The soft forms refuse a soft buffer that overlaps the BYTES of the typed buffer.
+ * A call reads nothing outside [ptr, ptr + frames * N * element size).  The kernels take 16-byte loads (16 int8 or 8 fp16
+ * values) only where the address and the row stride N * element size both allow them -- int8 rows of N = 648 do not --
+ * and read element by element otherwise.
+ * Every handle takes typed calls: every algorithm, message type and engine; early termination, polling, both hand-overs
+ * of the stragglers, the CRC stop and the debug taps behave as with float input.  The streaming engines read the
+ * caller's rows themselves; the one-launch and record kernels get one widening pass (llr_widen_kernel) into max_batch * N
+ * floats the handle owns, allocated by its first typed call and released with it.  The plain entry points launch and
+ * move exactly what they did, before and after a typed call.
+ * ldpc_decode_typed / ldpc_decode_soft_typed: host buffers, as ldpc_decode (launch groups, device lists).  Launch groups,
+ *   the pinned ring and the copies are sized in bytes of the element type and the device staging slots hold the narrow
+ *   elements.  Narrow channel values are always STAGED (or copied directly from memory the caller page-locked itself):
+ *   LDPC_HOST_INPUT_LOCK_PAGES is treated as LDPC_HOST_INPUT_STAGED for them.  The rule that cuts a single-group call in
+ *   two keeps its threshold of 256 MiB of input, so a narrow call is cut later (at 4x the frames with int8).
+ * ldpc_llr_quantize_device: the sender's side of the rule, for chains that stay in HBM and for sweeps of the quantisation
+ *   itself.  t = y / llr_unit, one IEEE fp32 divide; then
+ *     LDPC_LLR_I8:  NaN -> 0; otherwise rintf(t), ties to even, clamped to [-127, 127] (+-inf give +-127; -128 is never
+ *                   produced);
+ *     LDPC_LLR_F16: NaN stays NaN; otherwise t is clamped to +-65504 and rounded to binary16, nearest even;
+ *     LDPC_LLR_F32: LDPC_ERR_ARG.
+ *   count values; y_dev and out_dev must not overlap (LDPC_ERR_ARG); enqueued on `stream`, returns without waiting. */
+enum ldpc_llr_type { LDPC_LLR_F32 = 0, LDPC_LLR_F16 = 1, LDPC_LLR_I8 = 2 };
+int ldpc_decode_typed_device(ldpc_decoder *d, const void *llr_dev, int32_t llr_type, float llr_unit, int64_t frames,
+                             uint8_t *out_dev, int64_t out_bytes, int32_t *iters_dev, void *stream);
+int ldpc_decode_soft_typed_device(ldpc_decoder *d, const void *llr_dev, int32_t llr_type, float llr_unit, int64_t frames,
+                                  uint8_t *out_dev, int64_t out_bytes, int32_t *iters_dev, float *soft_dev,
+                                  int64_t soft_floats, int32_t soft_kind, void *stream);
+int ldpc_decode_typed(ldpc_decoder *d, const void *llr_host, int32_t llr_type, float llr_unit, int64_t frames,
+                      uint8_t *out_host, int64_t out_bytes, int32_t *iters);
+int ldpc_decode_soft_typed(ldpc_decoder *d, const void *llr_host, int32_t llr_type, float llr_unit, int64_t frames,
+                           uint8_t *out_host, int64_t out_bytes, int32_t *iters, float *soft_host, int64_t soft_floats,
+                           int32_t soft_kind);
+int ldpc_llr_quantize_device(const float *y_dev, int64_t count, int32_t llr_type, float llr_unit, void *out_dev,
+                             int32_t device, void *stream);
+
 /* Per-kernel HIP-event timing of subsequent decode calls (two event records per
  * launch on the decode stream; off by default).  enable = 1: every call; enable = k > 1:
  * every k-th ldpc_decode_device call, starting with the next one (the events cost about 2 %

@@ -12,4 +12,4 @@ Product layout:
 Nothing here imports oracle/ (test infrastructure).
 """
 from .capi import (ALGO_LAYERED, ALGO_MS, ALGO_SP, PACK_BITS, PACK_BYTES, Decoder, Encoder, Graph, LdpcError, Modem, RateMatcher,  # noqa: F401
-                   TransportBlock, code_bytes, device_count, out_bytes, parity_structure, shard_range)
+                   TransportBlock, code_bytes, device_count, out_bytes, parity_structure, quantize_device, shard_range)

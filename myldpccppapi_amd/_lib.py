@@ -98,6 +98,8 @@ EXPORTS = (
     "ldpc_tb_attach", "ldpc_tb_check",
     "ldpc_decoder_crc_stops", "ldpc_crc_weights", "ldpc_tb_frame_crc", "ldpc_decoder_config_init_sized",
     "ldpc_decode_soft_device", "ldpc_decode_soft",
+    "ldpc_decode_typed_device", "ldpc_decode_soft_typed_device", "ldpc_decode_typed", "ldpc_decode_soft_typed",
+    "ldpc_llr_quantize_device",
 )
 
 
@@ -140,6 +142,12 @@ def load():
     L.ldpc_decode_device.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp]
     L.ldpc_decode_soft.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, ctypes.c_int32]
     L.ldpc_decode_soft_device.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, ctypes.c_int32, vp]
+    f32, i32 = ctypes.c_float, ctypes.c_int32
+    L.ldpc_decode_typed.argtypes = [vp, vp, i32, f32, ctypes.c_int64, vp, ctypes.c_int64, vp]
+    L.ldpc_decode_typed_device.argtypes = [vp, vp, i32, f32, ctypes.c_int64, vp, ctypes.c_int64, vp, vp]
+    L.ldpc_decode_soft_typed.argtypes = [vp, vp, i32, f32, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, i32]
+    L.ldpc_decode_soft_typed_device.argtypes = [vp, vp, i32, f32, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, i32, vp]
+    L.ldpc_llr_quantize_device.argtypes = [vp, ctypes.c_int64, i32, f32, vp, i32, vp]
     L.ldpc_out_bytes.argtypes = [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]
     L.ldpc_out_bytes.restype = ctypes.c_int64
     L.ldpc_decoder_set_timing.argtypes = [vp, ctypes.c_int]

@@ -21,6 +21,9 @@ PARITY_KINDS = {1: "dual_diagonal", 2: "staircase"}        # enum ldpc_parity_ki
 HOST_INPUT = {"auto": 0, "staged": 1, "lock_pages": 2}     # enum ldpc_host_input
 SOFT_POSTERIOR, SOFT_EXTRINSIC = 1, 2                      # enum ldpc_soft_kind
 SOFT_KINDS = {"posterior": SOFT_POSTERIOR, "extrinsic": SOFT_EXTRINSIC}
+LLR_F32, LLR_F16, LLR_I8 = 0, 1, 2                         # enum ldpc_llr_type
+LLR_TYPES = {"f32": LLR_F32, "f16": LLR_F16, "i8": LLR_I8}
+LLR_DTYPES = {np.dtype(np.float32): LLR_F32, np.dtype(np.float16): LLR_F16, np.dtype(np.int8): LLR_I8}
 ALGOS = {"sp": ALGO_SP, "ms": ALGO_MS, "layered": ALGO_LAYERED, "ms_fused": ALGO_MS_FUSED,
          "layered_host": ALGO_LAYERED_HOST, "bp": ALGO_BP, "layered_bp": ALGO_LAYERED_BP}
 
@@ -120,6 +123,14 @@ def device_count():
     return n.value if rc == 0 else 0
 
 
+def quantize_device(y_ptr, count, llr_type, llr_unit, out_ptr, device=0, stream=None):
+    """ldpc_llr_quantize_device: `count` float32 values at y_ptr -> int8 ("i8") or float16 ("f16") at out_ptr, the
+    sender's side of a typed decode call: t = y / llr_unit, rounded to nearest even and clamped to [-127, 127] / +-65504
+    (NaN -> 0 / NaN).  Device pointers; enqueued on `stream`, no wait."""
+    _lib.check(_lib.load().ldpc_llr_quantize_device(y_ptr, int(count), LLR_TYPES.get(llr_type, llr_type), float(llr_unit), out_ptr,
+                                                    int(device), stream))
+
+
 def out_bytes(K, frames, pack_mode=PACK_BYTES):
     return int(_lib.load().ldpc_out_bytes(K, frames, pack_mode))
 
@@ -212,11 +223,31 @@ class Decoder:
                                                    ctypes.byref(self._h)))
 
     # -- host buffers (the reference's Coder::decode signature) -------------
-    def decode(self, llr, want_iters=True, soft=None):
+    def decode(self, llr, want_iters=True, soft=None, llr_unit=None):
         """llr: float32 [frames, N] (numpy).  Returns (bytes uint8, iters int32); with soft="posterior" or "extrinsic"
         (ldpc_decode_soft) a third value, float32 [frames, N]: per frame the posterior of the round it stopped in, or
-        that minus the channel value."""
+        that minus the channel value.
+        llr_unit: the typed path (ldpc_decode_typed / ldpc_decode_soft_typed) -- the element type is the array's own
+        dtype, int8, float16 or float32 (unit exactly 1), and the decoder reads y = x * llr_unit.  Without llr_unit any
+        array is converted to float32 first, as always."""
         L = _lib.load()
+        if llr_unit is not None:
+            llr = np.asarray(llr)
+            if llr.dtype not in LLR_DTYPES:
+                raise TypeError("llr_unit given: llr must be int8, float16 or float32, not %s" % llr.dtype)
+            llr = np.ascontiguousarray(llr).reshape(-1, self.N)
+            frames, ty = llr.shape[0], LLR_DTYPES[llr.dtype]
+            out = np.zeros(out_bytes(self.K, frames, self.cfg.pack_mode), np.uint8)
+            iters = np.zeros(frames, np.int32)
+            if soft is None:
+                _lib.check(L.ldpc_decode_typed(self._h, llr.ctypes.data, ty, float(llr_unit), frames, out.ctypes.data, out.size,
+                                               iters.ctypes.data if want_iters else None))
+                return out, iters
+            vals = np.zeros((frames, self.N), np.float32)
+            _lib.check(L.ldpc_decode_soft_typed(self._h, llr.ctypes.data, ty, float(llr_unit), frames, out.ctypes.data, out.size,
+                                                iters.ctypes.data if want_iters else None, vals.ctypes.data, vals.size,
+                                                SOFT_KINDS.get(soft, soft)))
+            return out, iters, vals
         llr = np.ascontiguousarray(llr, np.float32).reshape(-1, self.N)
         frames = llr.shape[0]
         out = np.zeros(out_bytes(self.K, frames, self.cfg.pack_mode), np.uint8)
@@ -233,10 +264,22 @@ class Decoder:
 
     # -- buffers already in HBM ----------------------------------------------
     def decode_device(self, llr_ptr, frames, out_ptr, out_nbytes, iters_ptr=None, stream=None, soft_ptr=None, soft_floats=0,
-                      soft="posterior"):
+                      soft="posterior", llr_type=None, llr_unit=None):
         """ldpc_decode_device: out_ptr None = iteration counts and stats() only; iters_ptr None = bytes only.
-        soft_ptr: ldpc_decode_soft_device -- soft_floats >= frames * N float32 values of kind `soft` are written there."""
-        if soft_ptr is None and not soft_floats:
+        soft_ptr: ldpc_decode_soft_device -- soft_floats >= frames * N float32 values of kind `soft` are written there.
+        llr_type ("f32", "f16", "i8") / llr_unit: ldpc_decode_typed_device / ldpc_decode_soft_typed_device -- llr_ptr holds
+        elements of that type and the decoder reads y = x * llr_unit (default 1)."""
+        if llr_type is not None or llr_unit is not None:
+            ty = LLR_TYPES.get(llr_type, llr_type) if llr_type is not None else LLR_F32
+            unit = 1.0 if llr_unit is None else float(llr_unit)
+            if soft_ptr is None and not soft_floats:
+                _lib.check(_lib.load().ldpc_decode_typed_device(self._h, llr_ptr, ty, unit, frames, out_ptr, out_nbytes, iters_ptr,
+                                                                stream))
+            else:
+                _lib.check(_lib.load().ldpc_decode_soft_typed_device(self._h, llr_ptr, ty, unit, frames, out_ptr, out_nbytes,
+                                                                     iters_ptr, soft_ptr, int(soft_floats),
+                                                                     SOFT_KINDS.get(soft, soft), stream))
+        elif soft_ptr is None and not soft_floats:
             _lib.check(_lib.load().ldpc_decode_device(self._h, llr_ptr, frames, out_ptr, out_nbytes,
                                                       iters_ptr, stream))
         else:

@@ -489,7 +489,22 @@ int Coder::addDecodeType(enum decodeType deType)
  * ldpc_decode.  srcLength bytes are written. */
 int Coder::decode(float *postCode, char *srcCode, int srcLength, enum decodeType deType)
 {
-    return decodeFrames(postCode, srcCode, srcLength, deType, nullptr, 0);
+    return decodeFrames(postCode, LDPC_LLR_F32, 1.0f, srcCode, srcLength, deType, nullptr, 0);
+}
+
+/* decode() on int8 / fp16 channel values (ldpc_decode_typed): the decoder reads y = x * llrUnit */
+int Coder::decodeTyped(const void *postCode, int llrType, float llrUnit, char *srcCode, int srcLength, enum decodeType deType)
+{
+    return decodeFrames(postCode, llrType, llrUnit, srcCode, srcLength, deType, nullptr, 0);
+}
+
+int Coder::decodeSoftTyped(const void *postCode, int llrType, float llrUnit, char *srcCode, int srcLength, enum decodeType deType,
+                           float *soft, int kind)
+{
+    if (!soft) return fail(LDPC_ERR_ARG, "decodeSoftTyped: soft is NULL");
+    if (kind != LDPC_SOFT_POSTERIOR && kind != LDPC_SOFT_EXTRINSIC) return fail(LDPC_ERR_ARG, "decodeSoftTyped: unknown kind");
+    if (deType == DecodeSP) return fail(LDPC_ERR_UNSUPPORTED, "decodeSoftTyped: DecodeSP has no soft output (see decodeSoft)");
+    return decodeFrames(postCode, llrType, llrUnit, srcCode, srcLength, deType, soft, kind);
 }
 
 int Coder::decodeSoft(float *postCode, char *srcCode, int srcLength, enum decodeType deType, float *soft, int kind)
@@ -499,11 +514,13 @@ int Coder::decodeSoft(float *postCode, char *srcCode, int srcLength, enum decode
     if (deType == DecodeSP)
         return fail(LDPC_ERR_UNSUPPORTED, "decodeSoft: DecodeSP works in the probability domain, where the posterior has "
                     "saturated by the time a frame stops; the min-sum decode types, DecodeBP and DecodeLayeredBP carry soft output");
-    return decodeFrames(postCode, srcCode, srcLength, deType, soft, kind);
+    return decodeFrames(postCode, LDPC_LLR_F32, 1.0f, srcCode, srcLength, deType, soft, kind);
 }
 
-/* soft != nullptr: ldpc_decode_soft, N floats per frame of the mother code */
-int Coder::decodeFrames(float *postCode, char *srcCode, int srcLength, enum decodeType deType, float *soft, int kind)
+/* soft != nullptr: ldpc_decode_soft, N floats per frame of the mother code.  (llrType, llrUnit): the element type of
+ * postCode, LDPC_LLR_F32 with unit 1 for decode() and decodeSoft() */
+int Coder::decodeFrames(const void *postCode, int llrType, float llrUnit, char *srcCode, int srcLength, enum decodeType deType,
+                        float *soft, int kind)
 {
     if (!isDecoder) return fail(LDPC_ERR_STATE, "decode: call forDecoder() first");
     if (!postCode || !srcCode || srcLength <= 0) return fail(LDPC_ERR_ARG, "decode: bad arguments");
@@ -545,15 +562,20 @@ int Coder::decodeFrames(float *postCode, char *srcCode, int srcLength, enum deco
         d = it->second;
     }
     std::vector<float> recovered;
+    if (rmE && llrType != LDPC_LLR_F32)
+        return fail(LDPC_ERR_UNSUPPORTED, "decodeTyped: rate recovery (setRateMatch) sums float values; quantise behind it "
+                    "(ldpc_rate_recover_device, ldpc_llr_quantize_device, ldpc_decode_typed_device)");
     if (rmE) {
         /* E received values per frame -> the N channel values the decoder reads */
         recovered.resize((size_t)codeSize * ldpcN);
-        int rm = ldpc_rate_recover(&rmSpec, postCode, codeSize, rmK0, rmE, nullptr, 0, recovered.data(), device);
+        int rm = ldpc_rate_recover(&rmSpec, static_cast<const float *>(postCode), codeSize, rmK0, rmE, nullptr, 0, recovered.data(), device);
         if (rm) return fail(rm, ldpc_last_error());
         postCode = recovered.data();
     }
-    int rc = soft ? ldpc_decode_soft(d, postCode, codeSize, (uint8_t *)srcCode, srcLength, nullptr, soft, (int64_t)codeSize * ldpcN, kind)
-                  : ldpc_decode(d, postCode, codeSize, (uint8_t *)srcCode, srcLength, nullptr);
+    /* LDPC_LLR_F32 with unit 1: these are ldpc_decode_soft and ldpc_decode */
+    int rc = soft ? ldpc_decode_soft_typed(d, postCode, llrType, llrUnit, codeSize, (uint8_t *)srcCode, srcLength, nullptr, soft,
+                                           (int64_t)codeSize * ldpcN, kind)
+                  : ldpc_decode_typed(d, postCode, llrType, llrUnit, codeSize, (uint8_t *)srcCode, srcLength, nullptr);
     if (rc) return fail(rc, ldpc_last_error());
     ldpc_decode_stats st;
     if (ldpc_decoder_stats(d, &st) == LDPC_OK) lastTime = st.batch_time;

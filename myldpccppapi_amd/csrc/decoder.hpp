@@ -190,7 +190,7 @@ struct HostPath {
 struct TimedSpan {
     Event a, b;
     int kind = 0;       /* 0 check, 1 var, 2 layer, 3 other, 4 check with column-local fusion, 5 check group, 6 var group,
-                           7 soft_settle_kernel (soft output) */
+                           7 soft_settle_kernel (soft output), 8 llr_widen_kernel (typed input in front of a one-launch kernel) */
     int degree = 0;     /* groups: the bucket's highest degree */
     int64_t bytes = 0;  /* algorithmic bytes of the launch in the two-kernel formulation (16 E + 4 N in total) */
     int64_t moved = 0;  /* bytes this kernel's own loads and stores move (less when columns are fused in) */
@@ -253,6 +253,9 @@ struct ldpc_decoder {
     int64_t last_frames = 0;
     int32_t last_tiles = 0;
 
+    ldpc::DevBuf<float> llr_wide;       /* one-launch and record kernels: [max_batch][N] floats a typed call (llr_type != F32)
+                                           widens into (llr_input.hpp: llr_widen_kernel); made by the handle's first typed call */
+
     ldpc::FloodPlan flood;
     ldpc::HostPath host;
     ldpc::Timing tm;
@@ -289,6 +292,9 @@ struct ldpc_decoder {
 };
 
 namespace ldpc {
+
+/* a typed call's (llr, llr_type, llr_unit): LDPC_OK or LDPC_ERR_ARG with the message set (ldpc_hip.hip) */
+int llr_in_check(const void *p, int32_t type, float unit);
 
 inline hipError_t span_begin(ldpc_decoder *d, hipStream_t s, int kind, int degree = 0, int64_t bytes = 0, int64_t moved = -1,
                              int lo = 0)

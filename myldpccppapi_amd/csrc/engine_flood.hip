@@ -96,7 +96,7 @@ static ldpc::CheckArgs check_args(const ldpc_decoder *d, const ldpc::TailRef &tr
     return a;
 }
 
-template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t frames,
+template <int V> int run_flooding(ldpc_decoder *d, const ldpc::LlrIn &llr, int64_t frames,
                                   uint8_t *out_dev, int64_t out_bytes, int32_t *iters_dev,
                                   hipStream_t s, int start_round = 1);
 
@@ -266,7 +266,7 @@ template <int V> int compact_and_finish(ldpc_decoder *d, int64_t frames, int cou
         soft_map_kernel<0><<<(unsigned)((count + kBlock - 1) / kBlock), kBlock, 0, s>>>(c->flood.soft_map.p, d->flood.cmap.p, d->soft.fmap, count);
         c->soft = SoftReq{d->soft.dst, d->soft.kind, c->flood.soft_map.p};
     }
-    const int rc = dispatch_v(cv, [&](auto v) { return run_flooding<decltype(v)::value>(c, nullptr, count, nullptr, 0, nullptr, s, it + 1); });
+    const int rc = dispatch_v(cv, [&](auto v) { return run_flooding<decltype(v)::value>(c, ldpc::LlrIn{}, count, nullptr, 0, nullptr, s, it + 1); });
     c->soft = SoftReq{};
     if (rc) return rc;
     d->flood.handed_to = c;
@@ -281,7 +281,7 @@ template <int V> int compact_and_finish(ldpc_decoder *d, int64_t frames, int cou
     return LDPC_OK;
 }
 
-template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t frames,
+template <int V> int run_flooding(ldpc_decoder *d, const ldpc::LlrIn &llr, int64_t frames,
                                   uint8_t *out_dev, int64_t out_bytes, int32_t *iters_dev,
                                   hipStream_t s, int start_round)
 {
@@ -327,10 +327,10 @@ template <int V> int run_flooding(ldpc_decoder *d, const float *llr_dev, int64_t
     d->flood.first_round_from_chan = q_less;
     if (!resume) {
         LDPC_HIP_TRY(span_begin(d, s, 3));
-        InitArgs a{llr_dev, d->flood.chan.p, q_less ? nullptr : d->flood.Q.p, d->hard.p, d->col_ptr.p, d->flood.col_qedge.p,
-                   d->E, frames, d->N, d->cfg.llr_scale};
+        InitArgs a{llr.p, d->flood.chan.p, q_less ? nullptr : d->flood.Q.p, d->hard.p, d->col_ptr.p, d->flood.col_qedge.p,
+                   d->E, frames, d->N, d->cfg.llr_scale, llr.unit};
         dim3 grid((d->N + kInitCols - 1) / kInitCols, tiles);
-        d->flood.fns.init<<<grid, kBlock, 0, s>>>(a);
+        d->flood.fns.init_in[llr.type]<<<grid, kBlock, 0, s>>>(a);
         StateArgs st{d->done.p, nullptr, d->iters.p, nullptr, frames, 0, max_iter, freeze ? 1 : 0};
         /* overflow tiles (and unused tiles in between) are born finished: frames beyond `frames` */
         state_kernel<V><<<use_tail ? d->flood.TA : tiles, 64, 0, s>>>(st);
@@ -831,8 +831,8 @@ int ldpc::engine_flood_setup(ldpc_decoder *d, const ldpc_graph *g, size_t TF, bo
     return dispatch_v(d->V, [&](auto v) { return placement_search<decltype(v)::value>(d, TF); });
 }
 
-int ldpc::engine_flood_run(ldpc_decoder *d, const float *llr_dev, int64_t frames, uint8_t *out_dev, int64_t out_bytes,
+int ldpc::engine_flood_run(ldpc_decoder *d, const LlrIn &llr, int64_t frames, uint8_t *out_dev, int64_t out_bytes,
                            int32_t *iters_dev, hipStream_t s)
 {
-    return dispatch_v(d->V, [&](auto v) { return run_flooding<decltype(v)::value>(d, llr_dev, frames, out_dev, out_bytes, iters_dev, s); });
+    return dispatch_v(d->V, [&](auto v) { return run_flooding<decltype(v)::value>(d, llr, frames, out_dev, out_bytes, iters_dev, s); });
 }

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "tune.hpp"
+#include "llr_input.hpp"
 
 struct ldpc_decoder;
 struct ldpc_graph;
@@ -30,12 +31,14 @@ hipError_t engine_ldsp_plan_create(LdspPlan *pl, int32_t M, int32_t N, int64_t E
 hipError_t engine_ldsp_run(LdspPlan *pl, const FusedRun &r, hipStream_t s, int32_t *launched);
 hipError_t engine_fused_run(FusedPlan *pl, const FusedRun &r, hipStream_t s, int32_t *launched);
 hipError_t engine_layered_run(LayeredPlan *pl, const LayeredRun &r, hipStream_t s, int32_t *launched);
+/* llr_input.hip: y[i] = x[i] * unit for count elements of a narrow type (LlrIn::type != kLlrF32), enqueued on s */
+hipError_t engine_llr_widen(const LlrIn &in, float *y_dev, int64_t count, hipStream_t s);
 
 /* The streaming flooding engine works on the handle (decoder.hpp: ldpc_decoder::flood) and returns LDPC_* codes with
  * the message set.  setup: message arrays of TF frames, work lists, kernel tables, launch plan and, for a decoder that
  * is no hand-over child (top_level), link calibration and placement search. */
 int engine_flood_setup(ldpc_decoder *d, const ldpc_graph *g, size_t TF, bool top_level);
-int engine_flood_run(ldpc_decoder *d, const float *llr_dev, int64_t frames, uint8_t *out_dev, int64_t out_bytes,
+int engine_flood_run(ldpc_decoder *d, const LlrIn &llr, int64_t frames, uint8_t *out_dev, int64_t out_bytes,
                      int32_t *iters_dev, hipStream_t s);
 
 }  // namespace ldpc

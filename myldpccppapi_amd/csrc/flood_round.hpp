@@ -6,11 +6,12 @@
 
 #include "flood_common.hpp"
 #include "ldpc_expf.h"
+#include "llr_input.hpp"
 
 namespace ldpc {
 
 struct InitArgs {
-    const float *__restrict__ llr;        /* [frames][N] frame-major (reference layout) */
+    const void *__restrict__ llr;         /* [frames][N] frame-major (reference layout), elements of the kernel's IN */
     void *__restrict__ chan;              /* [T][N][F] (float or fp16) */
     void *__restrict__ Q;                 /* [T][E][F] */
     uint64_t *__restrict__ hard;          /* [T][N][V] */
@@ -20,15 +21,18 @@ struct InitArgs {
     int64_t frames;
     int32_t N;
     float llr_scale;
+    float llr_unit;                       /* narrow IN: y = (float)x * llr_unit (llr_input.hpp); unused for float */
 };
 
 /* decodeInit (decodeCL.c:3-22) / decodeInitMS (:113-124) + the transpose from the
  * reference's frame-major input to the tile layout.  One block = 32 columns x one
  * tile; the patch crosses LDS so both the read (along n) and the writes (along
- * frames) are contiguous.  Frames past `frames` are filled with y = +1. */
+ * frames) are contiguous.  Frames past `frames` are filled with y = +1.
+ * IN: element type of the caller's buffer.  float is the kernel as it always was; int8_t and _Float16 read the
+ * caller's rows directly (llr_patch_fill), cross LDS as floats and continue unchanged from patch[] on. */
 constexpr int kInitCols = 32;
 
-template <int ALGO, int V, typename T>
+template <int ALGO, int V, typename T, typename IN = float>
 __global__ __launch_bounds__(kBlock) void init_kernel(const InitArgs a)
 {
     constexpr int F = 64 * V;
@@ -36,7 +40,10 @@ __global__ __launch_bounds__(kBlock) void init_kernel(const InitArgs a)
     __shared__ float patch[kInitCols * LD];
     const int tile = blockIdx.y;
     const int n0 = blockIdx.x * kInitCols;
-    if ((a.N & 3) == 0 && n0 + kInitCols <= a.N && (reinterpret_cast<uintptr_t>(a.llr) & 15) == 0) {
+    const IN *__restrict__ llr = static_cast<const IN *>(a.llr);
+    if constexpr (!std::is_same<IN, float>::value) {
+        llr_patch_fill<IN, F, LD, kInitCols, kBlock, false>(patch, llr, a.llr_unit, a.frames, a.N, tile, n0, 1.0f);
+    } else if ((a.N & 3) == 0 && n0 + kInitCols <= a.N && (reinterpret_cast<uintptr_t>(llr) & 15) == 0) {
         /* 16-byte loads, all of a thread's F/32 requests in flight: 8 threads span the 32 columns
          * of a frame, 32 frames per pass */
         const int c4 = (threadIdx.x & 7) * 4, f0 = threadIdx.x >> 3;
@@ -45,7 +52,7 @@ __global__ __launch_bounds__(kBlock) void init_kernel(const InitArgs a)
         for (int i = 0; i < F / 32; ++i) {
             const int64_t frame = (int64_t)tile * F + f0 + 32 * i;
             vals[i] = float4{1.0f, 1.0f, 1.0f, 1.0f};
-            if (frame < a.frames) vals[i] = *reinterpret_cast<const float4 *>(a.llr + (size_t)frame * a.N + n0 + c4);
+            if (frame < a.frames) vals[i] = *reinterpret_cast<const float4 *>(llr + (size_t)frame * a.N + n0 + c4);
         }
 #pragma unroll
         for (int i = 0; i < F / 32; ++i) {
@@ -61,7 +68,7 @@ __global__ __launch_bounds__(kBlock) void init_kernel(const InitArgs a)
         for (int f = threadIdx.x / kInitCols; f < F; f += kBlock / kInitCols) {
             const int64_t frame = (int64_t)tile * F + f;
             float y = 1.0f;
-            if (frame < a.frames && n < a.N) y = a.llr[(size_t)frame * a.N + n];
+            if (frame < a.frames && n < a.N) y = llr[(size_t)frame * a.N + n];
             patch[c * LD + f] = y;
         }
     }

@@ -33,6 +33,7 @@ struct FloodFns {
     int check_group_width = 1;                                /* values per lane of the group check kernels */
     VarGroupFn var_group[kVarBuckets] = {};
     InitFn init = nullptr;
+    InitFn init_in[3] = {};                                   /* by enum ldpc_llr_type: [0] = init (float), fp16, int8 input */
     int max_check_unrolled = kMaxUnrolledDegree;
 };
 

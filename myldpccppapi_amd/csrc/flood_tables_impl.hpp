@@ -75,7 +75,9 @@ template <int ALGO, int V, typename T> void fill_v(FloodFns *f)
     f->var_group[0] = var_group_kernel<ALGO, V, T, 1, 4>;
     f->var_group[1] = var_group_kernel<ALGO, V, T, 5, 8>;
     f->var_group[2] = var_group_kernel<ALGO, V, T, 9, 16>;
-    f->init = init_kernel<ALGO, V, T>;
+    f->init = f->init_in[kLlrF32] = init_kernel<ALGO, V, T>;
+    f->init_in[kLlrF16] = init_kernel<ALGO, V, T, _Float16>;
+    f->init_in[kLlrI8] = init_kernel<ALGO, V, T, int8_t>;
     f->max_check_unrolled = DM;
     if (ALGO != kAlgoSP) {       /* min-sum and box-plus rows of degree 17..32: narrow unrolled kernels */
         CheckTableMS<ALGO, V, T, kMaxUnrolledCheckDegreeMS>::fill(f->check, f->check_wide);

@@ -103,18 +103,23 @@ hipError_t staged_copy(ldpc_decoder *d, uint8_t *dst, const uint8_t *src, size_t
 
 /* ldpc_decode on ONE device; `mode` was decided once per ldpc_decode call, before any thread of a device
  * list has touched the buffer. */
-int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t *out_host,
+int decode_host(ldpc_decoder *d, const ldpc::LlrIn &in, int64_t frames, uint8_t *out_host,
                 int64_t out_bytes, int32_t *iters, InputMode mode, float *soft_host = nullptr, int32_t soft_kind = 0)
 {
+    /* launch groups, the pinned ring and the copies are sized in bytes of the element type; the device staging slots hold
+     * the caller's elements as they are (a slot has room for max_batch * N floats) and the init kernels read them there */
+    const size_t esz = ldpc::llr_elem_size(in.type);
+    const uint8_t *llr_host = static_cast<const uint8_t *>(in.p);
     const int64_t total = ldpc_out_bytes(d->cfg.K, frames, d->cfg.pack_mode);
     LDPC_HIP_TRY(hipSetDevice(d->cfg.device));
     int64_t B = d->cfg.max_batch;
     /* A large call that is ONE launch group is cut into two: the second half's channel values travel while the first
      * half is decoded (one group exposes its whole copy: 21 ms of PCIe in front of a 94 ms decode for 4096 frames of the
      * headline code; half batches decode at 0.99 of the full batch's rate).  Only where the grouping cannot be seen in
-     * the output: K a multiple of 8 (MyLdpc.cpp:577-616 starts every group at byte off*K/8). */
+     * the output: K a multiple of 8 (MyLdpc.cpp:577-616 starts every group at byte off*K/8).  The threshold is in bytes
+     * of the caller's element type: a narrow call is cut later (4x the frames with int8 values), its copy being shorter. */
     if (frames <= B && frames >= 2048 && d->cfg.K % 8 == 0 &&
-        (size_t)frames * d->N * sizeof(float) >= ((size_t)256 << 20))
+        (size_t)frames * d->N * esz >= ((size_t)256 << 20))
         B = ((frames + 1) / 2 + 255) / 256 * 256;
     if (d->cfg.pack_mode == LDPC_PACK_BITS && (d->cfg.K % 8) && frames > B)
         return set_error(LDPC_ERR_UNSUPPORTED, "bit-packed output with K %% 8 != 0 cannot be chunked: "
@@ -143,7 +148,7 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
         LDPC_HIP_TRY(sl.h2d_done.ensure(false));
         LDPC_HIP_TRY(sl.all_done.ensure(false));
     }
-    if (mode != kInputDirect && (size_t)std::min(B, frames) * d->N * sizeof(float) > kStageBytes) {
+    if (mode != kInputDirect && (size_t)std::min(B, frames) * d->N * esz > kStageBytes) {
         const int rs = ensure_stager(d);
         if (rs) return rs;
     }
@@ -194,8 +199,8 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
         const int r1 = drain(sl);                /* the slot's previous tenant (group kk - nslots) */
         if (r1) return r1;
         const int64_t off = kk * B, n = std::min(B, frames - off);
-        const uint8_t *src = reinterpret_cast<const uint8_t *>(llr_host + (size_t)off * d->N);
-        const size_t bytes = (size_t)n * d->N * sizeof(float);
+        const uint8_t *src = llr_host + (size_t)off * d->N * esz;
+        const size_t bytes = (size_t)n * d->N * esz;
         uint8_t *dst = reinterpret_cast<uint8_t *>(sl.llr.p);
         hipError_t e = hipSuccess;
         if (mode == kInputDirect) {
@@ -218,6 +223,7 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
             LDPC_STAMP("staging submitted", kk);
             return LDPC_OK;                      /* the job records h2d_done */
         } else {
+            /* float channel values only: decode_entry stages a typed call (the page arithmetic is float-sized) */
             const ldpc::GroupBlocks gb = ldpc::plan_group_blocks((uintptr_t)llr_host, frames, d->N, B, kk);
             bool locked = false;
             if (!gb.whole_by_cpu) {
@@ -265,11 +271,13 @@ int decode_host(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t 
         hipError_t e = hipStreamWaitEvent(d->stream.s, sl.h2d_done.e, 0);
         if (e != hipSuccess) { rc = set_error(LDPC_ERR_HIP, "host-to-device staging: %s", hipGetErrorString(e)); break; }
         const int64_t chunk_bytes = ldpc_out_bytes(d->cfg.K, n, d->cfg.pack_mode);
+        /* LDPC_LLR_F32 with unit 1: these are ldpc_decode_soft_device and ldpc_decode_device */
         if (soft_host)
-            rc = ldpc_decode_soft_device(d, sl.llr.p, n, sl.out.p, chunk_bytes, iters ? sl.iters.p : nullptr, sl.soft.p,
-                                         n * (int64_t)d->N, soft_kind, d->stream.s);
+            rc = ldpc_decode_soft_typed_device(d, sl.llr.p, in.type, in.unit, n, sl.out.p, chunk_bytes, iters ? sl.iters.p : nullptr,
+                                               sl.soft.p, n * (int64_t)d->N, soft_kind, d->stream.s);
         else
-            rc = ldpc_decode_device(d, sl.llr.p, n, sl.out.p, chunk_bytes, iters ? sl.iters.p : nullptr, d->stream.s);
+            rc = ldpc_decode_typed_device(d, sl.llr.p, in.type, in.unit, n, sl.out.p, chunk_bytes, iters ? sl.iters.p : nullptr,
+                                          d->stream.s);
         if (rc) break;
         LDPC_STAMP("decode enqueued", k);
         /* byte offset of this group's first frame: (off*K)/8 in both packings */
@@ -347,17 +355,22 @@ int32_t shard_unit(const ldpc_decoder_config &cfg, int64_t frames)
 }
 
 /* ldpc_decode (soft_host == nullptr) and ldpc_decode_soft: one device, or the frame ranges of a device list */
-int decode_entry(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t *out_host, int64_t out_bytes, int32_t *iters,
+int decode_entry(ldpc_decoder *d, const ldpc::LlrIn &in, int64_t frames, uint8_t *out_host, int64_t out_bytes, int32_t *iters,
                  float *soft_host, int32_t soft_kind)
 {
     if (!d) return set_error(LDPC_ERR_ARG, "decoder is NULL");
+    if (int rc = ldpc::llr_in_check(in.p, in.type, in.unit)) return rc;
+    const uint8_t *llr_host = static_cast<const uint8_t *>(in.p);
+    const size_t esz = ldpc::llr_elem_size(in.type);
     if (frames < 0) return set_error(LDPC_ERR_ARG, "frames < 0");
     if (frames == 0) return LDPC_OK;
     if (!llr_host || !out_host) return set_error(LDPC_ERR_ARG, "llr/out is NULL");
     if (out_bytes < 0) return set_error(LDPC_ERR_ARG, "out_bytes < 0");
     /* asked once, before any thread touches the buffer */
-    const InputMode mode = resolve_input_mode(d->cfg, llr_host, (size_t)frames * d->N * sizeof(float));
-    if (d->shards.empty()) return decode_host(d, llr_host, frames, out_host, out_bytes, iters, mode, soft_host, soft_kind);
+    InputMode mode = resolve_input_mode(d->cfg, llr_host, (size_t)frames * d->N * esz);
+    /* narrow channel values: staged, or direct from memory the caller page-locked; LOCK_PAGES is treated as staged */
+    if (in.type != LDPC_LLR_F32 && mode == kInputLock) mode = kInputStaged;
+    if (d->shards.empty()) return decode_host(d, in, frames, out_host, out_bytes, iters, mode, soft_host, soft_kind);
 
     /* several devices: each entry's own host thread decodes a contiguous frame range */
     const int n = (int)d->shards.size();
@@ -377,8 +390,9 @@ int decode_entry(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t
         const int64_t lo_i = lo[i], cnt = hi[i] - lo[i];
         const int64_t obytes = std::min(room, ldpc_out_bytes(d->cfg.K, cnt, d->cfg.pack_mode));
         const int32_t N = d->N;
-        jobs[i].fn = [sh, llr_host, out_host, iters, lo_i, cnt, base, obytes, N, mode, soft_host, soft_kind]() -> int {
-            return decode_host(sh, llr_host + (size_t)lo_i * N, cnt, out_host + base, obytes,
+        const ldpc::LlrIn part{llr_host + (size_t)lo_i * N * esz, in.type, in.unit};
+        jobs[i].fn = [sh, part, out_host, iters, lo_i, cnt, base, obytes, N, mode, soft_host, soft_kind]() -> int {
+            return decode_host(sh, part, cnt, out_host + base, obytes,
                                iters ? iters + lo_i : nullptr, mode, soft_host ? soft_host + (size_t)lo_i * N : nullptr, soft_kind);
         };
         d->shard_workers[i]->submit(&jobs[i]);
@@ -402,11 +416,18 @@ extern "C" {
 int ldpc_decode(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t *out_host,
                 int64_t out_bytes, int32_t *iters)
 {
-    return decode_entry(d, llr_host, frames, out_host, out_bytes, iters, nullptr, 0);
+    return decode_entry(d, ldpc::llr_in_float(llr_host), frames, out_host, out_bytes, iters, nullptr, 0);
 }
 
-int ldpc_decode_soft(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t *out_host, int64_t out_bytes,
-                     int32_t *iters, float *soft_host, int64_t soft_floats, int32_t soft_kind)
+int ldpc_decode_typed(ldpc_decoder *d, const void *llr_host, int32_t llr_type, float llr_unit, int64_t frames,
+                      uint8_t *out_host, int64_t out_bytes, int32_t *iters)
+{
+    return decode_entry(d, ldpc::LlrIn{llr_host, llr_type, llr_unit}, frames, out_host, out_bytes, iters, nullptr, 0);
+}
+
+/* ldpc_decode_soft and ldpc_decode_soft_typed */
+static int decode_soft_in(ldpc_decoder *d, const ldpc::LlrIn &in, int64_t frames, uint8_t *out_host, int64_t out_bytes,
+                          int32_t *iters, float *soft_host, int64_t soft_floats, int32_t soft_kind)
 {
     if (!d) return set_error(LDPC_ERR_ARG, "decoder is NULL");
     /* what ldpc_decode_soft_device refuses, before any launch group is staged */
@@ -419,7 +440,21 @@ int ldpc_decode_soft(ldpc_decoder *d, const float *llr_host, int64_t frames, uin
     if (frames > 0 && !soft_host) return set_error(LDPC_ERR_ARG, "soft is NULL");
     if (frames > 0 && soft_floats < frames * (int64_t)d->N)
         return set_error(LDPC_ERR_ARG, "soft_floats=%lld < %lld", (long long)soft_floats, (long long)(frames * (int64_t)d->N));
-    return decode_entry(d, llr_host, frames, out_host, out_bytes, iters, soft_host, soft_kind);
+    return decode_entry(d, in, frames, out_host, out_bytes, iters, soft_host, soft_kind);
+}
+
+int ldpc_decode_soft(ldpc_decoder *d, const float *llr_host, int64_t frames, uint8_t *out_host, int64_t out_bytes,
+                     int32_t *iters, float *soft_host, int64_t soft_floats, int32_t soft_kind)
+{
+    return decode_soft_in(d, ldpc::llr_in_float(llr_host), frames, out_host, out_bytes, iters, soft_host, soft_floats, soft_kind);
+}
+
+int ldpc_decode_soft_typed(ldpc_decoder *d, const void *llr_host, int32_t llr_type, float llr_unit, int64_t frames,
+                           uint8_t *out_host, int64_t out_bytes, int32_t *iters, float *soft_host, int64_t soft_floats,
+                           int32_t soft_kind)
+{
+    return decode_soft_in(d, ldpc::LlrIn{llr_host, llr_type, llr_unit}, frames, out_host, out_bytes, iters, soft_host, soft_floats,
+                          soft_kind);
 }
 
 int ldpc_host_block_plan(uint64_t base, int64_t frames, int32_t N, int32_t max_batch, int64_t group, uint64_t out[6])

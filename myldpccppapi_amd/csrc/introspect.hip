@@ -158,10 +158,11 @@ int ldpc_decoder_kernel_times(ldpc_decoder *d, ldpc_kernel_time *out, int32_t ca
         const ldpc::TimedSpan &sp = d->tm.spans[i];
         float ms = 0;
         LDPC_HIP_TRY(hipEventElapsedTime(&ms, sp.a.e, sp.b.e));
-        const int phase = (sp.kind == 4 || sp.kind == 5) ? 0 : (sp.kind == 6 ? 1 : (sp.kind == 7 ? 3 : sp.kind));   /* check / variable node */
+        const int phase = (sp.kind == 4 || sp.kind == 5) ? 0 : (sp.kind == 6 ? 1 : ((sp.kind == 7 || sp.kind == 8) ? 3 : sp.kind));   /* check / variable node */
         char name[64];
         if (sp.kind == 3) snprintf(name, sizeof name, "other");
         else if (sp.kind == 7) snprintf(name, sizeof name, "soft_settle_kernel");     /* soft calls only */
+        else if (sp.kind == 8) snprintf(name, sizeof name, "llr_widen_kernel");       /* typed calls on a one-launch kernel only */
         else if (d->use_fused && d->use_ldsp)   /* whole decode in one launch; [persistent grid x workgroup size, frames per workgroup] */
             snprintf(name, sizeof name, "%s[%dx%d,%d]", d->cfg.algo == LDPC_ALGO_LAYERED
                      ? (d->ms_corr ? "layered_ldsp_corr_kernel" : "layered_ldsp_kernel")

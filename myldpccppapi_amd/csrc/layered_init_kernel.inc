@@ -1,17 +1,21 @@
 /* layered_init_kernel.inc -- kernel body included by layered_kernels.hpp into layered_init_kernel and
- * layered_init_scaled_kernel, so that both are compiled from one text and the first exactly as before. */
+ * layered_init_scaled_kernel, so that both are compiled from one text and the first exactly as before.  IN: element type
+ * of the caller's buffer; a narrow one goes through llr_patch_fill (llr_input.hpp), float through the loop below. */
     constexpr int F = 64 * V;
     constexpr int LD = F + 1;
     __shared__ float patch[kInitCols * LD];
     const int tile = blockIdx.y;
     const int n0 = blockIdx.x * kInitCols;
-    {
+    const IN *__restrict__ llr = static_cast<const IN *>(a.llr);
+    if constexpr (!std::is_same<IN, float>::value) {
+        llr_patch_fill<IN, F, LD, kInitCols, kBlock, SCALED>(patch, llr, a.llr_unit, a.frames, a.N, tile, n0, scale);
+    } else {
         const int c = threadIdx.x & (kInitCols - 1);
         const int n = n0 + c;
         for (int f = threadIdx.x / kInitCols; f < F; f += kBlock / kInitCols) {
             const int64_t frame = (int64_t)tile * F + f;
             float y = 1.0f;
-            if (frame < a.frames && n < a.N) y = a.llr[(size_t)frame * a.N + n];
+            if (frame < a.frames && n < a.N) y = llr[(size_t)frame * a.N + n];
             if (SCALED) y = scale * y;
             patch[c * LD + f] = y;
         }

@@ -139,24 +139,25 @@ __global__ __launch_bounds__(kBlock) void layered_hard_kernel(const float *__res
 }
 
 struct LayeredInitArgs {
-    const float *__restrict__ llr;  /* [frames][N] */
+    const void *__restrict__ llr;   /* [frames][N], elements of the kernel's IN */
     float *__restrict__ P;          /* [T][N][F] */
     uint64_t *__restrict__ hard;    /* [T][N][V] */
     int64_t frames;
     int32_t N;
     int32_t zero_bits;              /* host-layered path: bits start at 0 (the reference: undefined) */
+    float llr_unit;                 /* narrow IN: y = (float)x * llr_unit (llr_input.hpp); unused for float */
 };
 
 /* lP = postCode (decodeCL.c:331-334), transposed into the tile layout; bits = y < 0.  SCALED (LDPC_ALGO_LAYERED_BP): the
  * value is chan = scale * y, one fp32 multiply, padding frames included; the other algorithms' kernel has no multiply. */
-template <int V>
+template <int V, typename IN = float>
 __global__ __launch_bounds__(kBlock) void layered_init_kernel(const LayeredInitArgs a)
 {
     constexpr bool SCALED = false;
     const float scale = 1.0f;
 #include "layered_init_kernel.inc"
 }
-template <int V>
+template <int V, typename IN = float>
 __global__ __launch_bounds__(kBlock) void layered_init_scaled_kernel(const LayeredInitArgs a, const float scale)
 {
     constexpr bool SCALED = true;
@@ -166,14 +167,15 @@ __global__ __launch_bounds__(kBlock) void layered_init_scaled_kernel(const Layer
 /* LDPC_ALGO_LAYERED_BP, extrinsic soft output: soft_settle_kernel leaves the posterior of every frame's stop round in the
  * caller's buffer (each value written once); this one pass afterwards subtracts chan = scale * y -- the fp32 product
  * formed first, then one subtraction.  The empty asm keeps the product a value of its own: contracted into an fma the
- * difference would be rounded once, from the exact product. */
-template <int kUnused = 0>
-__global__ __launch_bounds__(kBlock) void layered_bp_extrinsic_kernel(float *__restrict__ soft, const float *__restrict__ llr,
-                                                                      const float scale, int64_t count)
+ * difference would be rounded once, from the exact product.  IN: element type of the caller's buffer; y is the product
+ * x * unit of a narrow element, formed first (llr_value). */
+template <typename IN = float>
+__global__ __launch_bounds__(kBlock) void layered_bp_extrinsic_kernel(float *__restrict__ soft, const IN *__restrict__ llr,
+                                                                      const float scale, int64_t count, const float unit = 1.0f)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= count) return;
-    float chan = scale * llr[i];
+    float chan = scale * llr_value<IN>(llr[i], unit);
     asm volatile("" : "+v"(chan));
     soft[i] = soft[i] - chan;
 }
@@ -237,7 +239,7 @@ struct LayeredRun {
     hipError_t (*span_begin)(void *ctx, hipStream_t s, int kind, int degree, int64_t bytes) = nullptr;
     hipError_t (*span_end)(void *ctx, hipStream_t s) = nullptr;
     void *span_ctx = nullptr;
-    const float *llr_dev;
+    LlrIn llr;                      /* the caller's channel values: pointer, element type, unit (llr_input.hpp) */
     int64_t frames;
     uint8_t *out_dev;
     int64_t out_bytes;
@@ -311,10 +313,13 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
     if ((e = hipMemsetAsync(r.summary, 0, (r.crc_bits ? 4 : 2) * sizeof(int32_t), s))) return e;
     if ((e = hipMemsetAsync(pl->R.p, 0, (size_t)tiles * F * (size_t)pl->E * sizeof(float), s))) return e;
     {
-        LayeredInitArgs ia{r.llr_dev, pl->P.p, r.hard, r.frames, pl->N, pl->host_arith};
+        LayeredInitArgs ia{r.llr.p, pl->P.p, r.hard, r.frames, pl->N, pl->host_arith, r.llr.unit};
         dim3 grid((pl->N + kInitCols - 1) / kInitCols, tiles);
-        if (pl->bp) layered_init_scaled_kernel<V><<<grid, kBlock, 0, s>>>(ia, pl->llr_scale);
-        else layered_init_kernel<V><<<grid, kBlock, 0, s>>>(ia);
+        dispatch_llr(r.llr.type, [&](auto in) {
+            using IN = decltype(in);
+            if (pl->bp) layered_init_scaled_kernel<V, IN><<<grid, kBlock, 0, s>>>(ia, pl->llr_scale);
+            else layered_init_kernel<V, IN><<<grid, kBlock, 0, s>>>(ia);
+        });
         StateArgs st{r.done, nullptr, r.iters, nullptr, r.frames, 0, r.max_iter, 1};
         state_kernel<V><<<tiles, 64, 0, s>>>(st);
     }
@@ -352,9 +357,11 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
              * verdict; the frames that settle now leave P -- the posterior after the round's last layer, which later
              * rounds overwrite -- in the caller's buffer.  In the last round launched every running frame settles. */
             SoftArgs so{pl->P.p, nullptr, nullptr, nullptr, r.done, (r.early_term && it < rounds) ? fw : nullptr, r.soft,
-                        r.llr_dev, nullptr, nullptr, pl->E, r.frames, pl->N, pl->bp ? 0 : r.soft_extrinsic, TailRef{nullptr, 0, 0}};
+                        r.llr.p, nullptr, nullptr, pl->E, r.frames, pl->N, pl->bp ? 0 : r.soft_extrinsic, TailRef{nullptr, 0, 0}, r.llr.unit};
             if (r.span_begin && (e = r.span_begin(r.span_ctx, s, /*soft_settle_kernel*/ 7, 0,(int64_t)8 * pl->N * r.frames))) return e;
-            soft_settle_kernel<V, float><<<dim3((unsigned)((pl->N + kInitCols - 1) / kInitCols), (unsigned)tiles), kBlock, 0, s>>>(so);
+            dispatch_llr(r.llr.type, [&](auto in) {
+                soft_settle_kernel<V, float, decltype(in)><<<dim3((unsigned)((pl->N + kInitCols - 1) / kInitCols), (unsigned)tiles), kBlock, 0, s>>>(so);
+            });
             if (r.span_end && (e = r.span_end(r.span_ctx, s))) return e;
         }
         StateArgs st{r.done, fw, r.iters, nullptr, r.frames, it, r.max_iter, 1};
@@ -362,7 +369,11 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
     }
     if (pl->bp && r.soft && r.soft_extrinsic) {     /* posterior - chan, chan = llr_scale * y (layered_bp_extrinsic_kernel) */
         const int64_t count = r.frames * (int64_t)pl->N;
-        layered_bp_extrinsic_kernel<><<<(unsigned)((count + kBlock - 1) / kBlock), kBlock, 0, s>>>(r.soft, r.llr_dev, pl->llr_scale, count);
+        dispatch_llr(r.llr.type, [&](auto in) {
+            using IN = decltype(in);
+            layered_bp_extrinsic_kernel<IN><<<(unsigned)((count + kBlock - 1) / kBlock), kBlock, 0, s>>>(
+                r.soft, static_cast<const IN *>(r.llr.p), pl->llr_scale, count, r.llr.unit);
+        });
     }
     *launched = rounds;
     PackArgs pa{r.hard, r.out_dev, r.iters, r.iters_dev, r.frames, r.out_bytes, pl->N, r.K, r.pack_mode};

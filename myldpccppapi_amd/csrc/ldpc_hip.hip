@@ -66,6 +66,18 @@ int ldpc::set_error(int code, const char *fmt, ...)
 }
 
 std::string ldpc::last_error_text() { return g_err; }
+
+/* the element type, unit and address of a typed call's channel buffer (include/ldpc_hip.h: enum ldpc_llr_type) */
+int ldpc::llr_in_check(const void *p, int32_t type, float unit)
+{
+    if (type != LDPC_LLR_F32 && type != LDPC_LLR_F16 && type != LDPC_LLR_I8) return set_error(LDPC_ERR_ARG, "unknown llr_type %d", type);
+    /* written so that NaN fails it */
+    if (!(unit > 0.0f && unit <= 3.402823466e38f)) return set_error(LDPC_ERR_ARG, "llr_unit must be positive and finite");
+    if (type == LDPC_LLR_F32 && unit != 1.0f)
+        return set_error(LDPC_ERR_ARG, "LDPC_LLR_F32: llr_unit must be exactly 1 (float channel values are read as they are)");
+    if (type == LDPC_LLR_F16 && (reinterpret_cast<uintptr_t>(p) & 1)) return set_error(LDPC_ERR_ARG, "llr: fp16 values need 2-byte alignment");
+    return LDPC_OK;
+}
 void ldpc::restore_error(const std::string &text) { g_err = text; }
 
 /* ================================================================== C ABI */
@@ -554,8 +566,9 @@ int ldpc_decoder_create_multi(const ldpc_graph *g, const ldpc_decoder_config *cf
     return LDPC_OK;
 }
 
-int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, uint8_t *out_dev,
-                       int64_t out_bytes, int32_t *iters_dev, void *stream)
+/* ldpc_decode_device and ldpc_decode_typed_device: `in` has passed ldpc::llr_in_check */
+static int decode_device_in(ldpc_decoder *d, const ldpc::LlrIn &in, int64_t frames, uint8_t *out_dev,
+                            int64_t out_bytes, int32_t *iters_dev, void *stream)
 {
     if (!d) return set_error(LDPC_ERR_ARG, "decoder is NULL");
     if (!d->shards.empty())
@@ -566,7 +579,7 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
                     d->cfg.max_batch);
     if (out_bytes < 0) return set_error(LDPC_ERR_ARG, "out_bytes < 0");
     if (frames == 0) { d->last_frames = 0; d->tm.have_last = false; return LDPC_OK; }
-    if (!llr_dev) return set_error(LDPC_ERR_ARG, "llr is NULL");
+    if (!in.p) return set_error(LDPC_ERR_ARG, "llr is NULL");
     const int64_t need = ldpc_out_bytes(d->cfg.K, frames, d->cfg.pack_mode);
     /* bytes this call may store: none without out_dev (iteration counts and stats only) */
     const int64_t room = out_dev ? std::min(out_bytes, need) : 0;
@@ -583,6 +596,17 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
     if (out_dev) LDPC_HIP_TRY(hipMemsetAsync(out_dev, 0, (size_t)room, s));
     int rc;
     if (d->use_fused) {
+        /* the one-launch and record kernels read floats: a typed call widens into the handle's own buffer first, made by
+         * the handle's first typed call (a plain call launches and moves what it always did) */
+        const float *llr_dev = static_cast<const float *>(in.p);
+        if (in.type != LDPC_LLR_F32) {
+            LDPC_HIP_TRY(d->llr_wide.ensure((size_t)d->cfg.max_batch * d->N));
+            hipError_t e = ldpc::span_begin(d, s, 8, 0, frames * (int64_t)d->N * (int64_t)(4 + ldpc::llr_elem_size(in.type)));
+            if (e == hipSuccess) e = ldpc::engine_llr_widen(in, d->llr_wide.p, frames * (int64_t)d->N, s);
+            if (e == hipSuccess) e = ldpc::span_end(d, s);
+            if (e != hipSuccess) return set_error(LDPC_ERR_HIP, "widening the channel values: %s", hipGetErrorString(e));
+            llr_dev = d->llr_wide.p;
+        }
         ldpc::FusedRun run{llr_dev, frames, out_dev, room, iters_dev, d->cfg.K,
                            d->cfg.max_iter, d->tm.tap_iter, d->cfg.early_term, d->summary.p,
                            d->cfg.algo == LDPC_ALGO_MS_FUSED ? 1 : (d->cfg.algo == LDPC_ALGO_MS ? 2 : (d->cfg.algo == LDPC_ALGO_SP ? 3 : 0)),
@@ -603,7 +627,7 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
         };
         run.span_end = [](void *c, hipStream_t st) { return ldpc::span_end((ldpc_decoder *)c, st); };
         run.span_ctx = d;
-        run.llr_dev = llr_dev; run.frames = frames; run.out_dev = out_dev;
+        run.llr = in; run.frames = frames; run.out_dev = out_dev;
         run.out_bytes = room; run.iters_dev = iters_dev;
         run.K = d->cfg.K; run.max_iter = d->cfg.max_iter; run.tap_iter = d->tm.tap_iter;
         run.early_term = d->cfg.early_term; run.pack_mode = d->cfg.pack_mode;
@@ -615,7 +639,7 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
         rc = (e == hipSuccess) ? LDPC_OK
                                : set_error(LDPC_ERR_HIP, "layered decode: %s", hipGetErrorString(e));
     } else {
-        rc = ldpc::engine_flood_run(d, llr_dev, frames, out_dev, room, iters_dev, s);
+        rc = ldpc::engine_flood_run(d, in, frames, out_dev, room, iters_dev, s);
     }
     if (rc) return rc;
     LDPC_HIP_TRY(hipEventRecord(d->tm.ev_end.e, s));
@@ -623,8 +647,22 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
     return LDPC_OK;
 }
 
-int ldpc_decode_soft_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, uint8_t *out_dev, int64_t out_bytes,
-                            int32_t *iters_dev, float *soft_dev, int64_t soft_floats, int32_t soft_kind, void *stream)
+int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, uint8_t *out_dev,
+                       int64_t out_bytes, int32_t *iters_dev, void *stream)
+{
+    return decode_device_in(d, ldpc::llr_in_float(llr_dev), frames, out_dev, out_bytes, iters_dev, stream);
+}
+
+int ldpc_decode_typed_device(ldpc_decoder *d, const void *llr_dev, int32_t llr_type, float llr_unit, int64_t frames,
+                             uint8_t *out_dev, int64_t out_bytes, int32_t *iters_dev, void *stream)
+{
+    if (int rc = ldpc::llr_in_check(llr_dev, llr_type, llr_unit)) return rc;
+    return decode_device_in(d, ldpc::LlrIn{llr_dev, llr_type, llr_unit}, frames, out_dev, out_bytes, iters_dev, stream);
+}
+
+/* ldpc_decode_soft_device and ldpc_decode_soft_typed_device */
+static int decode_soft_device_in(ldpc_decoder *d, const ldpc::LlrIn &in, int64_t frames, uint8_t *out_dev, int64_t out_bytes,
+                                 int32_t *iters_dev, float *soft_dev, int64_t soft_floats, int32_t soft_kind, void *stream)
 {
     if (!d) return set_error(LDPC_ERR_ARG, "decoder is NULL");
     if (!d->shards.empty())
@@ -645,14 +683,32 @@ int ldpc_decode_soft_device(ldpc_decoder *d, const float *llr_dev, int64_t frame
         if (reinterpret_cast<uintptr_t>(soft_dev) & 3) return set_error(LDPC_ERR_ARG, "soft is not 4-byte aligned");
         const int64_t need = frames * (int64_t)d->N;
         if (soft_floats < need) return set_error(LDPC_ERR_ARG, "soft_floats=%lld < %lld", (long long)soft_floats, (long long)need);
-        if (llr_dev && soft_dev < llr_dev + need && llr_dev < soft_dev + need)
+        const uintptr_t l0 = reinterpret_cast<uintptr_t>(in.p), l1 = l0 + (uintptr_t)need * ldpc::llr_elem_size(in.type);
+        const uintptr_t s0 = reinterpret_cast<uintptr_t>(soft_dev), s1 = s0 + (uintptr_t)need * sizeof(float);
+        if (in.p && s0 < l1 && l0 < s1)
             return set_error(LDPC_ERR_ARG, "soft overlaps llr: the channel values are read while soft values are written");
     }
     /* the plain entry point does the rest; the request lives on the handle for exactly this call */
     d->soft = ldpc::SoftReq{frames > 0 ? soft_dev : nullptr, soft_kind, nullptr};
-    const int rc = ldpc_decode_device(d, llr_dev, frames, out_dev, out_bytes, iters_dev, stream);
+    const int rc = decode_device_in(d, in, frames, out_dev, out_bytes, iters_dev, stream);
     d->soft = ldpc::SoftReq{};
     return rc;
+}
+
+int ldpc_decode_soft_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, uint8_t *out_dev, int64_t out_bytes,
+                            int32_t *iters_dev, float *soft_dev, int64_t soft_floats, int32_t soft_kind, void *stream)
+{
+    return decode_soft_device_in(d, ldpc::llr_in_float(llr_dev), frames, out_dev, out_bytes, iters_dev, soft_dev, soft_floats,
+                                 soft_kind, stream);
+}
+
+int ldpc_decode_soft_typed_device(ldpc_decoder *d, const void *llr_dev, int32_t llr_type, float llr_unit, int64_t frames,
+                                  uint8_t *out_dev, int64_t out_bytes, int32_t *iters_dev, float *soft_dev, int64_t soft_floats,
+                                  int32_t soft_kind, void *stream)
+{
+    if (int rc = ldpc::llr_in_check(llr_dev, llr_type, llr_unit)) return rc;
+    return decode_soft_device_in(d, ldpc::LlrIn{llr_dev, llr_type, llr_unit}, frames, out_dev, out_bytes, iters_dev, soft_dev,
+                                 soft_floats, soft_kind, stream);
 }
 
 }  /* extern "C" */

@@ -35,7 +35,7 @@ struct SoftArgs {
     const uint64_t *__restrict__ done;    /* [T][V] frames frozen before this round */
     const uint64_t *__restrict__ fail;    /* [T][V] this round's verdict; nullptr: every running frame settles */
     float *__restrict__ soft;             /* [frames][N] the caller's buffer, frame-major */
-    const float *__restrict__ llr;        /* layered, extrinsic: the caller's channel values [frames][N] */
+    const void *__restrict__ llr;         /* layered, extrinsic: the caller's channel values [frames][N], elements of IN */
     const int32_t *__restrict__ fmap;     /* a hand-over child: slot -> frame of the caller's batch; nullptr: identity */
     const int32_t *__restrict__ tail_map; /* device-side tail: overflow slot -> frame (flood_handover.hpp) */
     int64_t E;
@@ -43,11 +43,13 @@ struct SoftArgs {
     int32_t N;
     int32_t extrinsic;
     TailRef tail;
+    float llr_unit;                       /* layered, extrinsic, narrow IN: y = (float)x * llr_unit (llr_input.hpp) */
 };
 
 /* grid (ceil(N / kInitCols), tiles), block kBlock.  T: storage type of the flooding messages; the layered form is
- * soft_settle_kernel<V, float> with R == nullptr. */
-template <int V, typename T>
+ * soft_settle_kernel<V, float> with R == nullptr.  IN: element type of the caller's channel values, which only the layered
+ * extrinsic form reads: y is the product x * llr_unit of a narrow element, formed first. */
+template <int V, typename T, typename IN = float>
 __global__ __launch_bounds__(kBlock) void soft_settle_kernel(const SoftArgs a)
 {
     constexpr int F = 64 * V;
@@ -109,7 +111,7 @@ __global__ __launch_bounds__(kBlock) void soft_settle_kernel(const SoftArgs a)
         if (over) frame = a.tail_map[frame];
         else if (a.fmap) frame = a.fmap[frame];
         float p = patch[c * LD + f];
-        if (!a.R && a.extrinsic) p = p - a.llr[(size_t)frame * a.N + n];
+        if (!a.R && a.extrinsic) p = p - llr_value<IN>(static_cast<const IN *>(a.llr)[(size_t)frame * a.N + n], a.llr_unit);
         a.soft[(size_t)frame * a.N + n] = p;
     }
 }

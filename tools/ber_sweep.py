@@ -70,6 +70,11 @@ ap.add_argument("--no-interleave", action="store_true", help="with --modulation:
 ap.add_argument("--transport-block", default=None, metavar="A[,C]",
                 help="with --payload random: A payload bits per transport block, C code blocks (default: the rule of ldpc_tb_spec_init)")
 ap.add_argument("--msg-dtype", choices=("f32", "f16", "f8"), default="f32", help="message storage (f16: --algo ms and bp; f8: --algo ms)")
+ap.add_argument("--llr-type", choices=("f32", "f16", "i8"), default="f32",
+                help="quantise the channel values on the device (ldpc_llr_quantize_device) behind the channel / rate-recover step "
+                     "and decode them through ldpc_decode_typed_device")
+ap.add_argument("--llr-unit", type=float, default=None, help="with --llr-type f16 / i8: the decoder reads y = x * unit (default: "
+                                                             "i8 0.05, f16 1/256)")
 ap.add_argument("--crc-stop", action="store_true", help="with --transport-block: frames also stop once their CRC passes")
 ap.add_argument("--soft-check", action="store_true",
                 help="every batch is decoded once more with soft output (not --algo sp): prints the finite non-zero posteriors whose sign "
@@ -189,6 +194,20 @@ def channel_batch(first, sd, seed):
     rm.recover_device(rx.data_ptr(), B, K0, E, None, False, y.data_ptr(), stream)
 
 
+def quantise_batch():
+    """--llr-type: the float values in y become int8 / fp16 elements in yq, which is what the decoder is given"""
+    if yq is not None:
+        L.quantize_device(y.data_ptr(), y.numel(), args.llr_type, llr_unit, yq.data_ptr(), 0, torch.cuda.current_stream().cuda_stream)
+
+
+def decode_batch(out_t, it_t, **kw):
+    if yq is None:
+        dec.decode_device(y.data_ptr(), B, out_t.data_ptr(), out_t.numel(), it_t.data_ptr() if it_t is not None else None, None, **kw)
+    else:
+        dec.decode_device(yq.data_ptr(), B, out_t.data_ptr(), out_t.numel(), it_t.data_ptr() if it_t is not None else None, None,
+                          llr_type=args.llr_type, llr_unit=llr_unit, **kw)
+
+
 def modem_batch(bits, n, first, sd, seed, dst, stream):
     """bits uint8 [B, n] -> symbols + noise -> demapped values float32 [B, n] in dst."""
     md.transmit_device(bits.data_ptr(), B, n, sd, seed, sym.data_ptr(), sym.numel(), first, "bits", stream)
@@ -219,14 +238,18 @@ if args.soft_check:
 def soft_check():
     """The batch in y once more through ldpc_decode_soft_device: (posteriors of the K output bits that are finite and not
     zero, those among them whose sign is not the output bit, bytes that differ from the plain call's)."""
-    dec.decode_device(y.data_ptr(), B, out2.data_ptr(), out2.numel(), None, None, soft_ptr=soft.data_ptr(), soft_floats=soft.numel(),
-                      soft="posterior")
+    decode_batch(out2, None, soft_ptr=soft.data_ptr(), soft_floats=soft.numel(), soft="posterior")
     bits = ((out2.view(B, K // 8).to(torch.int32)[:, :, None] >> shifts) & 1).reshape(B, K)
     p = soft[:, :K]
     ok = torch.isfinite(p) & (p != 0)
     return int(ok.sum()), int((ok & ((p < 0) != (bits != 0))).sum()), int((out2 != out).sum())
 
 
+yq, llr_unit = None, 1.0
+if args.llr_type != "f32":
+    llr_unit = args.llr_unit if args.llr_unit is not None else (0.05 if args.llr_type == "i8" else 1.0 / 256)
+    yq = torch.empty((B, N), dtype=torch.int8 if args.llr_type == "i8" else torch.float16, device="cuda")
+    print("typed input: llr_type=%s llr_unit=%g (%d bytes per frame instead of %d)" % (args.llr_type, llr_unit, N * yq.element_size(), 4 * N))
 if rm is not None:
     print("rate matching: punctured=%d fillers=[%d,%d) E=%d k0=%d erasure_llr=%g effective rate (K - fillers)/E = %.4f" % (
         P, FLO, FHI, E, K0, args.erasure_llr, rate))
@@ -244,7 +267,8 @@ points = [float(x) for x in args.snr.split(",")]
 # one untimed batch first: the first launch of every kernel (the library's and torch's) pays one-time costs
 point_decoder(10.0 ** (-points[-1] / 20.0))
 channel_batch(0, 10.0 ** (-points[-1] / 20.0), args.seed + 1)
-dec.decode_device(y.data_ptr(), B, out.data_ptr(), out.numel(), it.data_ptr(), None)
+quantise_batch()
+decode_batch(out, it)
 channel.count_errors_device(out, src, B)
 float(it.float().sum())
 torch.cuda.synchronize()
@@ -258,7 +282,8 @@ for snr in points:
     t0 = time.perf_counter()
     for b in range(args.batches):
         channel_batch(b * B, sd, args.seed)
-        dec.decode_device(y.data_ptr(), B, out.data_ptr(), out.numel(), it.data_ptr(), None)
+        quantise_batch()
+        decode_batch(out, it)
         e = channel.count_errors_device(out, src, B)
         tot = [t + x for t, x in zip(tot, e)]
         if tb is not None:
