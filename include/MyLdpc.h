@@ -36,6 +36,8 @@
  *   - setModulation(): test() sends QPSK / 16- / 64- / 256-QAM symbols through the "modem" section of ldpc_hip.h.
  *   - setTransportBlock(): every frame carries payload bits plus a CRC ("transport block" section of ldpc_hip.h), which
  *     decode() checks: crcPassed() / lastCrcFailures().
+ *   - setOuterBch(): every frame carries payload bits plus the parity of a BCH code ("outer code" section of ldpc_hip.h),
+ *     with which decode() repairs up to t wrong bits per frame: bchStatus() / bchCounts().
  */
 #ifndef MYLDPC_H_
 #define MYLDPC_H_
@@ -156,6 +158,21 @@ public:
      * Runs on the GPU `setDevice` names (ldpc_tb_attach / ldpc_tb_check).  Off by default: without this call every byte and
      * length is as in the reference.  Before encode() and decode().  Returns 0 or an ldpc_status. */
     int setTransportBlock(int payloadBits, int crcBits = -1);
+    /* Outer BCH code ("outer code" section of ldpc_hip.h), as a DVB-S2 frame has one around its LDPC information bits:
+     * every frame carries k = n - r payload bits, the r parity bits of the BCH code that corrects t errors (1 .. 12;
+     * GF(2^14) up to n = 16383, else GF(2^16); r = 14 t or 16 t there) and zero fillers up to K.  n = -1 means K; n % 8 == 0,
+     * n <= K, K % 8 == 0 and k % 8 == 0 are required.  Then encode() reads k / 8 source bytes per frame, decode() writes
+     * the k / 8 payload bytes per frame after the outer decoder has repaired up to t wrong bits, srcLength counts
+     * payload bytes in both, and getCodeSize / getPriorCodeLength / getPostCodeLength follow.  bchStatus(frame) of the
+     * last decode(): 0 clean, 1 .. t bits repaired, -1 not decodable (the payload is then what the inner decoder left),
+     * -2 no such frame; bchCounts(): {frames failed, frames repaired, bits repaired}.  Composes with setEncodeOnDevice,
+     * setRateMatch and setModulation.  Mutually exclusive with setTransportBlock(): the second of the two calls returns
+     * LDPC_ERR_STATE.  Runs on the GPU `setDevice` names (ldpc_bch_encode / ldpc_bch_decode).  Off by default.  Before
+     * encode() and decode().  Returns 0 or an ldpc_status. */
+    int setOuterBch(int t, int n = -1);
+    int bchStatus(int frame) const { return frame >= 0 && (size_t)frame < bchStatusOfFrame.size() ? bchStatusOfFrame[(size_t)frame] : -2; }
+    struct BchCounts { int failed, corrected, bits; };
+    BchCounts bchCounts() const { return BchCounts{bchFailed, bchCorrected, bchBits}; }
     /* CRC-aided early termination (ldpc_hip.h: crc_kind / crc_bits): with setTransportBlock() every frame carries a CRC,
      * and a frame then also stops in the first round in which its payload and CRC bits pass it -- usually a round before
      * its syndrome is clean.  Needs setTransportBlock() with crcBits != 0 first (LDPC_ERR_STATE otherwise).  DecodeSP,
@@ -215,6 +232,10 @@ private:
     ldpc_rate_spec rmSpec = {};
     ldpc_modem_spec modSpec = {};    /* setModulation(); Qm = 0: off */
     ldpc_tb_spec tbSpec = {};        /* setTransportBlock(); A = 0: off */
+    ldpc_bch_spec bchSpec = {};      /* setOuterBch(); bchK = 0: off */
+    int bchK = 0;                    /* payload bits per frame */
+    std::vector<int32_t> bchStatusOfFrame;   /* per frame of the last decode() */
+    int bchFailed = 0, bchCorrected = 0, bchBits = 0;
     std::vector<unsigned char> crcOk;/* per frame of the last decode() */
     int crcFailures = 0;
     bool crcEarlyStop = false;       /* setCrcEarlyStop() */

@@ -785,6 +785,69 @@ int ldpc_tb_attach(const ldpc_tb_spec *spec, const uint8_t *payload_host, int64_
 int ldpc_tb_check(const ldpc_tb_spec *spec, const uint8_t *dec_host, int64_t tbs, uint8_t *payload_host, uint8_t *cb_ok_host,
                   uint8_t *tb_ok_host, int32_t device);
 
+/* ---- outer code: a binary BCH code around the information bits of a frame, in front of ldpc_encode_device and behind a
+ *      decoder, as a DVB-S2 frame is BCH o LDPC: it removes the few wrong bits a decoder leaves at its round budget and tells
+ *      the receiver whether a frame is good without the sent bytes.  A plain parameter set and a row layout, as
+ *      ldpc_tb_spec is: no handle, no device state visible to the caller (the library caches derived plans; the cache is
+ *      thread-safe).  "DVB-S2-profile": the generator is computed from the field polynomial, it has not been compared
+ *      with the polynomials the standard prints.
+ *
+ * The rule, bit for bit (project bit order: bit i of a row is bit i % 8 of byte i / 8):
+ *   Field GF(2^m) = GF(2)[x] / prim, alpha = x.  g(x) = lcm of the minimal polynomials over GF(2) of alpha^j,
+ *   j = 1 .. 2t; r = deg g, k = n - r.  n <= 2^m - 1 (a shortened code), n % 8 == 0, k >= 8 and k % 8 == 0.
+ *   ldpc_bch_spec_init: m = 14, prim = 0x402B (x^14+x^5+x^3+x+1) for n <= 16383, else m = 16, prim = 0x1002D
+ *   (x^16+x^5+x^3+x^2+1); callers may overwrite m and prim.  r = 168 / 140 / 112 and 192 / 160 / 128 at t = 12 / 10 / 8.
+ *   Polynomials as in the CRC section: bit i of the n code bits is the coefficient of x^(n-1-i).  The message
+ *   a_0 .. a_(k-1) is followed by the parity p_0 .. p_(r-1), p(x) = x^r a(x) mod g(x) with a(x) = sum a_i x^(k-1-i) and
+ *   p(x) = sum p_j x^(r-1-j): register zero, no reflection, no final XOR.
+ *   Encode: row f of src receives bits [0, k) = payload row f (k/8 bytes), bits [k, n) the parity, bits
+ *   [n, 8 row_bytes) zeros; every byte of every row is written.  With row_bytes = K/8 the result is what
+ *   ldpc_encode_device takes as src_dev.
+ *   Syndromes of received bits v_i: S_j = v(alpha^j), j = 1 .. 2t, v(x) = sum v_i x^(n-1-i); an error at bit i has
+ *   locator alpha^(n-1-i).
+ *   Decode, a bounded-distance decoder defined by its result: all S_j = 0: status 0.  Else, if a set P of bit positions
+ *   in [0, n) with 1 <= |P| <= t exists whose flipping makes all 2t syndromes zero (it is unique, d >= 2t + 1): the
+ *   bits are flipped and status = |P|.  Otherwise status = -1 and no bit is changed.  Positions >= n never count as
+ *   error positions (a locator polynomial with a root outside [0, n) is a failure); bits [n, 8 row_bytes) of the input
+ *   are ignored.  Outputs, each nullable, at least one given: payload_dev, frames * k/8 bytes, the first k bits after
+ *   the flips; status_dev, one int32 per frame.
+ *   Tally (blocks, as ldpc_tb_tally_device; ref_dev NULL = all zero): counts[0] = frames with status -1, [1] = frames
+ *   whose payload differs from ref, [2] = frames that differ although status >= 0 (miscorrected or undetected),
+ *   [3] = frames with status > 0, [4] = sum of the positive statuses (bits corrected), [5] = frames with status -1
+ *   although the payload is equal.
+ *
+ * ldpc_bch_layout (host only): out = {k, r, number of distinct minimal polynomials, m}.
+ * ldpc_bch_generator (host only): the coefficients g_0 .. g_r (one byte each, 0 or 1) of any valid (m, prim, t), without
+ *   the byte rules on n and k; *r receives the degree; g may be NULL (then only *r), cap < r + 1 is LDPC_ERR_ARG.
+ * The pointer rules of ldpc_decode_device apply to the *_device calls, which enqueue on `stream`, return without waiting
+ *   and allocate nothing: byte buffers may have any alignment, status_dev needs its natural 4-byte alignment; nothing
+ *   outside the stated sizes is read or written (dec: frames * row_bytes bytes; src_bytes < frames * row_bytes is
+ *   LDPC_ERR_ARG); overlapping input and output is LDPC_ERR_ARG; a refused call has enqueued nothing; frames == 0 enqueues
+ *   nothing.  ldpc_bch_encode / ldpc_bch_decode take host buffers, block, and run the same kernels over chunks of
+ *   frames.  There is no CPU path.  Every argument error -- m outside 4 .. 16, a prim that is not primitive, t outside
+ *   1 .. 12 or 2t >= 2^m - 1, n, k, row_bytes, struct_size -- is LDPC_ERR_ARG with a message that names the field. */
+typedef struct ldpc_bch_spec {
+    uint32_t struct_size;          /* = sizeof(ldpc_bch_spec); ABI guard                                                 */
+    int32_t  m;                    /* field GF(2^m) = GF(2)[x] / prim, alpha = x; 4 <= m <= 16                          */
+    uint32_t prim;                 /* field polynomial, bit i = coefficient of x^i, x^m term included; must be primitive */
+    int32_t  t;                    /* designed correction capability, 1 <= t <= 12, 2t < 2^m - 1                        */
+    int32_t  n;                    /* code bits per frame (message + parity), n <= 2^m - 1 (shortened), n % 8 == 0       */
+    int32_t  row_bytes;            /* bytes per frame row on the encoder/decoder side, 8 * row_bytes >= n (e.g. K / 8)   */
+} ldpc_bch_spec;
+void ldpc_bch_spec_init(ldpc_bch_spec *spec, int32_t n, int32_t t, int32_t row_bytes);
+int ldpc_bch_layout(const ldpc_bch_spec *spec, int32_t out[4]);
+int ldpc_bch_generator(int32_t m, uint32_t prim, int32_t t, uint8_t *g, int32_t cap, int32_t *r);
+int ldpc_bch_encode_device(const ldpc_bch_spec *spec, const uint8_t *payload_dev, int64_t frames, uint8_t *src_dev, int64_t src_bytes,
+                           int32_t device, void *stream);
+int ldpc_bch_decode_device(const ldpc_bch_spec *spec, const uint8_t *dec_dev, int64_t frames, uint8_t *payload_dev, int32_t *status_dev,
+                           int32_t device, void *stream);
+int ldpc_bch_tally_device(const int32_t *status_dev, const uint8_t *payload_dev, const uint8_t *ref_dev, int64_t frames,
+                          int64_t bytes_per_frame, int64_t counts[6], int32_t device, void *stream);
+int ldpc_bch_encode(const ldpc_bch_spec *spec, const uint8_t *payload_host, int64_t frames, uint8_t *src_host, int64_t src_bytes,
+                    int32_t device);
+int ldpc_bch_decode(const ldpc_bch_spec *spec, const uint8_t *dec_host, int64_t frames, uint8_t *payload_host, int32_t *status_host,
+                    int32_t device);
+
 /* ---- measurement aid: the rate a plain float4 copy of `bytes` bytes (read + write counted)
  *      sustains on `device` right now, best of `reps` launches each with the default cache policy
  *      and with non-temporal loads and stores (the streaming kernels' policy), HIP-event timed on

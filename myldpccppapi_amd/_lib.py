@@ -81,6 +81,12 @@ class TbSpec(ctypes.Structure):
                 ("cb_crc", ctypes.c_int32), ("K", ctypes.c_int32)]
 
 
+class BchSpec(ctypes.Structure):
+    """Mirror of `ldpc_bch_spec`."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("m", ctypes.c_int32), ("prim", ctypes.c_uint32), ("t", ctypes.c_int32),
+                ("n", ctypes.c_int32), ("row_bytes", ctypes.c_int32)]
+
+
 #: every symbol include/ldpc_hip.h declares
 EXPORTS = (
     "ldpc_abi_version", "ldpc_last_error", "ldpc_device_count", "ldpc_graph_create",
@@ -100,6 +106,8 @@ EXPORTS = (
     "ldpc_decode_soft_device", "ldpc_decode_soft",
     "ldpc_decode_typed_device", "ldpc_decode_soft_typed_device", "ldpc_decode_typed", "ldpc_decode_soft_typed",
     "ldpc_llr_quantize_device",
+    "ldpc_bch_spec_init", "ldpc_bch_layout", "ldpc_bch_generator", "ldpc_bch_encode_device", "ldpc_bch_decode_device",
+    "ldpc_bch_tally_device", "ldpc_bch_encode", "ldpc_bch_decode",
 )
 
 
@@ -213,6 +221,16 @@ def load():
     L.ldpc_decoder_crc_stops.argtypes = [vp, i64p]
     L.ldpc_crc_weights.argtypes = [ctypes.c_int32, ctypes.c_int32, vp]
     L.ldpc_tb_frame_crc.argtypes = [tsp, i32p, i32p]
+    bsp = ctypes.POINTER(BchSpec)
+    L.ldpc_bch_spec_init.argtypes = [bsp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+    L.ldpc_bch_spec_init.restype = None
+    L.ldpc_bch_layout.argtypes = [bsp, i32p]
+    L.ldpc_bch_generator.argtypes = [ctypes.c_int32, ctypes.c_uint32, ctypes.c_int32, vp, ctypes.c_int32, i32p]
+    L.ldpc_bch_encode_device.argtypes = [bsp, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int32, vp]
+    L.ldpc_bch_decode_device.argtypes = [bsp, vp, ctypes.c_int64, vp, vp, ctypes.c_int32, vp]
+    L.ldpc_bch_tally_device.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int64, i64p, ctypes.c_int32, vp]
+    L.ldpc_bch_encode.argtypes = [bsp, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int32]
+    L.ldpc_bch_decode.argtypes = [bsp, vp, ctypes.c_int64, vp, vp, ctypes.c_int32]
     _lib = L
     return L
 

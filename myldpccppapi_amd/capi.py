@@ -1,5 +1,5 @@
-"""Thin Python objects over the C ABI (include/ldpc_hip.h): Graph, Decoder, Encoder, RateMatcher, Modem and
-TransportBlock.
+"""Thin Python objects over the C ABI (include/ldpc_hip.h): Graph, Decoder, Encoder, RateMatcher, Modem,
+TransportBlock and BchCode.
 
 Host-side plumbing only -- every decode runs in the HIP kernels of
 libldpc_hip.so.  numpy arrays are passed as host pointers, integers (e.g. a
@@ -619,3 +619,75 @@ class TransportBlock:
         _lib.check(_lib.load().ldpc_tb_check(ctypes.byref(self.spec), dec.ctypes.data, tbs, payload.ctypes.data, cb_ok.ctypes.data,
                                              tb_ok.ctypes.data, self.device))
         return payload, cb_ok, tb_ok
+
+
+class BchCode:
+    """The outer code in front of Encoder.encode_device and behind Decoder.decode_device (ldpc_bch_*, include/ldpc_hip.h):
+    a binary BCH code of n bits that corrects up to t errors, over GF(2^m) = GF(2)[x] / prim; m, prim: None = the rule
+    of ldpc_bch_spec_init (m = 14 / 0x402B up to n = 16383, else m = 16 / 0x1002D).  Rows of row_bytes bytes (None:
+    n / 8) hold the k = n - r message bits, the r parity bits and zeros.  A plain parameter set: no handle."""
+
+    def __init__(self, n, t, row_bytes=None, m=None, prim=None, device=0):
+        L = _lib.load()
+        self.spec = _lib.BchSpec()
+        L.ldpc_bch_spec_init(ctypes.byref(self.spec), int(n), int(t), int(n) // 8 if row_bytes is None else int(row_bytes))
+        if m is not None:
+            self.spec.m = int(m)
+        if prim is not None:
+            self.spec.prim = int(prim)
+        self.device = int(device)
+        self.k, self.r, self.nmin, self.m = self.layout()                     # an unusable spec fails here
+        self.n, self.t, self.row_bytes, self.prim = self.spec.n, self.spec.t, self.spec.row_bytes, self.spec.prim
+
+    def layout(self):
+        """(k, r, number of distinct minimal polynomials, m)."""
+        out = (ctypes.c_int32 * 4)()
+        _lib.check(_lib.load().ldpc_bch_layout(ctypes.byref(self.spec), out))
+        return tuple(int(v) for v in out)
+
+    @staticmethod
+    def generator_of(m, prim, t):
+        """uint8 [r + 1]: the coefficients g_0 .. g_r of the generator of any valid (m, prim, t).  Host arithmetic only."""
+        r = ctypes.c_int32()
+        _lib.check(_lib.load().ldpc_bch_generator(int(m), int(prim), int(t), None, 0, ctypes.byref(r)))
+        g = np.zeros(r.value + 1, np.uint8)
+        _lib.check(_lib.load().ldpc_bch_generator(int(m), int(prim), int(t), g.ctypes.data, g.size, None))
+        return g
+
+    def generator(self):
+        return self.generator_of(self.m, self.prim, self.t)
+
+    # -- buffers already in HBM (integers, e.g. a torch tensor's data_ptr()); enqueued on `stream`, no wait --------
+    def encode_device(self, payload_ptr, frames, src_ptr, src_nbytes, stream=None):
+        _lib.check(_lib.load().ldpc_bch_encode_device(ctypes.byref(self.spec), payload_ptr, int(frames), src_ptr, int(src_nbytes),
+                                                      self.device, stream))
+
+    def decode_device(self, dec_ptr, frames, payload_ptr=None, status_ptr=None, stream=None):
+        _lib.check(_lib.load().ldpc_bch_decode_device(ctypes.byref(self.spec), dec_ptr, int(frames), payload_ptr, status_ptr,
+                                                      self.device, stream))
+
+    def tally_device(self, status_ptr, payload_ptr, ref_ptr, frames, stream=None):
+        """Blocks.  (failed, wrong, miscorrected_or_undetected, corrected_frames, corrected_bits, failed_though_equal)
+        over `frames` frames of k/8 payload bytes."""
+        counts = (ctypes.c_int64 * 6)()
+        _lib.check(_lib.load().ldpc_bch_tally_device(status_ptr, payload_ptr, ref_ptr, int(frames), self.k // 8, counts, self.device, stream))
+        return tuple(int(v) for v in counts)
+
+    # -- host buffers (numpy); blocking ---------------------------------------------------------------------------
+    def encode(self, payload):
+        """payload: uint8 [frames, k/8] -> uint8 [frames, row_bytes], the source rows of the encoder."""
+        payload = np.ascontiguousarray(payload, np.uint8).reshape(-1, self.k // 8)
+        frames = payload.shape[0]
+        src = np.zeros((frames, self.row_bytes), np.uint8)
+        _lib.check(_lib.load().ldpc_bch_encode(ctypes.byref(self.spec), payload.ctypes.data, frames, src.ctypes.data, src.size, self.device))
+        return src
+
+    def decode(self, dec):
+        """dec: uint8 [frames, row_bytes] -> (payload uint8 [frames, k/8], status int32 [frames])."""
+        dec = np.ascontiguousarray(dec, np.uint8).reshape(-1, self.row_bytes)
+        frames = dec.shape[0]
+        payload = np.zeros((frames, self.k // 8), np.uint8)
+        status = np.zeros(frames, np.int32)
+        _lib.check(_lib.load().ldpc_bch_decode(ctypes.byref(self.spec), dec.ctypes.data, frames, payload.ctypes.data, status.ctypes.data,
+                                               self.device))
+        return payload, status

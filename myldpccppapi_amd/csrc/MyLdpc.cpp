@@ -77,8 +77,12 @@ int Coder::initCheckMatrix()
 /* Length helpers, MyLdpc.cpp:620-631; with setRateMatch(): E transmitted bits per frame take the place of the N code bits. */
 int Coder::getPriorCodeLength(int srcLength) { return getCodeSize(srcLength) * ((rmE ? rmE : ldpcN) / 8); }
 int Coder::getPostCodeLength(int srcLength) { return getCodeSize(srcLength) * (rmE ? rmE : ldpcN); }
-/* with setTransportBlock(): srcLength counts payload bytes, A / 8 per frame */
-int Coder::getCodeSize(int srcLength) { return tbSpec.A ? (srcLength + tbSpec.A / 8 - 1) / (tbSpec.A / 8) : frameCount(srcLength); }
+/* with setTransportBlock() or setOuterBch(): srcLength counts payload bytes, A / 8 or k / 8 per frame */
+int Coder::getCodeSize(int srcLength)
+{
+    const int per = tbSpec.A ? tbSpec.A / 8 : bchK / 8;
+    return per ? (srcLength + per - 1) / per : frameCount(srcLength);
+}
 
 /* ----------------------------------------------------------------- encoder */
 
@@ -132,10 +136,28 @@ int Coder::setTransportBlock(int payloadBits, int crcBits)
     spec.C = 1;
     spec.cb_crc = 0;
     int32_t lay[6];
+    if (bchK) return fail(LDPC_ERR_STATE, "setTransportBlock: setOuterBch() is in force: a frame carries one of the two");
     if (int rc = ldpc_tb_layout(&spec, lay)) return fail(rc, std::string("setTransportBlock: ") + ldpc_last_error());
     tbSpec = spec;
     crcOk.clear();
     crcFailures = 0;
+    return LDPC_SUCCESS;
+}
+
+/* The outer BCH code (the "outer code" section of ldpc_hip.h) around encode() and decode(): n code bits in front of zero
+ * fillers up to K */
+int Coder::setOuterBch(int t, int n)
+{
+    if (tbSpec.A) return fail(LDPC_ERR_STATE, "setOuterBch: setTransportBlock() is in force: a frame carries one of the two");
+    if (ldpcK % 8) return fail(LDPC_ERR_ARG, "setOuterBch: K must be a multiple of 8 (rows of K / 8 bytes)");
+    ldpc_bch_spec spec;
+    ldpc_bch_spec_init(&spec, n < 0 ? ldpcK : n, t, ldpcK / 8);
+    int32_t lay[4];
+    if (int rc = ldpc_bch_layout(&spec, lay)) return fail(rc, std::string("setOuterBch: ") + ldpc_last_error());
+    bchSpec = spec;
+    bchK = lay[0];
+    bchStatusOfFrame.clear();
+    bchFailed = bchCorrected = bchBits = 0;
     return LDPC_SUCCESS;
 }
 
@@ -241,6 +263,15 @@ int Coder::encode(char *srcCode, char *priorCode, int srcLength)
 {
     if (!isEncoder) return fail(LDPC_ERR_STATE, "encode: call forEncoder() first");
     if (!srcCode || !priorCode || srcLength <= 0) return fail(LDPC_ERR_ARG, "encode: bad arguments");
+    if (bchK) {
+        /* payload (the last frame zero-padded) -> K / 8 source bytes per frame: payload, parity, zero fillers */
+        const int frames = getCodeSize(srcLength);
+        std::vector<char> payload((size_t)frames * (bchK / 8), 0), source((size_t)frames * (ldpcK / 8));
+        memcpy(payload.data(), srcCode, (size_t)srcLength);
+        if (int rc = ldpc_bch_encode(&bchSpec, (const uint8_t *)payload.data(), frames, (uint8_t *)source.data(), (int64_t)source.size(), device))
+            return fail(rc, ldpc_last_error());
+        return encodeSource(source.data(), priorCode, (int)source.size());
+    }
     if (!tbSpec.A) return encodeSource(srcCode, priorCode, srcLength);
     /* payload (the last frame zero-padded) -> K / 8 source bytes per frame: payload, CRC, zero fillers */
     const int frames = getCodeSize(srcLength);
@@ -525,11 +556,11 @@ int Coder::decodeFrames(const void *postCode, int llrType, float llrUnit, char *
     if (!isDecoder) return fail(LDPC_ERR_STATE, "decode: call forDecoder() first");
     if (!postCode || !srcCode || srcLength <= 0) return fail(LDPC_ERR_ARG, "decode: bad arguments");
     const int codeSize = getCodeSize(srcLength);
-    /* with setTransportBlock() the decoders write whole frames of K / 8 bytes to a buffer of their own */
+    /* with setTransportBlock() or setOuterBch() the decoders write whole frames of K / 8 bytes to a buffer of their own */
     char *const payloadOut = srcCode;
     const int payloadLength = srcLength;
     std::vector<char> decoded;
-    if (tbSpec.A) {
+    if (tbSpec.A || bchK) {
         decoded.resize((size_t)codeSize * (ldpcK / 8));
         srcCode = decoded.data();
         srcLength = (int)decoded.size();
@@ -589,6 +620,19 @@ int Coder::decodeFrames(const void *postCode, int llrType, float llrUnit, char *
         memcpy(payloadOut, payload.data(), (size_t)payloadLength);
         crcFailures = 0;
         for (unsigned char ok : crcOk) crcFailures += !ok;
+    }
+    if (bchK) {
+        std::vector<char> payload((size_t)codeSize * (bchK / 8));
+        bchStatusOfFrame.assign((size_t)codeSize, 0);
+        rc = ldpc_bch_decode(&bchSpec, (const uint8_t *)decoded.data(), codeSize, (uint8_t *)payload.data(), bchStatusOfFrame.data(), device);
+        if (rc) return fail(rc, ldpc_last_error());
+        memcpy(payloadOut, payload.data(), (size_t)payloadLength);
+        bchFailed = bchCorrected = bchBits = 0;
+        for (int32_t st : bchStatusOfFrame) {
+            bchFailed += st < 0;
+            bchCorrected += st > 0;
+            bchBits += st > 0 ? st : 0;
+        }
     }
     return LDPC_SUCCESS;
 }

@@ -9,7 +9,7 @@ reference counts differing BYTES (Test.cpp:105-110); this prints byte errors too
 
     python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N>] [--algo sp|ms|layered|bp|layered_bp]
                               [--payload zero|random] [--rate-match P,FLO,FHI,E[,K0]] [--erasure-llr X]
-                              [--modulation bpsk|qpsk|qam16|qam64|qam256] [--no-interleave] [--transport-block A[,C]] [--crc-stop]
+                              [--modulation bpsk|qpsk|qam16|qam64|qam256] [--no-interleave] [--transport-block A[,C]] [--crc-stop] [--bch T[,N]]
                               [--msg-dtype f32|f16|f8] [--soft-check]
                               [--snr=1.0,1.5,...]  (write --snr=-0.5,0 for a list that starts with a minus) [--frames 4096] [--iters 50]
 --rate-match: code bits [0, P) punctured, [FLO, FHI) filler bits (known zeros; multiples of 8, inside the information part),
@@ -34,6 +34,13 @@ blocks as a receiver does, without the bytes that were sent (include/ldpc_hip.h,
 multiple of C.  Every point also prints the block error rate (blocks whose payload is wrong), the blocks whose CRCs failed
 (detected), the wrong blocks whose CRCs passed (undetected) and the right blocks whose CRCs failed (parity only).  The
 fillers [Kp, K) are sent unless --rate-match names them.
+--bch T[,N] (with --payload random; not with --transport-block): the random bytes are the k = N - r message bits of a BCH code
+that corrects T errors (N omitted: K; include/ldpc_hip.h, "outer code"); ldpc_bch_encode_device in front of the encoder adds the
+parity (and zero fillers up to K), ldpc_bch_decode_device behind the decoder repairs up to T wrong bits per frame.  Every point
+also prints the frames with a wrong bit among the N code bits after the LDPC decoder and the frames whose payload is wrong
+after the outer code, the frames it repaired, could not decode (status -1) and miscorrected, the bits it repaired, and
+residual_hist: how many frames the LDPC decoder left with 0, 1 .. T and more than T wrong bits (T + 2 bins).
+
 --crc-stop (with --transport-block whose frames carry a CRC of their own: C = 1, or C > 1 with CRC24B): the decoder also stops
 a frame in the first round in which its first Kp bits pass that CRC (include/ldpc_hip.h: crc_kind / crc_bits; the streaming
 kernels then run).  Every point of a --transport-block run prints crc_stops, the frames stopped in a round in which their
@@ -69,6 +76,8 @@ ap.add_argument("--modulation", choices=("bpsk", "qpsk", "qam16", "qam64", "qam2
 ap.add_argument("--no-interleave", action="store_true", help="with --modulation: no bit interleaver")
 ap.add_argument("--transport-block", default=None, metavar="A[,C]",
                 help="with --payload random: A payload bits per transport block, C code blocks (default: the rule of ldpc_tb_spec_init)")
+ap.add_argument("--bch", default=None, metavar="T[,N]",
+                help="with --payload random: outer BCH code that corrects T errors over N code bits (default: K)")
 ap.add_argument("--msg-dtype", choices=("f32", "f16", "f8"), default="f32", help="message storage (f16: --algo ms and bp; f8: --algo ms)")
 ap.add_argument("--llr-type", choices=("f32", "f16", "i8"), default="f32",
                 help="quantise the channel values on the device (ldpc_llr_quantize_device) behind the channel / rate-recover step "
@@ -83,6 +92,8 @@ args = ap.parse_args()
 assert not (args.soft_check and args.algo == "sp"), "--soft-check: sum-product has no soft output (include/ldpc_hip.h)"
 assert not args.transport_block or args.payload == "random", "--transport-block needs --payload random"
 assert args.transport_block or not args.crc_stop, "--crc-stop needs --transport-block"
+assert not args.bch or args.payload == "random", "--bch needs --payload random"
+assert not (args.bch and args.transport_block), "--bch and --transport-block exclude one another: a frame carries one of the two"
 assert args.modulation or not args.no_interleave, "--no-interleave needs --modulation"
 QM = {None: 0, "bpsk": 1, "qpsk": 2, "qam16": 4, "qam64": 6, "qam256": 8}[args.modulation]
 # llr_scale = 2 / sd^2 per SNR point: sp behind a demapper, bp always (its messages are LLRs)
@@ -113,6 +124,10 @@ if args.transport_block:
     tbv = [int(x) for x in args.transport_block.split(",")]
     tb = L.TransportBlock(tbv[0], K, C=tbv[1] if len(tbv) > 1 else None)
 crc_kind, crc_bits = tb.frame_crc() if args.crc_stop else (0, 0)
+bch = None
+if args.bch:
+    bv = [int(x) for x in args.bch.split(",")]
+    bch = L.BchCode(bv[1] if len(bv) > 1 else K, bv[0], row_bytes=K // 8)
 
 
 def make_decoder(llr_scale):
@@ -143,6 +158,12 @@ if tb is not None:
     back = torch.empty_like(pay)
     cb_ok = torch.empty(B, dtype=torch.uint8, device="cuda")
     tb_ok = torch.empty(TBS, dtype=torch.uint8, device="cuda")
+bpay = bback = bstatus = popcount = None
+if bch is not None:
+    bpay = torch.empty((B, bch.k // 8), dtype=torch.uint8, device="cuda")
+    bback = torch.empty_like(bpay)
+    bstatus = torch.empty(B, dtype=torch.int32, device="cuda")
+    popcount = torch.tensor([bin(v).count("1") for v in range(256)], dtype=torch.int64, device="cuda")
 rm = tx = rx = None
 rate = K / N
 if args.rate_match:
@@ -174,6 +195,9 @@ def channel_batch(first, sd, seed):
         if tb is not None:
             pay.random_(0, 256, generator=gen)
             tb.attach_device(pay.data_ptr(), TBS, src.data_ptr(), src.numel(), stream)   # payload, CRCs, zero fillers
+        elif bch is not None:
+            bpay.random_(0, 256, generator=gen)
+            bch.encode_device(bpay.data_ptr(), B, src.data_ptr(), src.numel(), stream)   # payload, parity, zero fillers
         else:
             src.random_(0, 256, generator=gen)
             if rm is not None:
@@ -256,6 +280,8 @@ if rm is not None:
 if tb is not None:
     print("transport block: A=%d tb_crc=%d C=%d cb_crc=%d, %d bits per code block, Kp=%d of K=%d, %d blocks per batch" % (
         tb.A, tb.tb_crc, tb.C, tb.cb_crc, tb.S, tb.Kp, K, TBS))
+if bch is not None:
+    print("outer code: BCH over GF(2^%d), t=%d n=%d k=%d r=%d, fillers [%d, %d)" % (bch.m, bch.t, bch.n, bch.k, bch.r, bch.n, K))
 if md is not None:
     print("modulation: %s (%d bits per symbol) interleave=%d llr_scale=%s" % (
         args.modulation, QM, md.spec.interleave, "2/sd^2 per point" if matched else "%g" % (8.0 if args.llr_scale is None else args.llr_scale)))
@@ -279,6 +305,8 @@ for snr in points:
     blocks = [0, 0, 0, 0]
     it_sum, conv, stops, rounds, dec_ms = 0.0, 0, 0, 0, 0.0
     soft_tot = [0, 0, 0]
+    outer = [0] * 6
+    hist = [0] * (bch.t + 2) if bch is not None else None
     t0 = time.perf_counter()
     for b in range(args.batches):
         channel_batch(b * B, sd, args.seed)
@@ -289,6 +317,11 @@ for snr in points:
         if tb is not None:
             tb.check_device(out.data_ptr(), TBS, back.data_ptr(), cb_ok.data_ptr(), tb_ok.data_ptr(), None)
             blocks = [t + x for t, x in zip(blocks, tb.tally_device(tb_ok.data_ptr(), back.data_ptr(), pay.data_ptr(), TBS, None))]
+        if bch is not None:
+            wrong = popcount[((out.view(B, K // 8) ^ src.view(B, K // 8))[:, :bch.n // 8]).long()].sum(dim=1)
+            hist = [h + int(x) for h, x in zip(hist, torch.bincount(wrong.clamp(max=bch.t + 1), minlength=bch.t + 2).tolist())]
+            bch.decode_device(out.data_ptr(), B, bback.data_ptr(), bstatus.data_ptr(), None)
+            outer = [t + x for t, x in zip(outer, bch.tally_device(bstatus.data_ptr(), bback.data_ptr(), bpay.data_ptr(), B, None))]
         it_sum += float(it.float().sum())
         st = dec.stats()
         conv += st["frames_converged"]
@@ -314,6 +347,10 @@ for snr in points:
         n = TBS * args.batches
         res.update({"blocks": n, "bler": blocks[1] / n, "blocks_crc_failed": blocks[0], "blocks_undetected": blocks[2],
                     "blocks_parity_only": blocks[3], "crc_stops": stops})
+    if bch is not None:
+        res.update({"frame_errors_after_ldpc": frames - hist[0], "frame_errors_after_bch": outer[1], "bch_repaired_frames": outer[3],
+                    "bch_failed_frames": outer[0], "bch_miscorrected_frames": outer[2], "bch_repaired_bits": outer[4],
+                    "residual_hist": hist})
     if args.soft_check:
         res.update({"soft_checked": soft_tot[0], "soft_sign_disagreements": soft_tot[1], "soft_bytes_differ": soft_tot[2]})
     print(json.dumps(res), flush=True)
