@@ -38,6 +38,8 @@
  *     decode() checks: crcPassed() / lastCrcFailures().
  *   - setOuterBch(): every frame carries payload bits plus the parity of a BCH code ("outer code" section of ldpc_hip.h),
  *     with which decode() repairs up to t wrong bits per frame: bchStatus() / bchCounts().
+ *   - setOsd(): decode() passes the frames a decoder leaves with a dirty syndrome through ordered-statistics decoding
+ *     ("ordered-statistics post-processing" section of ldpc_hip.h): osdCounts().
  */
 #ifndef MYLDPC_H_
 #define MYLDPC_H_
@@ -173,6 +175,19 @@ public:
     int bchStatus(int frame) const { return frame >= 0 && (size_t)frame < bchStatusOfFrame.size() ? bchStatusOfFrame[(size_t)frame] : -2; }
     struct BchCounts { int failed, corrected, bits; };
     BchCounts bchCounts() const { return BchCounts{bchFailed, bchCorrected, bchBits}; }
+    /* Ordered-statistics post-processing ("ordered-statistics post-processing" section of ldpc_hip.h): order 0 or 1 turns
+     * it on, -1 (the default) off.  decode() and decodeTyped() then run the soft form of the decode (posterior values) and
+     * ldpc_osd_run behind it with weight_scale 256: a frame whose hard decision has a dirty syndrome leaves as the codeword
+     * the rule picks, every other frame as the decoder wrote it.  The transport-block CRC and the outer BCH code see the
+     * result.  decodeSoft() and decodeSoftTyped() are unchanged: they return the decoder's own bytes and values.
+     * osdCounts() of the last decode(): {frames processed, frames where a flip was chosen}.  Call it before
+     * addDecodeType() (LDPC_ERR_STATE once a decoder exists).  Decode types without soft output (DecodeSP, and DecodeCPU,
+     * whose bytes are bit-packed) and codes that are not eligible fail in addDecodeType with the library's code and message.
+     * Not to be combined with setRateMatch(): the second of the two calls returns LDPC_ERR_STATE.  K % 8 == 0 is required.
+     * Returns 0 or an ldpc_status. */
+    int setOsd(int order);
+    struct OsdCounts { int processed, flipped; };
+    OsdCounts osdCounts() const { return OsdCounts{osdProcessed, osdFlipped}; }
     /* CRC-aided early termination (ldpc_hip.h: crc_kind / crc_bits): with setTransportBlock() every frame carries a CRC,
      * and a frame then also stops in the first round in which its payload and CRC bits pass it -- usually a round before
      * its syndrome is clean.  Needs setTransportBlock() with crcBits != 0 first (LDPC_ERR_STATE otherwise).  DecodeSP,
@@ -250,6 +265,9 @@ private:
     ldpc_graph *graph;
     std::map<int, ldpc_decoder *> decoders; /* decodeType -> handle */
     int cpuDecoderBatch;
+    int osdOrder = -1;               /* setOsd(); -1: off */
+    ldpc_osd *osd = nullptr;         /* made by the first addDecodeType() while setOsd() is in force */
+    int osdProcessed = 0, osdFlipped = 0;
 };
 
 float gaussian(float ave, float sd);

@@ -848,6 +848,67 @@ int ldpc_bch_encode(const ldpc_bch_spec *spec, const uint8_t *payload_host, int6
 int ldpc_bch_decode(const ldpc_bch_spec *spec, const uint8_t *dec_host, int64_t frames, uint8_t *payload_host, int32_t *status_host,
                     int32_t device);
 
+/* ---- ordered-statistics post-processing (OSD, orders 0 and 1) behind a decoder with soft output: the frames whose hard
+ *      decision has a dirty syndrome are re-encoded from their most reliable independent positions, optionally with every
+ *      single flip among them tried.  The output of a processed frame is always a codeword.  For short codes, where belief
+ *      propagation stops well short of maximum likelihood; the reference has no counterpart.
+ *
+ * The rule, bit for bit.  ldpc_osd_device is a pure function of the graph H (M x N), the soft values, `order` and
+ * `weight_scale`.  Input: frame f's row p_0 .. p_(N-1) of fp32 posteriors, as ldpc_decode_soft_device(...,
+ * LDPC_SOFT_POSTERIOR) writes them; positive <-> bit 0.
+ *   1. Hard bits.  h_n = (p_n < 0): zeros and NaN read as bit 0.  The stage takes its own hard decision, so it does not
+ *      depend on which decoder produced p.
+ *   2. Weights, integers, so that every sum below is exact and order-free:
+ *        t = fabsf(p_n) * weight_scale                               one fp32 multiply
+ *        w_n = (p_n != p_n) ? 0 : (int32)floorf(fminf(t, 65535.0f))
+ *      weight_scale must be finite and > 0, else LDPC_ERR_ARG.  A good default is 256: LLR units for the sum-product
+ *      decoders, a resolution of 1/256 of a channel unit for min-sum posteriors.
+ *   3. Order.  Position n precedes n' iff (w_n, n) < (w_n', n') lexicographically: the least reliable first, ties to the
+ *      index.
+ *   4. Least reliable basis.  Scan the positions in that order; a position joins the pivot set P iff its column of H is
+ *      linearly independent over GF(2) of the columns already in P.  |P| = rank(H) = rho <= M; the free set F is the other
+ *      N - rho positions.  For any bits on F there is exactly one codeword, so the result does not depend on which rows an
+ *      implementation pivots on.
+ *   5. Metric.  D(c) = sum of w_n over the n with c_n != h_n.  It fits int32: N <= 4096 and w <= 65535.
+ *   6. Order 0.  c0 is the codeword that agrees with h on F.
+ *   7. Order 1.  For every j in F, c^j is the codeword that agrees with h on F except at j.  The result is the candidate of
+ *      the smallest D among c0 and all c^j; on a tie c0 wins, then the smallest position j.
+ *   8. Which frames.  A frame whose h has a zero syndrome is left alone; every other frame is processed.
+ *   9. Outputs per frame, each nullable, at least one given:
+ *        code_dev    N bytes, 0 or 1 (LDPC_CODE_BITS layout): the chosen codeword, or h for an untouched frame;
+ *        out_dev     the first K bits of that row, packed as the decoders' LDPC_PACK_BYTES does for K % 8 == 0: K/8 bytes
+ *                    at byte f * K/8, LSB first; K % 8 != 0 with out_dev given is LDPC_ERR_ARG; every frame's bytes are
+ *                    written;
+ *        status_dev  int32: 0 = the frame was clean and untouched, 1 = c0 was chosen, 2 = a flip was chosen;
+ *        metric_dev  int32: D of the chosen codeword, 0 for an untouched frame.
+ *
+ * The handle owns the dense bit image of H (built from the graph on the host, uploaded once), the graph's rows for the
+ *   syndrome and one dirty flag per frame.  Eligibility is a fixed rule -- both N <= 4096 and M * ceil(N / 32) <= 28672
+ *   32-bit words (112 KiB of the 160 KiB of LDS a workgroup can have; the rest holds keys, weights, pivot bookkeeping and
+ *   the candidate search) -- anything larger is LDPC_ERR_UNSUPPORTED with both numbers in the message.  802.16e (576, 288),
+ *   (1152, 576), (1152, 960) and the BG1-profile test code (1088, M = 736) fit; (2304, 1152) does not.
+ * ldpc_osd_create: K outside (0, N], max_frames <= 0 are LDPC_ERR_ARG.  On a machine without a device the handle is still
+ *   made (host analysis only), so that the argument checks of the compute calls answer everywhere; the compute calls then
+ *   give LDPC_ERR_HIP after their argument checks.  There is no CPU path.
+ * ldpc_osd_device: enqueues on `stream` (a hipStream_t, NULL = default stream), returns without waiting and allocates
+ *   nothing; no host round trip decides which frames are dirty.  The pointer rules of ldpc_decode_device apply: soft_dev,
+ *   status_dev and metric_dev need 4-byte alignment and no more, byte buffers any; nothing outside the sizes stated for
+ *   `frames` frames is read or written; frames == 0 enqueues nothing; a refused call has enqueued nothing.  LDPC_ERR_ARG,
+ *   with a message that names the field: order outside {0, 1}, a bad weight_scale, frames > max_frames, out_bytes <
+ *   frames * K/8, no output given, an output that overlaps soft_dev or another output.
+ * ldpc_osd_run: the same on host buffers, blocking, in chunks of max_frames (frames is not limited); its first call
+ *   allocates the staging buffers.
+ * ldpc_osd_info: out = {M, N, words per row = ceil(N / 32), LDS bytes of one workgroup}.
+ * A handle is not re-entrant: one per host thread / stream. */
+typedef struct ldpc_osd ldpc_osd;
+int ldpc_osd_create(const ldpc_graph *g, int32_t K, int32_t max_frames, int32_t device, ldpc_osd **out);
+int ldpc_osd_destroy(ldpc_osd *o);
+int ldpc_osd_device(ldpc_osd *o, const float *soft_dev, int64_t frames, int32_t order, float weight_scale, uint8_t *out_dev,
+                    int64_t out_bytes, uint8_t *code_dev, int32_t *status_dev, int32_t *metric_dev, void *stream);
+int ldpc_osd_run(ldpc_osd *o, const float *soft_host, int64_t frames, int32_t order, float weight_scale, uint8_t *out_host,
+                 int64_t out_bytes, uint8_t *code_host, int32_t *status_host, int32_t *metric_host);
+int ldpc_osd_info(const ldpc_osd *o, int32_t out[4]);
+
 /* ---- measurement aid: the rate a plain float4 copy of `bytes` bytes (read + write counted)
  *      sustains on `device` right now, best of `reps` launches each with the default cache policy
  *      and with non-temporal loads and stores (the streaming kernels' policy), HIP-event timed on

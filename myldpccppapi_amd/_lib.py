@@ -108,6 +108,7 @@ EXPORTS = (
     "ldpc_llr_quantize_device",
     "ldpc_bch_spec_init", "ldpc_bch_layout", "ldpc_bch_generator", "ldpc_bch_encode_device", "ldpc_bch_decode_device",
     "ldpc_bch_tally_device", "ldpc_bch_encode", "ldpc_bch_decode",
+    "ldpc_osd_create", "ldpc_osd_destroy", "ldpc_osd_device", "ldpc_osd_run", "ldpc_osd_info",
 )
 
 
@@ -231,6 +232,11 @@ def load():
     L.ldpc_bch_tally_device.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int64, i64p, ctypes.c_int32, vp]
     L.ldpc_bch_encode.argtypes = [bsp, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int32]
     L.ldpc_bch_decode.argtypes = [bsp, vp, ctypes.c_int64, vp, vp, ctypes.c_int32]
+    L.ldpc_osd_create.argtypes = [vp, i32, i32, i32, ctypes.POINTER(vp)]
+    L.ldpc_osd_destroy.argtypes = [vp]
+    L.ldpc_osd_device.argtypes = [vp, vp, ctypes.c_int64, i32, f32, vp, ctypes.c_int64, vp, vp, vp, vp]
+    L.ldpc_osd_run.argtypes = [vp, vp, ctypes.c_int64, i32, f32, vp, ctypes.c_int64, vp, vp, vp]
+    L.ldpc_osd_info.argtypes = [vp, i32p]
     _lib = L
     return L
 

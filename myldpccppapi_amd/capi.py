@@ -1,4 +1,4 @@
-"""Thin Python objects over the C ABI (include/ldpc_hip.h): Graph, Decoder, Encoder, RateMatcher, Modem,
+"""Thin Python objects over the C ABI (include/ldpc_hip.h): Graph, Decoder, Encoder, RateMatcher, Modem, Osd,
 TransportBlock and BchCode.
 
 Host-side plumbing only -- every decode runs in the HIP kernels of
@@ -691,3 +691,54 @@ class BchCode:
         _lib.check(_lib.load().ldpc_bch_decode(ctypes.byref(self.spec), dec.ctypes.data, frames, payload.ctypes.data, status.ctypes.data,
                                                self.device))
         return payload, status
+
+
+class Osd:
+    """Ordered-statistics post-processing behind Decoder.decode_device(soft_ptr=...) (ldpc_osd_*, include/ldpc_hip.h): the
+    frames whose hard decision (posterior < 0) has a dirty syndrome are re-encoded from their most reliable independent
+    positions (order 0), with every single flip among them tried (order 1).  Codes up to N = 4096 and
+    M * ceil(N / 32) <= 28672 words; LdpcError code 4 beyond.  On a machine without a device the handle is still made and
+    the compute calls raise code 2 after their argument checks."""
+
+    def __init__(self, graph, K, max_frames=4096, device=0):
+        L = _lib.load()
+        self.graph, self.K, self.N = graph, int(K), graph.N
+        self.max_frames, self.device = int(max_frames), int(device)
+        self._h = ctypes.c_void_p()
+        _lib.check(L.ldpc_osd_create(graph._h, self.K, self.max_frames, self.device, ctypes.byref(self._h)))
+
+    def info(self):
+        """dict(M, N, words_per_row, lds_bytes): the dense image's shape and one workgroup's LDS."""
+        out = (ctypes.c_int32 * 4)()
+        _lib.check(_lib.load().ldpc_osd_info(self._h, out))
+        return dict(M=out[0], N=out[1], words_per_row=out[2], lds_bytes=out[3])
+
+    def run_device(self, soft_ptr, frames, order=1, weight_scale=256.0, out_ptr=None, out_nbytes=0, code_ptr=None, status_ptr=None,
+                   metric_ptr=None, stream=None):
+        """Buffers already in HBM (integers, e.g. a torch tensor's data_ptr()); enqueued on `stream`, no wait."""
+        _lib.check(_lib.load().ldpc_osd_device(self._h, soft_ptr, int(frames), int(order), float(weight_scale), out_ptr, int(out_nbytes),
+                                               code_ptr, status_ptr, metric_ptr, stream))
+
+    def run(self, soft, order=1, weight_scale=256.0):
+        """soft: float32 [frames, N] -> (out uint8 [frames, K/8] or None when K % 8 != 0, code uint8 [frames, N],
+        status int32 [frames], metric int32 [frames]).  Host buffers, blocking, any number of frames."""
+        soft = np.ascontiguousarray(soft, np.float32).reshape(-1, self.N)
+        frames = soft.shape[0]
+        out = np.zeros((frames, self.K // 8), np.uint8) if self.K % 8 == 0 else None
+        code = np.zeros((frames, self.N), np.uint8)
+        status, metric = np.zeros(frames, np.int32), np.zeros(frames, np.int32)
+        _lib.check(_lib.load().ldpc_osd_run(self._h, soft.ctypes.data, frames, int(order), float(weight_scale),
+                                            None if out is None else out.ctypes.data, 0 if out is None else out.size, code.ctypes.data,
+                                            status.ctypes.data, metric.ctypes.data))
+        return out, code, status, metric
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None and _lib._lib is not None:
+            _lib.check(_lib._lib.ldpc_osd_destroy(h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

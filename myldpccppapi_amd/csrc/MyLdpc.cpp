@@ -36,6 +36,7 @@ Coder::Coder(int ldpcK, int ldpcN, enum rate_type rate)
 Coder::~Coder()
 {
     for (auto &kv : decoders) ldpc_decoder_destroy(kv.second);
+    if (osd) ldpc_osd_destroy(osd);
     if (encoder) ldpc_encoder_destroy(encoder);
     if (graph) ldpc_graph_destroy(graph);
 }
@@ -99,6 +100,7 @@ void Coder::setEncodeOnDevice(bool on) { encodeOnDevice = on; }
  * ldpc_rate_match / ldpc_rate_recover; the fast path is the device chain of the C ABI. */
 int Coder::setRateMatch(int E, int k0, int punctured, int fillerLo, int fillerHi, float erasureLlr)
 {
+    if (osdOrder >= 0) return fail(LDPC_ERR_STATE, "setRateMatch: setOsd() is in force: the two are not combined");
     ldpc_rate_spec spec;
     ldpc_rate_spec_init(&spec, ldpcN);
     spec.punctured = punctured;
@@ -158,6 +160,19 @@ int Coder::setOuterBch(int t, int n)
     bchK = lay[0];
     bchStatusOfFrame.clear();
     bchFailed = bchCorrected = bchBits = 0;
+    return LDPC_SUCCESS;
+}
+
+/* Ordered-statistics post-processing (the section of that name in ldpc_hip.h) behind the decoders addDecodeType makes
+ * from here on */
+int Coder::setOsd(int order)
+{
+    if (order < -1 || order > 1) return fail(LDPC_ERR_ARG, "setOsd: order must be -1 (off), 0 or 1");
+    if (order >= 0 && rmE) return fail(LDPC_ERR_STATE, "setOsd: setRateMatch() is in force: the two are not combined");
+    if (order >= 0 && ldpcK % 8) return fail(LDPC_ERR_ARG, "setOsd: K must be a multiple of 8 (rows of K / 8 bytes)");
+    if (!decoders.empty()) return fail(LDPC_ERR_STATE, "setOsd: call it before addDecodeType()");
+    osdOrder = order;
+    osdProcessed = osdFlipped = 0;
     return LDPC_SUCCESS;
 }
 
@@ -463,6 +478,15 @@ int Coder::addDecodeType(enum decodeType deType)
 {
     if (!isDecoder) return fail(LDPC_ERR_STATE, "addDecodeType: call forDecoder() first");
     if (decoders.count((int)deType)) return LDPC_SUCCESS;
+    if (osdOrder >= 0) {
+        if (deType == DecodeSP)
+            return fail(LDPC_ERR_UNSUPPORTED, "addDecodeType: DecodeSP has no soft output for setOsd() (see decodeSoft); the min-sum "
+                        "decode types, DecodeBP and DecodeLayeredBP have");
+        if (deType == DecodeCPU)
+            return fail(LDPC_ERR_UNSUPPORTED, "addDecodeType: DecodeCPU packs its bytes at bit offsets; setOsd() works on rows of K / 8 bytes");
+        if (!osd)
+            if (int rc = ldpc_osd_create(graph, ldpcK, batchSize, device, &osd)) return fail(rc, std::string("addDecodeType: ") + ldpc_last_error());
+    }
     if (deType == DecodeCPU) return LDPC_SUCCESS;   /* made on first use: needs the stream length (:438-439 is a no-op too) */
     ldpc_decoder_config cfg;
     ldpc_decoder_config_init(&cfg);
@@ -592,6 +616,14 @@ int Coder::decodeFrames(const void *postCode, int llrType, float llrUnit, char *
         if (it == decoders.end()) return fail(LDPC_ERR_STATE, "decode: addDecodeType() was not called for this type");
         d = it->second;
     }
+    /* setOsd(): the decode's soft form, then the frames with a dirty syndrome through ldpc_osd_run */
+    const bool withOsd = osdOrder >= 0 && !soft && osd && deType != DecodeCPU;
+    std::vector<float> posterior;
+    if (withOsd) {
+        posterior.resize((size_t)codeSize * ldpcN);
+        soft = posterior.data();
+        kind = LDPC_SOFT_POSTERIOR;
+    }
     std::vector<float> recovered;
     if (rmE && llrType != LDPC_LLR_F32)
         return fail(LDPC_ERR_UNSUPPORTED, "decodeTyped: rate recovery (setRateMatch) sums float values; quantise behind it "
@@ -612,6 +644,19 @@ int Coder::decodeFrames(const void *postCode, int llrType, float llrUnit, char *
     if (ldpc_decoder_stats(d, &st) == LDPC_OK) lastTime = st.batch_time;
     int64_t stops = 0;
     crcStops = ldpc_decoder_crc_stops(d, &stops) == LDPC_OK ? (long long)stops : 0;
+    if (withOsd) {
+        std::vector<uint8_t> rowsOut((size_t)codeSize * (ldpcK / 8));
+        std::vector<int32_t> status((size_t)codeSize, 0);
+        rc = ldpc_osd_run(osd, posterior.data(), codeSize, osdOrder, 256.0f, rowsOut.data(), (int64_t)rowsOut.size(), nullptr, status.data(),
+                          nullptr);
+        if (rc) return fail(rc, ldpc_last_error());
+        memcpy(srcCode, rowsOut.data(), std::min((size_t)srcLength, rowsOut.size()));
+        osdProcessed = osdFlipped = 0;
+        for (int32_t st : status) {
+            osdProcessed += st > 0;
+            osdFlipped += st == 2;
+        }
+    }
     if (tbSpec.A) {
         std::vector<char> payload((size_t)codeSize * (tbSpec.A / 8));
         crcOk.assign((size_t)codeSize, 0);

@@ -10,7 +10,7 @@ reference counts differing BYTES (Test.cpp:105-110); this prints byte errors too
     python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N>] [--algo sp|ms|layered|bp|layered_bp]
                               [--payload zero|random] [--rate-match P,FLO,FHI,E[,K0]] [--erasure-llr X]
                               [--modulation bpsk|qpsk|qam16|qam64|qam256] [--no-interleave] [--transport-block A[,C]] [--crc-stop] [--bch T[,N]]
-                              [--msg-dtype f32|f16|f8] [--soft-check]
+                              [--msg-dtype f32|f16|f8] [--soft-check] [--osd 0|1 [--osd-scale S]]
                               [--snr=1.0,1.5,...]  (write --snr=-0.5,0 for a list that starts with a minus) [--frames 4096] [--iters 50]
 --rate-match: code bits [0, P) punctured, [FLO, FHI) filler bits (known zeros; multiples of 8, inside the information part),
 E bits per frame sent from circular-buffer position K0 (default 0): ldpc_rate_match_device between the encoder and the
@@ -48,6 +48,12 @@ syndrome was not clean (0 without --crc-stop), next to the block counts -- block
 --soft-check (not with --algo sp): every batch is decoded a second time through ldpc_decode_soft_device; every point prints
 soft_checked, the posteriors of the K output bits that are finite and not zero, soft_sign_disagreements, those whose sign is
 not the output bit, and soft_bytes_differ against the plain call -- the last two must be 0, the run fails otherwise.
+--osd 0|1 (not with --algo sp; short codes: N <= 4096 and M * ceil(N / 32) <= 28672, e.g. wimax:0:576): the batch is decoded
+through ldpc_decode_soft_device and the frames whose posterior has a dirty syndrome go through ordered-statistics decoding of
+that order (include/ldpc_hip.h, "ordered-statistics post-processing"; ldpc_osd_device, weight_scale --osd-scale, default 256).
+Every point also prints frame_errors_before_osd / frame_errors_after_osd (frames whose K information bits are wrong),
+osd_processed (frames with a dirty syndrome), osd_flipped (frames where a flip was chosen) and osd_ms_per_batch (HIP events
+around ldpc_osd_device).  fer, ber and the error counts are those of the decoder alone.
 The DVB-S2 / BG1 codes are PROFILE SURROGATES (codes.py): the numbers are not the standards'."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -88,7 +94,10 @@ ap.add_argument("--crc-stop", action="store_true", help="with --transport-block:
 ap.add_argument("--soft-check", action="store_true",
                 help="every batch is decoded once more with soft output (not --algo sp): prints the finite non-zero posteriors whose sign "
                      "disagrees with the output bit -- must be 0")
+ap.add_argument("--osd", type=int, choices=(0, 1), default=None, help="ordered-statistics decoding of that order behind the decoder (not --algo sp)")
+ap.add_argument("--osd-scale", type=float, default=256.0, help="with --osd: weight_scale")
 args = ap.parse_args()
+assert args.osd is None or args.algo != "sp", "--osd: sum-product has no soft output (include/ldpc_hip.h)"
 assert not (args.soft_check and args.algo == "sp"), "--soft-check: sum-product has no soft output (include/ldpc_hip.h)"
 assert not args.transport_block or args.payload == "random", "--transport-block needs --payload random"
 assert args.transport_block or not args.crc_stop, "--crc-stop needs --transport-block"
@@ -269,6 +278,27 @@ def soft_check():
     return int(ok.sum()), int((ok & ((p < 0) != (bits != 0))).sum()), int((out2 != out).sum())
 
 
+osd = osd_soft = osd_out = osd_status = None
+if args.osd is not None:
+    assert K % 8 == 0, "--osd compares whole bytes per frame: K % 8 must be 0"
+    osd = L.Osd(g, K, max_frames=B)
+    osd_soft = torch.empty((B, N), dtype=torch.float32, device="cuda")
+    osd_out = torch.empty_like(out)
+    osd_status = torch.empty(B, dtype=torch.int32, device="cuda")
+
+
+def osd_batch():
+    """The posteriors of the batch just decoded through ldpc_osd_device: (ms, frame errors after, processed, flipped)."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    osd.run_device(osd_soft.data_ptr(), B, args.osd, args.osd_scale, osd_out.data_ptr(), osd_out.numel(), None, osd_status.data_ptr(), None,
+                   torch.cuda.current_stream().cuda_stream)
+    e1.record()
+    e1.synchronize()
+    after = channel.count_errors_device(osd_out, src, B)[2]
+    return e0.elapsed_time(e1), after, int((osd_status > 0).sum()), int((osd_status == 2).sum())
+
+
 yq, llr_unit = None, 1.0
 if args.llr_type != "f32":
     llr_unit = args.llr_unit if args.llr_unit is not None else (0.05 if args.llr_type == "i8" else 1.0 / 256)
@@ -306,14 +336,20 @@ for snr in points:
     it_sum, conv, stops, rounds, dec_ms = 0.0, 0, 0, 0, 0.0
     soft_tot = [0, 0, 0]
     outer = [0] * 6
+    osd_tot = [0.0, 0, 0, 0]
     hist = [0] * (bch.t + 2) if bch is not None else None
     t0 = time.perf_counter()
     for b in range(args.batches):
         channel_batch(b * B, sd, args.seed)
         quantise_batch()
-        decode_batch(out, it)
+        if osd is None:
+            decode_batch(out, it)
+        else:
+            decode_batch(out, it, soft_ptr=osd_soft.data_ptr(), soft_floats=osd_soft.numel(), soft="posterior")
         e = channel.count_errors_device(out, src, B)
         tot = [t + x for t, x in zip(tot, e)]
+        if osd is not None:
+            osd_tot = [t + x for t, x in zip(osd_tot, osd_batch())]
         if tb is not None:
             tb.check_device(out.data_ptr(), TBS, back.data_ptr(), cb_ok.data_ptr(), tb_ok.data_ptr(), None)
             blocks = [t + x for t, x in zip(blocks, tb.tally_device(tb_ok.data_ptr(), back.data_ptr(), pay.data_ptr(), TBS, None))]
@@ -351,6 +387,9 @@ for snr in points:
         res.update({"frame_errors_after_ldpc": frames - hist[0], "frame_errors_after_bch": outer[1], "bch_repaired_frames": outer[3],
                     "bch_failed_frames": outer[0], "bch_miscorrected_frames": outer[2], "bch_repaired_bits": outer[4],
                     "residual_hist": hist})
+    if osd is not None:
+        res.update({"osd_order": args.osd, "frame_errors_before_osd": tot[2], "frame_errors_after_osd": osd_tot[1], "osd_processed": osd_tot[2],
+                    "osd_flipped": osd_tot[3], "osd_ms_per_batch": round(osd_tot[0] / args.batches, 3)})
     if args.soft_check:
         res.update({"soft_checked": soft_tot[0], "soft_sign_disagreements": soft_tot[1], "soft_bytes_differ": soft_tot[2]})
     print(json.dumps(res), flush=True)
