@@ -566,8 +566,8 @@ int ldpc_count_errors_device(const uint8_t *out_dev, const uint8_t *ref_dev, int
  *     identity parity column and otherwise touch information and core parity columns only.  802.16e: c = M/z for
  *     all six seeds; codes.nr_bg1_profile_edges: c = 4, x = 1, 42 extension block rows.
  *   LDPC_PARITY_STAIRCASE: parity column K + m has its ones in rows m and m + 1 only (codes.dvbs2_profile_edges).
- * Anything else is LDPC_ERR_UNSUPPORTED with a message that names the condition that failed; there is no dense
- * elimination on the device.
+ * Anything else is LDPC_ERR_UNSUPPORTED from ldpc_parity_structure / ldpc_encoder_create, with a message that names the
+ * condition that failed; any other H is served by ldpc_encoder_create_dense (LDPC_PARITY_DENSE, below).
  * ldpc_parity_structure (host only, no device is touched): out[0] = enum ldpc_parity_kind, out[1] = c, out[2] = x,
  *   out[3] = a, out[4] = b, out[5] = extension block rows, out[6] = z, out[7] = 0 (all 0 but out[0] for a staircase).
  * Data (Coder::encode's): frame f reads the K/8 WHOLE source bytes from byte (f*K)/8 on (the product first: for
@@ -584,7 +584,7 @@ enum ldpc_code_format {
     LDPC_CODE_PACKED = 0, /* N/8 bytes per frame at byte f*N/8, LSB first (Coder::encode's priorCode); N % 8 == 0 */
     LDPC_CODE_BITS = 1    /* N bytes per frame, 0/1: what ldpc_awgn_device takes as bits_dev                      */
 };
-enum ldpc_parity_kind { LDPC_PARITY_DUAL_DIAGONAL = 1, LDPC_PARITY_STAIRCASE = 2 };
+enum ldpc_parity_kind { LDPC_PARITY_DUAL_DIAGONAL = 1, LDPC_PARITY_STAIRCASE = 2, LDPC_PARITY_DENSE = 3 /* below */ };
 int ldpc_parity_structure(const ldpc_graph *g, int32_t K, int32_t block_rows, int32_t out[8]);
 int ldpc_encoder_create(const ldpc_graph *g, int32_t K, int32_t block_rows, int32_t max_frames, int32_t device,
                         ldpc_encoder **out);
@@ -594,6 +594,48 @@ int ldpc_encode_device(ldpc_encoder *e, const uint8_t *src_dev, int64_t src_byte
 int ldpc_encode(ldpc_encoder *e, const uint8_t *src_host, int64_t src_bytes, uint8_t *code_host, int64_t code_bytes);
 /* bytes of `frames` codewords in `format` (0 for an unknown format, or LDPC_CODE_PACKED with N % 8 != 0) */
 int64_t ldpc_code_bytes(int32_t N, int64_t frames, int32_t format);
+
+/* ---- encoder for any H: LDPC_PARITY_DENSE, a dense GF(2) parity solve on the device.  The reference's forEncoder solved
+ *      a dense system for every code; here this is the path of the matrices that have neither structure above (MacKay,
+ *      Gallager, PEG, anything from an alist file).  ldpc_parity_structure never returns LDPC_PARITY_DENSE and
+ *      ldpc_encoder_create keeps refusing what it refuses.
+ * Dense structure: given H (M x N) and K with N - M <= K < N (and K >= 1), put rho = N - K, H_s = H[:, 0..K) and
+ *   H_p = H[:, K..N) (M x rho).  The code is encodable in this column order iff
+ *     rank(H_p) = rho  (the parity bits are determined), and
+ *     rank(H)   = rho  (every information word has a codeword; rows beyond the rank are redundant, not contradictory).
+ *   Then for every u the parity bits p are the unique solution of H_p p = H_s u, and the codeword is [u | p].  The
+ *   solution is unique, so the result does not depend on how an implementation eliminates.  Refusals
+ *   (LDPC_ERR_UNSUPPORTED, the message names the condition and the numbers): rank(H_p) < rho ("parity part is singular:
+ *   rank r of rho"); rank(H) > rho ("information bits are not free"); M > 16384.  K outside [N - M, N) is LDPC_ERR_ARG.
+ *   The data rules of ldpc_encode_device hold unchanged: frame f reads K/8 whole source bytes from byte (f*K)/8,
+ *   information bits K - K%8 .. K-1 are zero, LDPC_CODE_PACKED needs N % 8 == 0.
+ * Systematic order (ldpc_graph_systematic_order; host only, no device is touched): scan the columns N-1, N-2, ..., 0; a
+ *   column joins the pivot set iff it is linearly independent over GF(2) of the columns already in it (the construction
+ *   of step 4 of the OSD rule with the index in place of the reliability).  rho = |pivot set| = rank(H) -> *rank;
+ *   perm[0 .. N-rho) = the non-pivot columns in ascending order, perm[N-rho .. N) = the pivot columns in ascending
+ *   order; column perm[i] of H is column i of the re-ordered H'.  H' with K = N - rho is always encodable.  If
+ *   H[:, N-M..N) is nonsingular already (all six 802.16e seeds, both profile codes) perm is the identity.  A pure
+ *   function of H.
+ * ldpc_parity_dense (host only): out = {rho, rank(H_p), M, 64-bit words per row of T = ceil(M / 64)}; returns what
+ *   ldpc_encoder_create_dense would return before it looks for a device, out filled as far as it was computed.
+ * ldpc_parity_dense_rows (host only, a diagnostic like ldpc_host_block_plan): rows [first, first + rows) of the solve
+ *   matrix T (rho x M bits; bit j of a row = bit j % 64 of word j / 64, tail bits zero) with T H_p = I_rho over GF(2),
+ *   so that p = T (H_s u); `words` = the 64-bit words t_out holds, at least rows * ceil(M / 64).
+ * ldpc_encoder_create_dense: checks, in this order, the arguments, the M limit, the host analysis (bit-packed
+ *   Gauss-Jordan on [H_p | I_M]; the combinations of rows with an empty parity part are applied to the sparse H_s), and
+ *   only then the device (LDPC_ERR_HIP last).  It returns an ordinary ldpc_encoder: ldpc_encode_device, ldpc_encode and
+ *   ldpc_encoder_destroy serve it as they serve the structured kinds (same argument checks, stream semantics, chunking by
+ *   max_frames, no allocation per call).  The handle owns, besides the N bits per frame, M row sums per frame and T.
+ * Limits (fixed): M <= 16384 for the dense encoder (T is at most 32 MiB); M * N <= 2^27 bits for
+ *   ldpc_graph_systematic_order.  Larger inputs are LDPC_ERR_UNSUPPORTED with the numbers in the message.
+ *   Creation is the host elimination, at most M^2 (M + rho) / 128 word operations on one thread, far fewer on sparse H.
+ *   Measured (tools/encoder_measure.py --dense --cap, the host of an MI355X): 1 ms at M = 1152 and 0.06 s at M = 8064
+ *   (802.16e rate 1/2), 1.9 s at the limit M = 16384 (a shuffled triangular parity part with random fill, 98 k edges);
+ *   a random column-weight-3 H of 8192 x 16384 in its systematic order: 1.2 s, after 0.35 s for the order itself. */
+int ldpc_graph_systematic_order(const ldpc_graph *g, int32_t *perm /* N */, int32_t *rank);
+int ldpc_parity_dense(const ldpc_graph *g, int32_t K, int64_t out[4]);
+int ldpc_parity_dense_rows(const ldpc_graph *g, int32_t K, int32_t first, int32_t rows, uint64_t *t_out, int64_t words);
+int ldpc_encoder_create_dense(const ldpc_graph *g, int32_t K, int32_t max_frames, int32_t device, ldpc_encoder **out);
 
 /* ---- rate matching: puncturing, shortening (filler bits), repetition and HARQ soft combining between the encoder and
  *      the decoders, for data that stays in HBM.  The reference has no counterpart: it sends whole mother codewords.

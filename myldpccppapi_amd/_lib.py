@@ -109,6 +109,7 @@ EXPORTS = (
     "ldpc_bch_spec_init", "ldpc_bch_layout", "ldpc_bch_generator", "ldpc_bch_encode_device", "ldpc_bch_decode_device",
     "ldpc_bch_tally_device", "ldpc_bch_encode", "ldpc_bch_decode",
     "ldpc_osd_create", "ldpc_osd_destroy", "ldpc_osd_device", "ldpc_osd_run", "ldpc_osd_info",
+    "ldpc_graph_systematic_order", "ldpc_parity_dense", "ldpc_parity_dense_rows", "ldpc_encoder_create_dense",
 )
 
 
@@ -237,6 +238,10 @@ def load():
     L.ldpc_osd_device.argtypes = [vp, vp, ctypes.c_int64, i32, f32, vp, ctypes.c_int64, vp, vp, vp, vp]
     L.ldpc_osd_run.argtypes = [vp, vp, ctypes.c_int64, i32, f32, vp, ctypes.c_int64, vp, vp, vp]
     L.ldpc_osd_info.argtypes = [vp, i32p]
+    L.ldpc_graph_systematic_order.argtypes = [vp, vp, i32p]
+    L.ldpc_parity_dense.argtypes = [vp, i32, i64p]
+    L.ldpc_parity_dense_rows.argtypes = [vp, i32, i32, i32, vp, ctypes.c_int64]
+    L.ldpc_encoder_create_dense.argtypes = [vp, i32, i32, i32, ctypes.POINTER(vp)]
     _lib = L
     return L
 

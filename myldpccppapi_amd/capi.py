@@ -17,7 +17,7 @@ MSG_F32, MSG_F16, MSG_F8 = 0, 1, 2
 PACK_BYTES, PACK_BITS = 0, 1
 CODE_PACKED, CODE_BITS = 0, 1                              # enum ldpc_code_format
 CODE_FORMATS = {"packed": CODE_PACKED, "bits": CODE_BITS}
-PARITY_KINDS = {1: "dual_diagonal", 2: "staircase"}        # enum ldpc_parity_kind
+PARITY_KINDS = {1: "dual_diagonal", 2: "staircase", 3: "dense"}        # enum ldpc_parity_kind
 HOST_INPUT = {"auto": 0, "staged": 1, "lock_pages": 2}     # enum ldpc_host_input
 SOFT_POSTERIOR, SOFT_EXTRINSIC = 1, 2                      # enum ldpc_soft_kind
 SOFT_KINDS = {"posterior": SOFT_POSTERIOR, "extrinsic": SOFT_EXTRINSIC}
@@ -146,6 +146,32 @@ def parity_structure(graph, K, block_rows=0):
     out = (ctypes.c_int32 * 8)()
     _lib.check(_lib.load().ldpc_parity_structure(graph._h, int(K), int(block_rows), out))
     return dict(kind=PARITY_KINDS[out[0]], c=out[1], x=out[2], a=out[3], b=out[4], ext_rows=out[5], z=out[6])
+
+
+def systematic_order(graph):
+    """ldpc_graph_systematic_order: (perm, rank) -- column perm[i] of H is column i of the re-ordered H', which is
+    encodable with K = N - rank by DenseEncoder (codes.permute_columns applies perm).  Host only."""
+    perm = np.zeros(graph.N, np.int32)
+    rank = ctypes.c_int32(0)
+    _lib.check(_lib.load().ldpc_graph_systematic_order(graph._h, perm.ctypes.data, ctypes.byref(rank)))
+    return perm, rank.value
+
+
+def dense_parity(graph, K):
+    """ldpc_parity_dense: dict(rho, rank_hp, M, t_words) of the dense parity solve of H[:, K..N) -- host analysis only;
+    LdpcError code 4 if the parity part is singular, the information bits are not free or M > 16384."""
+    out = (ctypes.c_int64 * 4)()
+    _lib.check(_lib.load().ldpc_parity_dense(graph._h, int(K), out))
+    return dict(rho=out[0], rank_hp=out[1], M=out[2], t_words=out[3])
+
+
+def dense_parity_rows(graph, K, first, rows):
+    """ldpc_parity_dense_rows: uint64 [rows, ceil(M / 64)], rows [first, first + rows) of T with T H_p = I (bit j of a row =
+    bit j % 64 of word j // 64)."""
+    tw = (graph.M + 63) // 64
+    out = np.zeros((max(int(rows), 0), tw), np.uint64)
+    _lib.check(_lib.load().ldpc_parity_dense_rows(graph._h, int(K), int(first), int(rows), out.ctypes.data, out.size))
+    return out
 
 
 class Graph:
@@ -365,12 +391,13 @@ class Encoder:
     codes).  There is no CPU path: without a device the constructor raises LdpcError code 2."""
 
     def __init__(self, graph, K, block_rows=0, max_frames=4096, device=0):
-        L = _lib.load()
         self.graph, self.K, self.N = graph, int(K), graph.N
         self.block_rows, self.max_frames, self.device = int(block_rows), int(max_frames), int(device)
         self._h = ctypes.c_void_p()
-        _lib.check(L.ldpc_encoder_create(graph._h, self.K, self.block_rows, self.max_frames, self.device,
-                                         ctypes.byref(self._h)))
+        _lib.check(self._create(_lib.load()))
+
+    def _create(self, L):
+        return L.ldpc_encoder_create(self.graph._h, self.K, self.block_rows, self.max_frames, self.device, ctypes.byref(self._h))
 
     def structure(self):
         return parity_structure(self.graph, self.K, self.block_rows)
@@ -402,6 +429,22 @@ class Encoder:
             self.close()
         except Exception:
             pass
+
+
+class DenseEncoder(Encoder):
+    """An encoder handle for any H (ldpc_encoder_create_dense): the parity bits are the solution of H_p p = H_s u by a
+    dense GF(2) product on the device; encode / encode_device are Encoder's.  H[:, K..N) must have full column rank and
+    rank(H) = N - K: systematic_order + codes.permute_columns make any H so.  LdpcError code 4 otherwise, code 2 without
+    a device."""
+
+    def __init__(self, graph, K, max_frames=4096, device=0):
+        super().__init__(graph, K, 0, max_frames, device)
+
+    def _create(self, L):
+        return L.ldpc_encoder_create_dense(self.graph._h, self.K, self.max_frames, self.device, ctypes.byref(self._h))
+
+    def structure(self):
+        return dict(dense_parity(self.graph, self.K), kind="dense")
 
 
 class RateMatcher:

@@ -34,6 +34,14 @@ def row_major(rows, cols):
     return r.astype(np.int32), c.astype(np.int32)
 
 
+def permute_columns(rows, cols, perm):
+    """Edge list of H' whose column i is column perm[i] of H (capi.systematic_order's convention), row-major."""
+    perm = np.asarray(perm, np.int64)
+    inv = np.empty(perm.size, np.int64)
+    inv[perm] = np.arange(perm.size)
+    return row_major(rows, inv[np.asarray(cols, np.int64)])
+
+
 def wimax_dims(rate, N):
     """(K, M, z) of Coder(K, N, rate): z = N/24 (MyLdpc.cpp:55)."""
     z = N // NB

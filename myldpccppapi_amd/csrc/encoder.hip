@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/ldpc_hip.h"
+#include "encoder_dense.hpp"
 #include "encoder_kernels.hpp"
 #include "graph.hpp"
 #include "hip_host.hpp"
@@ -104,7 +105,10 @@ struct ldpc_encoder {
     int32_t device = 0, N = 0, K = 0, M = 0, max_frames = 0, Wmax = 0, chunks = 0;
     ParityStructure ps;
     DevBuf<uint64_t> X;        /* [N][W] bit-sliced codewords                                        */
-    DevBuf<uint64_t> aux;      /* dual diagonal: lambda of the core rows [c z][W]; staircase: chunk totals */
+    DevBuf<uint64_t> aux;      /* dual diagonal: lambda of the core rows [c z][W]; staircase: chunk totals;
+                                  dense: lambda of all rows [M][W]                                      */
+    DevBuf<uint64_t> T;        /* dense: the solve matrix [N - K][tw]                                   */
+    int32_t tw = 0;
     DevBuf<int32_t> ptr, col;  /* per row: the columns lambda_m (or an extension row's parity bit) sums  */
     DevBuf<uint8_t> src_stage, code_stage;   /* ldpc_encode(): made on its first call               */
 };
@@ -129,6 +133,14 @@ int enqueue(ldpc_encoder *e, const uint8_t *src_dev, int64_t src_bytes, int64_t 
             enc_stair_scan_kernel<<<wt, 64 * kEncScanWaves, 0, s>>>(e->aux.p, e->chunks, W);
             enc_stair_apply_kernel<<<dim3(blocks(e->M - kEncChunk), wt), kEncBlock, 0, s>>>(P, e->aux.p, e->M, W);
         }
+    } else if (e->ps.kind == LDPC_PARITY_DENSE) {
+        const int32_t rho = e->N - e->K;
+        enc_rows_kernel<<<dim3(blocks(e->M), wt), kEncBlock, 0, s>>>(X, e->ptr.p, e->col.p, 0, e->M, e->aux.p, W);
+        int32_t slices = 1;
+        const int32_t slice_cols = enc_dense_slices(e->M, rho, W, &slices);
+        if (slices > 1) LDPC_HIP_TRY(hipMemsetAsync(P, 0, (size_t)rho * W * sizeof(uint64_t), s));
+        enc_dense_kernel<<<dim3((unsigned)((rho + kDenseRows - 1) / kDenseRows), wt, (unsigned)slices), kEncBlock, kDenseLds, s>>>(
+            e->T.p, e->tw, e->aux.p, e->M, rho, P, W, slice_cols);
     } else {
         const int32_t core = e->ps.c * e->ps.z;
         enc_rows_kernel<<<dim3(blocks(core), wt), kEncBlock, 0, s>>>(X, e->ptr.p, e->col.p, 0, core, e->aux.p, W);
@@ -204,6 +216,68 @@ int ldpc_encoder_create(const ldpc_graph *g, int32_t K, int32_t block_rows, int3
     if (err == hipSuccess) err = e->aux.alloc(aux);
     if (err == hipSuccess) err = e->ptr.upload(ptr);
     if (err == hipSuccess) err = e->col.upload(col);
+    if (err != hipSuccess) {
+        delete e;
+        return set_error(err == hipErrorOutOfMemory ? LDPC_ERR_NOMEM : LDPC_ERR_HIP, "encoder buffers: %s", hipGetErrorString(err));
+    }
+    *out = e;
+    return LDPC_OK;
+}
+
+int ldpc_graph_systematic_order(const ldpc_graph *g, int32_t *perm, int32_t *rank) { return ldpc::systematic_order(g, perm, rank); }
+
+int ldpc_parity_dense(const ldpc_graph *g, int32_t K, int64_t out[4])
+{
+    if (!out) return set_error(LDPC_ERR_ARG, "out is NULL");
+    ldpc::DenseSolve ds;
+    const int rc = ldpc::dense_analyse(g, K, false, &ds);
+    out[0] = ds.rho; out[1] = ds.rank_hp; out[2] = ds.M; out[3] = ds.tw;
+    return rc;
+}
+
+int ldpc_parity_dense_rows(const ldpc_graph *g, int32_t K, int32_t first, int32_t rows, uint64_t *t_out, int64_t words)
+{
+    if (!t_out) return set_error(LDPC_ERR_ARG, "t_out is NULL");
+    ldpc::DenseSolve ds;
+    const int rc = ldpc::dense_analyse(g, K, true, &ds);
+    if (rc) return rc;
+    if (first < 0 || rows < 0 || (int64_t)first + rows > ds.rho)
+        return set_error(LDPC_ERR_ARG, "rows [%d, %d + %d) outside [0, rho = %d)", first, first, rows, ds.rho);
+    if (words < (int64_t)rows * ds.tw)
+        return set_error(LDPC_ERR_ARG, "words = %lld, %d rows of %d words need %lld", (long long)words, rows, ds.tw, (long long)((int64_t)rows * ds.tw));
+    std::copy_n(ds.T.begin() + (size_t)first * ds.tw, (size_t)rows * ds.tw, t_out);
+    return LDPC_OK;
+}
+
+int ldpc_encoder_create_dense(const ldpc_graph *g, int32_t K, int32_t max_frames, int32_t device, ldpc_encoder **out)
+{
+    if (!out) return set_error(LDPC_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    if (max_frames <= 0) return set_error(LDPC_ERR_ARG, "max_frames = %d must be positive", max_frames);
+    ldpc::DenseSolve ds;
+    int rc = ldpc::dense_analyse(g, K, true, &ds);      /* arguments, the M cap, then the elimination */
+    if (rc) return rc;
+    if ((rc = ldpc::use_device(device, "the encoder"))) return rc;
+    ldpc_encoder *e = new (std::nothrow) ldpc_encoder;
+    if (!e) return set_error(LDPC_ERR_NOMEM, "out of memory");
+    e->device = device; e->N = g->N; e->K = K; e->M = g->M; e->max_frames = max_frames; e->tw = ds.tw;
+    e->ps.kind = LDPC_PARITY_DENSE;
+    e->Wmax = (max_frames + 63) / 64;
+    /* lambda = H_s u: every row sums its information columns */
+    std::vector<int32_t> ptr((size_t)g->M + 1, 0), col;
+    col.reserve((size_t)g->E);
+    for (int32_t m = 0; m < g->M; ++m) {
+        for (int32_t k = g->row_ptr[m]; k < g->row_ptr[m + 1]; ++k)
+            if (g->cols[k] < K) col.push_back(g->cols[k]);
+        ptr[(size_t)m + 1] = (int32_t)col.size();
+    }
+    hipError_t err = e->X.alloc((size_t)g->N * e->Wmax);
+    if (err == hipSuccess) err = e->aux.alloc((size_t)g->M * e->Wmax);
+    if (err == hipSuccess) err = e->T.upload(ds.T);
+    if (err == hipSuccess) err = e->ptr.upload(ptr);
+    if (err == hipSuccess) err = e->col.upload(col);
+    if (err == hipSuccess)      /* up to 128 KiB of tables: above 64 KiB a launch must have opted in */
+        err = hipFuncSetAttribute((const void *)ldpc::enc_dense_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldpc::kDenseLds);
     if (err != hipSuccess) {
         delete e;
         return set_error(err == hipErrorOutOfMemory ? LDPC_ERR_NOMEM : LDPC_ERR_HIP, "encoder buffers: %s", hipGetErrorString(err));

@@ -13,6 +13,7 @@
  *                       circulant shifts are index arithmetic on rows, nothing is rotated
  *   enc_stair_*         staircase: p_m = p_{m-1} ^ lambda_m as a chunked prefix XOR over lambda (per chunk: local
  *                       prefix and total; exclusive scan of the totals; apply)
+ *   enc_dense_kernel    dense: p = T lambda, a bit-sliced GF(2) matrix product by the method of the Four Russians
  *   enc_store_kernel    X -> packed bytes (N/8 per frame) or one byte per code bit (N per frame)
  *
  * GF(2) only: no floating point.  Every kernel guards its rows by the counts it is given and its words by W;
@@ -180,6 +181,118 @@ __global__ __launch_bounds__(kEncBlock) void enc_stair_apply_kernel(uint64_t *__
     const int32_t w = (int32_t)blockIdx.y * 64 + (threadIdx.x & 63);
     if (m >= M || w >= W) return;
     P[(size_t)m * W + w] ^= T[(size_t)(m / kEncChunk) * W + w];
+}
+
+/* Dense structure: P[r][w] = XOR over the columns j < M with bit j of T's row r set of lam[j][w], r < rho -- a GF(2)
+ * matrix product whose right-hand side is bit-sliced (lam[M][W] = H_s u by enc_rows_kernel, T: rho rows of tw words).
+ * Method of the Four Russians: a workgroup owns kDenseRows output rows and 64 words and walks the M columns in stages of
+ * kDenseCols = 4 kDenseGroups columns.  Per stage it builds, per group of 4 lambda rows, the XOR of each of their 16
+ * subsets in LDS (tab[group][entry][lane], one XOR per entry in Gray-code order: entry i ^ (i >> 1) differs from its
+ * predecessor in bit ctz(i)); an output row then takes one 8-byte LDS read per 4 columns.  A stage lies inside one word of
+ * T, and the row is the wave's, so that word is one scalar load and the entry index is wave-uniform: every LDS access is
+ * base + 8 lane, free of bank conflicts.  The lambda rows of the next stage are loaded into registers before the current
+ * stage's reads, so their latency hides behind them.  grid.z cuts the columns into slices (enc_dense_slices): each
+ * slice adds its share into a zeroed P with a 64-bit atomic XOR.  Guards: rows by rho, words by W, lambda rows by M (T's tail bits
+ * are zero, but no load relies on that). */
+#ifndef LDPC_ENC_DENSE_ROWS
+#define LDPC_ENC_DENSE_ROWS 64      /* measurement builds (tools/encoder_measure.py --dense) override these two */
+#endif
+#ifndef LDPC_ENC_DENSE_GROUPS
+#define LDPC_ENC_DENSE_GROUPS 4
+#endif
+constexpr int kDenseRows = LDPC_ENC_DENSE_ROWS;        /* output rows per workgroup */
+constexpr int kDenseGroups = LDPC_ENC_DENSE_GROUPS;    /* tables of 16 entries per stage: 4, 8 or 16 */
+constexpr int kDenseCols = 4 * kDenseGroups;
+constexpr size_t kDenseLds = (size_t)kDenseGroups * 16 * 64 * sizeof(uint64_t);     /* 8 KiB per group */
+static_assert(kDenseRows % kEncWaves == 0 && kDenseGroups % kEncWaves == 0 && 64 % kDenseCols == 0, "dense encoder tile");
+
+__global__ __launch_bounds__(kEncBlock, 2) void enc_dense_kernel(const uint64_t *__restrict__ T, int32_t tw, const uint64_t *__restrict__ lam,
+                                                             int32_t M, int32_t rho, uint64_t *__restrict__ P, int32_t W, int32_t slice_cols)
+{
+    extern __shared__ uint64_t dense_tab[];     /* [kDenseGroups][16][64] */
+    constexpr int GW = kDenseGroups / kEncWaves, RW = kDenseRows / kEncWaves;
+    const int lane = threadIdx.x & 63;
+    const int wave = enc_wave();
+    const int32_t w = (int32_t)blockIdx.y * 64 + lane;
+    const bool live = w < W;
+    const int32_t wc = live ? w : 0;                                     /* every load is in bounds; a dead lane's is dropped */
+    const int32_t r0 = (int32_t)blockIdx.x * kDenseRows + wave * RW;      /* this wave's rows r0 .. r0 + RW */
+    uint64_t acc[RW], l[GW][4];
+#pragma unroll
+    for (int i = 0; i < RW; ++i) acc[i] = 0;
+    /* this wave builds the tables of groups wave GW .. wave GW + GW - 1; a lambda row beyond M reads as zero */
+    auto fetch = [&](int32_t j0) {
+#pragma unroll
+        for (int q = 0; q < GW; ++q)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int32_t j = j0 + 4 * (wave * GW + q) + i;
+                const uint64_t v = lam[(size_t)(j < M ? j : M - 1) * W + wc];
+                l[q][i] = live && j < M ? v : 0ull;
+            }
+    };
+    /* grid.z cuts the columns into slices of slice_cols (a multiple of kDenseCols); uniform for the workgroup */
+    const int32_t j_lo = (int32_t)blockIdx.z * slice_cols;
+    const int32_t j_hi = j_lo + slice_cols < M ? j_lo + slice_cols : M;
+    if (j_lo >= M) return;
+    fetch(j_lo);
+    const uint64_t *tl = dense_tab + lane;
+    for (int32_t j0 = j_lo; j0 < j_hi; j0 += kDenseCols) {
+#pragma unroll
+        for (int q = 0; q < GW; ++q) {
+            uint64_t *t = dense_tab + (size_t)(wave * GW + q) * 16 * 64 + lane;
+            uint64_t cur = 0;
+            t[0] = 0;
+#pragma unroll
+            for (int i = 1; i < 16; ++i) {
+                cur ^= l[q][__builtin_ctz(i)];
+                t[(i ^ (i >> 1)) * 64] = cur;
+            }
+        }
+        __syncthreads();
+        if (j0 + kDenseCols < j_hi) fetch(j0 + kDenseCols);
+        const uint64_t *trow = T + (j0 >> 6);
+        const int sh = j0 & 63;
+#pragma unroll
+        for (int i = 0; i < RW; ++i) {
+            /* a row beyond rho reads row rho - 1 and is never stored */
+            const int32_t r = r0 + i < rho ? r0 + i : rho - 1;
+            const uint64_t bits = trow[(size_t)r * tw] >> sh;
+#pragma unroll
+            for (int g = 0; g < kDenseGroups; ++g)
+                acc[i] ^= tl[(g * 16 + (int)((bits >> (4 * g)) & 15u)) * 64];
+            /* four rows' reads (4 kDenseGroups) are issued together; without the fence all of a stage's reads and their
+             * addresses are hoisted and the kernel spills */
+            if (i % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();
+    }
+    if (!live) return;
+#pragma unroll
+    for (int i = 0; i < RW; ++i)
+        if (r0 + i < rho) {
+            /* more than one slice: P was zeroed and every slice adds its share (XOR commutes: the bytes do not depend
+             * on the order) */
+            if (gridDim.z > 1) atomicXor(reinterpret_cast<unsigned long long *>(P + (size_t)(r0 + i) * W + w), (unsigned long long)acc[i]);
+            else P[(size_t)(r0 + i) * W + w] = acc[i];
+        }
+}
+
+/* Slices of columns for enc_dense_kernel: few output rows or few words leave the 256 CUs with less than a workgroup each,
+ * and a workgroup's walk is a chain of dependent stages (load, build, read); cutting the columns gives kDenseTargetBlocks
+ * workgroups to overlap those chains.  Returns the columns per slice; *slices = grid.z */
+constexpr int kDenseTargetBlocks = 2048;
+constexpr int kDenseMaxSlices = 32;
+inline int32_t enc_dense_slices(int32_t M, int32_t rho, int32_t W, int32_t *slices)
+{
+    const int64_t blocks = (int64_t)((rho + kDenseRows - 1) / kDenseRows) * ((W + 63) / 64);
+    const int32_t stages = (M + kDenseCols - 1) / kDenseCols;
+    int64_t want = (kDenseTargetBlocks + blocks - 1) / blocks;
+    if (want > kDenseMaxSlices) want = kDenseMaxSlices;
+    if (want > stages) want = stages;
+    const int32_t per = (int32_t)((stages + want - 1) / want);      /* stages per slice */
+    *slices = (stages + per - 1) / per;
+    return per * kDenseCols;
 }
 
 /* 4 bits -> 4 bytes of 0/1 (bit k to byte k): k + 7 j = 8 k' only for j = k = k', and no two products share a bit */

@@ -7,7 +7,7 @@ b is frame b*frames + f of the seed's stream, so a point can be extended or re-r
 and errors counted by ldpc_count_errors_device; nothing crosses PCIe but the counts.  The
 reference counts differing BYTES (Test.cpp:105-110); this prints byte errors too.
 
-    python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N>] [--algo sp|ms|layered|bp|layered_bp]
+    python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N> | --alist PATH] [--algo sp|ms|layered|bp|layered_bp]
                               [--payload zero|random] [--rate-match P,FLO,FHI,E[,K0]] [--erasure-llr X]
                               [--modulation bpsk|qpsk|qam16|qam64|qam256] [--no-interleave] [--transport-block A[,C]] [--crc-stop] [--bch T[,N]]
                               [--msg-dtype f32|f16|f8] [--soft-check] [--osd 0|1 [--osd-scale S]]
@@ -54,6 +54,11 @@ that order (include/ldpc_hip.h, "ordered-statistics post-processing"; ldpc_osd_d
 Every point also prints frame_errors_before_osd / frame_errors_after_osd (frames whose K information bits are wrong),
 osd_processed (frames with a dirty syndrome), osd_flipped (frames where a flip was chosen) and osd_ms_per_batch (HIP events
 around ldpc_osd_device).  fer, ber and the error counts are those of the decoder alone.
+--alist PATH (in place of --code): any parity-check matrix in MacKay's alist format (codes.load_alist).  Its columns are put into
+the systematic order of ldpc_graph_systematic_order (include/ldpc_hip.h, "encoder for any H"; rho = rank(H), K = N - rho and
+whether the order was the identity are printed), the decoder runs on the re-ordered matrix, and --payload random encodes with the
+dense encoder (ldpc_encoder_create_dense).  Flooding algorithms only (--algo sp, ms or bp; no circulant size is known).  K % 8 != 0
+is fine: the bits between the frames of the byte stream are zero on both sides and the frame errors are counted per frame's bytes.
 The DVB-S2 / BG1 codes are PROFILE SURROGATES (codes.py): the numbers are not the standards'."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -64,6 +69,7 @@ from myldpccppapi_amd import codes
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--code", default="dvbs2_12")
+ap.add_argument("--alist", default=None, metavar="PATH", help="in place of --code: H from an alist file, re-ordered to be systematic; flooding algorithms only")
 ap.add_argument("--algo", default="sp")
 ap.add_argument("--snr", default="2.5,3.0,3.5,4.0,4.5,5.0")
 ap.add_argument("--frames", type=int, default=4096)
@@ -109,7 +115,17 @@ QM = {None: 0, "bpsk": 1, "qpsk": 2, "qam16": 4, "qam64": 6, "qam256": 8}[args.m
 matched = ((bool(QM) and args.algo == "sp") or args.algo in ("bp", "layered_bp")) and args.llr_scale is None
 
 layer = 0
-if args.code == "dvbs2_12":
+if args.alist:
+    if args.algo not in ("sp", "ms", "bp"):
+        ap.error("--alist: flooding algorithms only (--algo sp, ms or bp): an alist file names no circulant size for --algo %s" % args.algo)
+    rows, cols, M0, N = codes.load_alist(args.alist)
+    perm, rho = L.systematic_order(L.Graph(rows, cols, M0, N))
+    rows, cols = codes.permute_columns(rows, cols, perm)
+    K = N - rho
+    args.code = "alist:" + os.path.basename(args.alist)
+    print("alist %s: M=%d N=%d rho=rank(H)=%d K=%d (%d redundant rows) column order %s" % (
+        args.alist, M0, N, rho, K, M0 - rho, "is the identity" if np.array_equal(perm, np.arange(N)) else "re-ordered"))
+elif args.code == "dvbs2_12":
     N, K = 64800, 32400
     rows, cols = codes.dvbs2_profile_edges(N, K)
 elif args.code == "dvbs2_910":
@@ -124,7 +140,7 @@ else:
     rate, N = int(rate), int(N)
     K, M, layer = codes.wimax_dims(rate, N)
     rows, cols = codes.wimax_edges(rate, N)
-M = N - K
+M = M0 if args.alist else N - K
 assert layer or args.algo not in ("layered", "layered_bp"), "--algo %s needs the code's circulant size z: --code bg1 or wimax:<rate>:<N>" % args.algo
 g = L.Graph(rows, cols, M, N)
 B = args.frames
@@ -153,12 +169,29 @@ import time
 y = torch.empty((B, N), dtype=torch.float32, device="cuda")
 enc = src = code = None
 if args.payload == "random":
-    assert K % 8 == 0, "--payload random compares whole bytes per frame: K % 8 must be 0"
-    enc = L.Encoder(g, K, layer, max_frames=B)
-    src = torch.empty(B * K // 8, dtype=torch.uint8, device="cuda")
+    assert K % 8 == 0 or args.alist, "--payload random compares whole bytes per frame: K % 8 must be 0"
+    enc = L.DenseEncoder(g, K, max_frames=B) if args.alist else L.Encoder(g, K, layer, max_frames=B)
+    src = torch.empty(L.out_bytes(K, B), dtype=torch.uint8, device="cuda")
     code = torch.empty((B, N), dtype=torch.uint8, device="cuda")
     gen = torch.Generator(device="cuda")
     gen.manual_seed(args.seed)
+# K % 8 != 0 (--alist): frame f owns the K/8 bytes from byte (f K)/8 on; the bytes between frames are zero on both sides
+frame_bytes = between = None
+if K % 8:
+    frame_bytes = (torch.arange(B, dtype=torch.int64, device="cuda") * K // 8)[:, None] + torch.arange(K // 8, dtype=torch.int64, device="cuda")
+    between = torch.ones(L.out_bytes(K, B), dtype=torch.bool, device="cuda")
+    between[frame_bytes.reshape(-1)] = False
+
+
+def count_errors(out_t):
+    """(bit, byte, frame) errors of the decoded bytes against the source (all zero without --payload random)"""
+    if frame_bytes is None:
+        return channel.count_errors_device(out_t, src, B)
+    bits, byts, _ = channel.count_errors_device(out_t, src, 1)
+    diff = out_t if src is None else out_t ^ src
+    return bits, byts, int((diff[frame_bytes] != 0).any(dim=1).sum())
+
+
 pay = back = cb_ok = tb_ok = None
 if tb is not None:
     assert B % tb.C == 0, "--frames must be a multiple of the %d code blocks of a transport block" % tb.C
@@ -209,6 +242,8 @@ def channel_batch(first, sd, seed):
             bch.encode_device(bpay.data_ptr(), B, src.data_ptr(), src.numel(), stream)   # payload, parity, zero fillers
         else:
             src.random_(0, 256, generator=gen)
+            if between is not None:
+                src[between] = 0
             if rm is not None:
                 src.view(B, K // 8)[:, FLO // 8:FHI // 8] = 0      # filler bits are known zeros
         enc.encode_device(src.data_ptr(), src.numel(), B, code.data_ptr(), code.numel(), "bits", stream)
@@ -325,7 +360,7 @@ point_decoder(10.0 ** (-points[-1] / 20.0))
 channel_batch(0, 10.0 ** (-points[-1] / 20.0), args.seed + 1)
 quantise_batch()
 decode_batch(out, it)
-channel.count_errors_device(out, src, B)
+count_errors(out)
 float(it.float().sum())
 torch.cuda.synchronize()
 for snr in points:
@@ -346,7 +381,7 @@ for snr in points:
             decode_batch(out, it)
         else:
             decode_batch(out, it, soft_ptr=osd_soft.data_ptr(), soft_floats=osd_soft.numel(), soft="posterior")
-        e = channel.count_errors_device(out, src, B)
+        e = count_errors(out)
         tot = [t + x for t, x in zip(tot, e)]
         if osd is not None:
             osd_tot = [t + x for t, x in zip(osd_tot, osd_batch())]
