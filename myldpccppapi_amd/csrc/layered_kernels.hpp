@@ -21,7 +21,7 @@
  * written once per edge).  Frozen frames keep their hard bits (bit masks), their
  * P/R keep evolving unread -- no per-lane predication in the hot loop.
  *
- * LDPC_ALGO_LAYERED_BP (layer_bp_kernel, below) is the same engine with the box-plus row of flood_check.hpp.
+ * LDPC_ALGO_LAYERED_BP (kLayerBp, below) is the same engine with the box-plus row of flood_check.hpp.
  */
 #pragma once
 
@@ -59,58 +59,265 @@ __device__ __forceinline__ float cl_sign(float x)
     return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : (x == 0.0f ? x : 0.0f));
 }
 
-/* HOST = false: the arithmetic of the fused kernel decodeOnceTDMP (above).
- * HOST = true: the reference's host-layered path, Coder::decodeOnceTDMP (MyLdpc.cpp:889-976) over
- * refreshQTDMP / refreshRTDMP / refreshPostPTDMP (decodeCL.c:228-259, 283-290): q_k = P - R_k, the
- * check node of the MS kernel chain (sign = XOR of `< 0`, magnitude = fmin chain from 1000 ==
- * check_ms), P = q_k + R_k; the hard decision is taken once per iteration by layered_hard_kernel. */
-template <int D, int V, bool HOST = false>
-__global__ __launch_bounds__(kBlock) void layer_kernel(const LayerArgs a)
+/* The row rules of the streaming layered kernels; the frame around them -- rows of a wave, loads, stores, hard bits --
+ * is layer_kernel's (unrolled degrees) and layer_kernel_generic's (any degree). */
+enum LayerRule {
+    kLayerFused = 0,    /* the arithmetic of the fused kernel decodeOnceTDMP (above) */
+    kLayerCorr,         /* the same with normalized / offset min-sum (LayeredPlan::corr): the row's two candidates b, c go
+                           through ms_corr (flood_common.hpp) before the sign and the per-edge selection -- two operations
+                           per row, not per edge */
+    kLayerHost,         /* the reference's host-layered path, Coder::decodeOnceTDMP (MyLdpc.cpp:889-976) over refreshQTDMP /
+                           refreshRTDMP / refreshPostPTDMP (decodeCL.c:228-259, 283-290): q_k = P - R_k, the check node of
+                           the MS kernel chain (sign = XOR of `< 0`, magnitude = fmin chain from 1000 == check_ms),
+                           P = q_k + R_k; the hard decision is taken once per iteration by layered_hard_kernel */
+    kLayerBp,           /* layered log-domain sum-product (LDPC_ALGO_LAYERED_BP, include/ldpc_hip.h has the rule bit for
+                           bit): the row of LDPC_ALGO_BP (check_bp, flood_check.hpp) on x_k = q_k = P[col_k] - R_k:
+                           R_k = out_k, P[col_k] = q_k + R_k.  The row's sign comes from (x < 0), never from a product of
+                           messages, so an exact 0 does not kill a row */
+};
+
+/* What one wave of a layer launch works on: its rows, its lanes' part of the tile's P and R, the tile's hard bits. */
+template <int V> struct LayerWave {
+    static constexpr size_t F = 64 * V;
+    int lane, r_begin, r_end;
+    float *Pt, *Rt;
+    uint64_t *hard_t;
+    uint64_t frozen[V];
+    __device__ __forceinline__ explicit LayerWave(const LayerArgs &a)
+    {
+        lane = threadIdx.x & 63;
+        const int tile = blockIdx.y;
+        const int wave = (int)blockIdx.x * kWavesPerBlock + wave_id_in_block();
+        r_begin = wave * a.rows_per_wave;
+        r_end = min(r_begin + a.rows_per_wave, a.n_rows);
+        Pt = a.P + (size_t)tile * (size_t)a.N * F + (size_t)lane * V;
+        Rt = a.R + (size_t)tile * (size_t)a.E * F + (size_t)lane * V;
+        hard_t = a.hard + (size_t)tile * (size_t)a.N * V;
+#pragma unroll
+        for (int v = 0; v < V; ++v) frozen[v] = a.done[(size_t)tile * V + v];
+    }
+    /* bits = P < 0 (decodeCL.c:388-389), kept current per write; frozen frames keep theirs */
+    __device__ __forceinline__ void set_bits(int col, const float (&p)[V]) const
+    {
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const uint64_t w = __ballot(p[v] < 0.0f);
+            if (lane == 0) {
+                const uint64_t old = hard_t[(size_t)col * V + v];
+                hard_t[(size_t)col * V + v] = (old & frozen[v]) | (w & ~frozen[v]);
+            }
+        }
+    }
+};
+
+/* Rows of degree D: one load and one store of R and of P per edge.  Every instantiation takes the MsCorr, so that one
+ * table of one pointer type launches them all; only kLayerCorr reads it. */
+template <int D, int V, int RULE>
+__global__ __launch_bounds__(kBlock) void layer_kernel(const LayerArgs a, const MsCorr corr)
 {
-    constexpr bool CORR = false;
-    const MsCorr corr{1.0f, 0.0f};
-#include "layer_kernel.inc"
-}
-/* Normalized / offset min-sum (LayeredPlan::corr): the row's two candidates b, c go through ms_corr (flood_common.hpp)
- * before the sign and the per-edge selection -- two operations per row, not per edge. */
-template <int D, int V>
-__global__ __launch_bounds__(kBlock) void layer_corr_kernel(const LayerArgs a, const MsCorr corr)
-{
-    constexpr bool HOST = false, CORR = true;
-#include "layer_kernel.inc"
+    constexpr size_t F = 64 * V;
+    const int lane = threadIdx.x & 63;
+    const int tile = blockIdx.y;
+    if (tile_finished<V>(a.done, tile)) return;
+    const int wave = (int)blockIdx.x * kWavesPerBlock + wave_id_in_block();
+    const int r_begin = wave * a.rows_per_wave;
+    const int r_end = min(r_begin + a.rows_per_wave, a.n_rows);
+    float *Pt = a.P + (size_t)tile * (size_t)a.N * F + (size_t)lane * V;
+    float *Rt = a.R + (size_t)tile * (size_t)a.E * F + (size_t)lane * V;
+    uint64_t *hard_t = a.hard + (size_t)tile * (size_t)a.N * V;
+    uint64_t frozen[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) frozen[v] = a.done[(size_t)tile * V + v];
+    for (int r = r_begin; r < r_end; ++r) {
+        const int e0 = a.cls_e0[r];
+        int col[D];
+#pragma unroll
+        for (int k = 0; k < D; ++k) col[k] = a.edge_col[e0 + k];
+        float p[D][V], m[D][V];
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            vload<V>(m[k], Rt + (size_t)(e0 + k) * F);
+            vload<V>(p[k], Pt + (size_t)col[k] * F);
+        }
+        constexpr bool SUM = RULE == kLayerHost || RULE == kLayerBp;   /* the row is a function of the q_k: check_ms, check_bp */
+        if constexpr (SUM) {
+#pragma unroll
+            for (int k = 0; k < D; ++k)
+#pragma unroll
+                for (int v = 0; v < V; ++v) p[k][v] = p[k][v] - m[k][v];      /* q_k (refreshQTDMP) */
+            if constexpr (RULE == kLayerHost) check_ms<D, V>(p, m);               /* refreshRTDMP */
+            else check_bp<D, V, float>(p, m);                                     /* R_k = out_k */
+        } else {
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                float prod = 1.0f, b = 1000.0f, c = 1001.0f;   /* decodeCL.c:346-348 */
+                int bind = -1;
+                float sg[D];
+#pragma unroll
+                for (int k = 0; k < D; ++k) {                  /* :350-367 */
+                    const float q = p[k][v] - m[k][v];
+                    sg[k] = cl_sign(q);
+                    prod *= q;
+                    p[k][v] = q;
+                    const float mag = __builtin_fabsf(q);
+                    if (mag <= b) { c = b; b = mag; bind = k; }
+                    else if (mag > b && mag <= c) { c = mag; }
+                }
+                if (RULE == kLayerCorr) { b = ms_corr<float>(b, corr); c = ms_corr<float>(c, corr); }   /* once per row */
+                const float sa = cl_sign(prod);                /* :369 */
+                const float ab = sa * b, ac = sa * c;
+#pragma unroll
+                for (int k = 0; k < D; ++k) {                  /* :371-383 */
+                    const float rn = sg[k] * ((k == bind) ? ac : ab);
+                    m[k][v] = rn;
+                    p[k][v] = p[k][v] + rn;
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            if constexpr (SUM) {
+#pragma unroll
+                for (int v = 0; v < V; ++v) p[k][v] = p[k][v] + m[k][v];      /* P = q_k + R_k (refreshPostPTDMP) */
+            }
+            vstore<V>(Rt + (size_t)(e0 + k) * F, m[k]);
+            vstore<V>(Pt + (size_t)col[k] * F, p[k]);
+            if (RULE != kLayerHost) {
+#pragma unroll
+                for (int v = 0; v < V; ++v) {
+                    const uint64_t w = __ballot(p[k][v] < 0.0f);
+                    if (lane == 0) {
+                        const uint64_t old = hard_t[(size_t)col[k] * V + v];
+                        hard_t[(size_t)col[k] * V + v] = (old & frozen[v]) | (w & ~frozen[v]);
+                    }
+                }
+            }
+        }
+    }
 }
 
-/* Rows of any degree: same arithmetic with run-time loops, values re-read. */
-template <int V>
-__global__ __launch_bounds__(kBlock) void layer_kernel_generic(const LayerArgs a)
+/* A min-sum row of any degree: the same arithmetic with run-time loops, values re-read. */
+template <int V, bool CORR>
+__device__ __forceinline__ void layer_row_generic(const LayerArgs &a, const LayerWave<V> &w, int e0, const MsCorr corr)
 {
-    constexpr bool CORR = false;
-    const MsCorr corr{1.0f, 0.0f};
-#include "layer_kernel_generic.inc"
-}
-template <int V>
-__global__ __launch_bounds__(kBlock) void layer_corr_kernel_generic(const LayerArgs a, const MsCorr corr)
-{
-    constexpr bool CORR = true;
-#include "layer_kernel_generic.inc"
+    constexpr size_t F = 64 * V;
+    const int D = a.degree;
+    float prod[V], b[V], c[V], sa[V];
+    int bind[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) { prod[v] = 1.0f; b[v] = 1000.0f; c[v] = 1001.0f; bind[v] = -1; }
+    for (int k = 0; k < D; ++k) {
+        const int col = a.edge_col[e0 + k];
+        float m[V], p[V];
+        vload<V>(m, w.Rt + (size_t)(e0 + k) * F);
+        vload<V>(p, w.Pt + (size_t)col * F);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const float q = p[v] - m[v];
+            prod[v] *= q;
+            p[v] = q;
+            const float mag = __builtin_fabsf(q);
+            if (mag <= b[v]) { c[v] = b[v]; b[v] = mag; bind[v] = k; }
+            else if (mag > b[v] && mag <= c[v]) { c[v] = mag; }
+        }
+        vstore<V>(w.Pt + (size_t)col * F, p);          /* q parked in P, as decodeCL.c:357 */
+    }
+    if (CORR) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) { b[v] = ms_corr<float>(b[v], corr); c[v] = ms_corr<float>(c[v], corr); }
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) sa[v] = cl_sign(prod[v]);
+    for (int k = 0; k < D; ++k) {
+        const int col = a.edge_col[e0 + k];
+        float q[V], rn[V];
+        vload<V>(q, w.Pt + (size_t)col * F);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            rn[v] = cl_sign(q[v]) * ((k == bind[v]) ? sa[v] * c[v] : sa[v] * b[v]);
+            q[v] = q[v] + rn[v];
+        }
+        vstore<V>(w.Rt + (size_t)(e0 + k) * F, rn);
+        vstore<V>(w.Pt + (size_t)col * F, q);
+        w.set_bits(col, q);
+    }
 }
 
-/* Layered log-domain sum-product (LDPC_ALGO_LAYERED_BP, include/ldpc_hip.h has the rule bit for bit): the schedule, the
- * memory behaviour and the bookkeeping of layer_kernel with the row of LDPC_ALGO_BP (check_bp, flood_check.hpp) on
- * x_k = q_k = P[col_k] - R_k: R_k = out_k, P[col_k] = q_k + R_k.  The row's sign comes from (x < 0), never from a
- * product of messages, so an exact 0 does not kill a row. */
-template <int D, int V>
-__global__ __launch_bounds__(kBlock) void layer_bp_kernel(const LayerArgs a)
+/* A box-plus row of any degree: check_bp's association with run-time loops over a row that is updated in place, so the
+ * order matters: k ascends, the forward value f_{k-1} is carried in registers, and b_{k+1} is rebuilt from the row's end
+ * out of q_j = P[col_j] - R_j for j > k.
+ *
+ * Invariant: when step k begins, edges 0 .. k-1 of the row hold their new R and P, edges k .. D-1 their old ones.  Step k
+ * reads q_j = P[col_j] - R_j only for j >= k -- q_k itself and, for b_{k+1}, the j > k -- and takes everything it needs
+ * of the j < k from f = f_{k-1}, carried in registers and formed from q_{k-1} BEFORE step k-1 stored.  A row's columns
+ * are distinct (edges ascend strictly within a row) and rows of a layer share no column (layered_plan_create), so what
+ * step k stores at R_k and P[col_k] is read by no other edge of this row and by no other row of this launch. */
+template <int V>
+__device__ __forceinline__ void layer_row_generic_bp(const LayerArgs &a, const LayerWave<V> &w, int e0)
 {
-#include "layer_bp_kernel.inc"
+    constexpr size_t F = 64 * V;
+    const int D = a.degree;
+    /* t_j = bp_clamp(q_j) of an edge that still holds its old values */
+    auto load_t = [&](int j, float (&t)[V]) {
+        float pj[V], mj[V];
+        vload<V>(mj, w.Rt + (size_t)(e0 + j) * F);
+        vload<V>(pj, w.Pt + (size_t)a.edge_col[e0 + j] * F);
+#pragma unroll
+        for (int v = 0; v < V; ++v) t[v] = bp_clamp(pj[v] - mj[v]);
+    };
+    float f[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) f[v] = 0.0f;
+    for (int k = 0; k < D; ++k) {
+        const int col = a.edge_col[e0 + k];
+        float q[V], o[V];
+        {
+            float mk[V];
+            vload<V>(mk, w.Rt + (size_t)(e0 + k) * F);
+            vload<V>(q, w.Pt + (size_t)col * F);
+#pragma unroll
+            for (int v = 0; v < V; ++v) q[v] = q[v] - mk[v];
+        }
+        if (D == 1) {
+#pragma unroll
+            for (int v = 0; v < V; ++v) o[v] = 1000.0f;
+        } else if (k == D - 1) {
+#pragma unroll
+            for (int v = 0; v < V; ++v) o[v] = f[v];                       /* f_{D-2} */
+        } else {
+            float b[V], t[V];
+            load_t(D - 1, b);
+            for (int j = D - 2; j > k; --j) {
+                load_t(j, t);
+#pragma unroll
+                for (int v = 0; v < V; ++v) b[v] = bp_boxplus(t[v], b[v]);   /* b_j = t_j [+] b_{j+1} */
+            }
+#pragma unroll
+            for (int v = 0; v < V; ++v) o[v] = (k == 0) ? b[v] : bp_boxplus(f[v], b[v]);
+        }
+#pragma unroll
+        for (int v = 0; v < V; ++v) {                   /* f_k from q_k, before edge k is stored */
+            const float tk = bp_clamp(q[v]);
+            f[v] = (k == 0) ? tk : bp_boxplus(f[v], tk);
+            q[v] = q[v] + o[v];
+        }
+        vstore<V>(w.Rt + (size_t)(e0 + k) * F, o);
+        vstore<V>(w.Pt + (size_t)col * F, q);
+        w.set_bits(col, q);
+    }
 }
 
-/* Rows of any degree with run-time loops.  The update is in place, so the order matters: k ascends, the forward value
- * f_{k-1} is carried in registers, and b_{k+1} is rebuilt from the row's end out of q_j = P[col_j] - R_j for j > k. */
-template <int V>
-__global__ __launch_bounds__(kBlock) void layer_bp_kernel_generic(const LayerArgs a)
+/* Rows of any degree (LayerArgs::degree); the host arithmetic has unrolled degrees only. */
+template <int V, int RULE>
+__global__ __launch_bounds__(kBlock) void layer_kernel_generic(const LayerArgs a, const MsCorr corr)
 {
-#include "layer_bp_kernel_generic.inc"
+    static_assert(RULE != kLayerHost, "no generic row with the host arithmetic");
+    if (tile_finished<V>(a.done, blockIdx.y)) return;
+    const LayerWave<V> w(a);
+    for (int r = w.r_begin; r < w.r_end; ++r) {
+        if constexpr (RULE == kLayerBp) layer_row_generic_bp<V>(a, w, a.cls_e0[r]);
+        else layer_row_generic<V, RULE == kLayerCorr>(a, w, a.cls_e0[r], corr);
+    }
 }
 
 /* hardDecisionTDMP, decodeCL.c:261-280, after the last layer of an iteration: P > 0 -> 0, P < 0 -> 1,
@@ -149,19 +356,46 @@ struct LayeredInitArgs {
 };
 
 /* lP = postCode (decodeCL.c:331-334), transposed into the tile layout; bits = y < 0.  SCALED (LDPC_ALGO_LAYERED_BP): the
- * value is chan = scale * y, one fp32 multiply, padding frames included; the other algorithms' kernel has no multiply. */
-template <int V, typename IN = float>
-__global__ __launch_bounds__(kBlock) void layered_init_kernel(const LayeredInitArgs a)
+ * value is chan = scale * y, one fp32 multiply, padding frames included; the other algorithms' instantiation has no
+ * multiply and does not read scale.  IN: element type of the caller's buffer; a narrow one goes through llr_patch_fill
+ * (llr_input.hpp), float through the loop below. */
+template <int V, typename IN, bool SCALED>
+__global__ __launch_bounds__(kBlock) void layered_init_kernel(const LayeredInitArgs a, const float scale)
 {
-    constexpr bool SCALED = false;
-    const float scale = 1.0f;
-#include "layered_init_kernel.inc"
-}
-template <int V, typename IN = float>
-__global__ __launch_bounds__(kBlock) void layered_init_scaled_kernel(const LayeredInitArgs a, const float scale)
-{
-    constexpr bool SCALED = true;
-#include "layered_init_kernel.inc"
+    constexpr int F = 64 * V;
+    constexpr int LD = F + 1;
+    __shared__ float patch[kInitCols * LD];
+    const int tile = blockIdx.y;
+    const int n0 = blockIdx.x * kInitCols;
+    const IN *__restrict__ llr = static_cast<const IN *>(a.llr);
+    if constexpr (!std::is_same<IN, float>::value) {
+        llr_patch_fill<IN, F, LD, kInitCols, kBlock, SCALED>(patch, llr, a.llr_unit, a.frames, a.N, tile, n0, scale);
+    } else {
+        const int c = threadIdx.x & (kInitCols - 1);
+        const int n = n0 + c;
+        for (int f = threadIdx.x / kInitCols; f < F; f += kBlock / kInitCols) {
+            const int64_t frame = (int64_t)tile * F + f;
+            float y = 1.0f;
+            if (frame < a.frames && n < a.N) y = llr[(size_t)frame * a.N + n];
+            if (SCALED) y = scale * y;
+            patch[c * LD + f] = y;
+        }
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    for (int c = threadIdx.x >> 6; c < kInitCols; c += kWavesPerBlock) {
+        const int n = n0 + c;
+        if (n >= a.N) break;
+        float y[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) y[v] = patch[c * LD + lane * V + v];
+        vstore<V>(a.P + ((size_t)tile * a.N + n) * F + (size_t)lane * V, y);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const uint64_t w = __ballot(y[v] < 0.0f);
+            if (lane == 0) a.hard[((size_t)tile * a.N + n) * V + v] = a.zero_bits ? 0ull : w;
+        }
+    }
 }
 
 /* LDPC_ALGO_LAYERED_BP, extrinsic soft output: soft_settle_kernel leaves the posterior of every frame's stop round in the
@@ -193,10 +427,10 @@ struct LayeredPlan {
     int32_t M = 0, N = 0, layer_rows = 0;
     int64_t E = 0;
     int T = 0, V = 1;
-    int host_arith = 0;             /* 1: LDPC_ALGO_LAYERED_HOST (layer_kernel<.., HOST = true>) */
-    int corr = 0;                   /* 1: normalized / offset min-sum (layer_corr_kernel) with these: */
+    int host_arith = 0;             /* 1: LDPC_ALGO_LAYERED_HOST (kLayerHost) */
+    int corr = 0;                   /* 1: normalized / offset min-sum (kLayerCorr) with these: */
     float ms_scale = 1.0f, ms_offset = 0.0f;
-    int bp = 0;                     /* 1: LDPC_ALGO_LAYERED_BP (layer_bp_kernel), chan = llr_scale * y: */
+    int bp = 0;                     /* 1: LDPC_ALGO_LAYERED_BP (kLayerBp), chan = llr_scale * y: */
     float llr_scale = 1.0f;
     DevBuf<float> P, R;
     std::vector<LayerGroup> groups; /* ordered by layer */
@@ -260,27 +494,15 @@ struct LayeredRun {
 /* The launching code instantiates every kernel above: only the translation unit that defines
  * LDPC_ENGINE_LAYERED (engine_layered.hip) compiles it; the host driver calls engine_layered_run. */
 #ifdef LDPC_ENGINE_LAYERED
-using LayerFn = void (*)(const LayerArgs);
-template <int V, int D, bool HOST = false> struct LayerTable {
-    static void fill(LayerFn *t) { t[D] = layer_kernel<D, V, HOST>; LayerTable<V, D - 1, HOST>::fill(t); }
-};
-template <int V, bool HOST> struct LayerTable<V, 0, HOST> {
-    static void fill(LayerFn *t) { t[0] = HOST ? nullptr : layer_kernel_generic<V>; }
-};
-using LayerCorrFn = void (*)(const LayerArgs, const MsCorr);
-template <int V, int D> struct LayerCorrTable {
-    static void fill(LayerCorrFn *t) { t[D] = layer_corr_kernel<D, V>; LayerCorrTable<V, D - 1>::fill(t); }
-};
-template <int V> struct LayerCorrTable<V, 0> {
-    static void fill(LayerCorrFn *t) { t[0] = layer_corr_kernel_generic<V>; }
-};
-template <int V, int D> struct LayerBpTable {
-    static void fill(LayerFn *t) { t[D] = layer_bp_kernel<D, V>; LayerBpTable<V, D - 1>::fill(t); }
-};
-template <int V> struct LayerBpTable<V, 0> {
-    static void fill(LayerFn *t) { t[0] = layer_bp_kernel_generic<V>; }
-};
-
+using LayerFn = void (*)(const LayerArgs, const MsCorr);
+/* t[D] = the kernel of the rule for rows of degree D = 1 .. kMaxUnrolledLayerDegree, t[0] = the one for wider rows */
+template <int V, int RULE, int... D0>
+inline void layer_table_fill(LayerFn *t, std::integer_sequence<int, D0...>)
+{
+    if constexpr (RULE == kLayerHost) t[0] = nullptr;
+    else t[0] = layer_kernel_generic<V, RULE>;
+    ((t[D0 + 1] = layer_kernel<D0 + 1, V, RULE>), ...);
+}
 
 template <int V> __global__ void layered_summary_kernel(const int32_t *iters, const uint64_t *done,
                                                         int64_t frames, int32_t *summary)
@@ -301,11 +523,11 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
     const int tiles = (int)((r.frames + F - 1) / F);
     const size_t slot = (size_t)pl->T * V;
     LayerFn table[kMaxUnrolledLayerDegree + 1];
-    LayerCorrFn corr_table[kMaxUnrolledLayerDegree + 1];
-    if (pl->bp) LayerBpTable<V, kMaxUnrolledLayerDegree>::fill(table);
-    else if (pl->host_arith) LayerTable<V, kMaxUnrolledLayerDegree, true>::fill(table);
-    else LayerTable<V, kMaxUnrolledLayerDegree>::fill(table);
-    LayerCorrTable<V, kMaxUnrolledLayerDegree>::fill(corr_table);
+    const std::make_integer_sequence<int, kMaxUnrolledLayerDegree> degrees;
+    if (pl->corr) layer_table_fill<V, kLayerCorr>(table, degrees);
+    else if (pl->bp) layer_table_fill<V, kLayerBp>(table, degrees);
+    else if (pl->host_arith) layer_table_fill<V, kLayerHost>(table, degrees);
+    else layer_table_fill<V, kLayerFused>(table, degrees);
     const MsCorr corr{pl->ms_scale, pl->ms_offset};
     const int rounds = r.tap_iter ? (r.tap_iter < r.max_iter ? r.tap_iter : r.max_iter) : r.max_iter;
     hipError_t e;
@@ -317,8 +539,8 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
         dim3 grid((pl->N + kInitCols - 1) / kInitCols, tiles);
         dispatch_llr(r.llr.type, [&](auto in) {
             using IN = decltype(in);
-            if (pl->bp) layered_init_scaled_kernel<V, IN><<<grid, kBlock, 0, s>>>(ia, pl->llr_scale);
-            else layered_init_kernel<V, IN><<<grid, kBlock, 0, s>>>(ia);
+            const auto init = pl->bp ? layered_init_kernel<V, IN, true> : layered_init_kernel<V, IN, false>;
+            init<<<grid, kBlock, 0, s>>>(ia, pl->llr_scale);
         });
         StateArgs st{r.done, nullptr, r.iters, nullptr, r.frames, 0, r.max_iter, 1};
         state_kernel<V><<<tiles, 64, 0, s>>>(st);
@@ -334,8 +556,7 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
             if (!table[k]) return hipErrorInvalidValue;      /* host arithmetic: unrolled degrees only */
             if (r.span_begin && (e = r.span_begin(r.span_ctx, s, 2, g.degree,
                                                   (int64_t)16 * g.degree * g.count * r.frames))) return e;
-            if (pl->corr) corr_table[k]<<<grid, kBlock, 0, s>>>(a, corr);
-            else table[k]<<<grid, kBlock, 0, s>>>(a);
+            table[k]<<<grid, kBlock, 0, s>>>(a, corr);
             if (r.span_end && (e = r.span_end(r.span_ctx, s))) return e;
         }
         if (pl->host_arith) {

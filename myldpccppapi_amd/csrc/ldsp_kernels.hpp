@@ -124,6 +124,36 @@ __device__ __forceinline__ uint32_t ldsp_old_message(const uint4 rec, uint32_t z
     return mag | (((rec.z >> (d - 1 - k)) & 1u) << 31);
 }
 
+/* The slow path's pieces, shared by ldsp_row_any and ldsp_mscl_row_any.  First pass, per entry (decodeCL.c:355-366): */
+__device__ __forceinline__ void ldsp_any_step(float q, int k, float *prod, float *b, float *c, int *bind)
+{
+    *prod *= q;
+    const float mag = __builtin_fabsf(q);
+    if (mag <= *b) { *c = *b; *b = mag; *bind = k; }
+    else if (mag > *b && mag <= *c) { *c = mag; }
+}
+/* second pass, per entry: the new message, its sign appended to the record's, its zero bit (see ldsp_old_message) */
+__device__ __forceinline__ float ldsp_any_message(float q, int k, int bind, float ab, float ac, uint32_t *signs, uint32_t *zf)
+{
+    const float sel = (k == bind) ? ac : ab;
+    const float rn = cl_sign(q) * sel;
+    const uint32_t rb = __float_as_uint(rn);
+    *signs = (*signs << 1) | (rb >> 31);
+    if ((rb & 0x7fffffffu) != (__float_as_uint(sel) & 0x7fffffffu)) *zf |= 1u << k;   /* then it is a zero */
+    return rn;
+}
+/* the row's new record */
+__device__ __forceinline__ uint4 ldsp_any_record(float ab, float ac, uint32_t signs, int bind, uint32_t zf, uint32_t *zfp,
+                                                 uint32_t pext)
+{
+    uint32_t word = signs | ((uint32_t)bind << 24);
+    if (zf) {
+        word |= kLdspIrregular;
+        *zfp = zf;
+    }
+    return uint4{__float_as_uint(ab) & 0x7fffffffu, __float_as_uint(ac) & 0x7fffffffu, word, pext};
+}
+
 /* Any input: the reference's operations one by one (decodeCL.c:345-383) with run-time loops, q
  * parked in P between the two passes as the reference does. */
 template <bool CORR = false>
@@ -146,15 +176,11 @@ __device__ __forceinline__ uint4 ldsp_row_any(float *P, ldpc_const_i32 pk, int d
             q = __uint_as_float(old.w) - rold;
             qext = q;
         }
-        prod *= q;
-        const float mag = __builtin_fabsf(q);
-        if (mag <= b) { c = b; b = mag; bind = k; }
-        else if (mag > b && mag <= c) { c = mag; }
+        ldsp_any_step(q, k, &prod, &b, &c, &bind);
     }
     if (CORR) { b = ms_corr<float>(b, corr); c = ms_corr<float>(c, corr); }     /* normalized / offset min-sum */
     const float sa = cl_sign(prod);
     const float ab = sa * b, ac = sa * c;
-    const uint32_t mab = __float_as_uint(ab) & 0x7fffffffu, mac = __float_as_uint(ac) & 0x7fffffffu;
     uint32_t signs = 0, zf = 0, pext = 0;
     for (int k = 0; k < d; ++k) {
         float *p = P;
@@ -163,21 +189,12 @@ __device__ __forceinline__ uint4 ldsp_row_any(float *P, ldpc_const_i32 pk, int d
             p = ldsp_at(P, pk[k], pk[kLdspMaxDeg + k], r * 4, z * 4);
             q = *p;
         }
-        const float rn = cl_sign(q) * ((k == bind) ? ac : ab);
-        const float pn = q + rn;
+        const float pn = q + ldsp_any_message(q, k, bind, ab, ac, &signs, &zf);
         if (k < dl) *p = pn;
         else pext = __float_as_uint(pn);
         if (pn < 0.0f) *par ^= 1u;
-        const uint32_t rb = __float_as_uint(rn);
-        signs = (signs << 1) | (rb >> 31);
-        if ((rb & 0x7fffffffu) != ((k == bind) ? mac : mab)) zf |= 1u << k;   /* then it is a zero */
     }
-    uint32_t word = signs | ((uint32_t)bind << 24);
-    if (zf) {
-        word |= kLdspIrregular;
-        *zfp = zf;
-    }
-    return uint4{mab, mac, word, pext};
+    return ldsp_any_record(ab, ac, signs, bind, zf, zfp, pext);
 }
 
 /* Exact row width (DL entries in LDS + EXT external), straight-line code.  Returns false,
@@ -264,21 +281,192 @@ __device__ __forceinline__ uint64_t ldsp_row_parity(const float *P, ldpc_const_i
 #define LDPC_LDSP_WAVES_PER_EU 6
 #endif
 
-template <int MAXW>
-__global__ __launch_bounds__(64 * MAXW) __attribute__((amdgpu_waves_per_eu(LDPC_LDSP_WAVES_PER_EU)))
-void layered_ldsp_kernel(const LdspArgs a)
+/* ---- pieces that the kernels below share: the workgroup-wide OR and what a frame leaves behind.  r: the thread's row,
+ * recs / zfs: its records (the kernels' own pointers, + r applied). */
+
+/* OR over the workgroup through one LDS word (the kernels have no static LDS: P sits at LDS address 0 and the table's
+ * byte offsets are final addresses) */
+__device__ __forceinline__ bool ldsp_wg_any(uint32_t *wg_flag, int r, bool pred)
 {
-    constexpr bool CORR = false;
-    const MsCorr corr{1.0f, 0.0f};
-#include "ldsp_layered_kernel.inc"
+    if (r == 0) *wg_flag = 0u;
+    lds_barrier();
+    if (__ballot(pred) != 0ull && (r & 63) == 0) *wg_flag = 1u;
+    lds_barrier();
+    const uint32_t f = *wg_flag;
+    lds_barrier();                                             /* before the word is cleared again */
+    return f != 0u;
 }
-/* normalized / offset min-sum (LdspPlan::corr): b and c of every row through ms_corr, once per row */
-template <int MAXW>
-__global__ __launch_bounds__(64 * MAXW) __attribute__((amdgpu_waves_per_eu(LDPC_LDSP_WAVES_PER_EU)))
-void layered_ldsp_corr_kernel(const LdspArgs a, const MsCorr corr)
+
+/* tap: the frame's posteriors, the LDS-resident columns from P and the others from the records they travel with */
+__device__ __forceinline__ void ldsp_dump_p(const LdspArgs &a, const float *P, const uint4 *recs, int64_t frame, int r)
 {
-    constexpr bool CORR = true;
-#include "ldsp_layered_kernel.inc"
+    const ldpc_const_i32 hdr = as_constant(a.hdr), cslot = as_constant(a.col_slot);
+    const int z = a.z;
+    for (int bc = 0; bc < a.nb; ++bc) {
+        const int slot = cslot[bc];
+        if (slot >= 0) a.dump_p[(size_t)frame * a.N + bc * z + r] = P[slot * z + r];
+    }
+    for (int l = 0; l < a.layers; ++l)
+        if (hdr[l * 4 + 1])
+            a.dump_p[(size_t)frame * a.N + hdr[l * 4 + 2] + ldsp_wrap(r, hdr[l * 4 + 3], z)] =
+                __uint_as_float(recs[(size_t)l * z].w);
+}
+
+/* tap: the frame's check-to-variable messages in the reference's edge order, rebuilt from the records */
+__device__ __forceinline__ void ldsp_dump_r(const LdspArgs &a, const uint4 *recs, const uint32_t *zfs, int64_t frame, int r)
+{
+    const ldpc_const_i32 hdr = as_constant(a.hdr);
+    const int z = a.z;
+    for (int l = 0; l < a.layers; ++l) {
+        const int d = hdr[l * 4] + hdr[l * 4 + 1], e0 = a.layer_e0[l];
+        const uint4 rec = recs[(size_t)l * z];
+        const uint32_t zf = (rec.z & kLdspIrregular) ? zfs[(size_t)l * z] : 0u;
+        for (int k = 0; k < d; ++k)
+            a.dump_r[(size_t)frame * a.E + e0 + r * d + k] = __uint_as_float(ldsp_old_message(rec, zf, k, d));
+    }
+}
+
+/* the frame's iteration count and its share of the summary; by one thread per frame */
+__device__ __forceinline__ void ldsp_report(const LdspArgs &a, int64_t frame, int it, bool clean)
+{
+    if (a.iters) a.iters[frame] = it;
+    atomicMax(&a.summary[0], it);
+    if (clean) atomicAdd(&a.summary[1], 1);
+}
+
+/* CORR (every kernel of this file): normalized / offset min-sum (LdspPlan::corr), b and c of every row through ms_corr,
+ * once per row.  The kernels' trailing arguments C... are the MsCorr where CORR and none otherwise.  Measured at BG1
+ * Z = 384, batch 8192, three alternating runs against the kernels that had a body each: with a MsCorr that the plain
+ * instantiation does not read, flood_ldsp_kernel<8, true, false> (27 spilled registers, 24018 instructions; before: 32,
+ * 24042) took 54.99 ms against 54.50 .. 54.64; with the pack (30, 24037) 54.49 ms against 54.46 .. 54.51.  That the unread
+ * argument is what moves the register allocation is a supposition: the two builds are all that was compared. */
+__device__ __forceinline__ MsCorr ldsp_corr_of() { return MsCorr{1.0f, 0.0f}; }
+__device__ __forceinline__ MsCorr ldsp_corr_of(const MsCorr c) { return c; }
+
+template <int MAXW, bool CORR, class... C>
+__global__ __launch_bounds__(64 * MAXW) __attribute__((amdgpu_waves_per_eu(LDPC_LDSP_WAVES_PER_EU)))
+void layered_ldsp_kernel(const LdspArgs a, const C... c)
+{
+    static_assert(sizeof...(C) == (CORR ? 1 : 0), "the MsCorr, or nothing");
+    const MsCorr corr = ldsp_corr_of(c...);
+    extern __shared__ float lds[];
+    float *P = lds;                                                             /* [lds_cols][z] */
+    const int r = (int)threadIdx.x, LANES = (int)blockDim.x;
+    const int z = a.z;
+    uint32_t *wg_flag = reinterpret_cast<uint32_t *>(lds + (((size_t)a.lds_cols * z + 1) & ~(size_t)1));
+    const bool row = r < z;
+    const size_t ring = (size_t)blockIdx.x * ((size_t)a.layers * z) + r;        /* [layer][z], mine: + r */
+    uint4 *recs = a.recs + ring;
+    uint32_t *zfs = a.zf + ring;
+    const ldpc_const_i32 hdr = as_constant(a.hdr), pack = as_constant(a.pack), cslot = as_constant(a.col_slot);
+    for (int64_t frame = blockIdx.x; frame < a.frames; frame += gridDim.x) {
+        const float *y = a.llr + (size_t)frame * a.N;
+        if (row) {
+            for (int bc = 0; bc < a.nb; ++bc) {
+                const int slot = cslot[bc];
+                if (slot >= 0) P[slot * z + r] = y[bc * z + r];
+            }
+            /* iteration 0: R = 0 (|ab| = |ac| = 0, signs +); an external column starts from its
+             * channel value.  Written to the ring so that every layer step finds its record there. */
+            for (int l = 0; l < a.layers; ++l) {
+                uint4 rec = uint4{0u, 0u, 0u, 0u};
+                if (hdr[l * 4 + 1]) rec.w = __float_as_uint(y[hdr[l * 4 + 2] + ldsp_wrap(r, hdr[l * 4 + 3], z)]);
+                recs[(size_t)l * z] = rec;
+            }
+        }
+        uint4 cur = uint4{0u, 0u, 0u, 0u};
+        if (row) cur = recs[0];
+        __syncthreads();
+        int time = 0;
+        bool clean = false;
+        /* lane mask of the wave's rows of layer l whose hard decisions have odd parity */
+        auto layer_odd = [&](const int l) {
+            const int dl = hdr[l * 4], ext = hdr[l * 4 + 1];
+            const ldpc_const_i32 pk = pack + (size_t)l * kLdspPackStride;
+            uint64_t par = 0;
+            switch (dl) {
+#define LDPC_LDSP_CASE(D) case D + 1: par = ldsp_row_parity<D + 1>(P, pk, z, r); break;
+                LDPC_LDSP_WIDTHS(LDPC_LDSP_CASE)
+#undef LDPC_LDSP_CASE
+            default: break;
+            }
+            /* hard decision of the layer's external column: its posterior is in my record */
+            if (ext) par ^= __ballot(__uint_as_float(recs[(size_t)l * z].w) < 0.0f);
+            return par;
+        };
+        while (true) {
+            for (int l = 0; l < a.layers; ++l) {
+                /* the next layer step's record (wrapping into the next iteration), requested before
+                 * this step's work; with a single layer it is this step's own output */
+                const int ln = l + 1 < a.layers ? l + 1 : 0;
+                /* by every lane, outside any branch: a conditional request makes the compiler copy the
+                 * registers, and wait for them, where the branch ends -- at once.  Lanes beyond the last row
+                 * read their neighbours' records (the rings end with spare ones). */
+                uint4 nxt = recs[(size_t)ln * z];
+                const int dl = hdr[l * 4], ext = hdr[l * 4 + 1];
+                const ldpc_const_i32 pk = pack + (size_t)l * kLdspPackStride;
+                uint4 rec = uint4{0u, 0u, 0u, 0u};
+                if (row) {
+                    uint32_t par = 0;                               /* (ldsp_row_any's; not used here) */
+                    bool done = false;
+                    if (ext) {
+                        switch (dl) {
+#define LDPC_LDSP_CASE(D) case D: done = ldsp_row<D, 1, true, false, CORR>(P, pk, z, r, cur, &rec, &par, corr); break;
+                            LDPC_LDSP_WIDTHS(LDPC_LDSP_CASE)
+#undef LDPC_LDSP_CASE
+                        default: break;
+                        }
+                    } else {
+                        switch (dl) {
+#define LDPC_LDSP_CASE(D) case D + 1: done = ldsp_row<D + 1, 0, true, false, CORR>(P, pk, z, r, cur, &rec, &par, corr); break;
+                            LDPC_LDSP_WIDTHS(LDPC_LDSP_CASE)
+#undef LDPC_LDSP_CASE
+                        default: break;
+                        }
+                    }
+                    if (!done) rec = ldsp_row_any<CORR>(P, pk, dl, ext, z, r, cur, zfs + (size_t)l * z, &par, corr);
+                }
+                /* the requested record has had this step's work to arrive: take it -- on every path, not
+                 * inside the branch above -- BEFORE the store below is issued, or the wait for it would
+                 * cover the store as well and put a full memory round trip into every layer step */
+                asm volatile("" : "+v"(nxt.x), "+v"(nxt.y), "+v"(nxt.z), "+v"(nxt.w) : : "memory");
+                if (row) recs[(size_t)l * z] = rec;
+                if (a.layers == 1) nxt = rec;
+                lds_barrier();
+                cur = nxt;
+            }
+            /* syndrome of the hard decisions: every round when a clean frame stops early, else only
+             * after the last one (its only use then is the frame's converged flag) */
+            ++time;
+            int any_bad = 1;
+            if (a.early_term || time == a.rounds) {
+                /* the rows of the last layer first (their columns are in the iteration's final state like all
+                 * others, but a frame that has not converged nearly always shows it there already): only
+                 * when all of them are even the other layers are looked at.  The row code does not
+                 * keep parities: one layer's worth of reads here is cheaper than an instruction per edge. */
+                uint64_t bad = row ? layer_odd(a.layers - 1) : 0ull;
+                if (!ldsp_wg_any(wg_flag, r, bad != 0ull)) {
+                    if (row)
+                        for (int l = 0; l + 1 < a.layers; ++l) bad |= layer_odd(l);
+                    any_bad = ldsp_wg_any(wg_flag, r, bad != 0ull) ? 1 : 0;
+                }
+            }
+            clean = !any_bad;
+            if ((clean && a.early_term) || time == a.rounds) break;
+        }
+        /* toChar (decodeCL.c:414-423): the information columns sit in LDS at slot = block column */
+        const int64_t base = frame * (int64_t)a.K / 8;
+        for (int j = r; j < a.K / 8; j += LANES) {
+            unsigned byte = 0;
+#pragma unroll
+            for (int bit = 0; bit < 8; ++bit) byte |= (P[j * 8 + bit] < 0.0f ? 1u : 0u) << bit;
+            if (base + j < a.out_bytes) a.out[base + j] = (uint8_t)byte;
+        }
+        if (a.dump_p && row) ldsp_dump_p(a, P, recs, frame, r);
+        if (a.dump_r && row) ldsp_dump_r(a, recs, zfs, frame, r);
+        if (r == 0) ldsp_report(a, frame, clean ? time : a.max_iter, clean);
+        __syncthreads();                                           /* P is refilled for the next frame */
+    }
 }
 
 
@@ -286,20 +474,134 @@ void layered_ldsp_corr_kernel(const LdspArgs a, const MsCorr corr)
  * wave -- lanes [g z, (g + 1) z) are the rows of frame g -- each with its own posteriors in LDS and
  * its own record ring.  One wave per workgroup, so "barriers" only order the wave's own LDS
  * traffic; a frame whose syndrome is clean goes idle until the wave's last frame is done. */
-template <int kUnused = 0>       /* a template only so that several translation units may include this header */
+template <bool CORR, class... C>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LDPC_LDSP_WAVES_PER_EU)))
-void layered_ldsp_packed_kernel(const LdspArgs a, const int G)
+void layered_ldsp_packed_kernel(const LdspArgs a, const int G, const C... c)
 {
-    constexpr bool CORR = false;
-    const MsCorr corr{1.0f, 0.0f};
-#include "ldsp_layered_packed_kernel.inc"
-}
-template <int kUnused = 0>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LDPC_LDSP_WAVES_PER_EU)))
-void layered_ldsp_packed_corr_kernel(const LdspArgs a, const int G, const MsCorr corr)
-{
-    constexpr bool CORR = true;
-#include "ldsp_layered_packed_kernel.inc"
+    static_assert(sizeof...(C) == (CORR ? 1 : 0), "the MsCorr, or nothing");
+    const MsCorr corr = ldsp_corr_of(c...);
+    extern __shared__ float lds[];
+    const int lane = (int)threadIdx.x;
+    const int z = a.z;
+    const int g = lane / z, r = lane - g * z;
+    const bool member = g < G;                                      /* lane belongs to a frame slot */
+    const size_t frame_floats = ((size_t)a.lds_cols * z + 1) & ~(size_t)1;
+    float *P = lds + (size_t)(member ? g : 0) * frame_floats;       /* [lds_cols][z] of my frame */
+    uint64_t *extneg = reinterpret_cast<uint64_t *>(lds + (size_t)G * frame_floats);   /* [layers] lane masks */
+    const size_t ring = ((size_t)blockIdx.x * G + (member ? g : 0)) * ((size_t)a.layers * z) + r;
+    uint4 *recs = a.recs + ring;
+    uint32_t *zfs = a.zf + ring;
+    const ldpc_const_i32 hdr = as_constant(a.hdr), pack = as_constant(a.pack), cslot = as_constant(a.col_slot);
+    const uint64_t gmask = (z >= 64 ? ~0ull : ((1ull << z) - 1ull)) << (member ? g * z : 0);
+    for (int64_t frame0 = (int64_t)blockIdx.x * G; frame0 < a.frames; frame0 += (int64_t)gridDim.x * G) {
+        const int64_t frame = frame0 + g;
+        const bool mine = member && frame < a.frames;
+        const float *y = a.llr + (size_t)(mine ? frame : 0) * a.N;
+        if (mine) {
+            for (int bc = 0; bc < a.nb; ++bc) {
+                const int slot = cslot[bc];
+                if (slot >= 0) P[slot * z + r] = y[bc * z + r];
+            }
+            for (int l = 0; l < a.layers; ++l) {
+                uint4 rec = uint4{0u, 0u, 0u, 0u};
+                if (hdr[l * 4 + 1]) rec.w = __float_as_uint(y[hdr[l * 4 + 2] + ldsp_wrap(r, hdr[l * 4 + 3], z)]);
+                recs[(size_t)l * z] = rec;
+            }
+        }
+        uint4 cur = uint4{0u, 0u, 0u, 0u};
+        if (mine) cur = recs[0];
+        lds_barrier();
+        int time = 0, my_iters = a.max_iter;
+        bool active = mine, clean = false;
+        while (__ballot(active) != 0ull) {
+            uint32_t last_bad = 0;
+            for (int l = 0; l < a.layers; ++l) {
+                const int ln = l + 1 < a.layers ? l + 1 : 0;
+                uint4 nxt = uint4{0u, 0u, 0u, 0u};
+                if (active && a.layers > 1) nxt = recs[(size_t)ln * z];
+                const int dl = hdr[l * 4], ext = hdr[l * 4 + 1];
+                const ldpc_const_i32 pk = pack + (size_t)l * kLdspPackStride;
+                if (active) {
+                    uint4 rec;
+                    uint32_t par = 0;
+                    bool done = false;
+                    if (ext) {
+                        switch (dl) {
+#define LDPC_LDSP_CASE(D) case D: done = ldsp_row<D, 1, false, true, CORR>(P, pk, z, r, cur, &rec, &par, corr); break;
+                            LDPC_LDSP_WIDTHS(LDPC_LDSP_CASE)
+#undef LDPC_LDSP_CASE
+                        default: break;
+                        }
+                    } else {
+                        switch (dl) {
+#define LDPC_LDSP_CASE(D) case D + 1: done = ldsp_row<D + 1, 0, false, true, CORR>(P, pk, z, r, cur, &rec, &par, corr); break;
+                            LDPC_LDSP_WIDTHS(LDPC_LDSP_CASE)
+#undef LDPC_LDSP_CASE
+                        default: break;
+                        }
+                    }
+                    if (!done) rec = ldsp_row_any<CORR>(P, pk, dl, ext, z, r, cur, zfs + (size_t)l * z, &par, corr);
+                    last_bad = par;
+                    asm volatile("" : "+v"(nxt.x), "+v"(nxt.y), "+v"(nxt.z), "+v"(nxt.w) : : "memory");
+                    recs[(size_t)l * z] = rec;
+                    if (a.layers == 1) nxt = rec;
+                    if (ext) {
+                        const uint64_t neg = __ballot(__uint_as_float(rec.w) < 0.0f);
+                        const uint64_t act = __ballot(true);
+                        if (lane == (int)__builtin_ctzll(act)) extneg[l] = neg;
+                    }
+                }
+                lds_barrier();
+                cur = nxt;
+            }
+            ++time;
+            const bool check = a.early_term || time == a.rounds;
+            const uint64_t last_mask = __ballot(active && last_bad);
+            bool any_bad = true;
+            if (check && __ballot(active && (last_mask & gmask) == 0ull) != 0ull) {
+                /* some frame's last layer is all even: the full syndrome, for the frames that need it */
+                uint64_t bad = 0;
+                const bool need = active && (last_mask & gmask) == 0ull;
+                if (need) {
+                    for (int l = 0; l < a.layers; ++l) {
+                        const int dl = hdr[l * 4], ext = hdr[l * 4 + 1];
+                        const ldpc_const_i32 pk = pack + (size_t)l * kLdspPackStride;
+                        uint64_t par = 0;
+                        switch (dl) {
+#define LDPC_LDSP_CASE(D) case D + 1: par = ldsp_row_parity<D + 1>(P, pk, z, r); break;
+                            LDPC_LDSP_WIDTHS(LDPC_LDSP_CASE)
+#undef LDPC_LDSP_CASE
+                        default: break;
+                        }
+                        if (ext) par ^= extneg[l];
+                        bad |= par;
+                    }
+                    any_bad = (bad & gmask) != 0ull;
+                }
+            }
+            if (active) {
+                clean = check && !any_bad;
+                if ((clean && a.early_term) || time == a.rounds) {
+                    active = false;
+                    my_iters = clean ? time : a.max_iter;
+                }
+            }
+            lds_barrier();
+        }
+        if (mine) {
+            const int64_t base = frame * (int64_t)a.K / 8;
+            for (int j = r; j < a.K / 8; j += z) {
+                unsigned byte = 0;
+#pragma unroll
+                for (int bit = 0; bit < 8; ++bit) byte |= (P[j * 8 + bit] < 0.0f ? 1u : 0u) << bit;
+                if (base + j < a.out_bytes) a.out[base + j] = (uint8_t)byte;
+            }
+            if (a.dump_p) ldsp_dump_p(a, P, recs, frame, r);
+            if (a.dump_r) ldsp_dump_r(a, recs, zfs, frame, r);
+            if (r == 0) ldsp_report(a, frame, my_iters, clean);
+        }
+        lds_barrier();                                             /* P is refilled for the next frames */
+    }
 }
 
 
@@ -388,38 +690,23 @@ __device__ __forceinline__ uint4 ldsp_mscl_row_any(const float *Pold, float *Pne
     for (int k = 0; k < d; ++k) {
         const float rold = __uint_as_float(ldsp_old_message(old, ozf, k, d));
         const float pin = k < dl ? *ldsp_at(const_cast<float *>(Pold), pk[k], pk[kLdspMaxDeg + k], r * 4, z * 4) : pext_old;
-        const float q = pin - rold;
-        prod *= q;
-        const float mag = __builtin_fabsf(q);
-        if (mag <= b) { c = b; b = mag; bind = k; }
-        else if (mag > b && mag <= c) { c = mag; }
+        ldsp_any_step(pin - rold, k, &prod, &b, &c, &bind);
     }
     const float sa = cl_sign(prod);
     const float ab = sa * b, ac = sa * c;
-    const uint32_t mab = __float_as_uint(ab) & 0x7fffffffu, mac = __float_as_uint(ac) & 0x7fffffffu;
     uint32_t signs = 0, zf = 0, pext = 0;
     uint64_t pm = 0;
     for (int k = 0; k < d; ++k) {
         const float rold = __uint_as_float(ldsp_old_message(old, ozf, k, d));   /* P_old is untouched: same q again */
         float *pn_at = k < dl ? ldsp_at(Pnew, pk[k], pk[kLdspMaxDeg + k], r * 4, z * 4) : nullptr;
         const float pin = k < dl ? *ldsp_at(const_cast<float *>(Pold), pk[k], pk[kLdspMaxDeg + k], r * 4, z * 4) : pext_old;
-        const float q = pin - rold;
-        const float rn = cl_sign(q) * ((k == bind) ? ac : ab);
-        const float pn = (k < dl ? *pn_at : yext) + rn;
+        const float pn = (k < dl ? *pn_at : yext) + ldsp_any_message(pin - rold, k, bind, ab, ac, &signs, &zf);
         if (k < dl) *pn_at = pn;
         else { pext = __float_as_uint(pn); *ext_mask = __ballot(pn < 0.0f); }
-        const uint32_t rb = __float_as_uint(rn);
-        signs = (signs << 1) | (rb >> 31);
-        if ((rb & 0x7fffffffu) != ((k == bind) ? mac : mab)) zf |= 1u << k;
         pm ^= __ballot(pn < 0.0f);
     }
-    uint32_t word = signs | ((uint32_t)bind << 24);
-    if (zf) {
-        word |= kLdspIrregular;
-        *zfp = zf;
-    }
     *par_mask = pm;
-    return uint4{mab, mac, word, pext};
+    return ldsp_any_record(ab, ac, signs, bind, zf, zfp, pext);
 }
 
 template <int DL, int EXT>
@@ -504,41 +791,233 @@ __device__ __forceinline__ uint64_t ldsp_flood_parity(const float *P, ldpc_const
 #define LDPC_LDSP_WIDTHS1(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) \
     X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24)
 
-template <int MAXW, bool CHAIN>
+/* CORR needs CHAIN: the records hold the MS chain's corrected magnitudes; the reference's fused arithmetic takes no
+ * correction (ldsp_select_kernel has no such instantiation) */
+template <int MAXW, bool CHAIN, bool CORR, class... C>
 __global__ __launch_bounds__(64 * MAXW) __attribute__((amdgpu_waves_per_eu(LDPC_LDSP_WAVES_PER_EU)))
-void flood_ldsp_kernel(const LdspArgs a)
+void flood_ldsp_kernel(const LdspArgs a, const C... c)
 {
-    constexpr bool CORR = false;
-    const MsCorr corr{1.0f, 0.0f};
-#include "ldsp_flood_kernel.inc"
-}
-/* normalized / offset min-sum on the MS chain: the records hold the corrected magnitudes */
-template <int MAXW>
-__global__ __launch_bounds__(64 * MAXW) __attribute__((amdgpu_waves_per_eu(LDPC_LDSP_WAVES_PER_EU)))
-void flood_ldsp_corr_kernel(const LdspArgs a, const MsCorr corr)
-{
-    constexpr bool CHAIN = true;
-    constexpr bool CORR = true;
-#include "ldsp_flood_kernel.inc"
+    static_assert(sizeof...(C) == (CORR ? 1 : 0), "the MsCorr, or nothing");
+    const MsCorr corr = ldsp_corr_of(c...);
+    extern __shared__ float lds[];
+    const int r = (int)threadIdx.x, LANES = (int)blockDim.x, MW = LANES >> 6, wave = r >> 6;
+    const int z = a.z;
+    const size_t image = ((size_t)a.lds_cols * z + 1) & ~(size_t)1;
+    float *Pa = lds, *Pb = lds + image;                             /* old / new posteriors, [lds_cols][z] each */
+    uint64_t *extneg = reinterpret_cast<uint64_t *>(lds + 2 * image);   /* [layers][MW] */
+    uint32_t *wg_flag = reinterpret_cast<uint32_t *>(extneg + (size_t)a.layers * MW);
+    const bool row = r < z;
+    uint4 *recs = a.recs + (size_t)blockIdx.x * ((size_t)a.layers * z) + r;
+    uint32_t *zfs = a.zf + (size_t)blockIdx.x * ((size_t)a.layers * z) + r;
+    const ldpc_const_i32 hdr = as_constant(a.hdr), pack = as_constant(a.pack), cslot = as_constant(a.col_slot);
+    auto fill = [&](float *P, const float *y) {                    /* the LDS-resident columns' channel values */
+        if (row)
+            for (int bc = 0; bc < a.nb; ++bc) {
+                const int slot = cslot[bc];
+                if (slot >= 0) P[slot * z + r] = y[bc * z + r];
+            }
+    };
+    for (int64_t frame = blockIdx.x; frame < a.frames; frame += gridDim.x) {
+        const float *y = a.llr + (size_t)frame * a.N;
+        fill(Pa, y);                                               /* Q_0 = y: P_0 = y, R_0 = 0 */
+        int time = 0;
+        bool clean = false;
+        uint4 cur = uint4{0u, 0u, 0u, 0u};
+        while (true) {
+            fill(Pb, y);                                           /* refreshPostPMS starts from the channel value */
+            __syncthreads();
+            uint64_t last_bad = 0;
+            for (int l = 0; l < a.layers; ++l) {
+                const int ln = l + 1 < a.layers ? l + 1 : 0;
+                uint4 nxt = uint4{0u, 0u, 0u, 0u};
+                if (row && a.layers > 1 && (time > 0 || ln == 0)) nxt = recs[(size_t)ln * z];
+                const int dl = hdr[l * 4], ext = hdr[l * 4 + 1];
+                const ldpc_const_i32 pk = pack + (size_t)l * kLdspPackStride;
+                if (row) {
+                    float yext = 0.0f;
+                    if (ext) yext = y[hdr[l * 4 + 2] + ldsp_wrap(r, hdr[l * 4 + 3], z)];
+                    const float pext_old = time == 0 ? yext : __uint_as_float(cur.w);
+                    uint4 rec = cur;
+                    uint64_t pm = 0, em = 0;
+                    bool done = CHAIN;                             /* the chain arithmetic has no slow path */
+                    if (ext) {
+                        switch (dl) {
+#define LDPC_LDSP_CASE(D) case D:                                                                                  \
+                            if (CHAIN) ldsp_flood_row<D, 1, CORR>(Pa, Pb, pk, z, r, cur, pext_old, yext, &rec, &pm, &em, corr);        \
+                            else done = ldsp_mscl_row<D, 1>(Pa, Pb, pk, z, r, cur, pext_old, yext, &rec, &pm, &em);         \
+                            break;
+                            LDPC_LDSP_WIDTHS(LDPC_LDSP_CASE)
+#undef LDPC_LDSP_CASE
+                        default: break;
+                        }
+                    } else {
+                        switch (dl) {
+#define LDPC_LDSP_CASE(D) case D + 1:                                                                              \
+                            if (CHAIN) ldsp_flood_row<D + 1, 0, CORR>(Pa, Pb, pk, z, r, cur, 0.0f, 0.0f, &rec, &pm, &em, corr);        \
+                            else done = ldsp_mscl_row<D + 1, 0>(Pa, Pb, pk, z, r, cur, 0.0f, 0.0f, &rec, &pm, &em);         \
+                            break;
+                            LDPC_LDSP_WIDTHS(LDPC_LDSP_CASE)
+#undef LDPC_LDSP_CASE
+                        default: break;
+                        }
+                    }
+                    if (!CHAIN && !done)
+                        rec = ldsp_mscl_row_any(Pa, Pb, pk, dl, ext, z, r, cur, pext_old, yext, zfs + (size_t)l * z, &pm, &em);
+                    if (ext && (r & 63) == 0) extneg[l * MW + wave] = em;
+                    last_bad = pm;
+                    asm volatile("" : "+v"(nxt.x), "+v"(nxt.y), "+v"(nxt.z), "+v"(nxt.w) : : "memory");
+                    recs[(size_t)l * z] = rec;
+                    if (a.layers == 1) nxt = rec;
+                }
+                lds_barrier();
+                cur = nxt;
+            }
+            ++time;
+            int any_bad = 1;
+            /* the last layer's rows have just written the final posteriors of their columns */
+            if ((a.early_term || time == a.rounds) && !ldsp_wg_any(wg_flag, r, row && last_bad != 0ull)) {
+                uint64_t bad = 0;
+                if (row) {
+                    for (int l = 0; l < a.layers; ++l) {
+                        const ldpc_const_i32 pk = pack + (size_t)l * kLdspPackStride;
+                        uint64_t par = 0;
+                        switch (hdr[l * 4]) {
+#define LDPC_LDSP_CASE(D) case D: par = ldsp_flood_parity<D, CHAIN>(Pb, pk, z, r); break;
+                            LDPC_LDSP_WIDTHS1(LDPC_LDSP_CASE)
+#undef LDPC_LDSP_CASE
+                        default: break;
+                        }
+                        if (hdr[l * 4 + 1]) par ^= extneg[l * MW + wave];
+                        bad |= par;
+                    }
+                }
+                any_bad = ldsp_wg_any(wg_flag, r, bad != 0ull) ? 1 : 0;
+            }
+            clean = !any_bad;
+            float *t = Pa; Pa = Pb; Pb = t;                         /* the new posteriors are the next round's old ones */
+            if ((clean && a.early_term) || time == a.rounds) break;
+        }
+        /* Pa holds the final posteriors; the information columns sit at slot = block column */
+        const int64_t base = frame * (int64_t)a.K / 8;
+        for (int j = r; j < a.K / 8; j += LANES) {
+            unsigned byte = 0;
+#pragma unroll
+            for (int bit = 0; bit < 8; ++bit) byte |= (ldsp_flood_bit<CHAIN>(Pa[j * 8 + bit]) ? 1u : 0u) << bit;
+            if (base + j < a.out_bytes) a.out[base + j] = (uint8_t)byte;
+        }
+        if (a.dump_p && row) ldsp_dump_p(a, Pa, recs, frame, r);
+        if (a.dump_r && row) ldsp_dump_r(a, recs, zfs, frame, r);
+        if (r == 0) ldsp_report(a, frame, clean ? time : a.max_iter, clean);
+        __syncthreads();
+    }
 }
 
 /* flood_ldsp_kernel for circulants of <= 32 rows: G = 64 / z frames per wave, one wave per
  * workgroup (see layered_ldsp_packed_kernel). */
-template <bool CHAIN>
+template <bool CHAIN, bool CORR, class... C>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LDPC_LDSP_WAVES_PER_EU)))
-void flood_ldsp_packed_kernel(const LdspArgs a, const int G)
+void flood_ldsp_packed_kernel(const LdspArgs a, const int G, const C... c)
 {
-    constexpr bool CORR = false;
-    const MsCorr corr{1.0f, 0.0f};
-#include "ldsp_flood_packed_kernel.inc"
-}
-template <int kUnused = 0>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LDPC_LDSP_WAVES_PER_EU)))
-void flood_ldsp_packed_corr_kernel(const LdspArgs a, const int G, const MsCorr corr)
-{
-    constexpr bool CHAIN = true;
-    constexpr bool CORR = true;
-#include "ldsp_flood_packed_kernel.inc"
+    static_assert(sizeof...(C) == (CORR ? 1 : 0), "the MsCorr, or nothing");
+    const MsCorr corr = ldsp_corr_of(c...);
+    extern __shared__ float lds[];
+    const int lane = (int)threadIdx.x;
+    const int z = a.z;
+    const int g = lane / z, r = lane - g * z;
+    const bool member = g < G;
+    const size_t image = ((size_t)a.N + 1) & ~(size_t)1;
+    float *Pa = lds + (size_t)(member ? g : 0) * 2 * image, *Pb = Pa + image;
+    uint4 *recs = a.recs + ((size_t)blockIdx.x * G + (member ? g : 0)) * ((size_t)a.layers * z) + r;
+    uint32_t *zfs = a.zf + ((size_t)blockIdx.x * G + (member ? g : 0)) * ((size_t)a.layers * z) + r;
+    const ldpc_const_i32 hdr = as_constant(a.hdr), pack = as_constant(a.pack);
+    const uint64_t gmask = (z >= 64 ? ~0ull : ((1ull << z) - 1ull)) << (member ? g * z : 0);
+    for (int64_t frame0 = (int64_t)blockIdx.x * G; frame0 < a.frames; frame0 += (int64_t)gridDim.x * G) {
+        const int64_t frame = frame0 + g;
+        const bool mine = member && frame < a.frames;
+        const float *y = a.llr + (size_t)(mine ? frame : 0) * a.N;
+        if (mine)
+            for (int n = r; n < a.N; n += z) Pa[n] = y[n];
+        int time = 0, my_iters = a.max_iter;
+        bool active = mine, clean = false;
+        uint4 cur = uint4{0u, 0u, 0u, 0u};
+        while (__ballot(active) != 0ull) {
+            if (active)
+                for (int n = r; n < a.N; n += z) Pb[n] = y[n];
+            lds_barrier();
+            uint64_t last_bad = 0;
+            for (int l = 0; l < a.layers; ++l) {
+                const int ln = l + 1 < a.layers ? l + 1 : 0;
+                uint4 nxt = uint4{0u, 0u, 0u, 0u};
+                if (active && a.layers > 1 && (time > 0 || ln == 0)) nxt = recs[(size_t)ln * z];
+                const int d = hdr[l * 4];
+                const ldpc_const_i32 pk = pack + (size_t)l * kLdspPackStride;
+                if (active) {
+                    uint4 rec = cur;
+                    uint64_t pm = 0, em = 0;
+                    bool done = CHAIN;
+                    switch (d) {
+#define LDPC_LDSP_CASE(D) case D:                                                                                  \
+                        if (CHAIN) ldsp_flood_row<D, 0, CORR>(Pa, Pb, pk, z, r, cur, 0.0f, 0.0f, &rec, &pm, &em, corr);                \
+                        else done = ldsp_mscl_row<D, 0>(Pa, Pb, pk, z, r, cur, 0.0f, 0.0f, &rec, &pm, &em);                 \
+                        break;
+                        LDPC_LDSP_WIDTHS1(LDPC_LDSP_CASE)
+#undef LDPC_LDSP_CASE
+                    default: break;
+                    }
+                    if (!CHAIN && !done)
+                        rec = ldsp_mscl_row_any(Pa, Pb, pk, d, 0, z, r, cur, 0.0f, 0.0f, zfs + (size_t)l * z, &pm, &em);
+                    last_bad = pm;
+                    asm volatile("" : "+v"(nxt.x), "+v"(nxt.y), "+v"(nxt.z), "+v"(nxt.w) : : "memory");
+                    recs[(size_t)l * z] = rec;
+                    if (a.layers == 1) nxt = rec;
+                }
+                lds_barrier();
+                cur = nxt;
+            }
+            ++time;
+            const bool check = a.early_term || time == a.rounds;
+            bool any_bad = true;
+            const bool need = active && check && (last_bad & gmask) == 0ull;
+            if (__ballot(need) != 0ull) {
+                uint64_t bad = 0;
+                if (need) {
+                    for (int l = 0; l < a.layers; ++l) {
+                        const ldpc_const_i32 pk = pack + (size_t)l * kLdspPackStride;
+                        switch (hdr[l * 4]) {
+#define LDPC_LDSP_CASE(D) case D: bad |= ldsp_flood_parity<D, CHAIN>(Pb, pk, z, r); break;
+                            LDPC_LDSP_WIDTHS1(LDPC_LDSP_CASE)
+#undef LDPC_LDSP_CASE
+                        default: break;
+                        }
+                    }
+                    any_bad = (bad & gmask) != 0ull;
+                }
+            }
+            if (active) {
+                clean = check && !any_bad;
+                float *t = Pa; Pa = Pb; Pb = t;
+                if ((clean && a.early_term) || time == a.rounds) {
+                    active = false;
+                    my_iters = clean ? time : a.max_iter;
+                }
+            }
+            lds_barrier();
+        }
+        if (mine) {
+            const int64_t base = frame * (int64_t)a.K / 8;
+            for (int j = r; j < a.K / 8; j += z) {
+                unsigned byte = 0;
+#pragma unroll
+                for (int bit = 0; bit < 8; ++bit) byte |= (ldsp_flood_bit<CHAIN>(Pa[j * 8 + bit]) ? 1u : 0u) << bit;
+                if (base + j < a.out_bytes) a.out[base + j] = (uint8_t)byte;
+            }
+            if (a.dump_p)
+                for (int n = r; n < a.N; n += z) a.dump_p[(size_t)frame * a.N + n] = Pa[n];
+            if (a.dump_r) ldsp_dump_r(a, recs, zfs, frame, r);
+            if (r == 0) ldsp_report(a, frame, my_iters, clean);
+        }
+        lds_barrier();
+    }
 }
 
 /* ---------------------------------------------------------------- host side */
@@ -554,31 +1033,40 @@ struct LdspPlan {
     int flood = 0;                      /* 0 layered kernels; flood_ldsp_kernel with 1: the MS chain's arithmetic (DecodeMS /
                                            DecodeCPU), 2: the fused reference kernel's (DecodeMSCL) */
     int32_t grid = 0, block = 0, maxw = 0, per_cu = 0, wg_frames = 1;   /* wg_frames: frames per one-wave workgroup (z <= 32) */
-    int corr = 0;                       /* 1: normalized / offset min-sum (the *_corr_kernel forms, flood 0 or 1) with mc; set
+    int corr = 0;                       /* 1: normalized / offset min-sum (the CORR instantiations, flood 0 or 1) with mc; set
                                            before ldsp_plan_create */
     MsCorr mc{1.0f, 0.0f};
     size_t lds_bytes = 0;
+    const void *kernel = nullptr;       /* ldsp_select_kernel's choice: the function whose dynamic-LDS limit was raised,
+                                           whose occupancy sized the grid and which ldsp_run launches */
 };
 
 /* the plan builder and the launcher reference every kernel above: compiled by engine_ldsp.hip only
  * (LDPC_ENGINE_LDSP); the host driver calls engine_ldsp_plan_create / engine_ldsp_run */
 #ifdef LDPC_ENGINE_LDSP
-typedef void (*LdspKernel)(const LdspArgs);
-inline LdspKernel ldsp_kernel_for(int maxw) { return maxw <= 8 ? layered_ldsp_kernel<8> : layered_ldsp_kernel<16>; }
-typedef void (*LdspCorrKernel)(const LdspArgs, const MsCorr);
-inline LdspCorrKernel ldsp_corr_kernel_for(int maxw) { return maxw <= 8 ? layered_ldsp_corr_kernel<8> : layered_ldsp_corr_kernel<16>; }
-inline LdspCorrKernel flood_ldsp_corr_kernel_for(int maxw) { return maxw <= 8 ? flood_ldsp_corr_kernel<8> : flood_ldsp_corr_kernel<16>; }
+/* The one place that names the instantiations: the arithmetic (LdspPlan::flood, corr) and the launch form (packed:
+ * several frames per one-wave workgroup; else workgroups of up to 8 or up to 16 waves) to the kernel.  Unpacked kernels
+ * take (LdspArgs[, MsCorr]), packed ones (LdspArgs, int G[, MsCorr]): leading parts of the list that ldsp_run passes.
+ * nullptr: the reference's fused flooding arithmetic (flood = 2) takes no correction. */
+inline const void *ldsp_select_kernel(int flood, bool corr, bool packed, int maxw)
+{
+    const void *p = nullptr, *u = nullptr;
+    const bool w8 = maxw <= 8;
+#define LDPC_LDSP_FORMS(PACKED, UNPACKED, ...)                                                                          \
+    (p = (const void *)PACKED<__VA_ARGS__>, u = w8 ? (const void *)UNPACKED<8, __VA_ARGS__> : (const void *)UNPACKED<16, __VA_ARGS__>)
+    if (flood == 0 && !corr) LDPC_LDSP_FORMS(layered_ldsp_packed_kernel, layered_ldsp_kernel, false);
+    else if (flood == 0) LDPC_LDSP_FORMS(layered_ldsp_packed_kernel, layered_ldsp_kernel, true, MsCorr);
+    else if (flood == 1 && !corr) LDPC_LDSP_FORMS(flood_ldsp_packed_kernel, flood_ldsp_kernel, true, false);
+    else if (flood == 1) LDPC_LDSP_FORMS(flood_ldsp_packed_kernel, flood_ldsp_kernel, true, true, MsCorr);
+    else if (!corr) LDPC_LDSP_FORMS(flood_ldsp_packed_kernel, flood_ldsp_kernel, false, false);
+#undef LDPC_LDSP_FORMS
+    return packed ? p : u;
+}
 
 /* Detect the QC structure, decide which block columns travel with a record (met by one layer
  * only, last entry of that layer's rows, not an information column), lay the others out in LDS,
  * size the persistent grid and allocate its record rings.  eligible = false (and hipSuccess)
  * when the code does not fit this kernel. */
-inline LdspKernel flood_ldsp_kernel_for(int maxw, int kind)
-{
-    if (kind == 1) return maxw <= 8 ? flood_ldsp_kernel<8, true> : flood_ldsp_kernel<16, true>;
-    return maxw <= 8 ? flood_ldsp_kernel<8, false> : flood_ldsp_kernel<16, false>;
-}
-
 inline hipError_t ldsp_plan_create(LdspPlan *pl, int32_t M, int32_t N, int64_t E, const std::vector<int32_t> &row_ptr,
                                    const std::vector<int32_t> &cols, int32_t z, int32_t K, int64_t max_batch, int device,
                                    const Tune &tune, int flood = 0)
@@ -639,14 +1127,8 @@ inline hipError_t ldsp_plan_create(LdspPlan *pl, int32_t M, int32_t N, int64_t E
     hipError_t e;
     if ((e = pl->hdr.upload(hdr)) || (e = pl->pack.upload(pack)) || (e = pl->col_slot.upload(slot)) || (e = pl->layer_e0.upload(e0)))
         return e;
-    const void *k = flood ? (pl->wg_frames > 1 ? (flood == 1 ? (const void *)flood_ldsp_packed_kernel<true> : (const void *)flood_ldsp_packed_kernel<false>)
-                                               : (const void *)flood_ldsp_kernel_for(mw <= 8 ? 8 : 16, flood))
-                    : pl->wg_frames > 1 ? (const void *)layered_ldsp_packed_kernel<0> : (const void *)ldsp_kernel_for(mw <= 8 ? 8 : 16);
-    if (pl->corr) {
-        if (flood == 2) return hipErrorInvalidValue;                /* the reference's fused arithmetic takes no correction */
-        k = flood ? (pl->wg_frames > 1 ? (const void *)flood_ldsp_packed_corr_kernel<0> : (const void *)flood_ldsp_corr_kernel_for(mw <= 8 ? 8 : 16))
-                  : pl->wg_frames > 1 ? (const void *)layered_ldsp_packed_corr_kernel<0> : (const void *)ldsp_corr_kernel_for(mw <= 8 ? 8 : 16);
-    }
+    const void *k = pl->kernel = ldsp_select_kernel(flood, pl->corr != 0, pl->wg_frames > 1, pl->maxw);
+    if (!k) return hipErrorInvalidValue;
     /* the attribute belongs to the function, not to this plan: always the maximum, so that decoders
      * of different codes can coexist */
     if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdspMaxLds))) return e;
@@ -689,15 +1171,11 @@ inline hipError_t ldsp_run(LdspPlan *pl, const FusedRun &r, hipStream_t s, int32
                r.max_iter, rounds, r.early_term};
     const unsigned grid = (unsigned)std::min<int64_t>((r.frames + pl->wg_frames - 1) / pl->wg_frames, pl->grid);
     if (!pl->eligible || grid == 0) return hipErrorInvalidValue;
-    if (pl->corr && pl->flood == 1 && pl->wg_frames > 1) flood_ldsp_packed_corr_kernel<0><<<grid, 64, pl->lds_bytes, s>>>(a, pl->wg_frames, pl->mc);
-    else if (pl->corr && pl->flood == 1) flood_ldsp_corr_kernel_for(pl->maxw)<<<grid, pl->block, pl->lds_bytes, s>>>(a, pl->mc);
-    else if (pl->corr && pl->wg_frames > 1) layered_ldsp_packed_corr_kernel<0><<<grid, 64, pl->lds_bytes, s>>>(a, pl->wg_frames, pl->mc);
-    else if (pl->corr) ldsp_corr_kernel_for(pl->maxw)<<<grid, pl->block, pl->lds_bytes, s>>>(a, pl->mc);
-    else if (pl->flood == 1 && pl->wg_frames > 1) flood_ldsp_packed_kernel<true><<<grid, 64, pl->lds_bytes, s>>>(a, pl->wg_frames);
-    else if (pl->flood && pl->wg_frames > 1) flood_ldsp_packed_kernel<false><<<grid, 64, pl->lds_bytes, s>>>(a, pl->wg_frames);
-    else if (pl->flood) flood_ldsp_kernel_for(pl->maxw, pl->flood)<<<grid, pl->block, pl->lds_bytes, s>>>(a);
-    else if (pl->wg_frames > 1) layered_ldsp_packed_kernel<0><<<grid, 64, pl->lds_bytes, s>>>(a, pl->wg_frames);
-    else ldsp_kernel_for(pl->maxw)<<<grid, pl->block, pl->lds_bytes, s>>>(a);
+    /* (a[, corr]), packed: (a, G[, corr]) -- see ldsp_select_kernel; a plain kernel takes the list without its end */
+    int G = pl->wg_frames;
+    void *args[3] = {&a, &G, &pl->mc};
+    if (pl->wg_frames <= 1) args[1] = &pl->mc;
+    if ((e = hipLaunchKernel(pl->kernel, dim3(grid), dim3((unsigned)pl->block), args, pl->lds_bytes, s))) return e;
     *launched = rounds;
     if ((e = hipGetLastError())) return e;
     return fused_soft_finish(r, pl->N, s);

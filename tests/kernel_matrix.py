@@ -5,7 +5,7 @@ put rows and columns of every degree class the streaming flooding kernels distin
 unrolled body, bucket launch and generic kernel runs against the oracle."""
 import numpy as np
 
-from myldpccppapi_amd import capi, codes
+from myldpccppapi_amd import capi, channel, codes
 
 
 def irregular_code(row_degs, col_degs, seed):
@@ -167,3 +167,49 @@ FLOOD_PLANS = {
 
 def all_tune_keys():
     return set(capi.TUNE_FIELDS) | set(capi.TUNE_INTS)
+
+
+# ---- shared by test_gpu_kernel_matrix.py and test_gpu_ms_correction.py
+
+def channel_frames(N, frames, lo, hi, seed):
+    """All-zero codeword over AWGN, the noise level of each frame drawn from [lo, hi] (frames stop at every
+    iteration from 1 to max_iter)."""
+    y = channel.awgn_frames(N, 0, frames, 1.0, seed=seed)
+    sd = np.random.default_rng(seed).uniform(lo, hi, frames).astype(np.float32)[:, None]
+    return (np.float32(1) + (y - np.float32(1)) * sd).astype(np.float32)
+
+
+def qc_base(z, mb, info_w, nb_info, seed, empty_col=None):
+    """mb layers: layer l has info_w[l] information block columns and parity block column nb_info + l (a diagonal:
+    the last entry of each layer, met by that layer only).  Every information block column is used at least once
+    (except `empty_col`, used by none)."""
+    rng = np.random.default_rng(seed)
+    nb = nb_info + mb
+    base = -np.ones((mb, nb), np.int64)
+    cand = [j for j in range(nb_info) if j != empty_col]
+    for l in range(mb):
+        base[l, rng.choice(cand, info_w[l], replace=False)] = rng.integers(0, z, info_w[l])
+        base[l, nb_info + l] = rng.integers(0, z)
+    for j in cand:
+        if (base[:nb_info, j] < 0).all():
+            l = int(np.argmin((base >= 0).sum(axis=1)))
+            base[l, j] = rng.integers(0, z)
+    return base
+
+
+# name: (z, base, expected one-launch eligibility: fused (LDS-resident), fused sum-product, record kernel)
+QC_SHAPES = {
+    "z24": (24, qc_base(24, 4, [5, 6, 7, 4], 10, seed=1), dict(fused=True, sp=True, ldsp=True)),
+    "z200_4waves": (200, qc_base(200, 4, [3, 4, 3, 2], 5, seed=2), dict(fused=True, sp=True, ldsp=True)),
+    "z600_maxw16": (600, qc_base(600, 3, [3, 2, 3], 5, seed=3), dict(fused=False, sp=False, ldsp=True)),
+    "row28": (16, qc_base(16, 3, [27, 5, 9], 27, seed=4), dict(fused=True, sp=False, ldsp=False)),
+    "empty_block_col": (32, qc_base(32, 4, [4, 5, 4, 5], 9, seed=5, empty_col=4), None),
+}
+
+
+def ldsp_shape(name):
+    """flood_ldsp_kernel[G x B, F] -> (G, B, F)"""
+    inner = name[name.index("[") + 1:name.index("]")]
+    gb, f = inner.split(",")
+    g, b = gb.split("x")
+    return int(g), int(b), int(f)

@@ -19,14 +19,6 @@ f32 = np.float32
 MAXIT = 20
 
 
-def _channel(N, frames, lo, hi, seed):
-    """All-zero codeword over AWGN, the noise level of each frame drawn from [lo, hi] (frames stop at every
-    iteration from 1 to MAXIT)."""
-    y = channel.awgn_frames(N, 0, frames, 1.0, seed=seed)
-    sd = np.random.default_rng(seed).uniform(lo, hi, frames).astype(f32)[:, None]
-    return (f32(1) + (y - f32(1)) * sd).astype(f32)
-
-
 def _frame_bytes(out, K, frames):
     return np.asarray(out).reshape(frames, K // 8)
 
@@ -39,7 +31,7 @@ def mcode():
     K = (N - M) // 8 * 8
     g = L.Graph(rows, cols, M, N)
     og = oracle.Graph(rows, cols, M, N, K)
-    y = _channel(N, 4 * 64 * 4 + 5, 0.15, 0.8, seed=20261016)
+    y = km.channel_frames(N, 4 * 64 * 4 + 5, 0.15, 0.8, seed=20261016)
     want = {}
     for algo in ("sp", "ms", "ms16"):
         want[algo] = oracle.decode(og, y, "ms" if algo == "ms16" else algo, max_iter=MAXIT, tap_iter=2,
@@ -166,7 +158,7 @@ def ira_codes():
             rows, cols, M, N, K = km.ira_code(d, 400, extra, seed=d)
             K8 = K // 8 * 8
             og = oracle.Graph(rows, cols, M, N, K8)
-            y = _channel(N, 133, 0.5, 0.9, seed=100 + d)
+            y = km.channel_frames(N, 133, 0.5, 0.9, seed=100 + d)
             out[d, kind] = dict(g=L.Graph(rows, cols, M, N), K=K8, y=y,
                                 want=oracle.decode(og, y, "ms", max_iter=25, tap_iter=2),
                                 want_sp=oracle.decode(og, y, "sp", max_iter=25) if kind == "ride" else None)
@@ -244,45 +236,17 @@ def test_column_fused_forms(built, ira_codes, d):
 
 # --------------------------------------------------------------------------- one-launch kernels on QC shapes
 
-def _qc_base(z, mb, info_w, nb_info, seed, empty_col=None):
-    """mb layers: layer l has info_w[l] information block columns and parity block column nb_info + l (a diagonal:
-    the last entry of each layer, met by that layer only).  Every information block column is used at least once
-    (except `empty_col`, used by none)."""
-    rng = np.random.default_rng(seed)
-    nb = nb_info + mb
-    base = -np.ones((mb, nb), np.int64)
-    cand = [j for j in range(nb_info) if j != empty_col]
-    for l in range(mb):
-        base[l, rng.choice(cand, info_w[l], replace=False)] = rng.integers(0, z, info_w[l])
-        base[l, nb_info + l] = rng.integers(0, z)
-    for j in cand:
-        if (base[:nb_info, j] < 0).all():
-            l = int(np.argmin((base >= 0).sum(axis=1)))
-            base[l, j] = rng.integers(0, z)
-    return base
-
-
-# name: (z, base, expected one-launch eligibility: fused (LDS-resident), fused sum-product, record kernel)
-QC_SHAPES = {
-    "z24": (24, _qc_base(24, 4, [5, 6, 7, 4], 10, seed=1), dict(fused=True, sp=True, ldsp=True)),
-    "z200_4waves": (200, _qc_base(200, 4, [3, 4, 3, 2], 5, seed=2), dict(fused=True, sp=True, ldsp=True)),
-    "z600_maxw16": (600, _qc_base(600, 3, [3, 2, 3], 5, seed=3), dict(fused=False, sp=False, ldsp=True)),
-    "row28": (16, _qc_base(16, 3, [27, 5, 9], 27, seed=4), dict(fused=True, sp=False, ldsp=False)),
-    "empty_block_col": (32, _qc_base(32, 4, [4, 5, 4, 5], 9, seed=5, empty_col=4), None),
-}
-
-
 @pytest.fixture(scope="module")
 def qc_cases():
     out = {}
-    for name, (z, base, elig) in QC_SHAPES.items():
+    for name, (z, base, elig) in km.QC_SHAPES.items():
         mb, nb = base.shape
         rows, cols = codes.qc_edges(base, z)
         M, N = mb * z, nb * z
         K = (nb - mb) * z // 8 * 8
         og = oracle.Graph(rows, cols, M, N, K)
         B = 12
-        y = _channel(N, B, 0.55, 0.85, seed=z)
+        y = km.channel_frames(N, B, 0.55, 0.85, seed=z)
         y[3, ::3] = 0.0                          # zeros: rows that take the slow path of the record kernel
         want = {a: oracle.decode(og, y, a, layer_rows=z if a == "layered" else 0, max_iter=12, tap_iter=2)
                 for a in ("layered", "ms", "ms_fused", "sp")}
@@ -315,14 +279,6 @@ def _expected_kernel(algo, choice, elig, max_row):
     raise ValueError(algo)
 
 
-def _ldsp_shape(name):
-    """flood_ldsp_kernel[G x B, F] -> (G, B, F)"""
-    inner = name[name.index("[") + 1:name.index("]")]
-    gb, f = inner.split(",")
-    g, b = gb.split("x")
-    return int(g), int(b), int(f)
-
-
 QC_RUNS = [(algo, choice, extra) for algo in ("layered", "ms", "ms_fused", "sp")
            for choice in {"layered": ("1", "ldsp", "0"), "ms": ("1", "ldsp", "0"), "ms_fused": ("1", "ldsp"),
                           "sp": ("1", "0")}[algo]
@@ -334,7 +290,7 @@ QC_RUNS = [(algo, choice, extra) for algo in ("layered", "ms", "ms_fused", "sp")
            if extra is not None]
 
 
-@pytest.mark.parametrize("shape", list(QC_SHAPES))
+@pytest.mark.parametrize("shape", list(km.QC_SHAPES))
 def test_one_launch_kernels_on_qc_shapes(built, qc_cases, shape):
     """layered, ms, ms_fused and sp through the LDS-resident, record and streaming choices (plus run-time row
     loops, 12 record waves, record kernels without external columns or without frame packing, the unpacked
@@ -372,7 +328,7 @@ def test_one_launch_kernels_on_qc_shapes(built, qc_cases, shape):
         assert np.array_equal(iters[ok], want["iters"][ok]), what
         if expect is not None:
             assert any(n.startswith(expect) for n in names), (what, expect, names)
-            ld = [_ldsp_shape(n) for n in names if "ldsp_kernel[" in n]
+            ld = [km.ldsp_shape(n) for n in names if "ldsp_kernel[" in n]
             if ld:
                 grid, block, frames = ld[0]
                 waves = max((z + 63) // 64, extra.get("ldsp_waves", 0))
@@ -396,13 +352,13 @@ def test_record_kernel_grid_and_waves(built, per_cu):
     import torch
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     z = 48
-    base = _qc_base(z, 4, [4, 6, 5, 3], 8, seed=6)
+    base = km.qc_base(z, 4, [4, 6, 5, 3], 8, seed=6)
     rows, cols = codes.qc_edges(base, z)
     M, N = base.shape[0] * z, base.shape[1] * z
     K = (N - M) // 8 * 8
     g, og = L.Graph(rows, cols, M, N), oracle.Graph(rows, cols, M, N, K)
     B = cus + 37
-    y = _channel(N, B, 0.5, 0.85, seed=48)
+    y = km.channel_frames(N, B, 0.5, 0.85, seed=48)
     for algo in ("layered", "ms"):
         want = oracle.decode(og, y, algo, layer_rows=z if algo == "layered" else 0, max_iter=12)
         ok = want["undefined"] == 0 if "undefined" in want else np.ones(B, bool)
@@ -416,6 +372,6 @@ def test_record_kernel_grid_and_waves(built, per_cu):
             assert np.array_equal(out.reshape(B, K // 8)[ok], want["out"].reshape(B, K // 8)[ok]), (algo, per_cu, waves)
             assert np.array_equal(iters[ok], want["iters"][ok]), (algo, per_cu, waves)
             assert len(names) == 1, names
-            grid, block, frames = _ldsp_shape(names[0])
+            grid, block, frames = km.ldsp_shape(names[0])
             assert (grid, block, frames) == (min(B, per_cu * cus), 64 * max(1, waves), 1), (algo, per_cu, waves, names)
             dec.close()

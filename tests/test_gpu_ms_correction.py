@@ -13,6 +13,7 @@ from myldpccppapi_amd import channel, codes
 from ms_correction_ref import Code, flood_ms, layered_ms
 from coder_harness import coder_ms_correction_exe
 from util import kernel_choice
+import kernel_matrix as km
 
 pytestmark = pytest.mark.gpu
 
@@ -201,6 +202,61 @@ def test_layered_corrected_bg1_profile(built):
     K = 22 * Z
     y = channel.awgn_frames(N, 0, 6, 0.7, seed=5)
     _layered_case(rows, cols, M, N, K, Z, y, 0.75, 0.0, it=8)
+
+
+# name: (km.QC_SHAPES entry, extra tuning, frames per workgroup); the workgroup is
+# ceil(z / 64) waves: z = 600 has 10, which only the 16-wave instantiations hold
+RECORD_FORMS = {
+    "z24_packed": ("z24", {}, 2),
+    "z24_unpacked": ("z24", {"ldsp_pack": False}, 1),
+    "z200_4waves": ("z200_4waves", {}, 1),
+    "z600_maxw16": ("z600_maxw16", {}, 1),
+}
+_record_refs = {}
+
+
+def _record_ref(shape, algo, scale, offset):
+    """code, channel values and the numpy reference of one (shape, algorithm, setting): 12 frames, 12 iterations"""
+    key = (shape, algo, scale, offset)
+    if key not in _record_refs:
+        z, base, _ = km.QC_SHAPES[shape]
+        mb, nb = base.shape
+        rows, cols = codes.qc_edges(base, z)
+        M, N = mb * z, nb * z
+        K = (nb - mb) * z // 8 * 8
+        # a noise level per frame: in every case some frames stop after 1 to 5 iterations and some run all 12
+        y = km.channel_frames(N, 12, 0.3, 0.7, seed=z)
+        y[3, ::3] = 0.0                          # zeros: rows that take the slow path of the record kernels
+        code = Code(rows, cols, M, N, K)
+        ref = (layered_ms(code, y, z, 12, scale=scale, offset=offset) if algo == "layered"
+               else flood_ms(code, y, 12, scale=scale, offset=offset))
+        _record_refs[key] = (rows, cols, M, N, K, z, y, ref)
+    return _record_refs[key]
+
+
+@pytest.mark.parametrize("scale,offset", [(0.75, 0.0), (0.0, 0.25)])
+@pytest.mark.parametrize("form", list(RECORD_FORMS))
+def test_corrected_record_kernels_in_every_launch_form(built, form, scale, offset):
+    """The corrected record kernels in each form the selector can pick -- several frames per wave, one frame per
+    one-wave workgroup, 4 waves, 10 waves (MAXW = 16) -- layered and flooding: bytes, iteration counts, the reported
+    kernel name and launch shape [grid x block, frames per workgroup].  The name comes from the decoder's settings, not
+    from the selector's pointer: which instantiation ran shows in the bytes (the correction) and in the launch itself
+    (640 threads need the 16-wave kernel's launch bound)."""
+    shape, extra, wg_frames = RECORD_FORMS[form]
+    for algo, expect in (("layered", "layered_ldsp_corr_kernel["), ("ms", "flood_ldsp_corr_kernel[")):
+        rows, cols, M, N, K, z, y, ref = _record_ref(shape, algo, scale, offset)
+        B, kb = y.shape[0], K // 8
+        what = (form, algo, scale, offset)
+        ok = ref["undefined"] == 0 if algo == "layered" else np.ones(B, bool)
+        dec = L.Decoder(L.Graph(rows, cols, M, N), K, max_batch=B, algo=algo, layer_rows=z, max_iter=12,
+                        tune=dict(kernel_choice("ldsp"), **extra), ms_scale=scale, ms_offset=offset)
+        out, iters, names = _kernels_run(dec, y)
+        dec.close()
+        assert np.array_equal(out.reshape(B, kb)[ok], ref["out"].reshape(B, kb)[ok]), what
+        assert np.array_equal(iters[ok], ref["iters"][ok]), what
+        assert names and all(n.startswith(expect) or n == "other" for n in names), (what, names)
+        shapes = {km.ldsp_shape(n) for n in names if n != "other"}
+        assert shapes == {((B + wg_frames - 1) // wg_frames, 64 * ((z + 63) // 64), wg_frames)}, (what, names)
 
 
 def test_coder_min_sum_correction_equals_the_c_abi(built, tmp_path):
