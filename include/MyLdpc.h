@@ -101,7 +101,7 @@ public:
 
     /* ---- additions ------------------------------------------------------ */
     void setMaxIterations(int times) { this->times = times; }   /* before addDecodeType */
-    void setLlrScale(float s) { llrScale = s; }                 /* DecodeSP, DecodeBP and DecodeLayeredBP (2 / sd^2 for BPSK in noise sd); before addDecodeType */
+    void setLlrScale(float s) { llrScale = s; }                 /* DecodeSP, DecodeBP and DecodeLayeredBP (2 / sd^2 for BPSK in noise sd); with LDPC_MSG_I8 the LSBs per unit; before addDecodeType */
     void setDevice(int ordinal) { device = ordinal; devices.clear(); }
     /* Several HIP devices behind one Coder (the reference opens devices[0] only, MyLdpc.cpp:235):
      * decode() then cuts the frame stream into one contiguous range per entry and decodes the
@@ -124,8 +124,10 @@ public:
      * LDPC_MSG_F32 (the default, the reference's arithmetic), LDPC_MSG_F16 or LDPC_MSG_F8 (one E4M3 byte per message).
      * DecodeMS and DecodeCPU take all three, DecodeBP takes F32 and F16 (DecodeLayeredBP, like every layered type, F32 only), and give the bytes of the C ABI decoder with that
      * msg_dtype; with any other decode type a type other than LDPC_MSG_F32 makes addDecodeType fail as ldpc_decoder_create does
-     * (LDPC_ERR_UNSUPPORTED; an unknown value: LDPC_ERR_ARG).  Before addDecodeType(). */
-    void setMessageType(int msgDtype) { msgType = msgDtype; }
+     * (LDPC_ERR_UNSUPPORTED; an unknown value: LDPC_ERR_ARG).  LDPC_MSG_I8 (DecodeMS and DecodeCPU only) stores saturating
+     * integers of `bits` = 4, 5, 6 or 8 bits (0 = 8; with any other type bits must be 0); setLlrScale() is then the number
+     * of LSBs per unit of channel value.  Before addDecodeType(). */
+    void setMessageType(int msgDtype, int bits = 0) { msgType = msgDtype; msgBits = bits; }
     /* encode() on the GPU `setDevice` names (ldpc_encode, include/ldpc_hip.h) instead of the host: same bytes.
      * forEncoder() then creates the device encoder and skips the host precompute, so it also serves the seed whose
      * parity part the host solves by dense elimination only (rate_3_4_b: any N, where the host path stops at
@@ -225,6 +227,7 @@ private:
     int hostInput = 0;               /* setHostInput() */
     float msScale = 0.0f, msOffset = 0.0f; /* setMinSumCorrection() */
     int msgType = 0;                 /* setMessageType(): LDPC_MSG_F32 */
+    int msgBits = 0;                 /* setMessageType(): bits per message with LDPC_MSG_I8 */
     int makeDecoder(const ldpc_decoder_config &cfg, ldpc_decoder **out);
     const signed char *hSeed;
     int seedRowLength;

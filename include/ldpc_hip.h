@@ -131,7 +131,7 @@ enum ldpc_algo {
  * work as for LDPC_ALGO_LAYERED. */
 
 /* How the streaming flooding min-sum decoder (LDPC_ALGO_MS) stores its messages; the arithmetic is fp32 in one
- * operation order for all three.  F16 and F8 are this library's own definitions (the reference is fp32 only) and are
+ * operation order for all four.  F16 and F8 are this library's own definitions (the reference is fp32 only) and are
  * LDPC_ERR_UNSUPPORTED with every other algorithm (LDPC_ALGO_LAYERED_BP included: the layered engine is fp32) -- except that LDPC_ALGO_BP takes F16 (not F8); the one-launch and record kernels are fp32 and are never selected
  * for them (F8 with LDPC_TUNE_FUSED / LDPC_TUNE_LDSP forced on: LDPC_ERR_UNSUPPORTED).  An unknown value: LDPC_ERR_ARG.
  *   LDPC_MSG_F16: channel values and variable->check messages are rounded to binary16 (nearest even) where they are
@@ -143,8 +143,31 @@ enum ldpc_algo {
  *     (y8 = s8(y); round 1 reads them as Q), to the variable->check messages where they are stored, and to the
  *     check->variable message where it is PRODUCED, in registers too: corrected, s8(fmaxf(m - ms_offset, 0) * ms_scale);
  *     plain, every |q| is an E4M3 value already and only the start value 1000 is affected, which reads 448.  The
- *     posterior -- hard decision and soft output alike -- is y8 + R_e1 + R_e2 + ... in fp32, ascending edge id. */
-enum ldpc_msg_dtype { LDPC_MSG_F32 = 0, LDPC_MSG_F16 = 1, LDPC_MSG_F8 = 2 };
+ *     posterior -- hard decision and soft output alike -- is y8 + R_e1 + R_e2 + ... in fp32, ascending edge id.
+ *   LDPC_MSG_I8: fixed point, the datapath of a hardware decoder: saturating q-bit integers, q = msg_bits (config field
+ *     below) one of 4, 5, 6, 8; 0 means 8, any other value is LDPC_ERR_ARG, as is a non-zero msg_bits with another
+ *     msg_dtype.  L = 2^(q-1) - 1, that is 7, 15, 31 or 127.  A message is a two's-complement byte holding an integer in
+ *     [-L, L]; the code -128 is never produced; the zero message is the byte 0x00.  LDPC_ALGO_MS only (every other
+ *     algorithm: LDPC_ERR_UNSUPPORTED); the one-launch and record kernels are never selected (forcing them:
+ *     LDPC_ERR_UNSUPPORTED, as for F8).  The kernels compute in fp32, which on integers below 2^24 is exact integer
+ *     arithmetic, so the rule can be restated in integers alone:
+ *       Store rule:  sq(x) = clamp(rintf(x), -L, L): ties go to even, NaN gives 0, +-inf gives +-L.
+ *       Channel:     c[n] = sq(llr_scale * y[n]), one fp32 multiply.  llr_scale is here the number of LSBs per unit of
+ *                    channel value; it must be finite and > 0, else LDPC_ERR_ARG.  With typed input (ldpc_decode_typed),
+ *                    y = (float)x * llr_unit as always, so int8 input with llr_unit = 1 and llr_scale = 1 goes straight
+ *                    through.  Padding frames read y = 1.  Round 1 reads c as Q, as fp8 does.
+ *       Check row, plain:  min-sum on the stored integers; the start value 1000 reads L, so a degree-1 row gives L.
+ *       Check row, corrected (ms_scale / ms_offset): each of the two candidates becomes
+ *                    m' = fminf(truncf(fmaxf(m - ms_offset, 0) * ms_scale), L), in fp32 and in this order, where the value
+ *                    is PRODUCED, in registers too.  With ms_scale = 0.75 this is exactly (3m) >> 2.  ms_offset is in
+ *                    LSBs and need not be an integer.
+ *       Posterior:   P = c + R_e1 + R_e2 + ... in ascending edge id: exact, an accumulator wide enough never to saturate.
+ *       Bits and messages out:  bit = !(P > 0);  Q = sq(P - R) where stored (only the clamp acts).
+ *       Soft output: P, or P - c, in LSBs as fp32.
+ *     Freezing, iters, the CRC rule, both pack modes and the debug taps are LDPC_ALGO_MS's. */
+/* The value 3 is not assigned and stays LDPC_ERR_ARG: callers and tests of the library have used it as their example of
+ * an unknown msg_dtype since LDPC_MSG_F8, and what was refused stays refused. */
+enum ldpc_msg_dtype { LDPC_MSG_F32 = 0, LDPC_MSG_F16 = 1, LDPC_MSG_F8 = 2, LDPC_MSG_I8 = 4 };
 
 /* ldpc_decode() and the caller's input buffer (the reference copies it with a blocking
  * enqueueWriteBuffer, MyLdpc.cpp:796 / :988).
@@ -177,7 +200,8 @@ typedef struct ldpc_decoder_config {
     int32_t msg_dtype;      /* enum ldpc_msg_dtype                                         */
     int32_t max_iter;       /* `times`, MyLdpc.cpp:24 (reference: 40)                      */
     float llr_scale;        /* SP: q = exp(llr_scale*y)..., decodeCL.c:9 (reference: 8); BP: chan = llr_scale * y, the
-                               LLR (> 0 and finite, else LDPC_ERR_ARG); ignored by the min-sum algorithms  */
+                               LLR (> 0 and finite, else LDPC_ERR_ARG); ignored by the min-sum algorithms -- except with
+                               LDPC_MSG_I8: the LSBs per unit of channel value, c = sq(llr_scale * y) (> 0 and finite) */
     int32_t early_term;     /* 1: frames freeze when their syndrome is clean (reference
                                behaviour, decodeCL.c:27,48-49); 0: always run max_iter      */
     int32_t device;         /* HIP device ordinal                                          */
@@ -262,6 +286,13 @@ typedef struct ldpc_decoder_config {
     int32_t crc_kind;           /* 0 = off, else enum ldpc_crc_kind: LDPC_CRC16, LDPC_CRC24A, LDPC_CRC24B             */
     int32_t crc_bits;           /* the CRC covers hard bits [0, crc_bits) of every frame, parity included:
                                    24 < crc_bits <= K (16 < for LDPC_CRC16)                                           */
+    /* ---- fixed-point messages (appended; a struct_size of offsetof(ldpc_decoder_config, msg_bits), the size before
+     *      these fields, is accepted and means 0, as the two shorter sizes do).  The struct grows by 16 bytes, not 4: a
+     *      struct_size 4 or 8 bytes past the previous full size has always been refused as an ABI mismatch and stays
+     *      refused, so no caller's wrong size turns into a read behind its struct. ------------------------------------ */
+    int32_t msg_bits;           /* LDPC_MSG_I8: q = 4, 5, 6 or 8 bits per message (0 = 8), enum ldpc_msg_dtype above;
+                                   with any other msg_dtype it must be 0 (LDPC_ERR_ARG)                                */
+    int32_t msg_reserved[3];    /* must be 0 (LDPC_ERR_ARG otherwise)                                                  */
 } ldpc_decoder_config;
 
 /* two-bit fields of tune_flags: LDPC_TUNE_ON(f) forces the choice on, LDPC_TUNE_OFF(f) off */
@@ -328,8 +359,8 @@ int ldpc_graph_info(const ldpc_graph *g, int32_t *M, int32_t *N, int64_t *E, int
 /* ---- decoder: replaces Coder::forDecoder's device setup + addDecodeType,
  *      MyLdpc.cpp:226-305, 307-552 -------------------------------------------- */
 /* Reference defaults.  The caller says how large its struct is, so that the call never writes behind it:
- * ldpc_decoder_config_init_sized fills the first struct_size bytes -- one of the three sizes ldpc_decoder_create accepts:
- * offsetof(ms_scale), offsetof(crc_kind), sizeof -- and stores struct_size itself; any other size is LDPC_ERR_ARG and
+ * ldpc_decoder_config_init_sized fills the first struct_size bytes -- one of the four sizes ldpc_decoder_create accepts:
+ * offsetof(ms_scale), offsetof(crc_kind), offsetof(msg_bits), sizeof -- and stores struct_size itself; any other size is LDPC_ERR_ARG and
  * nothing is written.  The exported function ldpc_decoder_config_init is what callers built against the header before
  * crc_kind / crc_bits call with their shorter struct: it fills offsetof(ldpc_decoder_config, crc_kind) bytes and stores
  * that as struct_size (CRC off).  Code compiled against THIS header gets its own struct's size through the macro below,
@@ -438,7 +469,7 @@ int ldpc_decode_soft(ldpc_decoder *d, const float *llr_host, int64_t frames, uin
  *       y = (float)x * llr_unit          one fp32 multiply; the widening is exact
  * and everything else is exactly what the handle does when ldpc_decode_device is given that y: SP forms
  * exp(llr_scale * y), BP and LAYERED_BP form chan = llr_scale * y, min-sum stores y; with LDPC_MSG_F16 / LDPC_MSG_F8 the
- * value is rounded where it is stored.  Two roundings, never one: the product x * llr_unit is a value of its own, never
+ * value is rounded where it is stored, with LDPC_MSG_I8 it is sq(llr_scale * y), a second multiply of its own.  Two roundings, never one: the product x * llr_unit is a value of its own, never
  * folded with llr_scale and never contracted into the conversion to fp16.  Padding frames read y = +1.0f exactly, not
  * 1 * llr_unit.  Soft output, extrinsic kind: the y_n of the rule above is this product (BP, LAYERED_BP: llr_scale * y).
  *   LDPC_LLR_I8:  all 256 codes are legal; -128 reads -128 * llr_unit.  Any alignment.

@@ -46,6 +46,12 @@ class DecoderConfigCrc(DecoderConfig):
     _fields_ = [("crc_kind", ctypes.c_int32), ("crc_bits", ctypes.c_int32)]
 
 
+class DecoderConfigMsg(DecoderConfigCrc):
+    """The whole of `ldpc_decoder_config`: DecoderConfigCrc is the struct as it was before msg_bits (a size the library
+    still accepts, msg_bits = 0); this one has msg_bits and the three reserved ints behind it."""
+    _fields_ = [("msg_bits", ctypes.c_int32), ("msg_reserved", ctypes.c_int32 * 3)]
+
+
 class DecodeStats(ctypes.Structure):
     """Mirror of `ldpc_decode_stats`."""
     _fields_ = [("iterations_launched", ctypes.c_int32), ("batch_time", ctypes.c_int32),

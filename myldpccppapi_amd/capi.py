@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import DecoderConfig, DecodeStats, LdpcError  # noqa: F401
 
 ALGO_SP, ALGO_MS, ALGO_LAYERED, ALGO_MS_FUSED, ALGO_LAYERED_HOST, ALGO_BP, ALGO_LAYERED_BP = 0, 1, 2, 3, 4, 5, 6
-MSG_F32, MSG_F16, MSG_F8 = 0, 1, 2
+MSG_F32, MSG_F16, MSG_F8, MSG_I8 = 0, 1, 2, 4    # 3 is not assigned
 PACK_BYTES, PACK_BITS = 0, 1
 CODE_PACKED, CODE_BITS = 0, 1                              # enum ldpc_code_format
 CODE_FORMATS = {"packed": CODE_PACKED, "bits": CODE_BITS}
@@ -217,13 +217,16 @@ class Decoder:
     def __init__(self, graph, K, max_batch, algo="sp", max_iter=40, llr_scale=8.0, early_term=True,
                  device=0, layer_rows=0, pack_mode=PACK_BYTES, frames_per_lane=0, poll_interval=0,
                  msg_dtype=MSG_F32, tune=None, devices=None, host_input="auto", host_copy_threads=0,
-                 ms_scale=0.0, ms_offset=0.0, crc_kind=0, crc_bits=0):
+                 ms_scale=0.0, ms_offset=0.0, crc_kind=0, crc_bits=0, msg_bits=0):
         L = _lib.load()
-        cfg = _lib.DecoderConfigCrc()
+        cfg = _lib.DecoderConfigMsg()
         _lib.check(L.ldpc_decoder_config_init_sized(ctypes.byref(cfg), ctypes.sizeof(cfg)))
         cfg.K, cfg.max_batch = int(K), int(max_batch)
         cfg.algo = ALGOS[algo] if isinstance(algo, str) else int(algo)
-        cfg.msg_dtype = {"f32": MSG_F32, "f16": MSG_F16, "f8": MSG_F8}.get(msg_dtype, msg_dtype)
+        cfg.msg_dtype = {"f32": MSG_F32, "f16": MSG_F16, "f8": MSG_F8, "i8": MSG_I8}.get(msg_dtype, msg_dtype)
+        # fixed-point messages, msg_dtype "i8": saturating integers of msg_bits = 4, 5, 6 or 8 bits (0 = 8); llr_scale is
+        # then the LSBs per unit of channel value (include/ldpc_hip.h: LDPC_MSG_I8)
+        cfg.msg_bits = int(msg_bits)
         cfg.max_iter, cfg.llr_scale = int(max_iter), float(llr_scale)
         cfg.early_term, cfg.device, cfg.layer_rows = int(bool(early_term)), int(device), int(layer_rows)
         cfg.pack_mode, cfg.frames_per_lane, cfg.poll_interval = int(pack_mode), int(frames_per_lane), int(poll_interval)

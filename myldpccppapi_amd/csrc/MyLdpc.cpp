@@ -500,6 +500,7 @@ int Coder::addDecodeType(enum decodeType deType)
     cfg.pack_mode = LDPC_PACK_BYTES;
     cfg.layer_rows = z;
     cfg.msg_dtype = msgType;                           /* setMessageType(): ldpc_decoder_create refuses what it does not carry */
+    cfg.msg_bits = msgBits;
     cfg.algo = (deType == DecodeSP) ? LDPC_ALGO_SP : (deType == DecodeMS) ? LDPC_ALGO_MS
                : (deType == DecodeMSCL) ? LDPC_ALGO_MS_FUSED : (deType == DecodeBP) ? LDPC_ALGO_BP
                : (deType == DecodeLayeredBP) ? LDPC_ALGO_LAYERED_BP : LDPC_ALGO_LAYERED;
@@ -602,7 +603,8 @@ int Coder::decodeFrames(const void *postCode, int llrType, float llrUnit, char *
             cfg.layer_rows = z;                              /* circulant size: lets the record / one-launch kernels apply
                                                                 (with a correction: the record kernel or the streaming ones) */
             cfg.ms_scale = msScale; cfg.ms_offset = msOffset;
-            cfg.msg_dtype = msgType;
+            cfg.msg_dtype = msgType; cfg.msg_bits = msgBits;
+            if (msgType == LDPC_MSG_I8) cfg.llr_scale = llrScale;    /* the LSBs per unit of channel value; min-sum reads it in no other case */
             if (int rc = applyCrcEarlyStop(cfg)) return rc;
             int rc = makeDecoder(cfg, &d);
             if (rc) return fail(rc, ldpc_last_error());

@@ -39,10 +39,15 @@ template <typename Fn> inline int dispatch_v(int V, Fn &&fn)
                   : V == 2 ? fn(std::integral_constant<int, 2>{}) : fn(std::integral_constant<int, 4>{});
 }
 
-/* the run-time message size (4: float, 2: fp16 storage, 1: fp8 storage) as a type: fn(T{}) */
-template <typename Fn> inline void dispatch_msg(int64_t msg_size, Fn &&fn)
+/* the run-time message kind (enum ldpc_msg_dtype: float, fp16, fp8 or fixed-point storage) as a type: fn(T{}).  fp8 and
+ * fixed point are both one byte, so the size does not tell them apart.  For kernels that load, copy and zero-fill only:
+ * every fixed-point width is q8any there (flood_common.hpp); the kernels that store come from the tables. */
+template <typename Fn> inline void dispatch_msg(int msg_kind, Fn &&fn)
 {
-    if (msg_size == 1) fn(f8{}); else if (msg_size == 2) fn(_Float16{}); else fn(float{});
+    if (msg_kind == LDPC_MSG_I8) fn(q8any{});
+    else if (msg_kind == LDPC_MSG_F8) fn(f8{});
+    else if (msg_kind == LDPC_MSG_F16) fn(_Float16{});
+    else fn(float{});
 }
 
 struct RowClass {
@@ -80,7 +85,9 @@ constexpr int kIdleFat = LDPC_IDLE_FAT;
  * creation-time measurements chose.  A handle that runs a layered or a one-launch kernel leaves all of it empty. */
 struct FloodPlan {
     DevBuf<uint8_t> chan, Q, R;         /* message arrays: msg_size bytes per element */
-    int msg_size = 4;                   /* 4 = fp32, 2 = fp16 (LDPC_MSG_F16), 1 = fp8 E4M3 (LDPC_MSG_F8) */
+    int msg_size = 4;                   /* 4 = fp32, 2 = fp16 (LDPC_MSG_F16), 1 = fp8 E4M3 (LDPC_MSG_F8) or fixed point (LDPC_MSG_I8) */
+    int msg_kind = LDPC_MSG_F32;        /* enum ldpc_msg_dtype: what dispatch_msg goes by */
+    int msg_bits = 0;                   /* LDPC_MSG_I8: 4, 5, 6 or 8 (config value 0 resolved to 8); otherwise 0 */
     /* Q in writer order (CheckArgs::qpos): slot of every edge, and col_edge with slots in place of edge ids (init_kernel) */
     DevBuf<int32_t> qpos, col_qedge;
     std::vector<int32_t> h_qpos;

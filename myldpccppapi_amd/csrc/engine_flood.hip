@@ -205,7 +205,7 @@ template <int V> int enqueue_soft(ldpc_decoder *d, hipStream_t s, int tiles, int
     SoftArgs a{d->flood.chan.p, d->flood.R.p, d->col_ptr.p, d->col_edge.p, d->done.p, fail, d->soft.dst, nullptr,
                d->soft.fmap, d->flood.tail_map.p, d->E, frames, d->N, d->soft.kind == LDPC_SOFT_EXTRINSIC ? 1 : 0, tr};
     const dim3 grid((unsigned)((d->N + kInitCols - 1) / kInitCols), (unsigned)tiles);
-    dispatch_msg(d->flood.msg_size, [&](auto t) { soft_settle_kernel<V, decltype(t)><<<grid, kBlock, 0, s>>>(a); });
+    dispatch_msg(d->flood.msg_kind, [&](auto t) { soft_settle_kernel<V, decltype(t)><<<grid, kBlock, 0, s>>>(a); });
     LDPC_HIP_TRY(span_end(d, s));
     return LDPC_OK;
 }
@@ -232,7 +232,7 @@ template <int V> int compact_and_finish(ldpc_decoder *d, int64_t frames, int cou
     /* many frames: one coalesced pass over the parent's rows through LDS; few: one sector per value */
     const bool rowwise = count >= 128;
     const int ptiles = (int)((frames + 64 * V - 1) / (64 * V));
-    dispatch_msg(d->flood.msg_size, [&](auto t) {
+    dispatch_msg(d->flood.msg_kind, [&](auto t) {
         using T = decltype(t);
         const T *pq = (const T *)d->flood.Q.p, *pc = (const T *)d->flood.chan.p;
         T *cq = (T *)c->flood.Q.p, *cc = (T *)c->flood.chan.p;
@@ -392,7 +392,7 @@ template <int V> int run_flooding(ldpc_decoder *d, const ldpc::LlrIn &llr, int64
                  * below the threshold after this round (decided by the kernel; usually it just returns) */
                 ta.iter = it;
                 const unsigned tg = (unsigned)std::min<int64_t>(1024, d->E + 2 * (int64_t)d->N);
-                dispatch_msg(d->flood.msg_size, [&](auto t) { tail_gather_kernel<V, decltype(t)><<<tg, kBlock, 0, s>>>(ta); });
+                dispatch_msg(d->flood.msg_kind, [&](auto t) { tail_gather_kernel<V, decltype(t)><<<tg, kBlock, 0, s>>>(ta); });
             }
             LDPC_HIP_TRY(span_end(d, s));
             if (poll) {
@@ -638,7 +638,10 @@ int plan_launches(ldpc_decoder *d)
 int setup_flooding(ldpc_decoder *d, const ldpc_graph *g, size_t TF)
 {
     const ldpc_decoder_config *cfg = &d->cfg;
-    d->flood.msg_size = cfg->msg_dtype == LDPC_MSG_F8 ? 1 : cfg->msg_dtype == LDPC_MSG_F16 ? 2 : 4;
+    const bool i8 = cfg->msg_dtype == LDPC_MSG_I8;
+    d->flood.msg_kind = cfg->msg_dtype;
+    d->flood.msg_bits = i8 ? (cfg->msg_bits ? cfg->msg_bits : 8) : 0;
+    d->flood.msg_size = (i8 || cfg->msg_dtype == LDPC_MSG_F8) ? 1 : cfg->msg_dtype == LDPC_MSG_F16 ? 2 : 4;
     LDPC_HIP_TRY(d->flood.chan.alloc(TF * d->N * d->flood.msg_size));
     LDPC_HIP_TRY(d->flood.Q.alloc(TF * (size_t)d->E * d->flood.msg_size));
     LDPC_HIP_TRY(d->flood.R.alloc(TF * (size_t)d->E * d->flood.msg_size));
@@ -647,6 +650,12 @@ int setup_flooding(ldpc_decoder *d, const ldpc_graph *g, size_t TF)
     /* the kernels live in flood_sp.hip / flood_ms*.hip / flood_msc*.hip / flood_bp*.hip (flood_tables.hpp) */
     ldpc::FloodFns *fns = &d->flood.fns;
     if (cfg->algo == LDPC_ALGO_SP) ldpc::fill_flood_sp(d->V, fns);
+    else if (i8) {
+        /* fixed point: the width is the kernels' compile-time L (ldpc_decoder_create has refused every other algorithm and width) */
+        const int q = d->flood.msg_bits;
+        if (d->ms_corr) (q == 4 ? ldpc::fill_flood_msci4 : q == 5 ? ldpc::fill_flood_msci5 : q == 6 ? ldpc::fill_flood_msci6 : ldpc::fill_flood_msci8)(d->V, fns);
+        else (q == 4 ? ldpc::fill_flood_msi4 : q == 5 ? ldpc::fill_flood_msi5 : q == 6 ? ldpc::fill_flood_msi6 : ldpc::fill_flood_msi8)(d->V, fns);
+    }
     else if (cfg->algo == LDPC_ALGO_BP && cfg->msg_dtype == LDPC_MSG_F16) ldpc::fill_flood_bp16(d->V, fns);
     else if (cfg->algo == LDPC_ALGO_BP) ldpc::fill_flood_bp(d->V, fns);
     else if (d->ms_corr && cfg->msg_dtype == LDPC_MSG_F8) ldpc::fill_flood_msc8(d->V, fns);

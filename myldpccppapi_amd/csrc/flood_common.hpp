@@ -171,16 +171,86 @@ template <> __device__ __forceinline__ void vstore<4>(f8 *p, const float (&s)[4]
     st_stream(reinterpret_cast<uint32_t *>(p), (uint32_t)f8_pack2(s[2], s[3], lo, true));
 }
 
+/* fixed-point message storage (msg_dtype = LDPC_MSG_I8, msg_bits = q): one two's-complement byte per message holding
+ * an integer in [-L, L], L = 2^(q-1) - 1 a compile-time parameter; arithmetic in fp32, which is exact integer arithmetic
+ * here (every sum stays far below 2^24).  Loads sign-extend and widen exactly.  Stores apply sq (include/ldpc_hip.h):
+ * clamp to [-L, L] in fp32 (one v_med3_f32; nothing out of range ever reaches a conversion), then ONE add of
+ * 1.5 * 2^23: in [2^23, 2^24) the fp32 grid is the integers, so the add itself rounds to nearest, ties to even, and the
+ * low byte of the sum's bit pattern (0x4B400000 + n) is n in two's complement -- no v_rndne_f32, no v_cvt_i32_f32, no
+ * mask.  v_perm_b32 gathers the low bytes: 4 messages are 4 med3 + 4 add + 2 perm + 1 or = 2.75 VALU instructions per
+ * message (the fp8 store: 3.5), a load one v_cvt_f32_i32 with an SDWA byte select and sign extension per message.  -0 gives the byte 0; the code -128
+ * is never produced.  sq's NaN case can only come from the caller's channel values -- a stored message is never NaN or
+ * infinite -- and is settled there, once per channel value (MsgChan), not in every store; a NaN that did reach a store
+ * would leave v_med3_f32 as -L, in range.  (T)0 is the byte 0x00, the zero message of the hand-over kernels. */
+template <int L> struct q8 {
+    int8_t bits;
+    q8() = default;
+    __host__ __device__ constexpr explicit q8(int) : bits(0) {}
+};
+static_assert(sizeof(q8<127>) == 1, "one byte per message");
+
+constexpr float kQ8Magic = 12582912.0f;     /* 1.5 * 2^23 */
+/* sq(x) as a dword whose LOW BYTE is the code (the upper bytes are the magic number's and are dropped by the pack) */
+template <int L> __device__ __forceinline__ uint32_t q8_code(float x)
+{
+    return __float_as_uint(__builtin_amdgcn_fmed3f(x, -(float)L, (float)L) + kQ8Magic);
+}
+
+template <int V, int L> __device__ __forceinline__ void vload(float (&d)[V], const q8<L> *p)
+{
+    static_assert(V == 1 || V == 2 || V == 4, "1, 2 or 4 messages per lane");
+    if constexpr (V == 1) {
+        d[0] = (float)(int)ld_stream(reinterpret_cast<const int8_t *>(p));
+    } else if constexpr (V == 2) {
+        const int w = (int)ld_stream(reinterpret_cast<const int16_t *>(p));     /* sign-extended: the high byte is ready */
+        d[0] = (float)(int)(int8_t)w; d[1] = (float)(w >> 8);
+    } else {
+        const int w = (int)ld_stream(reinterpret_cast<const uint32_t *>(p));
+        d[0] = (float)(int)(int8_t)w; d[1] = (float)(int)(int8_t)(w >> 8);
+        d[2] = (float)(int)(int8_t)(w >> 16); d[3] = (float)(w >> 24);
+    }
+}
+template <int V, int L> __device__ __forceinline__ void vstore(q8<L> *p, const float (&s)[V])
+{
+    static_assert(V == 1 || V == 2 || V == 4, "1, 2 or 4 messages per lane");
+    /* v_perm_b32 selectors: 0..3 bytes of the second operand, 4..7 of the first, 0x0c the constant 0 */
+    if constexpr (V == 1) {
+        st_stream(reinterpret_cast<uint8_t *>(p), (uint8_t)q8_code<L>(s[0]));
+    } else if constexpr (V == 2) {
+        st_stream(reinterpret_cast<uint16_t *>(p), (uint16_t)__builtin_amdgcn_perm(q8_code<L>(s[1]), q8_code<L>(s[0]), 0x0c0c0400u));
+    } else {
+        const uint32_t lo = __builtin_amdgcn_perm(q8_code<L>(s[1]), q8_code<L>(s[0]), 0x0c0c0400u);
+        const uint32_t hi = __builtin_amdgcn_perm(q8_code<L>(s[3]), q8_code<L>(s[2]), 0x04000c0cu);
+        st_stream(reinterpret_cast<uint32_t *>(p), lo | hi);
+    }
+}
+
 /* a check->variable magnitude as its storage type holds it, applied where the message is produced: the column-fused
- * kernels keep some R in registers without ever storing them */
+ * kernels keep some R in registers without ever storing them.  Fixed point: the corrected magnitude is truncated, as
+ * hardware does it ((3m) >> 2 for ms_scale = 0.75), and saturates at L */
 template <typename T> struct MsgRound;
 template <> struct MsgRound<float> { static __device__ __forceinline__ float of(float r) { return r; } };
 template <> struct MsgRound<hf> { static __device__ __forceinline__ float of(float r) { return (float)(hf)r; } };
 template <> struct MsgRound<f8> { static __device__ __forceinline__ float of(float r) { return f8_round(r); } };
+template <int L> struct MsgRound<q8<L>> { static __device__ __forceinline__ float of(float r) { return fminf(truncf(r), (float)L); } };
 /* plain min-sum: a row's magnitude candidates are |q| of stored messages -- values of T already -- or the start value
- * 1000, which no E4M3 value reaches: it reads 448 */
+ * 1000, which no E4M3 value reaches: it reads 448; fixed point: L */
 template <typename T> struct MsgStart { static __device__ __forceinline__ float of(float m) { return m; } };
 template <> struct MsgStart<f8> { static __device__ __forceinline__ float of(float m) { return fminf(m, kF8Max); } };
+template <int L> struct MsgStart<q8<L>> { static __device__ __forceinline__ float of(float m) { return fminf(m, (float)L); } };
+/* the min-sum channel value in front of its store: y as it is for the floating-point types; fixed point: llr_scale * y,
+ * one fp32 multiply, the number of LSBs, with sq's NaN -> 0 (the store does the rest of sq) */
+template <typename T> struct MsgChan { static __device__ __forceinline__ float of(float y, float) { return y; } };
+template <int L> struct MsgChan<q8<L>> {
+    static __device__ __forceinline__ float of(float y, float llr_scale)
+    {
+        const float t = llr_scale * y;
+        return t != t ? 0.0f : t;
+    }
+};
+/* message kinds whose one-byte elements only differ in how a STORE converts: kernels that load, copy and zero-fill
+ * (hand-over, soft output) are instantiated once, for q8<127> */
+typedef q8<127> q8any;
 
 __device__ __forceinline__ int wave_id_in_block()
 {

@@ -93,8 +93,9 @@ __global__ __launch_bounds__(kBlock) void init_kernel(const InitArgs a)
                 asm volatile("" : "+v"(t));
                 ch[v] = q[v] = t;
             } else {
-                ch[v] = y;                                          /* fp16 storage rounds it here */
-                q[v] = y;                                           /* :121 */
+                const float c = MsgChan<T>::of(y, a.llr_scale);     /* y; fixed point: llr_scale * y */
+                ch[v] = c;                                          /* fp16 storage rounds it here */
+                q[v] = c;                                           /* :121 */
             }
         }
         vstore<V>(static_cast<T *>(a.chan) + ((size_t)tile * a.N + n) * F + (size_t)lane * V, ch);

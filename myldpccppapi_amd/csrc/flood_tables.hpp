@@ -45,6 +45,14 @@ void fill_flood_msc(int V, FloodFns *f);     /* corrected min-sum (kAlgoMSC), fp
 void fill_flood_msc16(int V, FloodFns *f);   /* corrected min-sum, fp16 message storage     (flood_msc16.hip) */
 void fill_flood_ms8(int V, FloodFns *f);     /* min-sum, fp8 (E4M3) message storage         (flood_ms8.hip)   */
 void fill_flood_msc8(int V, FloodFns *f);    /* corrected min-sum, fp8 message storage      (flood_msc8.hip)  */
+void fill_flood_msi4(int V, FloodFns *f);    /* min-sum, 4-bit fixed-point message storage (flood_msi4.hip)   */
+void fill_flood_msci4(int V, FloodFns *f);   /* corrected min-sum, 4-bit fixed point        (flood_msci4.hip)  */
+void fill_flood_msi5(int V, FloodFns *f);    /* min-sum, 5-bit fixed-point message storage (flood_msi5.hip)   */
+void fill_flood_msci5(int V, FloodFns *f);   /* corrected min-sum, 5-bit fixed point        (flood_msci5.hip)  */
+void fill_flood_msi6(int V, FloodFns *f);    /* min-sum, 6-bit fixed-point message storage (flood_msi6.hip)   */
+void fill_flood_msci6(int V, FloodFns *f);   /* corrected min-sum, 6-bit fixed point        (flood_msci6.hip)  */
+void fill_flood_msi8(int V, FloodFns *f);    /* min-sum, 8-bit fixed-point message storage (flood_msi8.hip)   */
+void fill_flood_msci8(int V, FloodFns *f);   /* corrected min-sum, 8-bit fixed point        (flood_msci8.hip)  */
 void fill_flood_bp(int V, FloodFns *f);      /* log-domain sum-product (kAlgoBP), fp32 messages (flood_bp.hip)  */
 void fill_flood_bp16(int V, FloodFns *f);    /* log-domain sum-product, fp16 message storage    (flood_bp16.hip) */
 

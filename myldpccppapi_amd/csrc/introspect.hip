@@ -152,8 +152,13 @@ int ldpc_decoder_kernel_times(ldpc_decoder *d, ldpc_kernel_time *out, int32_t ca
     static const char *algo_name_f8[] = {"sp8", "ms8", "layered8", "ms_fused8", "layered_host8", "bp8", "layered_bp8"};
     static const char *algo_name_corr_f8[] = {"sp8", "msc8", "layered8", "ms_fused8", "layered_host8", "bp8", "layered_bp8"};
     const int msz = d->flood.msg_size;
-    const char **algo_name = d->ms_corr ? (msz == 1 ? algo_name_corr_f8 : msz == 2 ? algo_name_corr_f16 : algo_name_corr_f32)
-                                        : (msz == 1 ? algo_name_f8 : msz == 2 ? algo_name_f16 : algo_name_f32);
+    /* fixed point (LDPC_MSG_I8, min-sum only): msi<q> / msci<q> */
+    char name_i8[8];
+    snprintf(name_i8, sizeof name_i8, "%s%d", d->ms_corr ? "msci" : "msi", d->flood.msg_bits);
+    const char *algo_name_i8[] = {"sp", name_i8, "layered", "ms_fused", "layered_host", "bp", "layered_bp"};
+    const char **algo_name = d->flood.msg_kind == LDPC_MSG_I8 ? algo_name_i8
+                             : d->ms_corr ? (msz == 1 ? algo_name_corr_f8 : msz == 2 ? algo_name_corr_f16 : algo_name_corr_f32)
+                                          : (msz == 1 ? algo_name_f8 : msz == 2 ? algo_name_f16 : algo_name_f32);
     for (size_t i = 0; i < d->tm.spans_used; ++i) {
         const ldpc::TimedSpan &sp = d->tm.spans[i];
         float ms = 0;
@@ -317,6 +322,8 @@ int ldpc_decoder_dump(ldpc_decoder *d, int32_t which, float *host_out, int64_t c
                         _Float16 h;
                         memcpy(&h, &tile[(ir * F + fi) * 2], 2);
                         host_out[f * per + i] = (float)h;
+                    } else if (d->flood.msg_kind == LDPC_MSG_I8) {
+                        host_out[f * per + i] = (float)(int8_t)tile[ir * F + fi];
                     } else {
                         host_out[f * per + i] = e4m3_widen(tile[ir * F + fi]);
                     }

@@ -43,8 +43,8 @@ int pick_frames_per_lane(const ldpc_decoder_config &cfg, int32_t max_row_deg, in
      * holds a whole row (P and R) per lane. */
     int deg = (cfg.algo == LDPC_ALGO_LAYERED || cfg.algo == LDPC_ALGO_LAYERED_BP) ? max_row_deg : max_col_deg;
     if (cfg.algo == LDPC_ALGO_MS || cfg.algo == LDPC_ALGO_BP) deg = (deg + 1) / 2;   /* min-sum variable nodes (BP's too) need half the registers */
-    /* fp8 messages: 4 values are one dword per lane, the least a lane should move -- from one full tile on */
-    if (cfg.msg_dtype == LDPC_MSG_F8 && cfg.max_batch >= 256 && deg <= 8) return 4;
+    /* one-byte messages (fp8, fixed point): 4 values are one dword per lane, the least a lane should move -- from one full tile on */
+    if ((cfg.msg_dtype == LDPC_MSG_F8 || cfg.msg_dtype == LDPC_MSG_I8) && cfg.max_batch >= 256 && deg <= 8) return 4;
     if (cfg.max_batch >= 1024 && deg <= 8) return 4;
     if (cfg.max_batch >= 256 && deg <= ldpc::kMaxUnrolledDegree) return 2;
     return 1;
@@ -172,10 +172,11 @@ int ldpc_graph_info(const ldpc_graph *g, int32_t *M, int32_t *N, int64_t *E, int
 int ldpc_decoder_config_init_sized(ldpc_decoder_config *cfg, uint32_t struct_size)
 {
     if (!cfg) return set_error(LDPC_ERR_ARG, "config is NULL");
-    if (struct_size != sizeof(ldpc_decoder_config) && struct_size != offsetof(ldpc_decoder_config, crc_kind) &&
-        struct_size != offsetof(ldpc_decoder_config, ms_scale))
-        return set_error(LDPC_ERR_ARG, "config struct_size %u is none of %zu, %zu, %zu (ABI mismatch)", struct_size,
-                    sizeof(ldpc_decoder_config), offsetof(ldpc_decoder_config, crc_kind), offsetof(ldpc_decoder_config, ms_scale));
+    if (struct_size != sizeof(ldpc_decoder_config) && struct_size != offsetof(ldpc_decoder_config, msg_bits) &&
+        struct_size != offsetof(ldpc_decoder_config, crc_kind) && struct_size != offsetof(ldpc_decoder_config, ms_scale))
+        return set_error(LDPC_ERR_ARG, "config struct_size %u is none of %zu, %zu, %zu, %zu (ABI mismatch)", struct_size,
+                    sizeof(ldpc_decoder_config), offsetof(ldpc_decoder_config, msg_bits), offsetof(ldpc_decoder_config, crc_kind),
+                    offsetof(ldpc_decoder_config, ms_scale));
     /* every field that has a non-zero default lies in front of ms_scale */
     memset(cfg, 0, struct_size);
     cfg->struct_size = struct_size;
@@ -197,15 +198,18 @@ void ldpc_decoder_config_init(ldpc_decoder_config *cfg)
     (void)ldpc_decoder_config_init_sized(cfg, (uint32_t)offsetof(ldpc_decoder_config, crc_kind));
 }
 
-/* The caller's config as the current struct: callers built against the header before ms_scale / ms_offset, or before
- * crc_kind / crc_bits, pass a shorter struct, of which only struct_size bytes are read; the fields it lacks are 0 (off). */
+/* The caller's config as the current struct: callers built against the header before ms_scale / ms_offset, before
+ * crc_kind / crc_bits or before msg_bits pass a shorter struct, of which only struct_size bytes are read; the fields it
+ * lacks are 0 (off; msg_bits: 8). */
 static int config_in(const ldpc_decoder_config *cfg, ldpc_decoder_config *full)
 {
     constexpr size_t kSizeBeforeMsCorr = offsetof(ldpc_decoder_config, ms_scale);
     constexpr size_t kSizeBeforeCrc = offsetof(ldpc_decoder_config, crc_kind);
-    if (cfg->struct_size != sizeof(ldpc_decoder_config) && cfg->struct_size != kSizeBeforeCrc && cfg->struct_size != kSizeBeforeMsCorr)
-        return set_error(LDPC_ERR_ARG, "config struct_size %u is none of %zu, %zu, %zu (ABI mismatch)", cfg->struct_size,
-                    sizeof(ldpc_decoder_config), kSizeBeforeCrc, kSizeBeforeMsCorr);
+    constexpr size_t kSizeBeforeMsgBits = offsetof(ldpc_decoder_config, msg_bits);
+    if (cfg->struct_size != sizeof(ldpc_decoder_config) && cfg->struct_size != kSizeBeforeMsgBits && cfg->struct_size != kSizeBeforeCrc &&
+        cfg->struct_size != kSizeBeforeMsCorr)
+        return set_error(LDPC_ERR_ARG, "config struct_size %u is none of %zu, %zu, %zu, %zu (ABI mismatch)", cfg->struct_size,
+                    sizeof(ldpc_decoder_config), kSizeBeforeMsgBits, kSizeBeforeCrc, kSizeBeforeMsCorr);
     memset(full, 0, sizeof *full);
     memcpy(full, cfg, cfg->struct_size);
     full->struct_size = sizeof *full;
@@ -255,8 +259,20 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     if (cfg->frames_per_lane != 0 && cfg->frames_per_lane != 1 && cfg->frames_per_lane != 2 &&
         cfg->frames_per_lane != 4)
         return set_error(LDPC_ERR_ARG, "frames_per_lane must be 0, 1, 2 or 4");
-    if (cfg->msg_dtype != LDPC_MSG_F32 && cfg->msg_dtype != LDPC_MSG_F16 && cfg->msg_dtype != LDPC_MSG_F8)
+    if (cfg->msg_dtype != LDPC_MSG_F32 && cfg->msg_dtype != LDPC_MSG_F16 && cfg->msg_dtype != LDPC_MSG_F8 && cfg->msg_dtype != LDPC_MSG_I8)
         return set_error(LDPC_ERR_ARG, "unknown msg_dtype %d", cfg->msg_dtype);
+    if (cfg->msg_reserved[0] || cfg->msg_reserved[1] || cfg->msg_reserved[2])
+        return set_error(LDPC_ERR_ARG, "msg_reserved must be 0");
+    if (cfg->msg_bits != 0 && cfg->msg_dtype != LDPC_MSG_I8)
+        return set_error(LDPC_ERR_ARG, "msg_bits=%d belongs to LDPC_MSG_I8 (msg_dtype is %d)", cfg->msg_bits, cfg->msg_dtype);
+    if (cfg->msg_bits != 0 && cfg->msg_bits != 4 && cfg->msg_bits != 5 && cfg->msg_bits != 6 && cfg->msg_bits != 8)
+        return set_error(LDPC_ERR_ARG, "msg_bits must be 0 (8), 4, 5, 6 or 8, not %d", cfg->msg_bits);
+    if (cfg->msg_dtype == LDPC_MSG_I8 && cfg->algo != LDPC_ALGO_MS)
+        return set_error(LDPC_ERR_UNSUPPORTED, "fixed-point messages (LDPC_MSG_I8) are built for flooding min-sum only "
+                    "(SP and BP have no integer datapath here; the layered decoders and the reference-reproducing ones are fp32)");
+    /* written so that NaN fails it */
+    if (cfg->msg_dtype == LDPC_MSG_I8 && !(cfg->llr_scale > 0.0f && cfg->llr_scale <= 3.402823466e38f))
+        return set_error(LDPC_ERR_ARG, "LDPC_MSG_I8: llr_scale must be positive and finite (the LSBs per unit of channel value)");
     if (cfg->msg_dtype == LDPC_MSG_F8 && cfg->algo != LDPC_ALGO_MS)
         return set_error(LDPC_ERR_UNSUPPORTED, "fp8 messages are built for flooding min-sum only "
                     "(the probability-domain SP needs fp32 range; BP is fp32 / fp16; the layered decoders, LAYERED_BP among them, and the "
@@ -271,11 +287,12 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
             return set_error(LDPC_ERR_UNSUPPORTED, "LDPC_ALGO_BP / LDPC_ALGO_LAYERED_BP: the LDS-resident one-launch kernels and the record kernels (LDPC_TUNE_FUSED / "
                         "LDPC_TUNE_LDSP forced on) carry no box-plus check node; the streaming kernels do");
     }
-    if (cfg->msg_dtype == LDPC_MSG_F8) {
+    if (cfg->msg_dtype == LDPC_MSG_F8 || cfg->msg_dtype == LDPC_MSG_I8) {
         const ldpc::Tune t = ldpc::tune_from_config(*cfg);
         if (ldpc::tune_forced_on(t.fused) || ldpc::tune_forced_on(t.ldsp))
-            return set_error(LDPC_ERR_UNSUPPORTED, "fp8 messages: the LDS-resident one-launch kernels and the record kernels (LDPC_TUNE_FUSED / "
-                        "LDPC_TUNE_LDSP forced on) are fp32; the streaming kernels carry the fp8 rule");
+            return set_error(LDPC_ERR_UNSUPPORTED, "%s messages: the LDS-resident one-launch kernels and the record kernels (LDPC_TUNE_FUSED / "
+                        "LDPC_TUNE_LDSP forced on) are fp32; the streaming kernels carry the %s rule",
+                        cfg->msg_dtype == LDPC_MSG_F8 ? "fp8" : "fixed-point", cfg->msg_dtype == LDPC_MSG_F8 ? "fp8" : "fixed-point");
     }
     /* CRC-aided early termination: the streaming kernels carry the rule (crc_term_kernel), nothing else does */
     const bool crc_term = cfg->crc_kind != 0;
@@ -308,11 +325,11 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     d->h_cols = g->cols;
     const ldpc::Tune tune = d->tune = ldpc::tune_from_config(*cfg);
     d->flood.syn_xcd = ldpc::tune_pick(tune.syn_xcd, true);
-    /* fp8 messages: the forms that move a dword per lane at V = 4 are the automatic choice -- check kernels in wide waves
+    /* one-byte messages (fp8 and fixed point alike): the forms that move a dword per lane at V = 4 are the automatic choice -- check kernels in wide waves
      * where every row has one (degree <= kMaxUnrolledDegree; above, the bucket launches, V values per lane), the
      * column-fused kernel wide unless the creation-time measurement prefers the half form.  The narrow forms move one
      * byte per lane; the tuning fields still select them, results never depend on the choice. */
-    const bool f8 = cfg->msg_dtype == LDPC_MSG_F8;
+    const bool f8 = cfg->msg_dtype == LDPC_MSG_F8 || cfg->msg_dtype == LDPC_MSG_I8;
     d->flood.check_wide = ldpc::tune_pick(tune.check_wide, f8 && g->max_row_deg <= ldpc::kMaxUnrolledDegree);
     d->flood.link_form = ldpc::tune_pick(tune.link_half, false) ? 2 : (ldpc::tune_pick(tune.link_narrow, !f8 || ldpc::tune_forced_on(tune.link_deep)) ? 1 : 0);   /* deep is a narrow form */
     d->flood.link_deep = ldpc::tune_pick(tune.link_deep, false);

@@ -10,7 +10,7 @@ reference counts differing BYTES (Test.cpp:105-110); this prints byte errors too
     python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N> | --alist PATH] [--algo sp|ms|layered|bp|layered_bp]
                               [--payload zero|random] [--rate-match P,FLO,FHI,E[,K0]] [--erasure-llr X]
                               [--modulation bpsk|qpsk|qam16|qam64|qam256] [--no-interleave] [--transport-block A[,C]] [--crc-stop] [--bch T[,N]]
-                              [--msg-dtype f32|f16|f8] [--soft-check] [--osd 0|1 [--osd-scale S]]
+                              [--msg-dtype f32|f16|f8|i8 [--msg-bits Q --llr-scale S]] [--soft-check] [--osd 0|1 [--osd-scale S]]
                               [--snr=1.0,1.5,...]  (write --snr=-0.5,0 for a list that starts with a minus) [--frames 4096] [--iters 50]
 --rate-match: code bits [0, P) punctured, [FLO, FHI) filler bits (known zeros; multiples of 8, inside the information part),
 E bits per frame sent from circular-buffer position K0 (default 0): ldpc_rate_match_device between the encoder and the
@@ -74,11 +74,12 @@ ap.add_argument("--algo", default="sp")
 ap.add_argument("--snr", default="2.5,3.0,3.5,4.0,4.5,5.0")
 ap.add_argument("--frames", type=int, default=4096)
 ap.add_argument("--iters", type=int, default=50)
-ap.add_argument("--llr-scale", type=float, default=None, help="channel scale of sp and bp (sp: default 8, with --modulation 2 / sd^2 per point; bp: 2 / sd^2 per point)")
+ap.add_argument("--llr-scale", type=float, default=None, help="channel scale of sp and bp (sp: default 8, with --modulation 2 / sd^2 per point; bp: 2 / sd^2 per point); "
+                                                                  "with --msg-dtype i8 the LSBs per unit of channel value (default 8)")
 ap.add_argument("--batches", type=int, default=1, help="batches of --frames per SNR point")
 ap.add_argument("--seed", type=int, default=20260101)
 ap.add_argument("--ms-scale", type=float, default=0.0, help="normalized min-sum factor (ms / layered; 0 = off)")
-ap.add_argument("--ms-offset", type=float, default=0.0, help="offset min-sum offset, units of y (0 = off)")
+ap.add_argument("--ms-offset", type=float, default=0.0, help="offset min-sum offset, units of y -- with --msg-dtype i8: LSBs (0 = off)")
 ap.add_argument("--payload", choices=("zero", "random"), default="zero",
                 help="random: source bytes drawn on the device, encoded by ldpc_encode_device, errors counted against them")
 ap.add_argument("--rate-match", default=None, metavar="P,FLO,FHI,E[,K0]", help="puncture [0,P), fillers [FLO,FHI), send E bits from K0")
@@ -90,7 +91,10 @@ ap.add_argument("--transport-block", default=None, metavar="A[,C]",
                 help="with --payload random: A payload bits per transport block, C code blocks (default: the rule of ldpc_tb_spec_init)")
 ap.add_argument("--bch", default=None, metavar="T[,N]",
                 help="with --payload random: outer BCH code that corrects T errors over N code bits (default: K)")
-ap.add_argument("--msg-dtype", choices=("f32", "f16", "f8"), default="f32", help="message storage (f16: --algo ms and bp; f8: --algo ms)")
+ap.add_argument("--msg-dtype", choices=("f32", "f16", "f8", "i8"), default="f32",
+                help="message storage (f16: --algo ms and bp; f8: --algo ms; i8: --algo ms, saturating integers of --msg-bits bits, "
+                     "channel c = sq(--llr-scale * y), --ms-offset in LSBs)")
+ap.add_argument("--msg-bits", type=int, default=0, help="with --msg-dtype i8: 4, 5, 6 or 8 bits per message (0 = 8)")
 ap.add_argument("--llr-type", choices=("f32", "f16", "i8"), default="f32",
                 help="quantise the channel values on the device (ldpc_llr_quantize_device) behind the channel / rate-recover step "
                      "and decode them through ldpc_decode_typed_device")
@@ -158,7 +162,7 @@ if args.bch:
 def make_decoder(llr_scale):
     return L.Decoder(g, K, max_batch=B, algo=args.algo, max_iter=args.iters, llr_scale=llr_scale,
                      layer_rows=layer, poll_interval=2, ms_scale=args.ms_scale, ms_offset=args.ms_offset,
-                     crc_kind=crc_kind, crc_bits=crc_bits, msg_dtype=args.msg_dtype)
+                     crc_kind=crc_kind, crc_bits=crc_bits, msg_dtype=args.msg_dtype, msg_bits=args.msg_bits)
 
 
 dec = None if matched else make_decoder(8.0 if args.llr_scale is None else args.llr_scale)
