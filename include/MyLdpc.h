@@ -57,8 +57,13 @@ enum rate_type { rate_1_2, rate_2_3_a, rate_2_3_b, rate_3_4_a, rate_3_4_b, rate_
 
 enum decodeType { DecodeCPU, DecodeMS, DecodeSP, DecodeTDMP, DecodeTDMPCL, DecodeMSCL,
                   DecodeBP, /* not in the reference: log-domain sum-product, LDPC_ALGO_BP (include/ldpc_hip.h) */
-                  DecodeLayeredBP /* not in the reference: the layered schedule of DecodeTDMPCL (same circulant size) with
-                                     DecodeBP's check node, LDPC_ALGO_LAYERED_BP (include/ldpc_hip.h); fp32 messages only */ };
+                  DecodeLayeredBP, /* not in the reference: the layered schedule of DecodeTDMPCL (same circulant size) with
+                                     DecodeBP's check node, LDPC_ALGO_LAYERED_BP (include/ldpc_hip.h); fp32 messages only */
+                  DecodeLayeredFixed /* not in the reference: the layered schedule of DecodeTDMPCL (same circulant size) in
+                                     fixed point, LDPC_ALGO_LAYERED_FX (include/ldpc_hip.h): setMessageType(LDPC_MSG_I8,
+                                     bits) gives the message width, setPosteriorBits() the width of the saturating
+                                     posterior memory, setLlrScale() the LSBs per unit of channel value; it takes
+                                     setMinSumCorrection, setCrcEarlyStop, decodeSoft (values in LSBs) and decodeTyped */ };
 
 const int n_b = 24;
 
@@ -128,6 +133,10 @@ public:
      * integers of `bits` = 4, 5, 6 or 8 bits (0 = 8; with any other type bits must be 0); setLlrScale() is then the number
      * of LSBs per unit of channel value.  Before addDecodeType(). */
     void setMessageType(int msgDtype, int bits = 0) { msgType = msgDtype; msgBits = bits; }
+    /* DecodeLayeredFixed: the posterior memory holds `bits` bits, message bits <= bits <= 16 (0 = 16; include/ldpc_hip.h:
+     * post_bits); anything else makes addDecodeType fail as ldpc_decoder_create does.  Read by no other decode type.
+     * Before addDecodeType(). */
+    void setPosteriorBits(int bits) { postBits = bits; }
     /* encode() on the GPU `setDevice` names (ldpc_encode, include/ldpc_hip.h) instead of the host: same bytes.
      * forEncoder() then creates the device encoder and skips the host precompute, so it also serves the seed whose
      * parity part the host solves by dense elimination only (rate_3_4_b: any N, where the host path stops at
@@ -228,6 +237,7 @@ private:
     float msScale = 0.0f, msOffset = 0.0f; /* setMinSumCorrection() */
     int msgType = 0;                 /* setMessageType(): LDPC_MSG_F32 */
     int msgBits = 0;                 /* setMessageType(): bits per message with LDPC_MSG_I8 */
+    int postBits = 0;                /* setPosteriorBits(): DecodeLayeredFixed */
     int makeDecoder(const ldpc_decoder_config &cfg, ldpc_decoder **out);
     const signed char *hSeed;
     int seedRowLength;

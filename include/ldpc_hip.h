@@ -72,8 +72,13 @@ enum ldpc_algo {
                               fp32, one launch per layer                                    */
     LDPC_ALGO_BP = 5,      /* flooding sum-product in the LOG domain (box-plus check node): this library's own
                               definition, below; streaming kernels, fp32 or LDPC_MSG_F16 messages              */
-    LDPC_ALGO_LAYERED_BP = 6 /* layered (TDMP) schedule with LDPC_ALGO_BP's box-plus check node: this library's own
+    LDPC_ALGO_LAYERED_BP = 6,/* layered (TDMP) schedule with LDPC_ALGO_BP's box-plus check node: this library's own
                               definition, below; the streaming layered engine, fp32, one launch per layer    */
+    /* The value 7 is not assigned and stays "unknown algo" (LDPC_ERR_ARG): callers and tests of the library have used it as
+     * their example of an unknown algorithm since LDPC_ALGO_LAYERED_BP, and what was refused stays refused. */
+    LDPC_ALGO_LAYERED_FX = 8 /* layered (TDMP) min-sum in fixed point: q-bit messages (LDPC_MSG_I8, msg_bits) and a
+                              posterior MEMORY of post_bits bits that saturates: this library's own definition, below;
+                              the streaming layered engine, one byte per R and two per P, one launch per layer */
 };
 
 /* LDPC_ALGO_BP, bit for bit.  The reference's sum-product (LDPC_ALGO_SP) works on probabilities in fp32 and saturates at
@@ -130,6 +135,42 @@ enum ldpc_algo {
  * crc_kind, early termination on and off, both pack modes, ldpc_decode, ldpc_decode_soft and ldpc_decoder_create_multi
  * work as for LDPC_ALGO_LAYERED. */
 
+/* LDPC_ALGO_LAYERED_FX, bit for bit, in integers: the layered decoder a hardware team builds for a QC code.  In the
+ * flooding rule of LDPC_MSG_I8 (below) the posterior is recomputed every round in an accumulator that never saturates; in
+ * the layered schedule the posterior IS the state: it lives in a memory of p bits and saturates, and P - R_old is formed
+ * from the saturated P.
+ *   Configuration: msg_dtype = LDPC_MSG_I8 (any other: LDPC_ERR_ARG); msg_bits = q one of 4, 5, 6, 8 (0 = 8),
+ *                 L = 2^(q-1) - 1; post_bits = p with q <= p <= 16 (0 = 16), LP = 2^(p-1) - 1, anything else
+ *                 LDPC_ERR_ARG; layer_rows required and dividing M, layers column-disjoint, as for LDPC_ALGO_LAYERED;
+ *                 llr_scale finite and > 0 (LDPC_ERR_ARG otherwise): the LSBs per unit of channel value.  sq is the store
+ *                 rule of LDPC_MSG_I8: sq(x) = clamp(rintf(x), -L, L), ties to even, NaN gives 0, +-inf give +-L.
+ *   Start:        c[n] = sq(llr_scale * y[n]), one fp32 multiply; padding frames read y = 1.  The channel has q bits, as
+ *                 in flooding.  P[n] = c[n], R = 0, bit = (c < 0).
+ *   Row of a layer, edges e0 .. e0+D-1 in ascending edge id:
+ *                 t_k = P[col_k] - R_k                         exact, not clamped
+ *                 x_k = clamp(t_k, -L, L)                      the variable->check message
+ *                 the check row of LDPC_MSG_I8 on x_0 .. x_{D-1}: sign = XOR of (x_k < 0), so a zero counts as positive
+ *                   and does not kill the row; the two smallest |x_k| from the start value 1000, which reads L (a
+ *                   degree-1 row gives L); with ms_scale / ms_offset each of the two candidates, the start value
+ *                   among them as in LDPC_MSG_I8, becomes
+ *                   m' = fminf(truncf(fmaxf(m - ms_offset, 0) * ms_scale), L), fp32, in this order (ms_scale 0 meaning 1;
+ *                   ms_scale = 0.75 is exactly (3m) >> 2); edge k takes the second minimum iff it holds the first
+ *                 R_k = that message
+ *                 P[col_k] = clamp(t_k + R_k, -LP, LP)         from the UNCLAMPED t_k: only the posterior memory saturates
+ *                 bit = (P[col_k] < 0), kept current with every write; frozen frames keep theirs.
+ *   Rounds:       rounds, syndrome, freezing, iters, the CRC rule and both pack modes are LDPC_ALGO_LAYERED's, with
+ *                 early_term 0 or 1.
+ *   Soft output:  P after the last layer of the round the frame stopped in, in LSBs as fp32; extrinsic: P - c.
+ *   Debug taps:   0 = R, 2 = P, 3 = bits, as floats.
+ * Properties: with p = 16 and (1 + column degree) * 127 <= 32767 the posterior never saturates, and the rule is the
+ * plain layered schedule on integers.  The kernels compute in fp32 on integers far below 2^24, which is exact.
+ * Refusals, all before the device is touched: the LDPC_ERR_ARG cases above, and LDPC_TUNE_ON(FUSED) or LDPC_TUNE_ON(LDSP)
+ * is LDPC_ERR_UNSUPPORTED: it always runs the streaming layered engine.  post_bits != 0 with any other algorithm is
+ * LDPC_ERR_ARG.  LDPC_ALGO_LAYERED with LDPC_MSG_I8 stays LDPC_ERR_UNSUPPORTED: a different rule with different state is an
+ * algorithm of its own here, as LAYERED_HOST and LAYERED_BP are.  ldpc_decode, ldpc_decode_device, ldpc_decode_soft*,
+ * ldpc_decode_typed*, ldpc_decoder_create_multi, the debug taps, crc_kind and kernel times (spans named lfx) work as
+ * for LDPC_ALGO_LAYERED. */
+
 /* How the streaming flooding min-sum decoder (LDPC_ALGO_MS) stores its messages; the arithmetic is fp32 in one
  * operation order for all four.  F16 and F8 are this library's own definitions (the reference is fp32 only) and are
  * LDPC_ERR_UNSUPPORTED with every other algorithm (LDPC_ALGO_LAYERED_BP included: the layered engine is fp32) -- except that LDPC_ALGO_BP takes F16 (not F8); the one-launch and record kernels are fp32 and are never selected
@@ -147,8 +188,8 @@ enum ldpc_algo {
  *   LDPC_MSG_I8: fixed point, the datapath of a hardware decoder: saturating q-bit integers, q = msg_bits (config field
  *     below) one of 4, 5, 6, 8; 0 means 8, any other value is LDPC_ERR_ARG, as is a non-zero msg_bits with another
  *     msg_dtype.  L = 2^(q-1) - 1, that is 7, 15, 31 or 127.  A message is a two's-complement byte holding an integer in
- *     [-L, L]; the code -128 is never produced; the zero message is the byte 0x00.  LDPC_ALGO_MS only (every other
- *     algorithm: LDPC_ERR_UNSUPPORTED); the one-launch and record kernels are never selected (forcing them:
+ *     [-L, L]; the code -128 is never produced; the zero message is the byte 0x00.  LDPC_ALGO_MS, and LDPC_ALGO_LAYERED_FX
+ *     with the rule of its own above (every other algorithm: LDPC_ERR_UNSUPPORTED); the one-launch and record kernels are never selected (forcing them:
  *     LDPC_ERR_UNSUPPORTED, as for F8).  The kernels compute in fp32, which on integers below 2^24 is exact integer
  *     arithmetic, so the rule can be restated in integers alone:
  *       Store rule:  sq(x) = clamp(rintf(x), -L, L): ties go to even, NaN gives 0, +-inf gives +-L.
@@ -292,7 +333,10 @@ typedef struct ldpc_decoder_config {
      *      refused, so no caller's wrong size turns into a read behind its struct. ------------------------------------ */
     int32_t msg_bits;           /* LDPC_MSG_I8: q = 4, 5, 6 or 8 bits per message (0 = 8), enum ldpc_msg_dtype above;
                                    with any other msg_dtype it must be 0 (LDPC_ERR_ARG)                                */
-    int32_t msg_reserved[3];    /* must be 0 (LDPC_ERR_ARG otherwise)                                                  */
+    int32_t post_bits;          /* LDPC_ALGO_LAYERED_FX: p bits of posterior memory, msg_bits <= p <= 16 (0 = 16); with any
+                                   other algorithm it must be 0 (LDPC_ERR_ARG).  The first of the three words that were
+                                   msg_reserved[3]: size and offsets are unchanged                                     */
+    int32_t msg_reserved2[2];   /* must be 0 (LDPC_ERR_ARG otherwise)                                                  */
 } ldpc_decoder_config;
 
 /* two-bit fields of tune_flags: LDPC_TUNE_ON(f) forces the choice on, LDPC_TUNE_OFF(f) off */

@@ -46,10 +46,17 @@ class DecoderConfigCrc(DecoderConfig):
     _fields_ = [("crc_kind", ctypes.c_int32), ("crc_bits", ctypes.c_int32)]
 
 
+class _MsgTail(ctypes.Union):
+    """The three ints behind msg_bits: `post_bits; msg_reserved2[2]` in the header, which were `msg_reserved[3]`."""
+    _fields_ = [("msg_reserved", ctypes.c_int32 * 3), ("post_bits", ctypes.c_int32)]
+
+
 class DecoderConfigMsg(DecoderConfigCrc):
     """The whole of `ldpc_decoder_config`: DecoderConfigCrc is the struct as it was before msg_bits (a size the library
-    still accepts, msg_bits = 0); this one has msg_bits and the three reserved ints behind it."""
-    _fields_ = [("msg_bits", ctypes.c_int32), ("msg_reserved", ctypes.c_int32 * 3)]
+    still accepts, msg_bits = 0); this one has msg_bits and the three ints behind it.  The first of them is post_bits
+    (LDPC_ALGO_LAYERED_FX), which aliases msg_reserved[0]; the other two are reserved and must be 0."""
+    _anonymous_ = ("_tail",)
+    _fields_ = [("msg_bits", ctypes.c_int32), ("_tail", _MsgTail)]
 
 
 class DecodeStats(ctypes.Structure):

@@ -74,6 +74,10 @@ enum LayerRule {
                            bit): the row of LDPC_ALGO_BP (check_bp, flood_check.hpp) on x_k = q_k = P[col_k] - R_k:
                            R_k = out_k, P[col_k] = q_k + R_k.  The row's sign comes from (x < 0), never from a product of
                            messages, so an exact 0 does not kill a row */
+    kLayerFx,           /* layered min-sum in fixed point (LDPC_ALGO_LAYERED_FX, include/ldpc_hip.h has the rule bit for
+                           bit): the SUM path on one-byte R and int16 P with two clamps, the corrected row of LDPC_MSG_I8.
+                           Its kernels are the overloads of layer_kernel / layer_kernel_generic that take LayerFxArgs
+                           (below), instantiated by engine_layered_fx.hip alone */
 };
 
 /* What one wave of a layer launch works on: its rows, its lanes' part of the tile's P and R, the tile's hard bits. */
@@ -414,6 +418,292 @@ __global__ __launch_bounds__(kBlock) void layered_bp_extrinsic_kernel(float *__r
     soft[i] = soft[i] - chan;
 }
 
+/* ---- LDPC_ALGO_LAYERED_FX (kLayerFx): fixed-point layered min-sum, include/ldpc_hip.h has the rule bit for bit ----
+ *
+ * Storage: R [T][E][F] one byte per message (q8any: the loads and the store sequence of the flooding I8 kernels; the
+ * values are in [-L, L] before they reach the store, so its clamp at 127 never acts), P [T][N][F] two bytes per value
+ * (p16, below).  6 bytes per edge and frame-round instead of 16.  Arithmetic is fp32 on integers far below 2^24: exact.
+ * L, LP and the correction are launch arguments; plain min-sum runs the corrected row with scale 1 and offset 0, which is
+ * the identity on the integers of [0, L] and reads the start value 1000 as L, so there is one rule and not two. */
+
+/* the posterior memory: a two's-complement int16 holding an integer in [-LP, LP], LP <= 32767 (the row clamps, the
+ * store does not).  Per lane at V = 4 one dwordx2, at V = 2 one dword, at V = 1 one sign-extending short load.
+ *   load,  V = 4: global_load_dwordx2; per value one v_cvt_f32_i32 with an SDWA word select and sign extension (or
+ *                 v_bfe_i32 / v_ashrrev_i32 + v_cvt_f32_i32 where the backend prefers)
+ *   store, V = 4: 4 v_cvt_i32_f32 (exact: the values are integers) + 2 v_perm_b32 gathering the low words
+ *                 (selector 0x05040100) + global_store_dwordx2 = 1.5 VALU per value */
+struct p16 {
+    int16_t bits;
+};
+static_assert(sizeof(p16) == 2, "two bytes per posterior");
+typedef int vi2 __attribute__((ext_vector_type(2)));
+
+template <int V> __device__ __forceinline__ void vload(float (&d)[V], const p16 *p)
+{
+    static_assert(V == 1 || V == 2 || V == 4, "1, 2 or 4 posteriors per lane");
+    if constexpr (V == 1) {
+        d[0] = (float)(int)ld_stream(reinterpret_cast<const int16_t *>(p));
+    } else if constexpr (V == 2) {
+        const int w = ld_stream(reinterpret_cast<const int *>(p));
+        d[0] = (float)(int)(int16_t)w; d[1] = (float)(w >> 16);
+    } else {
+        const vi2 w = ld_stream(reinterpret_cast<const vi2 *>(p));
+        d[0] = (float)(int)(int16_t)w.x; d[1] = (float)(w.x >> 16);
+        d[2] = (float)(int)(int16_t)w.y; d[3] = (float)(w.y >> 16);
+    }
+}
+/* low words of two integers side by side: v_perm_b32, bytes 0..3 of the second operand, 4..7 of the first */
+__device__ __forceinline__ int p16_pack2(float lo, float hi)
+{
+    return (int)__builtin_amdgcn_perm((uint32_t)(int)hi, (uint32_t)(int)lo, 0x05040100u);
+}
+template <int V> __device__ __forceinline__ void vstore(p16 *p, const float (&s)[V])
+{
+    static_assert(V == 1 || V == 2 || V == 4, "1, 2 or 4 posteriors per lane");
+    if constexpr (V == 1) {
+        st_stream(reinterpret_cast<int16_t *>(p), (int16_t)(int)s[0]);
+    } else if constexpr (V == 2) {
+        st_stream(reinterpret_cast<int *>(p), p16_pack2(s[0], s[1]));
+    } else {
+        vi2 t; t.x = p16_pack2(s[0], s[1]); t.y = p16_pack2(s[2], s[3]);
+        st_stream(reinterpret_cast<vi2 *>(p), t);
+    }
+}
+
+struct LayerFxArgs {
+    p16 *__restrict__ P;                  /* [T][N][F] */
+    q8any *__restrict__ R;                /* [T][E][F] */
+    const int32_t *__restrict__ cls_e0;   /* as LayerArgs from here on */
+    const int32_t *__restrict__ edge_col;
+    uint64_t *hard;
+    const uint64_t *__restrict__ done;
+    int64_t E;
+    int32_t N;
+    int32_t n_rows;
+    int32_t rows_per_wave;
+    int32_t degree;
+    float L;                              /* 2^(q-1) - 1: messages */
+    float LP;                             /* 2^(p-1) - 1: posterior memory */
+};
+
+template <int V> struct LayerFxWave {
+    static constexpr size_t F = 64 * V;
+    int lane, r_begin, r_end;
+    p16 *Pt;
+    q8any *Rt;
+    uint64_t *hard_t;
+    uint64_t frozen[V];
+    __device__ __forceinline__ explicit LayerFxWave(const LayerFxArgs &a)
+    {
+        lane = threadIdx.x & 63;
+        const int tile = blockIdx.y;
+        const int wave = (int)blockIdx.x * kWavesPerBlock + wave_id_in_block();
+        r_begin = wave * a.rows_per_wave;
+        r_end = min(r_begin + a.rows_per_wave, a.n_rows);
+        Pt = a.P + (size_t)tile * (size_t)a.N * F + (size_t)lane * V;
+        Rt = a.R + (size_t)tile * (size_t)a.E * F + (size_t)lane * V;
+        hard_t = a.hard + (size_t)tile * (size_t)a.N * V;
+#pragma unroll
+        for (int v = 0; v < V; ++v) frozen[v] = a.done[(size_t)tile * V + v];
+    }
+    /* bit = (P < 0), kept current per write; frozen frames keep theirs */
+    __device__ __forceinline__ void set_bits(int col, const float (&p)[V]) const
+    {
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const uint64_t w = __ballot(p[v] < 0.0f);
+            if (lane == 0) {
+                const uint64_t old = hard_t[(size_t)col * V + v];
+                hard_t[(size_t)col * V + v] = (old & frozen[v]) | (w & ~frozen[v]);
+            }
+        }
+    }
+};
+
+/* a candidate of the row as its message: fminf(truncf(fmaxf(m - offset, 0) * scale), L), fp32, in this order */
+__device__ __forceinline__ float fx_corr(float m, const MsCorr &c, float L)
+{
+    return fminf(truncf(fmaxf(m - c.offset, 0.0f) * c.scale), L);
+}
+
+/* Rows of degree D in fixed point.  The SUM path of the float kernel (q = P - R, the check row, P = q + R) with the two
+ * clamps: the row reads x = clamp(t, -L, L), the posterior memory takes clamp(t + R, -LP, LP) from the unclamped t. */
+template <int D, int V, int RULE>
+__global__ __launch_bounds__(kBlock) void layer_kernel(const LayerFxArgs a, const MsCorr corr)
+{
+    static_assert(RULE == kLayerFx, "the fixed-point argument block belongs to kLayerFx");
+    constexpr size_t F = 64 * V;
+    if (tile_finished<V>(a.done, blockIdx.y)) return;
+    const LayerFxWave<V> w(a);
+    const float L = a.L, LP = a.LP;
+    for (int r = w.r_begin; r < w.r_end; ++r) {
+        const int e0 = a.cls_e0[r];
+        int col[D];
+#pragma unroll
+        for (int k = 0; k < D; ++k) col[k] = a.edge_col[e0 + k];
+        float t[D][V], m[D][V];
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            vload<V>(m[k], w.Rt + (size_t)(e0 + k) * F);
+            vload<V>(t[k], w.Pt + (size_t)col[k] * F);
+        }
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            float m1 = 1000.0f, m2 = 1000.0f;   /* min-sum's start value, a candidate like any other: fx_corr makes it L */
+            int idx = -1;
+            unsigned par = 0;
+            unsigned neg[D];
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                t[k][v] = t[k][v] - m[k][v];                                       /* t_k: exact, not clamped */
+                const float x = __builtin_amdgcn_fmed3f(t[k][v], -L, L);           /* the variable->check message */
+                const float mag = __builtin_fabsf(x);
+                neg[k] = (x < 0.0f) ? 1u : 0u;
+                par ^= neg[k];
+                if (mag < m1) { m2 = m1; m1 = mag; idx = k; }
+                else if (mag < m2) { m2 = mag; }
+            }
+            m1 = fx_corr(m1, corr, L); m2 = fx_corr(m2, corr, L);                  /* once per row */
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                const float b = (k == idx) ? m2 : m1;
+                const float rn = (par ^ neg[k]) ? -b : b;
+                m[k][v] = rn;
+                t[k][v] = __builtin_amdgcn_fmed3f(t[k][v] + rn, -LP, LP);          /* only the posterior memory saturates */
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            vstore<V>(w.Rt + (size_t)(e0 + k) * F, m[k]);
+            vstore<V>(w.Pt + (size_t)col[k] * F, t[k]);
+            w.set_bits(col[k], t[k]);
+        }
+    }
+}
+
+/* Rows of any degree in fixed point: two passes with run-time loops.  The first stores nothing (t_k may need 17 bits and
+ * cannot be parked in P as the float kernel parks q), the second forms t_k again from the edge's own old R and P: a row's
+ * columns are distinct and rows of a layer share none, so step k reads nothing an earlier step of this launch wrote. */
+template <int V, int RULE>
+__global__ __launch_bounds__(kBlock) void layer_kernel_generic(const LayerFxArgs a, const MsCorr corr)
+{
+    static_assert(RULE == kLayerFx, "the fixed-point argument block belongs to kLayerFx");
+    constexpr size_t F = 64 * V;
+    if (tile_finished<V>(a.done, blockIdx.y)) return;
+    const LayerFxWave<V> w(a);
+    const float L = a.L, LP = a.LP;
+    const int D = a.degree;
+    for (int r = w.r_begin; r < w.r_end; ++r) {
+        const int e0 = a.cls_e0[r];
+        float m1[V], m2[V];
+        int idx[V];
+        unsigned par[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) { m1[v] = 1000.0f; m2[v] = 1000.0f; idx[v] = -1; par[v] = 0; }
+        for (int k = 0; k < D; ++k) {
+            float m[V], p[V];
+            vload<V>(m, w.Rt + (size_t)(e0 + k) * F);
+            vload<V>(p, w.Pt + (size_t)a.edge_col[e0 + k] * F);
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                const float x = __builtin_amdgcn_fmed3f(p[v] - m[v], -L, L);
+                const float mag = __builtin_fabsf(x);
+                par[v] ^= (x < 0.0f) ? 1u : 0u;
+                if (mag < m1[v]) { m2[v] = m1[v]; m1[v] = mag; idx[v] = k; }
+                else if (mag < m2[v]) { m2[v] = mag; }
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < V; ++v) { m1[v] = fx_corr(m1[v], corr, L); m2[v] = fx_corr(m2[v], corr, L); }
+        for (int k = 0; k < D; ++k) {
+            const int col = a.edge_col[e0 + k];
+            float m[V], p[V];
+            vload<V>(m, w.Rt + (size_t)(e0 + k) * F);
+            vload<V>(p, w.Pt + (size_t)col * F);
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                const float t = p[v] - m[v];
+                const float b = (k == idx[v]) ? m2[v] : m1[v];
+                const unsigned s = par[v] ^ ((__builtin_amdgcn_fmed3f(t, -L, L) < 0.0f) ? 1u : 0u);
+                m[v] = s ? -b : b;
+                p[v] = __builtin_amdgcn_fmed3f(t + m[v], -LP, LP);
+            }
+            vstore<V>(w.Rt + (size_t)(e0 + k) * F, m);
+            vstore<V>(w.Pt + (size_t)col * F, p);
+            w.set_bits(col, p);
+        }
+    }
+}
+
+struct LayeredFxInitArgs {
+    const void *__restrict__ llr;   /* [frames][N], elements of the kernel's IN */
+    p16 *__restrict__ P;            /* [T][N][F] */
+    uint64_t *__restrict__ hard;    /* [T][N][V] */
+    int64_t frames;
+    int32_t N;
+    float llr_unit;                 /* narrow IN: y = (float)x * llr_unit (llr_input.hpp); unused for float */
+    float llr_scale;                /* LSBs per unit of channel value */
+    float L;
+};
+
+/* sq(llr_scale * y): one fp32 multiply, NaN -> 0 (MsgChan, once per channel value), the clamp, then the rounding to
+ * nearest even -- on a value in [-L, L], where rounding and clamping commute */
+__device__ __forceinline__ float fx_chan(float y, float llr_scale, float L)
+{
+    return __builtin_rintf(__builtin_amdgcn_fmed3f(MsgChan<q8any>::of(y, llr_scale), -L, L));
+}
+
+/* The quantising form of layered_init_kernel: P = c = sq(llr_scale * y) as int16, transposed into the tile layout;
+ * bits = c < 0.  Padding frames read y = 1.  All three input element types. */
+template <int V, typename IN>
+__global__ __launch_bounds__(kBlock) void layered_init_kernel(const LayeredFxInitArgs a)
+{
+    constexpr int F = 64 * V;
+    constexpr int LD = F + 1;
+    __shared__ float patch[kInitCols * LD];
+    const int tile = blockIdx.y;
+    const int n0 = blockIdx.x * kInitCols;
+    const IN *__restrict__ llr = static_cast<const IN *>(a.llr);
+    if constexpr (!std::is_same<IN, float>::value) {
+        llr_patch_fill<IN, F, LD, kInitCols, kBlock, false>(patch, llr, a.llr_unit, a.frames, a.N, tile, n0, 1.0f);
+    } else {
+        const int c = threadIdx.x & (kInitCols - 1);
+        const int n = n0 + c;
+        for (int f = threadIdx.x / kInitCols; f < F; f += kBlock / kInitCols) {
+            const int64_t frame = (int64_t)tile * F + f;
+            float y = 1.0f;
+            if (frame < a.frames && n < a.N) y = llr[(size_t)frame * a.N + n];
+            patch[c * LD + f] = y;
+        }
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    for (int c = threadIdx.x >> 6; c < kInitCols; c += kWavesPerBlock) {
+        const int n = n0 + c;
+        if (n >= a.N) break;
+        float y[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) y[v] = fx_chan(patch[c * LD + lane * V + v], a.llr_scale, a.L);
+        vstore<V>(a.P + ((size_t)tile * a.N + n) * F + (size_t)lane * V, y);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const uint64_t w = __ballot(y[v] < 0.0f);
+            if (lane == 0) a.hard[((size_t)tile * a.N + n) * V + v] = w;
+        }
+    }
+}
+
+/* LDPC_ALGO_LAYERED_FX, extrinsic soft output: soft_settle_kernel leaves P of every frame's stop round in the caller's
+ * buffer (each value written once); this one pass afterwards subtracts c = sq(llr_scale * y), integers both. */
+template <typename IN>
+__global__ __launch_bounds__(kBlock) void layered_fx_extrinsic_kernel(float *__restrict__ soft, const IN *__restrict__ llr,
+                                                                      float llr_scale, float L, int64_t count, float unit)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= count) return;
+    soft[i] = soft[i] - fx_chan(llr_value<IN>(llr[i], unit), llr_scale, L);
+}
+
 /* ------------------------------------------------------------- host side */
 
 constexpr int kMaxUnrolledLayerDegree = 24;
@@ -432,7 +722,11 @@ struct LayeredPlan {
     float ms_scale = 1.0f, ms_offset = 0.0f;
     int bp = 0;                     /* 1: LDPC_ALGO_LAYERED_BP (kLayerBp), chan = llr_scale * y: */
     float llr_scale = 1.0f;
-    DevBuf<float> P, R;
+    int fx = 0;                     /* 1: LDPC_ALGO_LAYERED_FX (kLayerFx): llr_scale, ms_scale / ms_offset (1 / 0 = plain) and */
+    float L = 127.0f, LP = 32767.0f;    /* the limits of a message and of the posterior memory */
+    DevBuf<float> P, R;             /* the float rules */
+    DevBuf<p16> Pfx;                /* kLayerFx: [T][N][F] int16 */
+    DevBuf<q8any> Rfx;              /* kLayerFx: [T][E][F] bytes */
     std::vector<LayerGroup> groups; /* ordered by layer */
 };
 
@@ -463,6 +757,11 @@ inline int layered_plan_create(LayeredPlan *pl, int32_t M, int32_t N, int64_t E,
         }
     }
     const size_t TF = (size_t)T * 64 * V;
+    if (pl->fx) {
+        if (pl->Pfx.alloc(TF * N) != hipSuccess) return -2;
+        if (pl->Rfx.alloc(TF * (size_t)E) != hipSuccess) return -2;
+        return 0;
+    }
     if (pl->P.alloc(TF * N) != hipSuccess) return -2;
     if (pl->R.alloc(TF * (size_t)E) != hipSuccess) return -2;
     return 0;
@@ -620,6 +919,116 @@ inline hipError_t layered_run(LayeredPlan *pl, const LayeredRun &r, hipStream_t 
 
 #endif  /* LDPC_ENGINE_LAYERED */
 
+/* The fixed-point rule is launched by a translation unit of its own (engine_layered_fx.hip defines
+ * LDPC_ENGINE_LAYERED_FX), so engine_layered.hip compiles what it always did. */
+#ifdef LDPC_ENGINE_LAYERED_FX
+using LayerFxFn = void (*)(const LayerFxArgs, const MsCorr);
+template <int V, int... D0>
+inline void layer_fx_table_fill(LayerFxFn *t, std::integer_sequence<int, D0...>)
+{
+    t[0] = layer_kernel_generic<V, kLayerFx>;
+    ((t[D0 + 1] = layer_kernel<D0 + 1, V, kLayerFx>), ...);
+}
+
+template <int V> __global__ void layered_fx_summary_kernel(const int32_t *iters, const uint64_t *done,
+                                                           int64_t frames, int32_t *summary)
+{
+    constexpr int F = 64 * V;
+    const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= frames) return;
+    const int64_t tile = f / F;
+    const int fi = (int)(f % F);
+    atomicMax(&summary[0], iters[f]);
+    if ((done[tile * V + fi % V] >> (fi / V)) & 1ull) atomicAdd(&summary[1], 1);
+}
+
+/* layered_run_v's round loop on the typed arrays: the same launches around the layers (state, syndrome, CRC, soft
+ * settle, pack, summary), 6 bytes per edge in the timing hook, spans of kind 2 */
+template <int V>
+inline hipError_t layered_fx_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_t s, int32_t *launched)
+{
+    constexpr int F = 64 * V;
+    const int tiles = (int)((r.frames + F - 1) / F);
+    const size_t slot = (size_t)pl->T * V;
+    LayerFxFn table[kMaxUnrolledLayerDegree + 1];
+    layer_fx_table_fill<V>(table, std::make_integer_sequence<int, kMaxUnrolledLayerDegree>());
+    const MsCorr corr{pl->ms_scale, pl->ms_offset};
+    const int rounds = r.tap_iter ? (r.tap_iter < r.max_iter ? r.tap_iter : r.max_iter) : r.max_iter;
+    constexpr int64_t kEdgeBytes = 2 * sizeof(q8any) + 2 * sizeof(p16);     /* R and P, each read and written */
+    hipError_t e;
+    if ((e = hipMemsetAsync(r.failw, 0, (size_t)(r.max_iter + 2) * slot * sizeof(uint64_t), s))) return e;
+    if ((e = hipMemsetAsync(r.summary, 0, (r.crc_bits ? 4 : 2) * sizeof(int32_t), s))) return e;
+    if ((e = hipMemsetAsync(pl->Rfx.p, 0, (size_t)tiles * F * (size_t)pl->E * sizeof(q8any), s))) return e;
+    {
+        LayeredFxInitArgs ia{r.llr.p, pl->Pfx.p, r.hard, r.frames, pl->N, r.llr.unit, pl->llr_scale, pl->L};
+        dim3 grid((pl->N + kInitCols - 1) / kInitCols, tiles);
+        dispatch_llr(r.llr.type, [&](auto in) {
+            layered_init_kernel<V, decltype(in)><<<grid, kBlock, 0, s>>>(ia);
+        });
+        StateArgs st{r.done, nullptr, r.iters, nullptr, r.frames, 0, r.max_iter, 1};
+        state_kernel<V><<<tiles, 64, 0, s>>>(st);
+    }
+    for (int it = 1; it <= rounds; ++it) {
+        for (auto &g : pl->groups) {
+            LayerFxArgs a{pl->Pfx.p, pl->Rfx.p, g.e0.p, r.edge_col, r.hard, r.done, pl->E, pl->N, g.count, 4, g.degree,
+                          pl->L, pl->LP};
+            const int waves = (g.count + a.rows_per_wave - 1) / a.rows_per_wave;
+            dim3 grid((waves + kWavesPerBlock - 1) / kWavesPerBlock, tiles);
+            const int k = g.degree <= kMaxUnrolledLayerDegree ? g.degree : 0;
+            if (r.span_begin && (e = r.span_begin(r.span_ctx, s, 2, g.degree,
+                                                  kEdgeBytes * g.degree * g.count * r.frames))) return e;
+            table[k]<<<grid, kBlock, 0, s>>>(a, corr);
+            if (r.span_end && (e = r.span_end(r.span_ctx, s))) return e;
+        }
+        if (!r.early_term && it != rounds) continue;
+        uint64_t *fw = r.failw + (size_t)it * slot;
+        SyndromeArgs sa{r.row_ptr, r.edge_col, r.hard, fw, r.done, pl->M, pl->N, 0, 0};
+        dim3 sgrid((pl->M + kBlock - 1) / kBlock, tiles);
+        syndrome_kernel<V><<<sgrid, kBlock, 0, s>>>(sa);
+        if (r.crc_bits) {
+            CrcTermArgs ca{r.hard, fw, r.done, r.crc_w, r.summary + 3, pl->N, r.crc_bits, TailRef{nullptr, 0, 0}};
+            crc_term_kernel<V><<<dim3((unsigned)tiles, V), 64 * crc_term_waves(r.crc_bits), 0, s>>>(ca);
+        }
+        if (r.soft) {       /* P of the frames that settle in this round, as floats (extrinsic: one pass at the end) */
+            SoftArgs so{pl->Pfx.p, nullptr, nullptr, nullptr, r.done, (r.early_term && it < rounds) ? fw : nullptr, r.soft,
+                        r.llr.p, nullptr, nullptr, pl->E, r.frames, pl->N, 0, TailRef{nullptr, 0, 0}, r.llr.unit};
+            if (r.span_begin && (e = r.span_begin(r.span_ctx, s, /*soft_settle_kernel*/ 7, 0, (int64_t)6 * pl->N * r.frames))) return e;
+            soft_settle_kernel<V, p16, float><<<dim3((unsigned)((pl->N + kInitCols - 1) / kInitCols), (unsigned)tiles), kBlock, 0, s>>>(so);
+            if (r.span_end && (e = r.span_end(r.span_ctx, s))) return e;
+        }
+        StateArgs st{r.done, fw, r.iters, nullptr, r.frames, it, r.max_iter, 1};
+        state_kernel<V><<<tiles, 64, 0, s>>>(st);
+    }
+    if (r.soft && r.soft_extrinsic) {       /* P - c, c = sq(llr_scale * y) */
+        const int64_t count = r.frames * (int64_t)pl->N;
+        dispatch_llr(r.llr.type, [&](auto in) {
+            using IN = decltype(in);
+            layered_fx_extrinsic_kernel<IN><<<(unsigned)((count + kBlock - 1) / kBlock), kBlock, 0, s>>>(
+                r.soft, static_cast<const IN *>(r.llr.p), pl->llr_scale, pl->L, count, r.llr.unit);
+        });
+    }
+    *launched = rounds;
+    PackArgs pa{r.hard, r.out_dev, r.iters, r.iters_dev, r.frames, r.out_bytes, pl->N, r.K, r.pack_mode};
+    if (r.out_dev || r.iters_dev) {
+        if (r.pack_mode == 0) {
+            pack_kernel<V><<<pack_grid<V>(r.K, tiles), kBlock, 0, s>>>(pa);
+        } else {
+            const int64_t n = r.out_bytes > r.frames ? r.out_bytes : r.frames;
+            pack_kernel<V><<<(unsigned)((n + kBlock - 1) / kBlock), kBlock, 0, s>>>(pa);
+        }
+    }
+    layered_fx_summary_kernel<V><<<(unsigned)((r.frames + 255) / 256), 256, 0, s>>>(r.iters, r.done, r.frames, r.summary);
+    return hipGetLastError();
+}
+
+inline hipError_t layered_fx_run(LayeredPlan *pl, const LayeredRun &r, hipStream_t s, int32_t *launched)
+{
+    if (pl->V == 1) return layered_fx_run_v<1>(pl, r, s, launched);
+    if (pl->V == 2) return layered_fx_run_v<2>(pl, r, s, launched);
+    return layered_fx_run_v<4>(pl, r, s, launched);
+}
+#endif  /* LDPC_ENGINE_LAYERED_FX */
+
 /* which: 0 = R [frame][E], 2 = P [frame][N], 3 = bits [frame][N] */
 inline hipError_t layered_dump(LayeredPlan *pl, int which, float *host_out, int64_t count, int64_t frames,
                                const uint64_t *hard_dev, const int32_t *)
@@ -631,9 +1040,19 @@ inline hipError_t layered_dump(LayeredPlan *pl, int which, float *host_out, int6
         if (count != frames * per) return hipErrorInvalidValue;
         const float *src = which == 0 ? pl->R.p : pl->P.p;
         std::vector<float> tile((size_t)per * F);
+        std::vector<int8_t> tile8(pl->fx && which == 0 ? tile.size() : 0);      /* kLayerFx: R bytes and P int16, widened */
+        std::vector<int16_t> tile16(pl->fx && which == 2 ? tile.size() : 0);
         for (int t = 0; t < tiles; ++t) {
-            hipError_t e = hipMemcpy(tile.data(), src + (size_t)t * per * F, tile.size() * sizeof(float),
-                                     hipMemcpyDeviceToHost);
+            hipError_t e;
+            if (!tile8.empty()) {
+                e = hipMemcpy(tile8.data(), pl->Rfx.p + (size_t)t * per * F, tile8.size(), hipMemcpyDeviceToHost);
+                for (size_t i = 0; i < tile8.size(); ++i) tile[i] = (float)tile8[i];
+            } else if (!tile16.empty()) {
+                e = hipMemcpy(tile16.data(), pl->Pfx.p + (size_t)t * per * F, tile16.size() * sizeof(int16_t), hipMemcpyDeviceToHost);
+                for (size_t i = 0; i < tile16.size(); ++i) tile[i] = (float)tile16[i];
+            } else {
+                e = hipMemcpy(tile.data(), src + (size_t)t * per * F, tile.size() * sizeof(float), hipMemcpyDeviceToHost);
+            }
             if (e != hipSuccess) return e;
             for (int fi = 0; fi < F; ++fi) {
                 const int64_t f = (int64_t)t * F + fi;

@@ -42,6 +42,9 @@ int pick_frames_per_lane(const ldpc_decoder_config &cfg, int32_t max_row_deg, in
      * kernels run in narrow waves, so only the column degree counts there; the layered kernel
      * holds a whole row (P and R) per lane. */
     int deg = (cfg.algo == LDPC_ALGO_LAYERED || cfg.algo == LDPC_ALGO_LAYERED_BP) ? max_row_deg : max_col_deg;
+    /* fixed-point layered: a row's R is a dword and its P a dwordx2 per lane at 4 frames per lane, whatever the row degree
+     * (the unrolled kernels hold the row in registers up to degree 24, the run-time kernel holds none of it) */
+    if (cfg.algo == LDPC_ALGO_LAYERED_FX) return cfg.max_batch >= 256 ? 4 : 1;
     if (cfg.algo == LDPC_ALGO_MS || cfg.algo == LDPC_ALGO_BP) deg = (deg + 1) / 2;   /* min-sum variable nodes (BP's too) need half the registers */
     /* one-byte messages (fp8, fixed point): 4 values are one dword per lane, the least a lane should move -- from one full tile on */
     if ((cfg.msg_dtype == LDPC_MSG_F8 || cfg.msg_dtype == LDPC_MSG_I8) && cfg.max_batch >= 256 && deg <= 8) return 4;
@@ -229,15 +232,16 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     if (cfg->max_iter <= 0 || cfg->max_iter > 100000) return set_error(LDPC_ERR_ARG, "max_iter out of range");
     if (cfg->algo != LDPC_ALGO_SP && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED &&
         cfg->algo != LDPC_ALGO_MS_FUSED && cfg->algo != LDPC_ALGO_LAYERED_HOST && cfg->algo != LDPC_ALGO_BP &&
-        cfg->algo != LDPC_ALGO_LAYERED_BP)
+        cfg->algo != LDPC_ALGO_LAYERED_BP && cfg->algo != LDPC_ALGO_LAYERED_FX)
         return set_error(LDPC_ERR_ARG, "unknown algo %d", cfg->algo);
+    const bool fx = cfg->algo == LDPC_ALGO_LAYERED_FX;
     /* comparisons written so that NaN fails them */
     if (!(cfg->ms_scale >= 0.0f && cfg->ms_scale <= 1.0f))
         return set_error(LDPC_ERR_ARG, "ms_scale must be 0 (off) or in (0, 1]");
     if (!(cfg->ms_offset >= 0.0f && cfg->ms_offset < 1000.0f))
         return set_error(LDPC_ERR_ARG, "ms_offset must be 0 (off) or in (0, 1000)");
     const bool ms_corr = cfg->ms_scale != 0.0f || cfg->ms_offset != 0.0f;
-    if (ms_corr && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED)
+    if (ms_corr && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED && !fx)
         return set_error(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset apply to LDPC_ALGO_MS and LDPC_ALGO_LAYERED only "
                     "(SP, BP and LAYERED_BP have no minimum to correct; MS_FUSED and LAYERED_HOST reproduce reference kernels)");
     const bool bp_row = cfg->algo == LDPC_ALGO_BP || cfg->algo == LDPC_ALGO_LAYERED_BP;      /* box-plus check node */
@@ -261,15 +265,27 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         return set_error(LDPC_ERR_ARG, "frames_per_lane must be 0, 1, 2 or 4");
     if (cfg->msg_dtype != LDPC_MSG_F32 && cfg->msg_dtype != LDPC_MSG_F16 && cfg->msg_dtype != LDPC_MSG_F8 && cfg->msg_dtype != LDPC_MSG_I8)
         return set_error(LDPC_ERR_ARG, "unknown msg_dtype %d", cfg->msg_dtype);
-    if (cfg->msg_reserved[0] || cfg->msg_reserved[1] || cfg->msg_reserved[2])
+    if (cfg->msg_reserved2[0] || cfg->msg_reserved2[1])
         return set_error(LDPC_ERR_ARG, "msg_reserved must be 0");
+    if (cfg->post_bits != 0 && !fx)
+        return set_error(LDPC_ERR_ARG, "post_bits=%d belongs to LDPC_ALGO_LAYERED_FX (algo is %d)", cfg->post_bits, cfg->algo);
+    if (fx && cfg->msg_dtype != LDPC_MSG_I8)
+        return set_error(LDPC_ERR_ARG, "LDPC_ALGO_LAYERED_FX is defined on fixed-point messages: msg_dtype must be LDPC_MSG_I8, not %d", cfg->msg_dtype);
     if (cfg->msg_bits != 0 && cfg->msg_dtype != LDPC_MSG_I8)
         return set_error(LDPC_ERR_ARG, "msg_bits=%d belongs to LDPC_MSG_I8 (msg_dtype is %d)", cfg->msg_bits, cfg->msg_dtype);
     if (cfg->msg_bits != 0 && cfg->msg_bits != 4 && cfg->msg_bits != 5 && cfg->msg_bits != 6 && cfg->msg_bits != 8)
         return set_error(LDPC_ERR_ARG, "msg_bits must be 0 (8), 4, 5, 6 or 8, not %d", cfg->msg_bits);
-    if (cfg->msg_dtype == LDPC_MSG_I8 && cfg->algo != LDPC_ALGO_MS)
-        return set_error(LDPC_ERR_UNSUPPORTED, "fixed-point messages (LDPC_MSG_I8) are built for flooding min-sum only "
-                    "(SP and BP have no integer datapath here; the layered decoders and the reference-reproducing ones are fp32)");
+    if (cfg->msg_dtype == LDPC_MSG_I8 && cfg->algo != LDPC_ALGO_MS && !fx)
+        return set_error(LDPC_ERR_UNSUPPORTED, "fixed-point messages (LDPC_MSG_I8) are built for flooding min-sum and, as an algorithm of "
+                    "its own, LDPC_ALGO_LAYERED_FX (SP and BP have no integer datapath here; LDPC_ALGO_LAYERED, LAYERED_BP and the "
+                    "reference-reproducing decoders are fp32)");
+    if (fx) {
+        const int q = cfg->msg_bits ? cfg->msg_bits : 8;
+        if (cfg->post_bits != 0 && (cfg->post_bits < q || cfg->post_bits > 16))
+            return set_error(LDPC_ERR_ARG, "post_bits=%d must be 0 (16) or in [msg_bits=%d, 16]", cfg->post_bits, q);
+        if (cfg->layer_rows <= 0 || g->M % cfg->layer_rows)
+            return set_error(LDPC_ERR_ARG, "LDPC_ALGO_LAYERED_FX: layer_rows=%d must be positive and divide M=%d", cfg->layer_rows, g->M);
+    }
     /* written so that NaN fails it */
     if (cfg->msg_dtype == LDPC_MSG_I8 && !(cfg->llr_scale > 0.0f && cfg->llr_scale <= 3.402823466e38f))
         return set_error(LDPC_ERR_ARG, "LDPC_MSG_I8: llr_scale must be positive and finite (the LSBs per unit of channel value)");
@@ -391,12 +407,19 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
                             "posteriors fit in LDS");
         }
         d->use_fused = true;
-    } else if (cfg->algo == LDPC_ALGO_LAYERED_HOST || cfg->algo == LDPC_ALGO_LAYERED_BP) {
+    } else if (cfg->algo == LDPC_ALGO_LAYERED_HOST || cfg->algo == LDPC_ALGO_LAYERED_BP || fx) {
         /* the streaming layered engine always.  LAYERED_BP: the record kernels' 16-byte check record holds two minima and
          * cannot hold a row's D independent messages, and the LDS-resident kernel carries no box-plus row */
         d->layered.host_arith = cfg->algo == LDPC_ALGO_LAYERED_HOST;
         d->layered.bp = cfg->algo == LDPC_ALGO_LAYERED_BP;
         d->layered.llr_scale = cfg->llr_scale;
+        if (fx) {       /* plain min-sum is the corrected row with scale 1, offset 0: the identity on [0, L] */
+            d->layered.fx = 1;
+            d->layered.L = (float)((1 << ((cfg->msg_bits ? cfg->msg_bits : 8) - 1)) - 1);
+            d->layered.LP = (float)((1 << ((cfg->post_bits ? cfg->post_bits : 16) - 1)) - 1);
+            d->layered.ms_scale = d->ms_scale;
+            d->layered.ms_offset = d->ms_offset;
+        }
         int rc = ldpc::layered_plan_create(&d->layered, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows, d->T, d->V);
         if (rc == -1) return set_error(LDPC_ERR_ARG, "layer_rows=%d must divide M=%d and rows of a layer "
                                   "must not share a column", cfg->layer_rows, g->M);
@@ -637,7 +660,8 @@ static int decode_device_in(ldpc_decoder *d, const ldpc::LlrIn &in, int64_t fram
                             : ldpc::engine_fused_run(&d->fused, run, s, &d->last_iterations);
         if (e == hipSuccess) e = ldpc::span_end(d, s);
         rc = (e == hipSuccess) ? LDPC_OK : set_error(LDPC_ERR_HIP, "fused decode: %s", hipGetErrorString(e));
-    } else if (d->cfg.algo == LDPC_ALGO_LAYERED || d->cfg.algo == LDPC_ALGO_LAYERED_HOST || d->cfg.algo == LDPC_ALGO_LAYERED_BP) {
+    } else if (d->cfg.algo == LDPC_ALGO_LAYERED || d->cfg.algo == LDPC_ALGO_LAYERED_HOST || d->cfg.algo == LDPC_ALGO_LAYERED_BP ||
+               d->cfg.algo == LDPC_ALGO_LAYERED_FX) {
         ldpc::LayeredRun run;
         run.span_begin = [](void *c, hipStream_t st, int kind, int deg, int64_t bytes) {
             return ldpc::span_begin((ldpc_decoder *)c, st, kind, deg, bytes);
@@ -652,7 +676,8 @@ static int decode_device_in(ldpc_decoder *d, const ldpc::LlrIn &in, int64_t fram
         run.row_ptr = d->row_ptr.p; run.edge_col = d->edge_col.p; run.summary = d->summary.p;
         run.crc_w = d->crc_w.p; run.crc_bits = d->cfg.crc_kind ? d->cfg.crc_bits : 0;
         run.soft = d->soft.dst; run.soft_extrinsic = d->soft.kind == LDPC_SOFT_EXTRINSIC ? 1 : 0;
-        hipError_t e = ldpc::engine_layered_run(&d->layered, run, s, &d->last_iterations);
+        hipError_t e = d->layered.fx ? ldpc::engine_layered_fx_run(&d->layered, run, s, &d->last_iterations)
+                                     : ldpc::engine_layered_run(&d->layered, run, s, &d->last_iterations);
         rc = (e == hipSuccess) ? LDPC_OK
                                : set_error(LDPC_ERR_HIP, "layered decode: %s", hipGetErrorString(e));
     } else {
