@@ -30,9 +30,8 @@ hipError_t engine_ldsp_plan_create(LdspPlan *pl, int32_t M, int32_t N, int64_t E
                                    const Tune &tune, int flood);
 hipError_t engine_ldsp_run(LdspPlan *pl, const FusedRun &r, hipStream_t s, int32_t *launched);
 hipError_t engine_fused_run(FusedPlan *pl, const FusedRun &r, hipStream_t s, int32_t *launched);
+/* every rule of the streaming layered engine (LayeredPlan::rule); engine_layered_fx.hip holds the fixed-point storage's half */
 hipError_t engine_layered_run(LayeredPlan *pl, const LayeredRun &r, hipStream_t s, int32_t *launched);
-/* engine_layered_fx.hip: LDPC_ALGO_LAYERED_FX, the same plan and run blocks on one-byte R and int16 P */
-hipError_t engine_layered_fx_run(LayeredPlan *pl, const LayeredRun &r, hipStream_t s, int32_t *launched);
 /* llr_input.hip: y[i] = x[i] * unit for count elements of a narrow type (LlrIn::type != kLlrF32), enqueued on s */
 hipError_t engine_llr_widen(const LlrIn &in, float *y_dev, int64_t count, hipStream_t s);
 

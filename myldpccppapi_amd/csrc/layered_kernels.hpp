@@ -21,14 +21,31 @@
  * written once per edge).  Frozen frames keep their hard bits (bit masks), their
  * P/R keep evolving unread -- no per-lane predication in the hot loop.
  *
- * LDPC_ALGO_LAYERED_BP (kLayerBp, below) is the same engine with the box-plus row of flood_check.hpp.
+ * Structure.  A rule (LayerRule) is a row arithmetic; a storage (LayerStore) is the element types of P and R.  The four
+ * float rules run on StoreF32; kLayerFx (LDPC_ALGO_LAYERED_FX) runs on StoreFx, one-byte R and int16 P.  Everything around
+ * the row arithmetic is written once over the storage:
+ *   LayerArgs<S>, LayerWave<V, S>     the argument block of a layer launch and what one wave of it works on, set_bits
+ *                                     included (LayerArgsFx adds L and LP behind the block, so the float kernarg has none)
+ *   layer_kernel_generic<V, RULE>     rows of any degree, the rule's row as a function with run-time loops
+ *   layered_init_kernel<V, IN, S, SCALED>, layered_extrinsic_kernel<IN, S>
+ *                                     the start of P and the extrinsic pass, the value of a channel sample (layer_chan:
+ *                                     y, llr_scale * y, or sq(llr_scale * y)) chosen at compile time
+ *   layered_run_v<V, S>               the driver: one round loop, one kernel table per rule
+ * The exception is the unrolled kernel, layer_kernel<D, V, RULE>: an overload per storage, and the float one writes the
+ * wave's set-up and the hard-bit write out by hand (the reason stands above it).
+ * The row arithmetics are not merged: layer_kernel's two float paths and its fixed-point body, layer_row_generic,
+ * layer_row_generic_bp and layer_row_generic_fx each follow their own definition bit for bit.  engine_layered.hip
+ * instantiates the driver on StoreF32 and engine_layered_fx.hip on StoreFx, so the library's largest unit builds beside the
+ * other; the host driver calls engine_layered_run, which forwards by LayeredPlan::rule.
  */
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <map>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -39,33 +56,13 @@
 
 namespace ldpc {
 
-struct LayerArgs {
-    float *__restrict__ P;                /* [T][N][F] */
-    float *__restrict__ R;                /* [T][E][F] */
-    const int32_t *__restrict__ cls_e0;   /* rows of this (layer, degree) group: first edge id */
-    const int32_t *__restrict__ edge_col; /* [E] */
-    uint64_t *hard;                       /* [T][N][V] */
-    const uint64_t *__restrict__ done;    /* [T][V] */
-    int64_t E;
-    int32_t N;
-    int32_t n_rows;
-    int32_t rows_per_wave;
-    int32_t degree;
-};
-
-/* OpenCL sign(): +-1, +-0 for +-0, 0 for NaN. */
-__device__ __forceinline__ float cl_sign(float x)
-{
-    return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : (x == 0.0f ? x : 0.0f));
-}
-
 /* The row rules of the streaming layered kernels; the frame around them -- rows of a wave, loads, stores, hard bits --
  * is layer_kernel's (unrolled degrees) and layer_kernel_generic's (any degree). */
 enum LayerRule {
     kLayerFused = 0,    /* the arithmetic of the fused kernel decodeOnceTDMP (above) */
-    kLayerCorr,         /* the same with normalized / offset min-sum (LayeredPlan::corr): the row's two candidates b, c go
-                           through ms_corr (flood_common.hpp) before the sign and the per-edge selection -- two operations
-                           per row, not per edge */
+    kLayerCorr,         /* the same with normalized / offset min-sum (LayeredPlan::ms_scale / ms_offset): the row's two
+                           candidates b, c go through ms_corr (flood_common.hpp) before the sign and the per-edge selection
+                           -- two operations per row, not per edge */
     kLayerHost,         /* the reference's host-layered path, Coder::decodeOnceTDMP (MyLdpc.cpp:889-976) over refreshQTDMP /
                            refreshRTDMP / refreshPostPTDMP (decodeCL.c:228-259, 283-290): q_k = P - R_k, the check node of
                            the MS kernel chain (sign = XOR of `< 0`, magnitude = fmin chain from 1000 == check_ms),
@@ -76,18 +73,121 @@ enum LayerRule {
                            messages, so an exact 0 does not kill a row */
     kLayerFx,           /* layered min-sum in fixed point (LDPC_ALGO_LAYERED_FX, include/ldpc_hip.h has the rule bit for
                            bit): the SUM path on one-byte R and int16 P with two clamps, the corrected row of LDPC_MSG_I8.
-                           Its kernels are the overloads of layer_kernel / layer_kernel_generic that take LayerFxArgs
-                           (below), instantiated by engine_layered_fx.hip alone */
+                           The only rule on StoreFx: the overload of layer_kernel on LayerArgsFx and layer_row_generic_fx in
+                           layer_kernel_generic, launched by the driver's instantiation in engine_layered_fx.hip */
 };
 
+/* ---- LDPC_ALGO_LAYERED_FX (kLayerFx): fixed-point layered min-sum, include/ldpc_hip.h has the rule bit for bit ----
+ *
+ * Storage: R [T][E][F] one byte per message (q8any: the loads and the store sequence of the flooding I8 kernels; the
+ * values are in [-L, L] before they reach the store, so its clamp at 127 never acts), P [T][N][F] two bytes per value
+ * (p16, below).  6 bytes per edge and frame-round instead of 16.  Arithmetic is fp32 on integers far below 2^24: exact.
+ * L, LP and the correction are launch arguments; plain min-sum runs the corrected row with scale 1 and offset 0, which is
+ * the identity on the integers of [0, L] and reads the start value 1000 as L, so there is one rule and not two. */
+
+/* the posterior memory: a two's-complement int16 holding an integer in [-LP, LP], LP <= 32767 (the row clamps, the
+ * store does not).  Per lane at V = 4 one dwordx2, at V = 2 one dword, at V = 1 one sign-extending short load.
+ *   load,  V = 4: global_load_dwordx2; per value one v_cvt_f32_i32 with an SDWA word select and sign extension (or
+ *                 v_bfe_i32 / v_ashrrev_i32 + v_cvt_f32_i32 where the backend prefers)
+ *   store, V = 4: 4 v_cvt_i32_f32 (exact: the values are integers) + 2 v_perm_b32 gathering the low words
+ *                 (selector 0x05040100) + global_store_dwordx2 = 1.5 VALU per value */
+struct p16 {
+    int16_t bits;
+};
+static_assert(sizeof(p16) == 2, "two bytes per posterior");
+typedef int vi2 __attribute__((ext_vector_type(2)));
+
+template <int V> __device__ __forceinline__ void vload(float (&d)[V], const p16 *p)
+{
+    static_assert(V == 1 || V == 2 || V == 4, "1, 2 or 4 posteriors per lane");
+    if constexpr (V == 1) {
+        d[0] = (float)(int)ld_stream(reinterpret_cast<const int16_t *>(p));
+    } else if constexpr (V == 2) {
+        const int w = ld_stream(reinterpret_cast<const int *>(p));
+        d[0] = (float)(int)(int16_t)w; d[1] = (float)(w >> 16);
+    } else {
+        const vi2 w = ld_stream(reinterpret_cast<const vi2 *>(p));
+        d[0] = (float)(int)(int16_t)w.x; d[1] = (float)(w.x >> 16);
+        d[2] = (float)(int)(int16_t)w.y; d[3] = (float)(w.y >> 16);
+    }
+}
+/* low words of two integers side by side: v_perm_b32, bytes 0..3 of the second operand, 4..7 of the first */
+__device__ __forceinline__ int p16_pack2(float lo, float hi)
+{
+    return (int)__builtin_amdgcn_perm((uint32_t)(int)hi, (uint32_t)(int)lo, 0x05040100u);
+}
+template <int V> __device__ __forceinline__ void vstore(p16 *p, const float (&s)[V])
+{
+    static_assert(V == 1 || V == 2 || V == 4, "1, 2 or 4 posteriors per lane");
+    if constexpr (V == 1) {
+        st_stream(reinterpret_cast<int16_t *>(p), (int16_t)(int)s[0]);
+    } else if constexpr (V == 2) {
+        st_stream(reinterpret_cast<int *>(p), p16_pack2(s[0], s[1]));
+    } else {
+        vi2 t; t.x = p16_pack2(s[0], s[1]); t.y = p16_pack2(s[2], s[3]);
+        st_stream(reinterpret_cast<vi2 *>(p), t);
+    }
+}
+
+template <class S> struct LayerArgs;
+struct LayerArgsFx;
+
+/* A storage: the element types of the posterior and the message array, the argument block a layer kernel on it takes,
+ * and the byte counts the timing hooks report. */
+template <typename PT, typename RT> struct LayerStore {
+    typedef PT P;
+    typedef RT R;
+    static constexpr bool kFixed = !std::is_same<PT, float>::value;
+    typedef std::conditional_t<kFixed, LayerArgsFx, LayerArgs<LayerStore>> Args;
+    static constexpr int64_t kEdgeBytes = 2 * sizeof(RT) + 2 * sizeof(PT);      /* R and P, each read and written */
+    static constexpr int64_t kSettleBytes = sizeof(PT) + sizeof(float);         /* soft settle: P read, a float written */
+};
+typedef LayerStore<float, float> StoreF32;      /* kLayerFused, kLayerCorr, kLayerHost, kLayerBp */
+typedef LayerStore<p16, q8any> StoreFx;         /* kLayerFx */
+/* the storage of a rule (a struct and not a conditional, so that the kernels' symbols stay readable) */
+template <int RULE> struct RuleOn { typedef StoreF32 Store; };
+template <> struct RuleOn<kLayerFx> { typedef StoreFx Store; };
+template <int RULE> using RuleStore = typename RuleOn<RULE>::Store;
+
+template <class S> struct LayerArgs {
+    typename S::P *__restrict__ P;        /* [T][N][F] */
+    typename S::R *__restrict__ R;        /* [T][E][F] */
+    const int32_t *__restrict__ cls_e0;   /* rows of this (layer, degree) group: first edge id */
+    const int32_t *__restrict__ edge_col; /* [E] */
+    uint64_t *hard;                       /* [T][N][V] */
+    const uint64_t *__restrict__ done;    /* [T][V] */
+    int64_t E;
+    int32_t N;
+    int32_t n_rows;
+    int32_t rows_per_wave;
+    int32_t degree;
+};
+struct LayerArgsFx : LayerArgs<StoreFx> {
+    float L;                              /* 2^(q-1) - 1: messages */
+    float LP;                             /* 2^(p-1) - 1: posterior memory */
+};
+
+/* OpenCL sign(): +-1, +-0 for +-0, 0 for NaN. */
+__device__ __forceinline__ float cl_sign(float x)
+{
+    return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : (x == 0.0f ? x : 0.0f));
+}
+
+/* a candidate of the fixed-point row as its message: fminf(truncf(fmaxf(m - offset, 0) * scale), L), fp32, in this order */
+__device__ __forceinline__ float fx_corr(float m, const MsCorr &c, float L)
+{
+    return fminf(truncf(fmaxf(m - c.offset, 0.0f) * c.scale), L);
+}
+
 /* What one wave of a layer launch works on: its rows, its lanes' part of the tile's P and R, the tile's hard bits. */
-template <int V> struct LayerWave {
+template <int V, class S> struct LayerWave {
     static constexpr size_t F = 64 * V;
     int lane, r_begin, r_end;
-    float *Pt, *Rt;
+    typename S::P *Pt;
+    typename S::R *Rt;
     uint64_t *hard_t;
     uint64_t frozen[V];
-    __device__ __forceinline__ explicit LayerWave(const LayerArgs &a)
+    __device__ __forceinline__ explicit LayerWave(const LayerArgs<S> &a)
     {
         lane = threadIdx.x & 63;
         const int tile = blockIdx.y;
@@ -114,11 +214,14 @@ template <int V> struct LayerWave {
     }
 };
 
-/* Rows of degree D: one load and one store of R and of P per edge.  Every instantiation takes the MsCorr, so that one
- * table of one pointer type launches them all; only kLayerCorr reads it. */
+/* Rows of degree D on StoreF32: one load and one store of R and of P per edge.  Every instantiation takes the MsCorr, so
+ * that one table of one pointer type launches all four rules; only kLayerCorr reads it.  The wave's set-up and its hard-bit
+ * write are written out here and not taken from LayerWave: with the struct, all 288 instantiations move by a few
+ * instructions and four of the kLayerBp ones spill one to three more SGPRs. */
 template <int D, int V, int RULE>
-__global__ __launch_bounds__(kBlock) void layer_kernel(const LayerArgs a, const MsCorr corr)
+__global__ __launch_bounds__(kBlock) void layer_kernel(const LayerArgs<StoreF32> a, const MsCorr corr)
 {
+    static_assert(RULE != kLayerFx, "the fixed-point rule has the overload on LayerArgsFx");
     constexpr size_t F = 64 * V;
     const int lane = threadIdx.x & 63;
     const int tile = blockIdx.y;
@@ -200,9 +303,65 @@ __global__ __launch_bounds__(kBlock) void layer_kernel(const LayerArgs a, const 
     }
 }
 
+/* Rows of degree D in fixed point.  The SUM path of the float kernel (q = P - R, the check row, P = q + R) with the two
+ * clamps: the row reads x = clamp(t, -L, L), the posterior memory takes clamp(t + R, -LP, LP) from the unclamped t. */
+template <int D, int V, int RULE>
+__global__ __launch_bounds__(kBlock) void layer_kernel(const LayerArgsFx a, const MsCorr corr)
+{
+    static_assert(RULE == kLayerFx, "the fixed-point argument block belongs to kLayerFx");
+    constexpr size_t F = 64 * V;
+    if (tile_finished<V>(a.done, blockIdx.y)) return;
+    const LayerWave<V, StoreFx> w(a);
+    const float L = a.L, LP = a.LP;
+    for (int r = w.r_begin; r < w.r_end; ++r) {
+        const int e0 = a.cls_e0[r];
+        int col[D];
+#pragma unroll
+        for (int k = 0; k < D; ++k) col[k] = a.edge_col[e0 + k];
+        float t[D][V], m[D][V];
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            vload<V>(m[k], w.Rt + (size_t)(e0 + k) * F);
+            vload<V>(t[k], w.Pt + (size_t)col[k] * F);
+        }
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            float m1 = 1000.0f, m2 = 1000.0f;   /* min-sum's start value, a candidate like any other: fx_corr makes it L */
+            int idx = -1;
+            unsigned par = 0;
+            unsigned neg[D];
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                t[k][v] = t[k][v] - m[k][v];                                       /* t_k: exact, not clamped */
+                const float x = __builtin_amdgcn_fmed3f(t[k][v], -L, L);           /* the variable->check message */
+                const float mag = __builtin_fabsf(x);
+                neg[k] = (x < 0.0f) ? 1u : 0u;
+                par ^= neg[k];
+                if (mag < m1) { m2 = m1; m1 = mag; idx = k; }
+                else if (mag < m2) { m2 = mag; }
+            }
+            m1 = fx_corr(m1, corr, L); m2 = fx_corr(m2, corr, L);                  /* once per row */
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                const float b = (k == idx) ? m2 : m1;
+                const float rn = (par ^ neg[k]) ? -b : b;
+                m[k][v] = rn;
+                t[k][v] = __builtin_amdgcn_fmed3f(t[k][v] + rn, -LP, LP);          /* only the posterior memory saturates */
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            vstore<V>(w.Rt + (size_t)(e0 + k) * F, m[k]);
+            vstore<V>(w.Pt + (size_t)col[k] * F, t[k]);
+            w.set_bits(col[k], t[k]);
+        }
+    }
+}
+
 /* A min-sum row of any degree: the same arithmetic with run-time loops, values re-read. */
 template <int V, bool CORR>
-__device__ __forceinline__ void layer_row_generic(const LayerArgs &a, const LayerWave<V> &w, int e0, const MsCorr corr)
+__device__ __forceinline__ void layer_row_generic(const LayerArgs<StoreF32> &a, const LayerWave<V, StoreF32> &w, int e0,
+                                                  const MsCorr corr)
 {
     constexpr size_t F = 64 * V;
     const int D = a.degree;
@@ -257,7 +416,7 @@ __device__ __forceinline__ void layer_row_generic(const LayerArgs &a, const Laye
  * are distinct (edges ascend strictly within a row) and rows of a layer share no column (layered_plan_create), so what
  * step k stores at R_k and P[col_k] is read by no other edge of this row and by no other row of this launch. */
 template <int V>
-__device__ __forceinline__ void layer_row_generic_bp(const LayerArgs &a, const LayerWave<V> &w, int e0)
+__device__ __forceinline__ void layer_row_generic_bp(const LayerArgs<StoreF32> &a, const LayerWave<V, StoreF32> &w, int e0)
 {
     constexpr size_t F = 64 * V;
     const int D = a.degree;
@@ -311,15 +470,65 @@ __device__ __forceinline__ void layer_row_generic_bp(const LayerArgs &a, const L
     }
 }
 
+/* A fixed-point row of any degree: two passes with run-time loops.  The first stores nothing (t_k may need 17 bits and
+ * cannot be parked in P as the float row parks q), the second forms t_k again from the edge's own old R and P: a row's
+ * columns are distinct and rows of a layer share none, so step k reads nothing an earlier step of this launch wrote. */
+template <int V>
+__device__ __forceinline__ void layer_row_generic_fx(const LayerArgsFx &a, const LayerWave<V, StoreFx> &w, int e0,
+                                                     const MsCorr corr)
+{
+    constexpr size_t F = 64 * V;
+    const float L = a.L, LP = a.LP;
+    const int D = a.degree;
+    float m1[V], m2[V];
+    int idx[V];
+    unsigned par[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) { m1[v] = 1000.0f; m2[v] = 1000.0f; idx[v] = -1; par[v] = 0; }
+    for (int k = 0; k < D; ++k) {
+        float m[V], p[V];
+        vload<V>(m, w.Rt + (size_t)(e0 + k) * F);
+        vload<V>(p, w.Pt + (size_t)a.edge_col[e0 + k] * F);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const float x = __builtin_amdgcn_fmed3f(p[v] - m[v], -L, L);
+            const float mag = __builtin_fabsf(x);
+            par[v] ^= (x < 0.0f) ? 1u : 0u;
+            if (mag < m1[v]) { m2[v] = m1[v]; m1[v] = mag; idx[v] = k; }
+            else if (mag < m2[v]) { m2[v] = mag; }
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) { m1[v] = fx_corr(m1[v], corr, L); m2[v] = fx_corr(m2[v], corr, L); }
+    for (int k = 0; k < D; ++k) {
+        const int col = a.edge_col[e0 + k];
+        float m[V], p[V];
+        vload<V>(m, w.Rt + (size_t)(e0 + k) * F);
+        vload<V>(p, w.Pt + (size_t)col * F);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const float t = p[v] - m[v];
+            const float b = (k == idx[v]) ? m2[v] : m1[v];
+            const unsigned s = par[v] ^ ((__builtin_amdgcn_fmed3f(t, -L, L) < 0.0f) ? 1u : 0u);
+            m[v] = s ? -b : b;
+            p[v] = __builtin_amdgcn_fmed3f(t + m[v], -LP, LP);
+        }
+        vstore<V>(w.Rt + (size_t)(e0 + k) * F, m);
+        vstore<V>(w.Pt + (size_t)col * F, p);
+        w.set_bits(col, p);
+    }
+}
+
 /* Rows of any degree (LayerArgs::degree); the host arithmetic has unrolled degrees only. */
 template <int V, int RULE>
-__global__ __launch_bounds__(kBlock) void layer_kernel_generic(const LayerArgs a, const MsCorr corr)
+__global__ __launch_bounds__(kBlock) void layer_kernel_generic(const typename RuleStore<RULE>::Args a, const MsCorr corr)
 {
     static_assert(RULE != kLayerHost, "no generic row with the host arithmetic");
     if (tile_finished<V>(a.done, blockIdx.y)) return;
-    const LayerWave<V> w(a);
+    const LayerWave<V, RuleStore<RULE>> w(a);
     for (int r = w.r_begin; r < w.r_end; ++r) {
         if constexpr (RULE == kLayerBp) layer_row_generic_bp<V>(a, w, a.cls_e0[r]);
+        else if constexpr (RULE == kLayerFx) layer_row_generic_fx<V>(a, w, a.cls_e0[r], corr);
         else layer_row_generic<V, RULE == kLayerCorr>(a, w, a.cls_e0[r], corr);
     }
 }
@@ -349,314 +558,37 @@ __global__ __launch_bounds__(kBlock) void layered_hard_kernel(const float *__res
     }
 }
 
-struct LayeredInitArgs {
-    const void *__restrict__ llr;   /* [frames][N], elements of the kernel's IN */
-    float *__restrict__ P;          /* [T][N][F] */
-    uint64_t *__restrict__ hard;    /* [T][N][V] */
+/* The value a rule starts P[n] with, and subtracts again for an extrinsic soft output, as a function of the channel
+ * sample y:
+ *   StoreF32          y (lP = postCode, decodeCL.c:331-334)
+ *   StoreF32, SCALED  LDPC_ALGO_LAYERED_BP: chan = llr_scale * y, one fp32 multiply, padding frames included
+ *   StoreFx           LDPC_ALGO_LAYERED_FX: sq(llr_scale * y): one fp32 multiply, NaN -> 0 (MsgChan, once per channel value),
+ *                     the clamp, then the rounding to nearest even -- on a value in [-L, L], where rounding and clamping
+ *                     commute.  SCALED is false. */
+template <class S, bool SCALED> __device__ __forceinline__ float layer_chan(float y, float llr_scale, float L)
+{
+    static_assert(!(S::kFixed && SCALED), "the fixed-point storage has one form");
+    if constexpr (S::kFixed) return __builtin_rintf(__builtin_amdgcn_fmed3f(MsgChan<q8any>::of(y, llr_scale), -L, L));
+    else if constexpr (SCALED) return llr_scale * y;
+    else return y;
+}
+
+template <class S> struct LayeredInitArgs {
+    const void *__restrict__ llr;       /* [frames][N], elements of the kernel's IN */
+    typename S::P *__restrict__ P;      /* [T][N][F] */
+    uint64_t *__restrict__ hard;        /* [T][N][V] */
     int64_t frames;
     int32_t N;
-    int32_t zero_bits;              /* host-layered path: bits start at 0 (the reference: undefined) */
-    float llr_unit;                 /* narrow IN: y = (float)x * llr_unit (llr_input.hpp); unused for float */
+    int32_t zero_bits;                  /* host-layered path: bits start at 0 (the reference: undefined) */
+    float llr_unit;                     /* narrow IN: y = (float)x * llr_unit (llr_input.hpp); unused for float */
+    float llr_scale, L;                 /* layer_chan's; the plain form reads neither */
 };
 
-/* lP = postCode (decodeCL.c:331-334), transposed into the tile layout; bits = y < 0.  SCALED (LDPC_ALGO_LAYERED_BP): the
- * value is chan = scale * y, one fp32 multiply, padding frames included; the other algorithms' instantiation has no
- * multiply and does not read scale.  IN: element type of the caller's buffer; a narrow one goes through llr_patch_fill
- * (llr_input.hpp), float through the loop below. */
-template <int V, typename IN, bool SCALED>
-__global__ __launch_bounds__(kBlock) void layered_init_kernel(const LayeredInitArgs a, const float scale)
-{
-    constexpr int F = 64 * V;
-    constexpr int LD = F + 1;
-    __shared__ float patch[kInitCols * LD];
-    const int tile = blockIdx.y;
-    const int n0 = blockIdx.x * kInitCols;
-    const IN *__restrict__ llr = static_cast<const IN *>(a.llr);
-    if constexpr (!std::is_same<IN, float>::value) {
-        llr_patch_fill<IN, F, LD, kInitCols, kBlock, SCALED>(patch, llr, a.llr_unit, a.frames, a.N, tile, n0, scale);
-    } else {
-        const int c = threadIdx.x & (kInitCols - 1);
-        const int n = n0 + c;
-        for (int f = threadIdx.x / kInitCols; f < F; f += kBlock / kInitCols) {
-            const int64_t frame = (int64_t)tile * F + f;
-            float y = 1.0f;
-            if (frame < a.frames && n < a.N) y = llr[(size_t)frame * a.N + n];
-            if (SCALED) y = scale * y;
-            patch[c * LD + f] = y;
-        }
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    for (int c = threadIdx.x >> 6; c < kInitCols; c += kWavesPerBlock) {
-        const int n = n0 + c;
-        if (n >= a.N) break;
-        float y[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) y[v] = patch[c * LD + lane * V + v];
-        vstore<V>(a.P + ((size_t)tile * a.N + n) * F + (size_t)lane * V, y);
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            const uint64_t w = __ballot(y[v] < 0.0f);
-            if (lane == 0) a.hard[((size_t)tile * a.N + n) * V + v] = a.zero_bits ? 0ull : w;
-        }
-    }
-}
-
-/* LDPC_ALGO_LAYERED_BP, extrinsic soft output: soft_settle_kernel leaves the posterior of every frame's stop round in the
- * caller's buffer (each value written once); this one pass afterwards subtracts chan = scale * y -- the fp32 product
- * formed first, then one subtraction.  The empty asm keeps the product a value of its own: contracted into an fma the
- * difference would be rounded once, from the exact product.  IN: element type of the caller's buffer; y is the product
- * x * unit of a narrow element, formed first (llr_value). */
-template <typename IN = float>
-__global__ __launch_bounds__(kBlock) void layered_bp_extrinsic_kernel(float *__restrict__ soft, const IN *__restrict__ llr,
-                                                                      const float scale, int64_t count, const float unit = 1.0f)
-{
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= count) return;
-    float chan = scale * llr_value<IN>(llr[i], unit);
-    asm volatile("" : "+v"(chan));
-    soft[i] = soft[i] - chan;
-}
-
-/* ---- LDPC_ALGO_LAYERED_FX (kLayerFx): fixed-point layered min-sum, include/ldpc_hip.h has the rule bit for bit ----
- *
- * Storage: R [T][E][F] one byte per message (q8any: the loads and the store sequence of the flooding I8 kernels; the
- * values are in [-L, L] before they reach the store, so its clamp at 127 never acts), P [T][N][F] two bytes per value
- * (p16, below).  6 bytes per edge and frame-round instead of 16.  Arithmetic is fp32 on integers far below 2^24: exact.
- * L, LP and the correction are launch arguments; plain min-sum runs the corrected row with scale 1 and offset 0, which is
- * the identity on the integers of [0, L] and reads the start value 1000 as L, so there is one rule and not two. */
-
-/* the posterior memory: a two's-complement int16 holding an integer in [-LP, LP], LP <= 32767 (the row clamps, the
- * store does not).  Per lane at V = 4 one dwordx2, at V = 2 one dword, at V = 1 one sign-extending short load.
- *   load,  V = 4: global_load_dwordx2; per value one v_cvt_f32_i32 with an SDWA word select and sign extension (or
- *                 v_bfe_i32 / v_ashrrev_i32 + v_cvt_f32_i32 where the backend prefers)
- *   store, V = 4: 4 v_cvt_i32_f32 (exact: the values are integers) + 2 v_perm_b32 gathering the low words
- *                 (selector 0x05040100) + global_store_dwordx2 = 1.5 VALU per value */
-struct p16 {
-    int16_t bits;
-};
-static_assert(sizeof(p16) == 2, "two bytes per posterior");
-typedef int vi2 __attribute__((ext_vector_type(2)));
-
-template <int V> __device__ __forceinline__ void vload(float (&d)[V], const p16 *p)
-{
-    static_assert(V == 1 || V == 2 || V == 4, "1, 2 or 4 posteriors per lane");
-    if constexpr (V == 1) {
-        d[0] = (float)(int)ld_stream(reinterpret_cast<const int16_t *>(p));
-    } else if constexpr (V == 2) {
-        const int w = ld_stream(reinterpret_cast<const int *>(p));
-        d[0] = (float)(int)(int16_t)w; d[1] = (float)(w >> 16);
-    } else {
-        const vi2 w = ld_stream(reinterpret_cast<const vi2 *>(p));
-        d[0] = (float)(int)(int16_t)w.x; d[1] = (float)(w.x >> 16);
-        d[2] = (float)(int)(int16_t)w.y; d[3] = (float)(w.y >> 16);
-    }
-}
-/* low words of two integers side by side: v_perm_b32, bytes 0..3 of the second operand, 4..7 of the first */
-__device__ __forceinline__ int p16_pack2(float lo, float hi)
-{
-    return (int)__builtin_amdgcn_perm((uint32_t)(int)hi, (uint32_t)(int)lo, 0x05040100u);
-}
-template <int V> __device__ __forceinline__ void vstore(p16 *p, const float (&s)[V])
-{
-    static_assert(V == 1 || V == 2 || V == 4, "1, 2 or 4 posteriors per lane");
-    if constexpr (V == 1) {
-        st_stream(reinterpret_cast<int16_t *>(p), (int16_t)(int)s[0]);
-    } else if constexpr (V == 2) {
-        st_stream(reinterpret_cast<int *>(p), p16_pack2(s[0], s[1]));
-    } else {
-        vi2 t; t.x = p16_pack2(s[0], s[1]); t.y = p16_pack2(s[2], s[3]);
-        st_stream(reinterpret_cast<vi2 *>(p), t);
-    }
-}
-
-struct LayerFxArgs {
-    p16 *__restrict__ P;                  /* [T][N][F] */
-    q8any *__restrict__ R;                /* [T][E][F] */
-    const int32_t *__restrict__ cls_e0;   /* as LayerArgs from here on */
-    const int32_t *__restrict__ edge_col;
-    uint64_t *hard;
-    const uint64_t *__restrict__ done;
-    int64_t E;
-    int32_t N;
-    int32_t n_rows;
-    int32_t rows_per_wave;
-    int32_t degree;
-    float L;                              /* 2^(q-1) - 1: messages */
-    float LP;                             /* 2^(p-1) - 1: posterior memory */
-};
-
-template <int V> struct LayerFxWave {
-    static constexpr size_t F = 64 * V;
-    int lane, r_begin, r_end;
-    p16 *Pt;
-    q8any *Rt;
-    uint64_t *hard_t;
-    uint64_t frozen[V];
-    __device__ __forceinline__ explicit LayerFxWave(const LayerFxArgs &a)
-    {
-        lane = threadIdx.x & 63;
-        const int tile = blockIdx.y;
-        const int wave = (int)blockIdx.x * kWavesPerBlock + wave_id_in_block();
-        r_begin = wave * a.rows_per_wave;
-        r_end = min(r_begin + a.rows_per_wave, a.n_rows);
-        Pt = a.P + (size_t)tile * (size_t)a.N * F + (size_t)lane * V;
-        Rt = a.R + (size_t)tile * (size_t)a.E * F + (size_t)lane * V;
-        hard_t = a.hard + (size_t)tile * (size_t)a.N * V;
-#pragma unroll
-        for (int v = 0; v < V; ++v) frozen[v] = a.done[(size_t)tile * V + v];
-    }
-    /* bit = (P < 0), kept current per write; frozen frames keep theirs */
-    __device__ __forceinline__ void set_bits(int col, const float (&p)[V]) const
-    {
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            const uint64_t w = __ballot(p[v] < 0.0f);
-            if (lane == 0) {
-                const uint64_t old = hard_t[(size_t)col * V + v];
-                hard_t[(size_t)col * V + v] = (old & frozen[v]) | (w & ~frozen[v]);
-            }
-        }
-    }
-};
-
-/* a candidate of the row as its message: fminf(truncf(fmaxf(m - offset, 0) * scale), L), fp32, in this order */
-__device__ __forceinline__ float fx_corr(float m, const MsCorr &c, float L)
-{
-    return fminf(truncf(fmaxf(m - c.offset, 0.0f) * c.scale), L);
-}
-
-/* Rows of degree D in fixed point.  The SUM path of the float kernel (q = P - R, the check row, P = q + R) with the two
- * clamps: the row reads x = clamp(t, -L, L), the posterior memory takes clamp(t + R, -LP, LP) from the unclamped t. */
-template <int D, int V, int RULE>
-__global__ __launch_bounds__(kBlock) void layer_kernel(const LayerFxArgs a, const MsCorr corr)
-{
-    static_assert(RULE == kLayerFx, "the fixed-point argument block belongs to kLayerFx");
-    constexpr size_t F = 64 * V;
-    if (tile_finished<V>(a.done, blockIdx.y)) return;
-    const LayerFxWave<V> w(a);
-    const float L = a.L, LP = a.LP;
-    for (int r = w.r_begin; r < w.r_end; ++r) {
-        const int e0 = a.cls_e0[r];
-        int col[D];
-#pragma unroll
-        for (int k = 0; k < D; ++k) col[k] = a.edge_col[e0 + k];
-        float t[D][V], m[D][V];
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            vload<V>(m[k], w.Rt + (size_t)(e0 + k) * F);
-            vload<V>(t[k], w.Pt + (size_t)col[k] * F);
-        }
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            float m1 = 1000.0f, m2 = 1000.0f;   /* min-sum's start value, a candidate like any other: fx_corr makes it L */
-            int idx = -1;
-            unsigned par = 0;
-            unsigned neg[D];
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-                t[k][v] = t[k][v] - m[k][v];                                       /* t_k: exact, not clamped */
-                const float x = __builtin_amdgcn_fmed3f(t[k][v], -L, L);           /* the variable->check message */
-                const float mag = __builtin_fabsf(x);
-                neg[k] = (x < 0.0f) ? 1u : 0u;
-                par ^= neg[k];
-                if (mag < m1) { m2 = m1; m1 = mag; idx = k; }
-                else if (mag < m2) { m2 = mag; }
-            }
-            m1 = fx_corr(m1, corr, L); m2 = fx_corr(m2, corr, L);                  /* once per row */
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-                const float b = (k == idx) ? m2 : m1;
-                const float rn = (par ^ neg[k]) ? -b : b;
-                m[k][v] = rn;
-                t[k][v] = __builtin_amdgcn_fmed3f(t[k][v] + rn, -LP, LP);          /* only the posterior memory saturates */
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            vstore<V>(w.Rt + (size_t)(e0 + k) * F, m[k]);
-            vstore<V>(w.Pt + (size_t)col[k] * F, t[k]);
-            w.set_bits(col[k], t[k]);
-        }
-    }
-}
-
-/* Rows of any degree in fixed point: two passes with run-time loops.  The first stores nothing (t_k may need 17 bits and
- * cannot be parked in P as the float kernel parks q), the second forms t_k again from the edge's own old R and P: a row's
- * columns are distinct and rows of a layer share none, so step k reads nothing an earlier step of this launch wrote. */
-template <int V, int RULE>
-__global__ __launch_bounds__(kBlock) void layer_kernel_generic(const LayerFxArgs a, const MsCorr corr)
-{
-    static_assert(RULE == kLayerFx, "the fixed-point argument block belongs to kLayerFx");
-    constexpr size_t F = 64 * V;
-    if (tile_finished<V>(a.done, blockIdx.y)) return;
-    const LayerFxWave<V> w(a);
-    const float L = a.L, LP = a.LP;
-    const int D = a.degree;
-    for (int r = w.r_begin; r < w.r_end; ++r) {
-        const int e0 = a.cls_e0[r];
-        float m1[V], m2[V];
-        int idx[V];
-        unsigned par[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) { m1[v] = 1000.0f; m2[v] = 1000.0f; idx[v] = -1; par[v] = 0; }
-        for (int k = 0; k < D; ++k) {
-            float m[V], p[V];
-            vload<V>(m, w.Rt + (size_t)(e0 + k) * F);
-            vload<V>(p, w.Pt + (size_t)a.edge_col[e0 + k] * F);
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                const float x = __builtin_amdgcn_fmed3f(p[v] - m[v], -L, L);
-                const float mag = __builtin_fabsf(x);
-                par[v] ^= (x < 0.0f) ? 1u : 0u;
-                if (mag < m1[v]) { m2[v] = m1[v]; m1[v] = mag; idx[v] = k; }
-                else if (mag < m2[v]) { m2[v] = mag; }
-            }
-        }
-#pragma unroll
-        for (int v = 0; v < V; ++v) { m1[v] = fx_corr(m1[v], corr, L); m2[v] = fx_corr(m2[v], corr, L); }
-        for (int k = 0; k < D; ++k) {
-            const int col = a.edge_col[e0 + k];
-            float m[V], p[V];
-            vload<V>(m, w.Rt + (size_t)(e0 + k) * F);
-            vload<V>(p, w.Pt + (size_t)col * F);
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                const float t = p[v] - m[v];
-                const float b = (k == idx[v]) ? m2[v] : m1[v];
-                const unsigned s = par[v] ^ ((__builtin_amdgcn_fmed3f(t, -L, L) < 0.0f) ? 1u : 0u);
-                m[v] = s ? -b : b;
-                p[v] = __builtin_amdgcn_fmed3f(t + m[v], -LP, LP);
-            }
-            vstore<V>(w.Rt + (size_t)(e0 + k) * F, m);
-            vstore<V>(w.Pt + (size_t)col * F, p);
-            w.set_bits(col, p);
-        }
-    }
-}
-
-struct LayeredFxInitArgs {
-    const void *__restrict__ llr;   /* [frames][N], elements of the kernel's IN */
-    p16 *__restrict__ P;            /* [T][N][F] */
-    uint64_t *__restrict__ hard;    /* [T][N][V] */
-    int64_t frames;
-    int32_t N;
-    float llr_unit;                 /* narrow IN: y = (float)x * llr_unit (llr_input.hpp); unused for float */
-    float llr_scale;                /* LSBs per unit of channel value */
-    float L;
-};
-
-/* sq(llr_scale * y): one fp32 multiply, NaN -> 0 (MsgChan, once per channel value), the clamp, then the rounding to
- * nearest even -- on a value in [-L, L], where rounding and clamping commute */
-__device__ __forceinline__ float fx_chan(float y, float llr_scale, float L)
-{
-    return __builtin_rintf(__builtin_amdgcn_fmed3f(MsgChan<q8any>::of(y, llr_scale), -L, L));
-}
-
-/* The quantising form of layered_init_kernel: P = c = sq(llr_scale * y) as int16, transposed into the tile layout;
- * bits = c < 0.  Padding frames read y = 1.  All three input element types. */
-template <int V, typename IN>
-__global__ __launch_bounds__(kBlock) void layered_init_kernel(const LayeredFxInitArgs a)
+/* P = layer_chan(y), transposed into the tile layout; bits = P < 0.  The patch holds y: padding frames read y = 1.  IN:
+ * element type of the caller's buffer; a narrow one goes through llr_patch_fill (llr_input.hpp), float through the loop
+ * below. */
+template <int V, typename IN, class S, bool SCALED>
+__global__ __launch_bounds__(kBlock) void layered_init_kernel(const LayeredInitArgs<S> a)
 {
     constexpr int F = 64 * V;
     constexpr int LD = F + 1;
@@ -683,25 +615,44 @@ __global__ __launch_bounds__(kBlock) void layered_init_kernel(const LayeredFxIni
         if (n >= a.N) break;
         float y[V];
 #pragma unroll
-        for (int v = 0; v < V; ++v) y[v] = fx_chan(patch[c * LD + lane * V + v], a.llr_scale, a.L);
+        for (int v = 0; v < V; ++v) y[v] = layer_chan<S, SCALED>(patch[c * LD + lane * V + v], a.llr_scale, a.L);
         vstore<V>(a.P + ((size_t)tile * a.N + n) * F + (size_t)lane * V, y);
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             const uint64_t w = __ballot(y[v] < 0.0f);
-            if (lane == 0) a.hard[((size_t)tile * a.N + n) * V + v] = w;
+            if (lane == 0) a.hard[((size_t)tile * a.N + n) * V + v] = a.zero_bits ? 0ull : w;
         }
     }
 }
 
-/* LDPC_ALGO_LAYERED_FX, extrinsic soft output: soft_settle_kernel leaves P of every frame's stop round in the caller's
- * buffer (each value written once); this one pass afterwards subtracts c = sq(llr_scale * y), integers both. */
-template <typename IN>
-__global__ __launch_bounds__(kBlock) void layered_fx_extrinsic_kernel(float *__restrict__ soft, const IN *__restrict__ llr,
-                                                                      float llr_scale, float L, int64_t count, float unit)
+/* Extrinsic soft output of a rule whose P does not start at y (LAYERED_BP, LAYERED_FX): soft_settle_kernel leaves the
+ * posterior of every frame's stop round in the caller's buffer (each value written once); this one pass afterwards
+ * subtracts layer_chan(y), formed first, then one subtraction.  The empty asm keeps the scaled form's product a value of
+ * its own: contracted into an fma the difference would be rounded once, from the exact product (the fixed-point value is an
+ * integer and loses nothing by it).  IN: element type of the caller's buffer; y is the product x * unit of a narrow element,
+ * formed first (llr_value). */
+template <typename IN, class S>
+__global__ __launch_bounds__(kBlock) void layered_extrinsic_kernel(float *__restrict__ soft, const IN *__restrict__ llr,
+                                                                   float llr_scale, float L, int64_t count, float unit)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= count) return;
-    soft[i] = soft[i] - fx_chan(llr_value<IN>(llr[i], unit), llr_scale, L);
+    float chan = layer_chan<S, !S::kFixed>(llr_value<IN>(llr[i], unit), llr_scale, L);
+    asm volatile("" : "+v"(chan));
+    soft[i] = soft[i] - chan;
+}
+
+/* summary[0] = the largest iteration count, summary[1] = the number of frames that stopped clean */
+template <int V> __global__ void layered_summary_kernel(const int32_t *iters, const uint64_t *done,
+                                                        int64_t frames, int32_t *summary)
+{
+    constexpr int F = 64 * V;
+    const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= frames) return;
+    const int64_t tile = f / F;
+    const int fi = (int)(f % F);
+    atomicMax(&summary[0], iters[f]);
+    if ((done[tile * V + fi % V] >> (fi / V)) & 1ull) atomicAdd(&summary[1], 1);
 }
 
 /* ------------------------------------------------------------- host side */
@@ -717,16 +668,15 @@ struct LayeredPlan {
     int32_t M = 0, N = 0, layer_rows = 0;
     int64_t E = 0;
     int T = 0, V = 1;
-    int host_arith = 0;             /* 1: LDPC_ALGO_LAYERED_HOST (kLayerHost) */
-    int corr = 0;                   /* 1: normalized / offset min-sum (kLayerCorr) with these: */
-    float ms_scale = 1.0f, ms_offset = 0.0f;
-    int bp = 0;                     /* 1: LDPC_ALGO_LAYERED_BP (kLayerBp), chan = llr_scale * y: */
-    float llr_scale = 1.0f;
-    int fx = 0;                     /* 1: LDPC_ALGO_LAYERED_FX (kLayerFx): llr_scale, ms_scale / ms_offset (1 / 0 = plain) and */
-    float L = 127.0f, LP = 32767.0f;    /* the limits of a message and of the posterior memory */
-    DevBuf<float> P, R;             /* the float rules */
-    DevBuf<p16> Pfx;                /* kLayerFx: [T][N][F] int16 */
-    DevBuf<q8any> Rfx;              /* kLayerFx: [T][E][F] bytes */
+    LayerRule rule = kLayerFused;   /* the one row arithmetic of this decoder; kLayerFx runs on StoreFx, the others on StoreF32 */
+    float ms_scale = 1.0f, ms_offset = 0.0f;    /* kLayerCorr, kLayerFx (1 / 0 = plain): normalized / offset min-sum */
+    float llr_scale = 1.0f;         /* kLayerBp: chan = llr_scale * y; kLayerFx: LSBs per unit of channel value */
+    float L = 127.0f, LP = 32767.0f;    /* kLayerFx: the limits of a message and of the posterior memory */
+    DevBuf<float> P, R;             /* StoreF32: [T][N][F], [T][E][F]; only the rule's storage is allocated */
+    DevBuf<p16> Pfx;                /* StoreFx: [T][N][F] int16 */
+    DevBuf<q8any> Rfx;              /* StoreFx: [T][E][F] bytes */
+    template <class S> DevBuf<typename S::P> &post() { if constexpr (S::kFixed) return Pfx; else return P; }
+    template <class S> DevBuf<typename S::R> &msgs() { if constexpr (S::kFixed) return Rfx; else return R; }
     std::vector<LayerGroup> groups; /* ordered by layer */
 };
 
@@ -757,14 +707,10 @@ inline int layered_plan_create(LayeredPlan *pl, int32_t M, int32_t N, int64_t E,
         }
     }
     const size_t TF = (size_t)T * 64 * V;
-    if (pl->fx) {
-        if (pl->Pfx.alloc(TF * N) != hipSuccess) return -2;
-        if (pl->Rfx.alloc(TF * (size_t)E) != hipSuccess) return -2;
-        return 0;
-    }
-    if (pl->P.alloc(TF * N) != hipSuccess) return -2;
-    if (pl->R.alloc(TF * (size_t)E) != hipSuccess) return -2;
-    return 0;
+    const bool ok = pl->rule == kLayerFx
+                        ? pl->Pfx.alloc(TF * N) == hipSuccess && pl->Rfx.alloc(TF * (size_t)E) == hipSuccess
+                        : pl->P.alloc(TF * N) == hipSuccess && pl->R.alloc(TF * (size_t)E) == hipSuccess;
+    return ok ? 0 : -2;
 }
 
 struct LayeredRun {
@@ -790,56 +736,52 @@ struct LayeredRun {
     int32_t soft_extrinsic = 0;
 };
 
-/* The launching code instantiates every kernel above: only the translation unit that defines
- * LDPC_ENGINE_LAYERED (engine_layered.hip) compiles it; the host driver calls engine_layered_run. */
+/* The launching code instantiates the kernels above: only the translation units that define LDPC_ENGINE_LAYERED compile
+ * it, engine_layered.hip for StoreF32 and engine_layered_fx.hip for StoreFx; the host driver calls engine_layered_run. */
 #ifdef LDPC_ENGINE_LAYERED
-using LayerFn = void (*)(const LayerArgs, const MsCorr);
+template <class S> using LayerFn = void (*)(const typename S::Args, const MsCorr);
 /* t[D] = the kernel of the rule for rows of degree D = 1 .. kMaxUnrolledLayerDegree, t[0] = the one for wider rows */
 template <int V, int RULE, int... D0>
-inline void layer_table_fill(LayerFn *t, std::integer_sequence<int, D0...>)
+inline void layer_table_fill(LayerFn<RuleStore<RULE>> *t, std::integer_sequence<int, D0...>)
 {
     if constexpr (RULE == kLayerHost) t[0] = nullptr;
     else t[0] = layer_kernel_generic<V, RULE>;
     ((t[D0 + 1] = layer_kernel<D0 + 1, V, RULE>), ...);
 }
 
-template <int V> __global__ void layered_summary_kernel(const int32_t *iters, const uint64_t *done,
-                                                        int64_t frames, int32_t *summary)
-{
-    constexpr int F = 64 * V;
-    const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= frames) return;
-    const int64_t tile = f / F;
-    const int fi = (int)(f % F);
-    atomicMax(&summary[0], iters[f]);
-    if ((done[tile * V + fi % V] >> (fi / V)) & 1ull) atomicAdd(&summary[1], 1);
-}
-
-template <int V>
+template <int V, class S>
 inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_t s, int32_t *launched)
 {
     constexpr int F = 64 * V;
+    const LayerRule rule = pl->rule;
+    const bool has_chan = S::kFixed || rule == kLayerBp;    /* P does not start at y (layer_chan) */
+    typename S::P *const P = pl->template post<S>().p;
+    typename S::R *const R = pl->template msgs<S>().p;
     const int tiles = (int)((r.frames + F - 1) / F);
     const size_t slot = (size_t)pl->T * V;
-    LayerFn table[kMaxUnrolledLayerDegree + 1];
+    LayerFn<S> table[kMaxUnrolledLayerDegree + 1];
     const std::make_integer_sequence<int, kMaxUnrolledLayerDegree> degrees;
-    if (pl->corr) layer_table_fill<V, kLayerCorr>(table, degrees);
-    else if (pl->bp) layer_table_fill<V, kLayerBp>(table, degrees);
-    else if (pl->host_arith) layer_table_fill<V, kLayerHost>(table, degrees);
+    if constexpr (S::kFixed) layer_table_fill<V, kLayerFx>(table, degrees);
+    else if (rule == kLayerCorr) layer_table_fill<V, kLayerCorr>(table, degrees);
+    else if (rule == kLayerBp) layer_table_fill<V, kLayerBp>(table, degrees);
+    else if (rule == kLayerHost) layer_table_fill<V, kLayerHost>(table, degrees);
     else layer_table_fill<V, kLayerFused>(table, degrees);
     const MsCorr corr{pl->ms_scale, pl->ms_offset};
     const int rounds = r.tap_iter ? (r.tap_iter < r.max_iter ? r.tap_iter : r.max_iter) : r.max_iter;
     hipError_t e;
     if ((e = hipMemsetAsync(r.failw, 0, (size_t)(r.max_iter + 2) * slot * sizeof(uint64_t), s))) return e;
     if ((e = hipMemsetAsync(r.summary, 0, (r.crc_bits ? 4 : 2) * sizeof(int32_t), s))) return e;
-    if ((e = hipMemsetAsync(pl->R.p, 0, (size_t)tiles * F * (size_t)pl->E * sizeof(float), s))) return e;
+    if ((e = hipMemsetAsync(R, 0, (size_t)tiles * F * (size_t)pl->E * sizeof(typename S::R), s))) return e;
     {
-        LayeredInitArgs ia{r.llr.p, pl->P.p, r.hard, r.frames, pl->N, pl->host_arith, r.llr.unit};
+        LayeredInitArgs<S> ia{r.llr.p, P, r.hard, r.frames, pl->N, rule == kLayerHost, r.llr.unit, pl->llr_scale, pl->L};
         dim3 grid((pl->N + kInitCols - 1) / kInitCols, tiles);
         dispatch_llr(r.llr.type, [&](auto in) {
             using IN = decltype(in);
-            const auto init = pl->bp ? layered_init_kernel<V, IN, true> : layered_init_kernel<V, IN, false>;
-            init<<<grid, kBlock, 0, s>>>(ia, pl->llr_scale);
+            auto init = layered_init_kernel<V, IN, S, false>;
+            if constexpr (!S::kFixed) {
+                if (rule == kLayerBp) init = layered_init_kernel<V, IN, S, true>;
+            }
+            init<<<grid, kBlock, 0, s>>>(ia);
         });
         StateArgs st{r.done, nullptr, r.iters, nullptr, r.frames, 0, r.max_iter, 1};
         state_kernel<V><<<tiles, 64, 0, s>>>(st);
@@ -847,20 +789,24 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
     int it = 0;
     for (it = 1; it <= rounds; ++it) {
         for (auto &g : pl->groups) {
-            LayerArgs a{pl->P.p, pl->R.p, g.e0.p, r.edge_col, r.hard, r.done, pl->E, pl->N, g.count,
-                        4, g.degree};
+            typename S::Args a{};
+            static_cast<LayerArgs<S> &>(a) = LayerArgs<S>{P, R, g.e0.p, r.edge_col, r.hard, r.done, pl->E, pl->N, g.count,
+                                                         4, g.degree};
+            if constexpr (S::kFixed) { a.L = pl->L; a.LP = pl->LP; }
             const int waves = (g.count + a.rows_per_wave - 1) / a.rows_per_wave;
             dim3 grid((waves + kWavesPerBlock - 1) / kWavesPerBlock, tiles);
             const int k = g.degree <= kMaxUnrolledLayerDegree ? g.degree : 0;
             if (!table[k]) return hipErrorInvalidValue;      /* host arithmetic: unrolled degrees only */
             if (r.span_begin && (e = r.span_begin(r.span_ctx, s, 2, g.degree,
-                                                  (int64_t)16 * g.degree * g.count * r.frames))) return e;
+                                                  S::kEdgeBytes * g.degree * g.count * r.frames))) return e;
             table[k]<<<grid, kBlock, 0, s>>>(a, corr);
             if (r.span_end && (e = r.span_end(r.span_ctx, s))) return e;
         }
-        if (pl->host_arith) {
-            dim3 hgrid((pl->N + kWavesPerBlock - 1) / kWavesPerBlock, tiles);
-            layered_hard_kernel<V><<<hgrid, kBlock, 0, s>>>(pl->P.p, r.hard, r.done, pl->N);
+        if constexpr (!S::kFixed) {
+            if (rule == kLayerHost) {
+                dim3 hgrid((pl->N + kWavesPerBlock - 1) / kWavesPerBlock, tiles);
+                layered_hard_kernel<V><<<hgrid, kBlock, 0, s>>>(P, r.hard, r.done, pl->N);
+            }
         }
         /* syndrome of this round's bits, freeze (decodeCL.c:393-410) */
         if (!r.early_term && it != rounds) continue;
@@ -875,24 +821,28 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
         if (r.soft) {
             /* soft_i (soft_kernels.hpp): `done` still holds the frames frozen before this round and fw this round's
              * verdict; the frames that settle now leave P -- the posterior after the round's last layer, which later
-             * rounds overwrite -- in the caller's buffer.  In the last round launched every running frame settles. */
-            SoftArgs so{pl->P.p, nullptr, nullptr, nullptr, r.done, (r.early_term && it < rounds) ? fw : nullptr, r.soft,
-                        r.llr.p, nullptr, nullptr, pl->E, r.frames, pl->N, pl->bp ? 0 : r.soft_extrinsic, TailRef{nullptr, 0, 0}, r.llr.unit};
-            if (r.span_begin && (e = r.span_begin(r.span_ctx, s, /*soft_settle_kernel*/ 7, 0,(int64_t)8 * pl->N * r.frames))) return e;
-            dispatch_llr(r.llr.type, [&](auto in) {
-                soft_settle_kernel<V, float, decltype(in)><<<dim3((unsigned)((pl->N + kInitCols - 1) / kInitCols), (unsigned)tiles), kBlock, 0, s>>>(so);
-            });
+             * rounds overwrite -- in the caller's buffer, as floats.  In the last round launched every running frame
+             * settles.  A rule with a chan of its own gets its extrinsic values in one pass at the end. */
+            SoftArgs so{P, nullptr, nullptr, nullptr, r.done, (r.early_term && it < rounds) ? fw : nullptr, r.soft,
+                        r.llr.p, nullptr, nullptr, pl->E, r.frames, pl->N, has_chan ? 0 : r.soft_extrinsic, TailRef{nullptr, 0, 0}, r.llr.unit};
+            const dim3 grid((unsigned)((pl->N + kInitCols - 1) / kInitCols), (unsigned)tiles);
+            if (r.span_begin && (e = r.span_begin(r.span_ctx, s, /*soft_settle_kernel*/ 7, 0, S::kSettleBytes * pl->N * r.frames))) return e;
+            if constexpr (S::kFixed) {
+                soft_settle_kernel<V, p16, float><<<grid, kBlock, 0, s>>>(so);       /* reads no llr: extrinsic is 0 */
+            } else {
+                dispatch_llr(r.llr.type, [&](auto in) { soft_settle_kernel<V, float, decltype(in)><<<grid, kBlock, 0, s>>>(so); });
+            }
             if (r.span_end && (e = r.span_end(r.span_ctx, s))) return e;
         }
         StateArgs st{r.done, fw, r.iters, nullptr, r.frames, it, r.max_iter, 1};
         state_kernel<V><<<tiles, 64, 0, s>>>(st);
     }
-    if (pl->bp && r.soft && r.soft_extrinsic) {     /* posterior - chan, chan = llr_scale * y (layered_bp_extrinsic_kernel) */
+    if (has_chan && r.soft && r.soft_extrinsic) {       /* posterior - chan (layered_extrinsic_kernel) */
         const int64_t count = r.frames * (int64_t)pl->N;
         dispatch_llr(r.llr.type, [&](auto in) {
             using IN = decltype(in);
-            layered_bp_extrinsic_kernel<IN><<<(unsigned)((count + kBlock - 1) / kBlock), kBlock, 0, s>>>(
-                r.soft, static_cast<const IN *>(r.llr.p), pl->llr_scale, count, r.llr.unit);
+            layered_extrinsic_kernel<IN, S><<<(unsigned)((count + kBlock - 1) / kBlock), kBlock, 0, s>>>(
+                r.soft, static_cast<const IN *>(r.llr.p), pl->llr_scale, pl->L, count, r.llr.unit);
         });
     }
     *launched = rounds;
@@ -910,124 +860,23 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
     return hipGetLastError();
 }
 
+template <class S>
 inline hipError_t layered_run(LayeredPlan *pl, const LayeredRun &r, hipStream_t s, int32_t *launched)
 {
-    if (pl->V == 1) return layered_run_v<1>(pl, r, s, launched);
-    if (pl->V == 2) return layered_run_v<2>(pl, r, s, launched);
-    return layered_run_v<4>(pl, r, s, launched);
+    if (pl->V == 1) return layered_run_v<1, S>(pl, r, s, launched);
+    if (pl->V == 2) return layered_run_v<2, S>(pl, r, s, launched);
+    return layered_run_v<4, S>(pl, r, s, launched);
 }
-
 #endif  /* LDPC_ENGINE_LAYERED */
 
-/* The fixed-point rule is launched by a translation unit of its own (engine_layered_fx.hip defines
- * LDPC_ENGINE_LAYERED_FX), so engine_layered.hip compiles what it always did. */
-#ifdef LDPC_ENGINE_LAYERED_FX
-using LayerFxFn = void (*)(const LayerFxArgs, const MsCorr);
-template <int V, int... D0>
-inline void layer_fx_table_fill(LayerFxFn *t, std::integer_sequence<int, D0...>)
+/* one tile of `count` elements of T from the device, widened to float */
+template <typename T> inline hipError_t layered_tile_to_host(std::vector<float> &tile, const void *dev)
 {
-    t[0] = layer_kernel_generic<V, kLayerFx>;
-    ((t[D0 + 1] = layer_kernel<D0 + 1, V, kLayerFx>), ...);
+    std::vector<T> raw(tile.size());
+    const hipError_t e = hipMemcpy(raw.data(), dev, raw.size() * sizeof(T), hipMemcpyDeviceToHost);
+    std::copy(raw.begin(), raw.end(), tile.begin());
+    return e;
 }
-
-template <int V> __global__ void layered_fx_summary_kernel(const int32_t *iters, const uint64_t *done,
-                                                           int64_t frames, int32_t *summary)
-{
-    constexpr int F = 64 * V;
-    const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= frames) return;
-    const int64_t tile = f / F;
-    const int fi = (int)(f % F);
-    atomicMax(&summary[0], iters[f]);
-    if ((done[tile * V + fi % V] >> (fi / V)) & 1ull) atomicAdd(&summary[1], 1);
-}
-
-/* layered_run_v's round loop on the typed arrays: the same launches around the layers (state, syndrome, CRC, soft
- * settle, pack, summary), 6 bytes per edge in the timing hook, spans of kind 2 */
-template <int V>
-inline hipError_t layered_fx_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_t s, int32_t *launched)
-{
-    constexpr int F = 64 * V;
-    const int tiles = (int)((r.frames + F - 1) / F);
-    const size_t slot = (size_t)pl->T * V;
-    LayerFxFn table[kMaxUnrolledLayerDegree + 1];
-    layer_fx_table_fill<V>(table, std::make_integer_sequence<int, kMaxUnrolledLayerDegree>());
-    const MsCorr corr{pl->ms_scale, pl->ms_offset};
-    const int rounds = r.tap_iter ? (r.tap_iter < r.max_iter ? r.tap_iter : r.max_iter) : r.max_iter;
-    constexpr int64_t kEdgeBytes = 2 * sizeof(q8any) + 2 * sizeof(p16);     /* R and P, each read and written */
-    hipError_t e;
-    if ((e = hipMemsetAsync(r.failw, 0, (size_t)(r.max_iter + 2) * slot * sizeof(uint64_t), s))) return e;
-    if ((e = hipMemsetAsync(r.summary, 0, (r.crc_bits ? 4 : 2) * sizeof(int32_t), s))) return e;
-    if ((e = hipMemsetAsync(pl->Rfx.p, 0, (size_t)tiles * F * (size_t)pl->E * sizeof(q8any), s))) return e;
-    {
-        LayeredFxInitArgs ia{r.llr.p, pl->Pfx.p, r.hard, r.frames, pl->N, r.llr.unit, pl->llr_scale, pl->L};
-        dim3 grid((pl->N + kInitCols - 1) / kInitCols, tiles);
-        dispatch_llr(r.llr.type, [&](auto in) {
-            layered_init_kernel<V, decltype(in)><<<grid, kBlock, 0, s>>>(ia);
-        });
-        StateArgs st{r.done, nullptr, r.iters, nullptr, r.frames, 0, r.max_iter, 1};
-        state_kernel<V><<<tiles, 64, 0, s>>>(st);
-    }
-    for (int it = 1; it <= rounds; ++it) {
-        for (auto &g : pl->groups) {
-            LayerFxArgs a{pl->Pfx.p, pl->Rfx.p, g.e0.p, r.edge_col, r.hard, r.done, pl->E, pl->N, g.count, 4, g.degree,
-                          pl->L, pl->LP};
-            const int waves = (g.count + a.rows_per_wave - 1) / a.rows_per_wave;
-            dim3 grid((waves + kWavesPerBlock - 1) / kWavesPerBlock, tiles);
-            const int k = g.degree <= kMaxUnrolledLayerDegree ? g.degree : 0;
-            if (r.span_begin && (e = r.span_begin(r.span_ctx, s, 2, g.degree,
-                                                  kEdgeBytes * g.degree * g.count * r.frames))) return e;
-            table[k]<<<grid, kBlock, 0, s>>>(a, corr);
-            if (r.span_end && (e = r.span_end(r.span_ctx, s))) return e;
-        }
-        if (!r.early_term && it != rounds) continue;
-        uint64_t *fw = r.failw + (size_t)it * slot;
-        SyndromeArgs sa{r.row_ptr, r.edge_col, r.hard, fw, r.done, pl->M, pl->N, 0, 0};
-        dim3 sgrid((pl->M + kBlock - 1) / kBlock, tiles);
-        syndrome_kernel<V><<<sgrid, kBlock, 0, s>>>(sa);
-        if (r.crc_bits) {
-            CrcTermArgs ca{r.hard, fw, r.done, r.crc_w, r.summary + 3, pl->N, r.crc_bits, TailRef{nullptr, 0, 0}};
-            crc_term_kernel<V><<<dim3((unsigned)tiles, V), 64 * crc_term_waves(r.crc_bits), 0, s>>>(ca);
-        }
-        if (r.soft) {       /* P of the frames that settle in this round, as floats (extrinsic: one pass at the end) */
-            SoftArgs so{pl->Pfx.p, nullptr, nullptr, nullptr, r.done, (r.early_term && it < rounds) ? fw : nullptr, r.soft,
-                        r.llr.p, nullptr, nullptr, pl->E, r.frames, pl->N, 0, TailRef{nullptr, 0, 0}, r.llr.unit};
-            if (r.span_begin && (e = r.span_begin(r.span_ctx, s, /*soft_settle_kernel*/ 7, 0, (int64_t)6 * pl->N * r.frames))) return e;
-            soft_settle_kernel<V, p16, float><<<dim3((unsigned)((pl->N + kInitCols - 1) / kInitCols), (unsigned)tiles), kBlock, 0, s>>>(so);
-            if (r.span_end && (e = r.span_end(r.span_ctx, s))) return e;
-        }
-        StateArgs st{r.done, fw, r.iters, nullptr, r.frames, it, r.max_iter, 1};
-        state_kernel<V><<<tiles, 64, 0, s>>>(st);
-    }
-    if (r.soft && r.soft_extrinsic) {       /* P - c, c = sq(llr_scale * y) */
-        const int64_t count = r.frames * (int64_t)pl->N;
-        dispatch_llr(r.llr.type, [&](auto in) {
-            using IN = decltype(in);
-            layered_fx_extrinsic_kernel<IN><<<(unsigned)((count + kBlock - 1) / kBlock), kBlock, 0, s>>>(
-                r.soft, static_cast<const IN *>(r.llr.p), pl->llr_scale, pl->L, count, r.llr.unit);
-        });
-    }
-    *launched = rounds;
-    PackArgs pa{r.hard, r.out_dev, r.iters, r.iters_dev, r.frames, r.out_bytes, pl->N, r.K, r.pack_mode};
-    if (r.out_dev || r.iters_dev) {
-        if (r.pack_mode == 0) {
-            pack_kernel<V><<<pack_grid<V>(r.K, tiles), kBlock, 0, s>>>(pa);
-        } else {
-            const int64_t n = r.out_bytes > r.frames ? r.out_bytes : r.frames;
-            pack_kernel<V><<<(unsigned)((n + kBlock - 1) / kBlock), kBlock, 0, s>>>(pa);
-        }
-    }
-    layered_fx_summary_kernel<V><<<(unsigned)((r.frames + 255) / 256), 256, 0, s>>>(r.iters, r.done, r.frames, r.summary);
-    return hipGetLastError();
-}
-
-inline hipError_t layered_fx_run(LayeredPlan *pl, const LayeredRun &r, hipStream_t s, int32_t *launched)
-{
-    if (pl->V == 1) return layered_fx_run_v<1>(pl, r, s, launched);
-    if (pl->V == 2) return layered_fx_run_v<2>(pl, r, s, launched);
-    return layered_fx_run_v<4>(pl, r, s, launched);
-}
-#endif  /* LDPC_ENGINE_LAYERED_FX */
 
 /* which: 0 = R [frame][E], 2 = P [frame][N], 3 = bits [frame][N] */
 inline hipError_t layered_dump(LayeredPlan *pl, int which, float *host_out, int64_t count, int64_t frames,
@@ -1038,21 +887,14 @@ inline hipError_t layered_dump(LayeredPlan *pl, int which, float *host_out, int6
     if (which == 0 || which == 2) {
         const int64_t per = which == 0 ? pl->E : pl->N;
         if (count != frames * per) return hipErrorInvalidValue;
-        const float *src = which == 0 ? pl->R.p : pl->P.p;
+        const bool fx = pl->rule == kLayerFx;       /* R bytes and P int16, widened */
         std::vector<float> tile((size_t)per * F);
-        std::vector<int8_t> tile8(pl->fx && which == 0 ? tile.size() : 0);      /* kLayerFx: R bytes and P int16, widened */
-        std::vector<int16_t> tile16(pl->fx && which == 2 ? tile.size() : 0);
         for (int t = 0; t < tiles; ++t) {
-            hipError_t e;
-            if (!tile8.empty()) {
-                e = hipMemcpy(tile8.data(), pl->Rfx.p + (size_t)t * per * F, tile8.size(), hipMemcpyDeviceToHost);
-                for (size_t i = 0; i < tile8.size(); ++i) tile[i] = (float)tile8[i];
-            } else if (!tile16.empty()) {
-                e = hipMemcpy(tile16.data(), pl->Pfx.p + (size_t)t * per * F, tile16.size() * sizeof(int16_t), hipMemcpyDeviceToHost);
-                for (size_t i = 0; i < tile16.size(); ++i) tile[i] = (float)tile16[i];
-            } else {
-                e = hipMemcpy(tile.data(), src + (size_t)t * per * F, tile.size() * sizeof(float), hipMemcpyDeviceToHost);
-            }
+            const size_t at = (size_t)t * per * F;
+            const hipError_t e = which == 0 ? (fx ? layered_tile_to_host<int8_t>(tile, pl->Rfx.p + at)
+                                                  : layered_tile_to_host<float>(tile, pl->R.p + at))
+                                            : (fx ? layered_tile_to_host<int16_t>(tile, pl->Pfx.p + at)
+                                                  : layered_tile_to_host<float>(tile, pl->P.p + at));
             if (e != hipSuccess) return e;
             for (int fi = 0; fi < F; ++fi) {
                 const int64_t f = (int64_t)t * F + fi;

@@ -410,11 +410,9 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     } else if (cfg->algo == LDPC_ALGO_LAYERED_HOST || cfg->algo == LDPC_ALGO_LAYERED_BP || fx) {
         /* the streaming layered engine always.  LAYERED_BP: the record kernels' 16-byte check record holds two minima and
          * cannot hold a row's D independent messages, and the LDS-resident kernel carries no box-plus row */
-        d->layered.host_arith = cfg->algo == LDPC_ALGO_LAYERED_HOST;
-        d->layered.bp = cfg->algo == LDPC_ALGO_LAYERED_BP;
+        d->layered.rule = fx ? ldpc::kLayerFx : cfg->algo == LDPC_ALGO_LAYERED_BP ? ldpc::kLayerBp : ldpc::kLayerHost;
         d->layered.llr_scale = cfg->llr_scale;
         if (fx) {       /* plain min-sum is the corrected row with scale 1, offset 0: the identity on [0, L] */
-            d->layered.fx = 1;
             d->layered.L = (float)((1 << ((cfg->msg_bits ? cfg->msg_bits : 8) - 1)) - 1);
             d->layered.LP = (float)((1 << ((cfg->post_bits ? cfg->post_bits : 16) - 1)) - 1);
             d->layered.ms_scale = d->ms_scale;
@@ -452,7 +450,7 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         }
         /* the streaming plan (and its P / R arrays in HBM) only when no LDS-resident kernel applies;
          * a detected QC structure already implies that rows of a layer share no column */
-        d->layered.corr = d->ms_corr;
+        d->layered.rule = d->ms_corr ? ldpc::kLayerCorr : ldpc::kLayerFused;
         d->layered.ms_scale = d->ms_scale;
         d->layered.ms_offset = d->ms_offset;
         int rc = d->use_fused ? 0 : ldpc::layered_plan_create(&d->layered, g->M, g->N, g->E, g->row_ptr, g->cols,
@@ -676,8 +674,7 @@ static int decode_device_in(ldpc_decoder *d, const ldpc::LlrIn &in, int64_t fram
         run.row_ptr = d->row_ptr.p; run.edge_col = d->edge_col.p; run.summary = d->summary.p;
         run.crc_w = d->crc_w.p; run.crc_bits = d->cfg.crc_kind ? d->cfg.crc_bits : 0;
         run.soft = d->soft.dst; run.soft_extrinsic = d->soft.kind == LDPC_SOFT_EXTRINSIC ? 1 : 0;
-        hipError_t e = d->layered.fx ? ldpc::engine_layered_fx_run(&d->layered, run, s, &d->last_iterations)
-                                     : ldpc::engine_layered_run(&d->layered, run, s, &d->last_iterations);
+        hipError_t e = ldpc::engine_layered_run(&d->layered, run, s, &d->last_iterations);
         rc = (e == hipSuccess) ? LDPC_OK
                                : set_error(LDPC_ERR_HIP, "layered decode: %s", hipGetErrorString(e));
     } else {

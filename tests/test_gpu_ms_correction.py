@@ -3,16 +3,19 @@
 layered kernels -- against the numpy restatement (ms_correction_ref.py, itself checked against the CPU oracle in
 test_ms_correction_cpu.py): bytes, iteration counts, all N hard bits and the check->variable tap, bit for bit.  Each
 case asserts which kernels ran; the LDS-resident one-launch kernels carry no correction and are refused."""
+import functools
 import subprocess
 
 import numpy as np
 import pytest
 
 import myldpccppapi_amd as L
+import oracle
 from myldpccppapi_amd import channel, codes
 from ms_correction_ref import Code, flood_ms, layered_ms
 from coder_harness import coder_ms_correction_exe
 from util import kernel_choice
+import bp_cases as bc
 import kernel_matrix as km
 
 pytestmark = pytest.mark.gpu
@@ -193,6 +196,77 @@ def test_layered_corrected_random_quasi_cyclic_codes(built):
         y[3, ::3] = 0.0
         scale, offset = SETTINGS[n % 3]
         _layered_case(rows, cols, M, N, K, z, y, scale, offset, it=9)
+
+
+UNROLLED = 24                       # kMaxUnrolledLayerDegree: wider rows take the run-time kernel
+MATRIX_MAXIT = 5                    # about 135 launches per round with layer_rows = 1
+MATRIX_TAP = 2
+MATRIX_SETTINGS = [(0.0, 0.0), (0.75, 0.0), (0.0, 0.25)]       # the plain rule, then the corrected one: scale, offset
+
+
+@functools.lru_cache(maxsize=None)
+def _matrix_want(scale, offset):
+    """The expectation of one setting on bp_cases.matrix(), every row a layer, computed once per process and read-only:
+    the plain rule's is the CPU oracle's (with its P tap), the corrected rule's layered_ms's (which taps no P).  The
+    oracle taps no bits, so the plain rule takes those of round MATRIX_TAP from layered_ms, which must agree with the
+    oracle on everything both give."""
+    m = bc.matrix()
+    w = layered_ms(m["code"], m["y"], 1, MATRIX_MAXIT, scale=scale, offset=offset, tap_iter=MATRIX_TAP)
+    w["p_tap"] = None
+    if scale == 0.0 and offset == 0.0:
+        og = oracle.Graph(m["rows"], m["cols"], m["M"], m["N"], m["K"])
+        o = oracle.decode(og, m["y"], "layered", layer_rows=1, max_iter=MATRIX_MAXIT, tap_iter=MATRIX_TAP)
+        run = o["iters"] >= MATRIX_TAP
+        for a, b in ((o["out"], w["out"]), (o["iters"], w["iters"]), (o["hard"], w["hard"]), (o["undefined"], w["undefined"]),
+                     (o["taps"]["r"][run], w["r_tap"][run])):
+            assert np.array_equal(a, b)
+        w = dict(out=o["out"], iters=o["iters"], hard=o["hard"], undefined=o["undefined"], r_tap=o["taps"]["r"],
+                 p_tap=o["taps"]["post"], hard_tap=w["hard_tap"])
+    for v in w.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return w
+
+
+@pytest.mark.parametrize("scale,offset", MATRIX_SETTINGS)
+@pytest.mark.parametrize("V", [1, 2, 4])
+def test_layered_min_sum_every_degree_class(built, V, scale, offset):
+    """The float min-sum rules of the streaming layered engine, plain and corrected, on the irregular matrix code with
+    layer_rows = 1 -- every row a layer of its own: rows of degree 0, 1, 2, every unrolled degree up to 24, and 25 ... 33
+    and 40 for the run-time kernel -- 70 frames, 5 rounds.  No frame is undefined in either reference, so none is masked:
+    bytes, iteration counts, all N hard bits, and R, the bits and (plain rule) P after round 2 of the frames that ran it,
+    exactly.  The timing spans name a launch of every degree, so both the unrolled and the run-time kernel ran."""
+    m = bc.matrix()
+    want = _matrix_want(scale, offset)
+    assert want["undefined"].sum() == 0
+    what = (V, scale, offset)
+    B = bc.MATRIX_FRAMES
+    dec = L.Decoder(L.Graph(m["rows"], m["cols"], m["M"], m["N"]), m["K"], max_batch=B, algo="layered", layer_rows=1,
+                    max_iter=MATRIX_MAXIT, frames_per_lane=V, tune=kernel_choice("0"), ms_scale=scale, ms_offset=offset)
+    dec.set_timing(True)
+    out, iters = dec.decode(m["y"])
+    names = {k["name"]: k["degree"] for k in dec.kernel_times() if k["phase"] == 2}
+    dec.set_timing(False)
+    assert np.array_equal(iters, want["iters"]), ("iterations",) + what
+    assert np.array_equal(out, want["out"]), ("bytes",) + what
+    assert np.array_equal(dec.dump(3, B).astype(np.uint8), want["hard"]), ("hard bits",) + what
+    run = np.nonzero(want["iters"] >= MATRIX_TAP)[0]
+    early = np.nonzero(want["iters"] < MATRIX_TAP)[0]
+    assert run.size > 0 and early.size > 0, what
+    dec.set_tap(MATRIX_TAP)
+    dec.decode(m["y"])
+    assert np.array_equal(dec.dump(0, B)[run], want["r_tap"][run]), ("R tap",) + what
+    if want["p_tap"] is not None:
+        assert np.array_equal(dec.dump(2, B)[run], want["p_tap"][run]), ("P tap",) + what
+    bits = dec.dump(3, B).astype(np.uint8)
+    assert np.array_equal(bits[run], want["hard_tap"][run]), ("bit tap",) + what
+    assert np.array_equal(bits[early], want["hard"][early]), ("bits of the frames that had stopped",) + what
+    dec.close()
+    rd, _ = km.degree_maps(m["rows"], m["cols"], m["M"], m["N"])
+    kernel = "layer_corr_kernel" if (scale, offset) != (0.0, 0.0) else "layer_kernel"
+    assert set(names) == {"%s<layered,%d,%d>" % (kernel, d, V) for d in rd if d > 0}, (what, sorted(names))
+    degrees = set(names.values())
+    assert {1, 2, 3, UNROLLED} <= degrees and {UNROLLED + 1, 33, 40} <= degrees, (what, sorted(degrees))
 
 
 def test_layered_corrected_bg1_profile(built):

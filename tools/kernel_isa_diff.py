@@ -2,9 +2,11 @@
 """Instruction-level comparison of the kernels of two builds of libldpc_hip.so: every gfx950 code object of the
 .hip_fatbin section is disassembled (llvm-objdump) and each kernel symbol of the OLD library is compared, branch
 targets normalised and the zero fill between functions ("...") left out, with the same symbol in the NEW one.
-Usage: tools/kernel_isa_diff.py <old libldpc_hip.so> <new libldpc_hip.so>
+Usage: tools/kernel_isa_diff.py [--rename REGEX=REPLACEMENT]... <old libldpc_hip.so> <new libldpc_hip.so>
+--rename: re.sub(REGEX, REPLACEMENT) on every (mangled) symbol of the OLD library before the names are matched, for a
+change that gives kernels other argument types or template arguments; several are applied in the order given.
 Prints how many symbols are missing / differ / were added; exit status 1 if any old symbol is missing or differs."""
-import os, re, struct, subprocess, sys, tempfile
+import argparse, os, re, struct, subprocess, sys, tempfile
 
 OBJDUMP = "/opt/rocm/llvm/bin/llvm-objdump"
 
@@ -47,7 +49,20 @@ def kernels(so):
     return funcs
 
 
-old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+ap = argparse.ArgumentParser()
+ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPLACEMENT")
+ap.add_argument("old")
+ap.add_argument("new")
+args = ap.parse_args()
+old, new = kernels(args.old), kernels(args.new)
+for rule in args.rename:
+    pat, _, repl = rule.partition("=")
+    renamed = {}
+    for s, body in old.items():
+        t = re.sub(pat, repl, s)
+        # two old kernels may become one new one only if they were the same code
+        assert renamed.setdefault(t, body) == body, "--rename %s maps different kernels to %s" % (rule, t)
+    old = renamed
 missing = [s for s in old if s not in new]
 differ = [s for s in old if s in new and old[s] != new[s]]
 print("old %d symbols, new %d: missing %d, differing %d, added %d" % (
