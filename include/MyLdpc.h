@@ -59,11 +59,18 @@ enum decodeType { DecodeCPU, DecodeMS, DecodeSP, DecodeTDMP, DecodeTDMPCL, Decod
                   DecodeBP, /* not in the reference: log-domain sum-product, LDPC_ALGO_BP (include/ldpc_hip.h) */
                   DecodeLayeredBP, /* not in the reference: the layered schedule of DecodeTDMPCL (same circulant size) with
                                      DecodeBP's check node, LDPC_ALGO_LAYERED_BP (include/ldpc_hip.h); fp32 messages only */
-                  DecodeLayeredFixed /* not in the reference: the layered schedule of DecodeTDMPCL (same circulant size) in
+                  DecodeLayeredFixed, /* not in the reference: the layered schedule of DecodeTDMPCL (same circulant size) in
                                      fixed point, LDPC_ALGO_LAYERED_FX (include/ldpc_hip.h): setMessageType(LDPC_MSG_I8,
                                      bits) gives the message width, setPosteriorBits() the width of the saturating
                                      posterior memory, setLlrScale() the LSBs per unit of channel value; it takes
-                                     setMinSumCorrection, setCrcEarlyStop, decodeSoft (values in LSBs) and decodeTyped */ };
+                                     setMinSumCorrection, setCrcEarlyStop, decodeSoft (values in LSBs) and decodeTyped */
+                  DecodeLayeredBPFixed /* not in the reference: DecodeLayeredFixed with DecodeLayeredBP's check node computed as
+                                     hardware does, min plus a correction from a table, LDPC_ALGO_LAYERED_BP_FX
+                                     (include/ldpc_hip.h): setMessageType(LDPC_MSG_I8, bits), setPosteriorBits() and
+                                     setLlrFractionBits() give the widths, setLlrScale() the LSBs per unit of channel value,
+                                     chosen so that llrScale * y is the LLR in LSBs of 2^-fractionBits; it takes
+                                     setCrcEarlyStop, decodeSoft (values in LSBs) and decodeTyped, and no
+                                     setMinSumCorrection (LDPC_ERR_UNSUPPORTED: there is no minimum to correct) */ };
 
 const int n_b = 24;
 
@@ -133,10 +140,14 @@ public:
      * integers of `bits` = 4, 5, 6 or 8 bits (0 = 8; with any other type bits must be 0); setLlrScale() is then the number
      * of LSBs per unit of channel value.  Before addDecodeType(). */
     void setMessageType(int msgDtype, int bits = 0) { msgType = msgDtype; msgBits = bits; }
-    /* DecodeLayeredFixed: the posterior memory holds `bits` bits, message bits <= bits <= 16 (0 = 16; include/ldpc_hip.h:
-     * post_bits); anything else makes addDecodeType fail as ldpc_decoder_create does.  Read by no other decode type.
-     * Before addDecodeType(). */
+    /* DecodeLayeredFixed and DecodeLayeredBPFixed: the posterior memory holds `bits` bits, message bits <= bits <= 16 (0 = 16;
+     * include/ldpc_hip.h: post_bits); anything else makes addDecodeType fail as ldpc_decoder_create does.  Read by no other
+     * decode type.  Before addDecodeType(). */
     void setPosteriorBits(int bits) { postBits = bits; }
+    /* DecodeLayeredBPFixed: one LSB of a message is 2^-bits LLR units, 0 <= bits <= 4 (include/ldpc_hip.h: bp_frac_bits);
+     * anything else makes addDecodeType fail as ldpc_decoder_create does.  Read by no other decode type.  Before
+     * addDecodeType(). */
+    void setLlrFractionBits(int bits) { fracBits = bits; }
     /* encode() on the GPU `setDevice` names (ldpc_encode, include/ldpc_hip.h) instead of the host: same bytes.
      * forEncoder() then creates the device encoder and skips the host precompute, so it also serves the seed whose
      * parity part the host solves by dense elimination only (rate_3_4_b: any N, where the host path stops at
@@ -237,7 +248,8 @@ private:
     float msScale = 0.0f, msOffset = 0.0f; /* setMinSumCorrection() */
     int msgType = 0;                 /* setMessageType(): LDPC_MSG_F32 */
     int msgBits = 0;                 /* setMessageType(): bits per message with LDPC_MSG_I8 */
-    int postBits = 0;                /* setPosteriorBits(): DecodeLayeredFixed */
+    int postBits = 0;                /* setPosteriorBits(): DecodeLayeredFixed, DecodeLayeredBPFixed */
+    int fracBits = 0;                /* setLlrFractionBits(): DecodeLayeredBPFixed */
     int makeDecoder(const ldpc_decoder_config &cfg, ldpc_decoder **out);
     const signed char *hSeed;
     int seedRowLength;

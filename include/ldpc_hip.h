@@ -76,9 +76,12 @@ enum ldpc_algo {
                               definition, below; the streaming layered engine, fp32, one launch per layer    */
     /* The value 7 is not assigned and stays "unknown algo" (LDPC_ERR_ARG): callers and tests of the library have used it as
      * their example of an unknown algorithm since LDPC_ALGO_LAYERED_BP, and what was refused stays refused. */
-    LDPC_ALGO_LAYERED_FX = 8 /* layered (TDMP) min-sum in fixed point: q-bit messages (LDPC_MSG_I8, msg_bits) and a
+    LDPC_ALGO_LAYERED_FX = 8,/* layered (TDMP) min-sum in fixed point: q-bit messages (LDPC_MSG_I8, msg_bits) and a
                               posterior MEMORY of post_bits bits that saturates: this library's own definition, below;
                               the streaming layered engine, one byte per R and two per P, one launch per layer */
+    LDPC_ALGO_LAYERED_BP_FX = 9 /* LDPC_ALGO_LAYERED_FX's schedule, widths and storage with a box-plus check node in integers:
+                              min plus a correction read from a table of bp_frac_bits fractional bits, as hardware box-plus
+                              decoders compute it: this library's own definition, below */
 };
 
 /* LDPC_ALGO_BP, bit for bit.  The reference's sum-product (LDPC_ALGO_SP) works on probabilities in fp32 and saturates at
@@ -171,6 +174,43 @@ enum ldpc_algo {
  * ldpc_decode_typed*, ldpc_decoder_create_multi, the debug taps, crc_kind and kernel times (spans named lfx) work as
  * for LDPC_ALGO_LAYERED. */
 
+/* LDPC_ALGO_LAYERED_BP_FX, bit for bit, in integers: LDPC_ALGO_LAYERED_FX with the check node of LDPC_ALGO_LAYERED_BP, the
+ * way a hardware box-plus decoder computes it: the minimum plus a small correction read from a table.
+ *   Configuration: as for LDPC_ALGO_LAYERED_FX -- msg_dtype = LDPC_MSG_I8, msg_bits = q one of 4, 5, 6, 8 (0 = 8),
+ *                 L = 2^(q-1) - 1, post_bits = p with q <= p <= 16 (0 = 16), LP = 2^(p-1) - 1, layer_rows required and
+ *                 dividing M, layers column-disjoint, llr_scale finite and > 0, each LDPC_ERR_ARG otherwise -- and one
+ *                 field more: bp_frac_bits = f, 0 <= f <= 4 (anything else: LDPC_ERR_ARG).  One LSB is 2^-f LLR units, and
+ *                 the caller chooses llr_scale so that llr_scale * y is the channel LLR in LSBs: for BPSK +-1 in noise of
+ *                 standard deviation sd, llr_scale = 2^f * 2 / sd^2.
+ *   Table:        T_f[d] = (int)floor(2^f * log(1 + exp(-d / 2^f)) + 0.5) for d = 0, 1, ..., computed in double on the host
+ *                 once per decoder and cut at the first d where it is 0; T_f[d] = 0 beyond.  T_0 = {1, 0}; T_4 has 57
+ *                 entries, the largest is T_4[0] = 11.  ldpc_bp_fx_table() returns the table the kernels use.
+ *   Box-plus:     for integers a, b in [-L, L]
+ *                     s = (a < 0) XOR (b < 0)                      a zero counts as positive, as in LDPC_ALGO_LAYERED_FX
+ *                     m = min(|a|, |b|)
+ *                     g = max(0, m + T[|a| + |b|] - T[||a| - |b||])
+ *                     a [+] b = s ? -g : g
+ *                 T does not increase, so g <= m <= L: nothing needs clamping.  It is commutative and not associative, so
+ *                 the association is part of the definition:
+ *   Row, D >= 2:  on x_0 .. x_{D-1} in ascending edge id
+ *                     forward  F_0 = x_0,          F_k = F_{k-1} [+] x_k
+ *                     backward B_{D-1} = x_{D-1},  B_k = x_k [+] B_{k+1}
+ *                     R_0 = B_1,  R_{D-1} = F_{D-2},  R_k = F_{k-1} [+] B_{k+1} otherwise
+ *                 (D = 2: R_0 = x_1, R_1 = x_0.)
+ *   Row, D = 1:   R_0 = +L.  LDPC_ALGO_LAYERED_BP gives a degree-1 row +1000.0f, min-sum's start value; here it reads L, as
+ *                 the start value does in LDPC_ALGO_LAYERED_FX.
+ *   Schedule:     LDPC_ALGO_LAYERED_FX's: c = sq(llr_scale * y), P = c, R = 0; t_k = P[col_k] - R_k exact;
+ *                 x_k = clamp(t_k, -L, L); R_k from the row above; P[col_k] = clamp(t_k + R_k, -LP, LP) from the unclamped
+ *                 t_k; bit = (P[col_k] < 0) kept current with every write.  Rounds, syndrome, freezing, iters, the CRC rule,
+ *                 both pack modes, typed input, soft output (P, or P - c, in LSBs as fp32), the debug taps, the host path
+ *                 and device lists are LDPC_ALGO_LAYERED_FX's.
+ * Properties: a [+] 0 = 0, and with an all-zero table the row is LDPC_ALGO_LAYERED_FX's plain min-sum row.  The sign of
+ * every non-zero R_k is the XOR of (x_j < 0) over j != k, as in min-sum.
+ * Refusals, all before the device is touched: the LDPC_ERR_ARG cases of LDPC_ALGO_LAYERED_FX and bp_frac_bits outside
+ * 0 .. 4; a non-zero ms_scale or ms_offset is LDPC_ERR_UNSUPPORTED (there is no minimum to correct), as is
+ * LDPC_TUNE_ON(FUSED) or LDPC_TUNE_ON(LDSP).  bp_frac_bits != 0 with any other algorithm is LDPC_ERR_ARG.  Kernel times
+ * name its spans lbfx. */
+
 /* How the streaming flooding min-sum decoder (LDPC_ALGO_MS) stores its messages; the arithmetic is fp32 in one
  * operation order for all four.  F16 and F8 are this library's own definitions (the reference is fp32 only) and are
  * LDPC_ERR_UNSUPPORTED with every other algorithm (LDPC_ALGO_LAYERED_BP included: the layered engine is fp32) -- except that LDPC_ALGO_BP takes F16 (not F8); the one-launch and record kernels are fp32 and are never selected
@@ -189,7 +229,7 @@ enum ldpc_algo {
  *     below) one of 4, 5, 6, 8; 0 means 8, any other value is LDPC_ERR_ARG, as is a non-zero msg_bits with another
  *     msg_dtype.  L = 2^(q-1) - 1, that is 7, 15, 31 or 127.  A message is a two's-complement byte holding an integer in
  *     [-L, L]; the code -128 is never produced; the zero message is the byte 0x00.  LDPC_ALGO_MS, and LDPC_ALGO_LAYERED_FX
- *     with the rule of its own above (every other algorithm: LDPC_ERR_UNSUPPORTED); the one-launch and record kernels are never selected (forcing them:
+ *     and LDPC_ALGO_LAYERED_BP_FX with the rules of their own above (every other algorithm: LDPC_ERR_UNSUPPORTED); the one-launch and record kernels are never selected (forcing them:
  *     LDPC_ERR_UNSUPPORTED, as for F8).  The kernels compute in fp32, which on integers below 2^24 is exact integer
  *     arithmetic, so the rule can be restated in integers alone:
  *       Store rule:  sq(x) = clamp(rintf(x), -L, L): ties go to even, NaN gives 0, +-inf gives +-L.
@@ -336,7 +376,10 @@ typedef struct ldpc_decoder_config {
     int32_t post_bits;          /* LDPC_ALGO_LAYERED_FX: p bits of posterior memory, msg_bits <= p <= 16 (0 = 16); with any
                                    other algorithm it must be 0 (LDPC_ERR_ARG).  The first of the three words that were
                                    msg_reserved[3]: size and offsets are unchanged                                     */
-    int32_t msg_reserved2[2];   /* must be 0 (LDPC_ERR_ARG otherwise)                                                  */
+    int32_t bp_frac_bits;       /* LDPC_ALGO_LAYERED_BP_FX: f fractional bits of an LSB, 0 <= f <= 4; with any other algorithm
+                                   it must be 0 (LDPC_ERR_ARG).  The first of the two words that were msg_reserved2[2]: size
+                                   and offsets are unchanged                                                           */
+    int32_t msg_reserved3;      /* must be 0 (LDPC_ERR_ARG otherwise)                                                  */
 } ldpc_decoder_config;
 
 /* two-bit fields of tune_flags: LDPC_TUNE_ON(f) forces the choice on, LDPC_TUNE_OFF(f) off */
@@ -464,6 +507,13 @@ int ldpc_decode_device(ldpc_decoder *d, const float *llr_dev, int64_t frames, ui
                        int64_t out_bytes, int32_t *iters_dev, void *stream);
 
 int64_t ldpc_out_bytes(int32_t K, int64_t frames, int32_t pack_mode);
+
+/* The correction table of LDPC_ALGO_LAYERED_BP_FX at f = bp_frac_bits fractional bits, T_f[0 .. *count - 1], the last entry
+ * being its first 0 -- the very numbers a decoder created with this f hands to its kernels.  *count is set whenever f is
+ * valid; out may be NULL to ask for the count alone, otherwise cap >= *count entries are needed (LDPC_ERR_ARG if fewer, as
+ * for f outside 0 .. 4 or count NULL).  No entry lies near a rounding tie (tests/test_layered_bp_fx_cpu.py), so the table
+ * does not depend on the host's libm.  Needs no device. */
+int ldpc_bp_fx_table(int32_t f, int32_t *out, int32_t cap, int32_t *count);
 
 /* ---- soft output: the decode above plus one fp32 value per frame and code bit --------------------------------
  * The rule, per frame.  Let i_f = iters[f] be the round in which frame f froze (its syndrome first was clean, or its

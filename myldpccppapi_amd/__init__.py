@@ -12,5 +12,5 @@ Product layout:
 Nothing here imports oracle/ (test infrastructure).
 """
 from .capi import (ALGO_LAYERED, ALGO_MS, ALGO_SP, PACK_BITS, PACK_BYTES, BchCode, Decoder, DenseEncoder, Encoder, Graph, LdpcError, Modem, Osd, RateMatcher,  # noqa: F401
-                   TransportBlock, code_bytes, dense_parity, dense_parity_rows, device_count, out_bytes, parity_structure, quantize_device, shard_range,
+                   TransportBlock, bp_fx_table, code_bytes, dense_parity, dense_parity_rows, device_count, out_bytes, parity_structure, quantize_device, shard_range,
                    systematic_order)

@@ -46,15 +46,22 @@ class DecoderConfigCrc(DecoderConfig):
     _fields_ = [("crc_kind", ctypes.c_int32), ("crc_bits", ctypes.c_int32)]
 
 
+class _MsgTailNames(ctypes.Structure):
+    """The names the header gives the second and third of the three ints (the first is post_bits)."""
+    _fields_ = [("_post_bits", ctypes.c_int32), ("bp_frac_bits", ctypes.c_int32), ("msg_reserved3", ctypes.c_int32)]
+
+
 class _MsgTail(ctypes.Union):
-    """The three ints behind msg_bits: `post_bits; msg_reserved2[2]` in the header, which were `msg_reserved[3]`."""
-    _fields_ = [("msg_reserved", ctypes.c_int32 * 3), ("post_bits", ctypes.c_int32)]
+    """The three ints behind msg_bits: `post_bits; bp_frac_bits; msg_reserved3` in the header, which were `msg_reserved[3]`."""
+    _anonymous_ = ("_names",)
+    _fields_ = [("msg_reserved", ctypes.c_int32 * 3), ("post_bits", ctypes.c_int32), ("_names", _MsgTailNames)]
 
 
 class DecoderConfigMsg(DecoderConfigCrc):
     """The whole of `ldpc_decoder_config`: DecoderConfigCrc is the struct as it was before msg_bits (a size the library
     still accepts, msg_bits = 0); this one has msg_bits and the three ints behind it.  The first of them is post_bits
-    (LDPC_ALGO_LAYERED_FX), which aliases msg_reserved[0]; the other two are reserved and must be 0."""
+    (LDPC_ALGO_LAYERED_FX and LAYERED_BP_FX), which aliases msg_reserved[0]; the second is bp_frac_bits (LDPC_ALGO_LAYERED_BP_FX),
+    which aliases msg_reserved[1]; the third is reserved and must be 0."""
     _anonymous_ = ("_tail",)
     _fields_ = [("msg_bits", ctypes.c_int32), ("_tail", _MsgTail)]
 
@@ -123,6 +130,7 @@ EXPORTS = (
     "ldpc_bch_tally_device", "ldpc_bch_encode", "ldpc_bch_decode",
     "ldpc_osd_create", "ldpc_osd_destroy", "ldpc_osd_device", "ldpc_osd_run", "ldpc_osd_info",
     "ldpc_graph_systematic_order", "ldpc_parity_dense", "ldpc_parity_dense_rows", "ldpc_encoder_create_dense",
+    "ldpc_bp_fx_table",
 )
 
 
@@ -255,6 +263,7 @@ def load():
     L.ldpc_parity_dense.argtypes = [vp, i32, i64p]
     L.ldpc_parity_dense_rows.argtypes = [vp, i32, i32, i32, vp, ctypes.c_int64]
     L.ldpc_encoder_create_dense.argtypes = [vp, i32, i32, i32, ctypes.POINTER(vp)]
+    L.ldpc_bp_fx_table.argtypes = [i32, i32p, i32, i32p]
     _lib = L
     return L
 

@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import DecoderConfig, DecodeStats, LdpcError  # noqa: F401
 
 ALGO_SP, ALGO_MS, ALGO_LAYERED, ALGO_MS_FUSED, ALGO_LAYERED_HOST, ALGO_BP, ALGO_LAYERED_BP = 0, 1, 2, 3, 4, 5, 6
-ALGO_LAYERED_FX = 8                                        # 7 is not assigned
+ALGO_LAYERED_FX, ALGO_LAYERED_BP_FX = 8, 9                  # 7 is not assigned
 MSG_F32, MSG_F16, MSG_F8, MSG_I8 = 0, 1, 2, 4    # 3 is not assigned
 PACK_BYTES, PACK_BITS = 0, 1
 CODE_PACKED, CODE_BITS = 0, 1                              # enum ldpc_code_format
@@ -26,7 +26,8 @@ LLR_F32, LLR_F16, LLR_I8 = 0, 1, 2                         # enum ldpc_llr_type
 LLR_TYPES = {"f32": LLR_F32, "f16": LLR_F16, "i8": LLR_I8}
 LLR_DTYPES = {np.dtype(np.float32): LLR_F32, np.dtype(np.float16): LLR_F16, np.dtype(np.int8): LLR_I8}
 ALGOS = {"sp": ALGO_SP, "ms": ALGO_MS, "layered": ALGO_LAYERED, "ms_fused": ALGO_MS_FUSED,
-         "layered_host": ALGO_LAYERED_HOST, "bp": ALGO_BP, "layered_bp": ALGO_LAYERED_BP, "layered_fx": ALGO_LAYERED_FX}
+         "layered_host": ALGO_LAYERED_HOST, "bp": ALGO_BP, "layered_bp": ALGO_LAYERED_BP, "layered_fx": ALGO_LAYERED_FX,
+         "layered_bp_fx": ALGO_LAYERED_BP_FX}
 
 # two-bit fields of ldpc_decoder_config.tune_flags (enum ldpc_tune_field): True forces on, False off
 TUNE_FIELDS = {"fused": 0, "ldsp": 2, "ldsp_ext": 4, "ldsp_pack": 6, "link_narrow": 8, "check_wide": 10,
@@ -53,6 +54,17 @@ def apply_tune(cfg, tune):
         else:
             raise KeyError("unknown tuning field %r" % k)
     cfg.tune_flags, cfg.tune_ldsp_shape = flags, shape
+
+
+def bp_fx_table(frac_bits):
+    """The correction table of algo "layered_bp_fx" at `frac_bits` fractional bits (ldpc_bp_fx_table): int32, up to and
+    including its first 0.  Needs no device."""
+    L = _lib.load()
+    n = ctypes.c_int32()
+    _lib.check(L.ldpc_bp_fx_table(int(frac_bits), None, 0, ctypes.byref(n)))
+    t = np.zeros(n.value, np.int32)
+    _lib.check(L.ldpc_bp_fx_table(int(frac_bits), t.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), t.size, ctypes.byref(n)))
+    return t
 
 
 def hbm_probe(device=0, nbytes=1 << 30, reps=5, by_policy=False):
@@ -218,7 +230,7 @@ class Decoder:
     def __init__(self, graph, K, max_batch, algo="sp", max_iter=40, llr_scale=8.0, early_term=True,
                  device=0, layer_rows=0, pack_mode=PACK_BYTES, frames_per_lane=0, poll_interval=0,
                  msg_dtype=MSG_F32, tune=None, devices=None, host_input="auto", host_copy_threads=0,
-                 ms_scale=0.0, ms_offset=0.0, crc_kind=0, crc_bits=0, msg_bits=0, post_bits=0):
+                 ms_scale=0.0, ms_offset=0.0, crc_kind=0, crc_bits=0, msg_bits=0, post_bits=0, bp_frac_bits=0):
         L = _lib.load()
         cfg = _lib.DecoderConfigMsg()
         _lib.check(L.ldpc_decoder_config_init_sized(ctypes.byref(cfg), ctypes.sizeof(cfg)))
@@ -230,6 +242,9 @@ class Decoder:
         cfg.msg_bits = int(msg_bits)
         # algo "layered_fx" (msg_dtype "i8"): the posterior memory has post_bits bits, msg_bits <= post_bits <= 16 (0 = 16)
         cfg.post_bits = int(post_bits)
+        # algo "layered_bp_fx" (msg_dtype "i8", msg_bits, post_bits as for "layered_fx"): box-plus rows from a correction table;
+        # one LSB is 2^-bp_frac_bits LLR units (0 ... 4) and llr_scale * y is the channel LLR in LSBs
+        cfg.bp_frac_bits = int(bp_frac_bits)
         cfg.max_iter, cfg.llr_scale = int(max_iter), float(llr_scale)
         cfg.early_term, cfg.device, cfg.layer_rows = int(bool(early_term)), int(device), int(layer_rows)
         cfg.pack_mode, cfg.frames_per_lane, cfg.poll_interval = int(pack_mode), int(frames_per_lane), int(poll_interval)

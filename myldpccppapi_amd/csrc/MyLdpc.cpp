@@ -504,8 +504,10 @@ int Coder::addDecodeType(enum decodeType deType)
     cfg.algo = (deType == DecodeSP) ? LDPC_ALGO_SP : (deType == DecodeMS) ? LDPC_ALGO_MS
                : (deType == DecodeMSCL) ? LDPC_ALGO_MS_FUSED : (deType == DecodeBP) ? LDPC_ALGO_BP
                : (deType == DecodeLayeredBP) ? LDPC_ALGO_LAYERED_BP
-               : (deType == DecodeLayeredFixed) ? LDPC_ALGO_LAYERED_FX : LDPC_ALGO_LAYERED;
-    if (deType == DecodeLayeredFixed) cfg.post_bits = postBits;     /* setPosteriorBits(); the circulant size as DecodeTDMPCL */
+               : (deType == DecodeLayeredFixed) ? LDPC_ALGO_LAYERED_FX
+               : (deType == DecodeLayeredBPFixed) ? LDPC_ALGO_LAYERED_BP_FX : LDPC_ALGO_LAYERED;
+    if (deType == DecodeLayeredFixed || deType == DecodeLayeredBPFixed) cfg.post_bits = postBits;     /* setPosteriorBits(); the circulant size as DecodeTDMPCL */
+    if (deType == DecodeLayeredBPFixed) cfg.bp_frac_bits = fracBits;    /* setLlrFractionBits() */
     if (deType == DecodeTDMP) {
         /* The reference's host-layered path (MyLdpc.cpp:889-976) sizes layer l as
          * hRowRange[l + z] - hRowRange[l] (:907, :958): right only when all rows of H have one weight

@@ -7,6 +7,6 @@ namespace ldpc {
 hipError_t engine_layered_fx_run(LayeredPlan *pl, const LayeredRun &r, hipStream_t s, int32_t *launched);   /* engine_layered_fx.hip */
 hipError_t engine_layered_run(LayeredPlan *pl, const LayeredRun &r, hipStream_t s, int32_t *launched)
 {
-    return pl->rule == kLayerFx ? engine_layered_fx_run(pl, r, s, launched) : layered_run<StoreF32>(pl, r, s, launched);
+    return pl->fixed() ? engine_layered_fx_run(pl, r, s, launched) : layered_run<StoreF32>(pl, r, s, launched);
 }
 }  // namespace ldpc

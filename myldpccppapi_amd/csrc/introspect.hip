@@ -75,7 +75,7 @@ int ldpc_decoder_stats(ldpc_decoder *d, ldpc_decode_stats *st)
      * one-launch kernels (frames leave individually inside the launch) report 0 */
     st->frame_rounds = 0;
     if (!d->use_fused && d->cfg.algo != LDPC_ALGO_LAYERED && d->cfg.algo != LDPC_ALGO_LAYERED_HOST && d->cfg.algo != LDPC_ALGO_LAYERED_BP &&
-        d->cfg.algo != LDPC_ALGO_LAYERED_FX) {
+        d->cfg.algo != LDPC_ALGO_LAYERED_FX && d->cfg.algo != LDPC_ALGO_LAYERED_BP_FX) {
         st->frame_rounds = d->cfg.early_term ? (int64_t)summary[2] * d->F
                                              : (int64_t)d->last_iterations * d->last_tiles * d->F;
         for (const ldpc_decoder *p = d->flood.handed_to; p; p = p->flood.handed_to) {      /* the child, and whom it handed over to */
@@ -179,6 +179,8 @@ int ldpc_decoder_kernel_times(ldpc_decoder *d, ldpc_kernel_time *out, int32_t ca
                      : d->cfg.algo == LDPC_ALGO_LAYERED ? "fused_layered_kernel" : "fused_flood_kernel");
         else if (d->cfg.algo == LDPC_ALGO_LAYERED_FX)      /* the tables above end at LAYERED_BP; every layer launch is one rule */
             snprintf(name, sizeof name, "layer_kernel<lfx,%d,%d>", sp.degree, d->V);
+        else if (d->cfg.algo == LDPC_ALGO_LAYERED_BP_FX)
+            snprintf(name, sizeof name, "layer_kernel<lbfx,%d,%d>", sp.degree, d->V);
         else if (sp.kind == 5 || sp.kind == 6)
             snprintf(name, sizeof name, "%s<%s,%d-%d,%d>", sp.kind == 5 ? "check_group_kernel" : "var_group_kernel",
                      algo_name[d->cfg.algo], sp.lo, sp.degree, d->V);
@@ -300,7 +302,7 @@ int ldpc_decoder_dump(ldpc_decoder *d, int32_t which, float *host_out, int64_t c
         return LDPC_OK;
     }
     if (d->cfg.algo == LDPC_ALGO_LAYERED || d->cfg.algo == LDPC_ALGO_LAYERED_HOST || d->cfg.algo == LDPC_ALGO_LAYERED_BP ||
-        d->cfg.algo == LDPC_ALGO_LAYERED_FX) {
+        d->cfg.algo == LDPC_ALGO_LAYERED_FX || d->cfg.algo == LDPC_ALGO_LAYERED_BP_FX) {
         hipError_t e = ldpc::layered_dump(&d->layered, which, host_out, count, frames, d->hard.p,
                                           d->h_cols.data());
         if (e == hipErrorInvalidValue) return set_error(LDPC_ERR_ARG, "bad `which`/count for layered dump");

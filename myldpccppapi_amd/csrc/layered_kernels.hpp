@@ -22,8 +22,8 @@
  * P/R keep evolving unread -- no per-lane predication in the hot loop.
  *
  * Structure.  A rule (LayerRule) is a row arithmetic; a storage (LayerStore) is the element types of P and R.  The four
- * float rules run on StoreF32; kLayerFx (LDPC_ALGO_LAYERED_FX) runs on StoreFx, one-byte R and int16 P.  Everything around
- * the row arithmetic is written once over the storage:
+ * float rules run on StoreF32; kLayerFx (LDPC_ALGO_LAYERED_FX) and kLayerBpFx (LDPC_ALGO_LAYERED_BP_FX) run on StoreFx, one-byte R
+ * and int16 P.  Everything around the row arithmetic is written once over the storage:
  *   LayerArgs<S>, LayerWave<V, S>     the argument block of a layer launch and what one wave of it works on, set_bits
  *                                     included (LayerArgsFx adds L and LP behind the block, so the float kernarg has none)
  *   layer_kernel_generic<V, RULE>     rows of any degree, the rule's row as a function with run-time loops
@@ -33,10 +33,12 @@
  *   layered_run_v<V, S>               the driver: one round loop, one kernel table per rule
  * The exception is the unrolled kernel, layer_kernel<D, V, RULE>: an overload per storage, and the float one writes the
  * wave's set-up and the hard-bit write out by hand (the reason stands above it).
- * The row arithmetics are not merged: layer_kernel's two float paths and its fixed-point body, layer_row_generic,
- * layer_row_generic_bp and layer_row_generic_fx each follow their own definition bit for bit.  engine_layered.hip
- * instantiates the driver on StoreF32 and engine_layered_fx.hip on StoreFx, so the library's largest unit builds beside the
- * other; the host driver calls engine_layered_run, which forwards by LayeredPlan::rule.
+ * The row arithmetics are not merged: layer_kernel's two float paths and its two fixed-point bodies, layer_row_generic,
+ * layer_row_generic_bp, layer_row_generic_fx and layer_row_generic_bpfx each follow their own definition bit for bit.
+ * engine_layered.hip instantiates the driver on StoreF32 and engine_layered_fx.hip on StoreFx, so the library's largest unit
+ * builds beside the other; engine_layered_bpfx.hip instantiates kLayerBpFx's kernels and hands them to the StoreFx driver
+ * as a table (layer_table_bpfx), a third unit beside the two.  The host driver calls engine_layered_run, which forwards by
+ * LayeredPlan::rule.
  */
 #pragma once
 
@@ -44,6 +46,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
 #include <map>
 #include <type_traits>
 #include <utility>
@@ -73,8 +76,12 @@ enum LayerRule {
                            messages, so an exact 0 does not kill a row */
     kLayerFx,           /* layered min-sum in fixed point (LDPC_ALGO_LAYERED_FX, include/ldpc_hip.h has the rule bit for
                            bit): the SUM path on one-byte R and int16 P with two clamps, the corrected row of LDPC_MSG_I8.
-                           The only rule on StoreFx: the overload of layer_kernel on LayerArgsFx and layer_row_generic_fx in
-                           layer_kernel_generic, launched by the driver's instantiation in engine_layered_fx.hip */
+                           The overload of layer_kernel on LayerArgsFx and layer_row_generic_fx in layer_kernel_generic,
+                           launched by the driver's instantiation in engine_layered_fx.hip */
+    kLayerBpFx,         /* layered box-plus in fixed point (LDPC_ALGO_LAYERED_BP_FX, include/ldpc_hip.h has the rule bit for
+                           bit): kLayerFx's schedule, storage and clamps with a row of min plus a correction read from a
+                           table (layer_rows_bpfx, layer_row_generic_bpfx below).  Its kernels are instantiated in
+                           engine_layered_bpfx.hip and handed to the driver as a table (layer_table_bpfx) */
 };
 
 /* ---- LDPC_ALGO_LAYERED_FX (kLayerFx): fixed-point layered min-sum, include/ldpc_hip.h has the rule bit for bit ----
@@ -143,10 +150,11 @@ template <typename PT, typename RT> struct LayerStore {
     static constexpr int64_t kSettleBytes = sizeof(PT) + sizeof(float);         /* soft settle: P read, a float written */
 };
 typedef LayerStore<float, float> StoreF32;      /* kLayerFused, kLayerCorr, kLayerHost, kLayerBp */
-typedef LayerStore<p16, q8any> StoreFx;         /* kLayerFx */
+typedef LayerStore<p16, q8any> StoreFx;         /* kLayerFx, kLayerBpFx */
 /* the storage of a rule (a struct and not a conditional, so that the kernels' symbols stay readable) */
 template <int RULE> struct RuleOn { typedef StoreF32 Store; };
 template <> struct RuleOn<kLayerFx> { typedef StoreFx Store; };
+template <> struct RuleOn<kLayerBpFx> { typedef StoreFx Store; };
 template <int RULE> using RuleStore = typename RuleOn<RULE>::Store;
 
 template <class S> struct LayerArgs {
@@ -303,14 +311,151 @@ __global__ __launch_bounds__(kBlock) void layer_kernel(const LayerArgs<StoreF32>
     }
 }
 
+/* ---- LDPC_ALGO_LAYERED_BP_FX (kLayerBpFx): box-plus rows in fixed point, include/ldpc_hip.h has the rule bit for bit ----
+ *
+ * The table.  T_f has at most 57 entries (f = 4), each at most 11.  The host pads it with zeros to kBpFxTable = 256 bytes, so
+ * that an index |a| + |b| <= 2 * 127 needs no clamp, and every block copies it into LDS once (64 lanes, one dword each).
+ * A look-up is one ds_read_u8: two per box-plus, no memory round trip.  Bytes 0 .. 127 are 32 dwords in 32 banks and equal
+ * addresses broadcast, so look-ups below 128 never conflict; one at 128 or above (q = 8 only, where it reads a zero) can
+ * share a bank with one below.  The alternatives were weighed for <19, 4>, 51 box-plus per frame and row: a table held
+ * wave-uniform in SGPRs needs a per-lane select over 15 dwords per look-up, a compare chain needs up to 11 compares per
+ * look-up at f = 4 (T is a step function with T[0] steps) and is short only for f <= 1; the LDS copy costs two DS
+ * instructions beside six VALU instructions per box-plus and no registers.
+ *
+ * Signs.  a [+] b = 0 whenever a or b is 0 (m = 0 and |a| + |b| = ||a| - |b||), so a zero stays a zero through every further
+ * box-plus and the sign the definition gives it ("a zero counts as positive") never reaches a result that is not itself 0.
+ * For every non-zero result the sign is the XOR of the signs of the inputs that went into it.  So the kernels split the
+ * row as min-sum does: the sign of R_k is the row's parity XOR (x_k < 0), and the forward / backward association runs on
+ * magnitudes alone -- min, sum, difference, two look-ups, subtract, add, max: six VALU instructions. */
+constexpr int kBpFxTable = 256;
+constexpr int kBpFxMaxFracBits = 4;
+
+/* T_f[d] = floor(2^f log(1 + exp(-d / 2^f)) + 0.5) in double, d = 0, 1, ... up to and including the first 0: the number of
+ * entries written (57 at f = 4, so cap = kBpFxTable always holds it).  Host code; ldpc_bp_fx_table hands it out. */
+inline int bp_fx_table_build(int f, int32_t *out, int cap)
+{
+    const double s = (double)(1 << f);
+    int n = 0;
+    while (n < cap) {
+        const int32_t v = (int32_t)std::floor(s * std::log(1.0 + std::exp(-(double)n / s)) + 0.5);
+        out[n++] = v;
+        if (v == 0) break;
+    }
+    return n;
+}
+
+/* |a [+] b| from |a| and |b|, both in [0, L]: max(0, m + T[|a| + |b|] - T[||a| - |b||]), where ||a| - |b|| = sum - 2 m */
+__device__ __forceinline__ int bpfx_box(int ma, int mb, const uint8_t *T)
+{
+    const int m = min(ma, mb), sum = ma + mb;
+    return max(m + (int)T[sum] - (int)T[sum - 2 * m], 0);
+}
+
+/* The table's address travels in the second argument of the launch.  Every layer kernel takes a MsCorr so that one table of
+ * one pointer type launches all rules; kLayerBpFx has no correction (ms_scale / ms_offset are refused), and its eight bytes
+ * carry the address instead, so that LayerArgsFx and with it every kLayerFx kernel stay as they were. */
+static_assert(sizeof(MsCorr) == sizeof(const uint8_t *), "the table's address takes the place of the correction");
+inline MsCorr bpfx_table_arg(const uint8_t *table)
+{
+    MsCorr c;
+    __builtin_memcpy(&c, &table, sizeof c);
+    return c;
+}
+__device__ __forceinline__ const uint8_t *bpfx_table_of(const MsCorr &c)
+{
+    const uint8_t *table;
+    __builtin_memcpy(&table, &c, sizeof table);
+    return table;
+}
+
+/* the block's copy of the table; every thread of the block comes here (a finished tile has left before, as a block) */
+__device__ __forceinline__ void bpfx_table_fill(uint8_t *T, const uint8_t *__restrict__ src)
+{
+    static_assert(kBpFxTable == 4 * 64, "one dword per lane of the first wave");
+    if (threadIdx.x < 64) reinterpret_cast<uint32_t *>(T)[threadIdx.x] = reinterpret_cast<const uint32_t *>(src)[threadIdx.x];
+    __syncthreads();
+}
+
+/* Rows of degree D under kLayerBpFx: the loads, clamps and stores of the kLayerFx kernel below; between them the magnitudes
+ * F_0 .. F_{D-2} forward, then B backward in one register while the messages come out: 3 (D - 2) box-plus per frame. */
+template <int D, int V>
+__device__ __forceinline__ void layer_rows_bpfx(const LayerArgsFx &a, const uint8_t *__restrict__ table)
+{
+    constexpr size_t F = 64 * V;
+    __shared__ __attribute__((aligned(16))) uint8_t T[kBpFxTable];
+    bpfx_table_fill(T, table);
+    const LayerWave<V, StoreFx> w(a);
+    const float L = a.L, LP = a.LP;
+    for (int r = w.r_begin; r < w.r_end; ++r) {
+        const int e0 = a.cls_e0[r];
+        int col[D];
+#pragma unroll
+        for (int k = 0; k < D; ++k) col[k] = a.edge_col[e0 + k];
+        float t[D][V], m[D][V];
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            vload<V>(m[k], w.Rt + (size_t)(e0 + k) * F);
+            vload<V>(t[k], w.Pt + (size_t)col[k] * F);
+        }
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            int mag[D];
+            unsigned par = 0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                t[k][v] = t[k][v] - m[k][v];                                       /* t_k: exact, not clamped */
+                const float x = __builtin_amdgcn_fmed3f(t[k][v], -L, L);           /* the variable->check message */
+                mag[k] = (int)__builtin_fabsf(x);
+                par ^= (x < 0.0f) ? 1u : 0u;
+            }
+            /* R_k = +-g, negative iff the parity XOR (x_k < 0); t_k < 0 says what x_k < 0 says, the clamp keeps the sign */
+            auto emit = [&](int k, int g) {
+                const float gf = (float)g;
+                const float rn = (par ^ ((t[k][v] < 0.0f) ? 1u : 0u)) ? -gf : gf;
+                m[k][v] = rn;
+                t[k][v] = __builtin_amdgcn_fmed3f(t[k][v] + rn, -LP, LP);          /* only the posterior memory saturates */
+            };
+            if constexpr (D == 1) {
+                emit(0, (int)L);                    /* LDPC_ALGO_LAYERED_BP's degree-1 row gives +1000, which reads L */
+            } else if constexpr (D == 2) {
+                emit(0, mag[1]); emit(1, mag[0]);
+            } else {
+                int fw[D - 1];
+                fw[0] = mag[0];
+#pragma unroll
+                for (int k = 1; k <= D - 2; ++k) fw[k] = bpfx_box(fw[k - 1], mag[k], T);        /* F_k */
+                emit(D - 1, fw[D - 2]);
+                int b = mag[D - 1];                                                              /* B_{D-1} */
+#pragma unroll
+                for (int k = D - 2; k >= 1; --k) {
+                    emit(k, bpfx_box(fw[k - 1], b, T));                                          /* F_{k-1} [+] B_{k+1} */
+                    b = bpfx_box(mag[k], b, T);                                                  /* B_k */
+                }
+                emit(0, b);                                                                      /* B_1 */
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            vstore<V>(w.Rt + (size_t)(e0 + k) * F, m[k]);
+            vstore<V>(w.Pt + (size_t)col[k] * F, t[k]);
+            w.set_bits(col[k], t[k]);
+        }
+    }
+}
+
 /* Rows of degree D in fixed point.  The SUM path of the float kernel (q = P - R, the check row, P = q + R) with the two
- * clamps: the row reads x = clamp(t, -L, L), the posterior memory takes clamp(t + R, -LP, LP) from the unclamped t. */
+ * clamps: the row reads x = clamp(t, -L, L), the posterior memory takes clamp(t + R, -LP, LP) from the unclamped t.
+ * kLayerBpFx has the same frame and another row (layer_rows_bpfx above). */
 template <int D, int V, int RULE>
 __global__ __launch_bounds__(kBlock) void layer_kernel(const LayerArgsFx a, const MsCorr corr)
 {
-    static_assert(RULE == kLayerFx, "the fixed-point argument block belongs to kLayerFx");
+    static_assert(RULE == kLayerFx || RULE == kLayerBpFx, "the fixed-point argument block belongs to kLayerFx and kLayerBpFx");
     constexpr size_t F = 64 * V;
     if (tile_finished<V>(a.done, blockIdx.y)) return;
+    if constexpr (RULE == kLayerBpFx) {
+        layer_rows_bpfx<D, V>(a, bpfx_table_of(corr));
+        return;
+    }
     const LayerWave<V, StoreFx> w(a);
     const float L = a.L, LP = a.LP;
     for (int r = w.r_begin; r < w.r_end; ++r) {
@@ -519,17 +664,95 @@ __device__ __forceinline__ void layer_row_generic_fx(const LayerArgsFx &a, const
     }
 }
 
+/* A fixed-point box-plus row of any degree.  It keeps layer_row_generic_fx's premise -- nothing is parked in P, every t_j
+ * is formed again from the edge's own old R and P -- and takes layer_row_generic_bp's order for the rest: k ascends, the
+ * forward magnitude F_{k-1} and the parity of x_0 .. x_{k-1} are carried in registers, and B_{k+1} with the parity of the
+ * x_j, j > k, is rebuilt from the row's end out of edges that still hold their old values (the invariant stated at
+ * layer_row_generic_bp holds word for word).  So the forward values take neither a pass of their own nor scratch memory:
+ * the price is D (D - 1) / 2 box-plus and re-reads per row instead of 3 (D - 2), paid only by rows wider than
+ * kMaxUnrolledLayerDegree, and the register count does not depend on D. */
+template <int V>
+__device__ __forceinline__ void layer_row_generic_bpfx(const LayerArgsFx &a, const LayerWave<V, StoreFx> &w, int e0,
+                                                       const uint8_t *T)
+{
+    constexpr size_t F = 64 * V;
+    const float L = a.L, LP = a.LP;
+    const int D = a.degree;
+    /* t_j of an edge that still holds its old values, and |x_j|, (x_j < 0) of x_j = clamp(t_j, -L, L) */
+    auto load_t = [&](int j, float (&t)[V], int (&mag)[V], unsigned (&neg)[V]) {
+        float pj[V], mj[V];
+        vload<V>(mj, w.Rt + (size_t)(e0 + j) * F);
+        vload<V>(pj, w.Pt + (size_t)a.edge_col[e0 + j] * F);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            t[v] = pj[v] - mj[v];
+            const float x = __builtin_amdgcn_fmed3f(t[v], -L, L);
+            mag[v] = (int)__builtin_fabsf(x);
+            neg[v] = (x < 0.0f) ? 1u : 0u;
+        }
+    };
+    int f[V];
+    unsigned pf[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) { f[v] = 0; pf[v] = 0; }
+    for (int k = 0; k < D; ++k) {
+        const int col = a.edge_col[e0 + k];
+        float t[V], tj[V];
+        int mk[V], mj[V], o[V];
+        unsigned nk[V], nj[V], pb[V];
+        load_t(k, t, mk, nk);
+#pragma unroll
+        for (int v = 0; v < V; ++v) pb[v] = 0;
+        if (D == 1) {
+#pragma unroll
+            for (int v = 0; v < V; ++v) o[v] = (int)L;                      /* as the unrolled kernel */
+        } else if (k == D - 1) {
+#pragma unroll
+            for (int v = 0; v < V; ++v) o[v] = f[v];                        /* F_{D-2} */
+        } else {
+            int b[V];
+            load_t(D - 1, tj, b, pb);
+            for (int j = D - 2; j > k; --j) {
+                load_t(j, tj, mj, nj);
+#pragma unroll
+                for (int v = 0; v < V; ++v) { b[v] = bpfx_box(mj[v], b[v], T); pb[v] ^= nj[v]; }   /* B_j = x_j [+] B_{j+1} */
+            }
+#pragma unroll
+            for (int v = 0; v < V; ++v) o[v] = (k == 0) ? b[v] : bpfx_box(f[v], b[v], T);
+        }
+        float rn[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) {                   /* F_k and the parity up to k, before edge k is stored */
+            const float g = (float)o[v];
+            rn[v] = (pf[v] ^ pb[v]) ? -g : g;
+            f[v] = (k == 0) ? mk[v] : bpfx_box(f[v], mk[v], T);
+            pf[v] ^= nk[v];
+            t[v] = __builtin_amdgcn_fmed3f(t[v] + rn[v], -LP, LP);
+        }
+        vstore<V>(w.Rt + (size_t)(e0 + k) * F, rn);
+        vstore<V>(w.Pt + (size_t)col * F, t);
+        w.set_bits(col, t);
+    }
+}
+
 /* Rows of any degree (LayerArgs::degree); the host arithmetic has unrolled degrees only. */
 template <int V, int RULE>
 __global__ __launch_bounds__(kBlock) void layer_kernel_generic(const typename RuleStore<RULE>::Args a, const MsCorr corr)
 {
     static_assert(RULE != kLayerHost, "no generic row with the host arithmetic");
     if (tile_finished<V>(a.done, blockIdx.y)) return;
+    if constexpr (RULE == kLayerBpFx) {
+        __shared__ __attribute__((aligned(16))) uint8_t T[kBpFxTable];
+        bpfx_table_fill(T, bpfx_table_of(corr));
+        const LayerWave<V, StoreFx> w(a);
+        for (int r = w.r_begin; r < w.r_end; ++r) layer_row_generic_bpfx<V>(a, w, a.cls_e0[r], T);
+        return;
+    }
     const LayerWave<V, RuleStore<RULE>> w(a);
     for (int r = w.r_begin; r < w.r_end; ++r) {
         if constexpr (RULE == kLayerBp) layer_row_generic_bp<V>(a, w, a.cls_e0[r]);
         else if constexpr (RULE == kLayerFx) layer_row_generic_fx<V>(a, w, a.cls_e0[r], corr);
-        else layer_row_generic<V, RULE == kLayerCorr>(a, w, a.cls_e0[r], corr);
+        else if constexpr (RULE != kLayerBpFx) layer_row_generic<V, RULE == kLayerCorr>(a, w, a.cls_e0[r], corr);
     }
 }
 
@@ -668,10 +891,13 @@ struct LayeredPlan {
     int32_t M = 0, N = 0, layer_rows = 0;
     int64_t E = 0;
     int T = 0, V = 1;
-    LayerRule rule = kLayerFused;   /* the one row arithmetic of this decoder; kLayerFx runs on StoreFx, the others on StoreF32 */
+    LayerRule rule = kLayerFused;   /* the one row arithmetic of this decoder; kLayerFx and kLayerBpFx run on StoreFx, the
+                                       others on StoreF32 */
+    bool fixed() const { return rule == kLayerFx || rule == kLayerBpFx; }
     float ms_scale = 1.0f, ms_offset = 0.0f;    /* kLayerCorr, kLayerFx (1 / 0 = plain): normalized / offset min-sum */
-    float llr_scale = 1.0f;         /* kLayerBp: chan = llr_scale * y; kLayerFx: LSBs per unit of channel value */
-    float L = 127.0f, LP = 32767.0f;    /* kLayerFx: the limits of a message and of the posterior memory */
+    float llr_scale = 1.0f;         /* kLayerBp: chan = llr_scale * y; kLayerFx, kLayerBpFx: LSBs per unit of channel value */
+    float L = 127.0f, LP = 32767.0f;    /* kLayerFx, kLayerBpFx: the limits of a message and of the posterior memory */
+    DevBuf<uint8_t> bp_table;       /* kLayerBpFx: T_f padded with zeros to kBpFxTable bytes (ldpc_decoder_create) */
     DevBuf<float> P, R;             /* StoreF32: [T][N][F], [T][E][F]; only the rule's storage is allocated */
     DevBuf<p16> Pfx;                /* StoreFx: [T][N][F] int16 */
     DevBuf<q8any> Rfx;              /* StoreFx: [T][E][F] bytes */
@@ -707,7 +933,7 @@ inline int layered_plan_create(LayeredPlan *pl, int32_t M, int32_t N, int64_t E,
         }
     }
     const size_t TF = (size_t)T * 64 * V;
-    const bool ok = pl->rule == kLayerFx
+    const bool ok = pl->fixed()
                         ? pl->Pfx.alloc(TF * N) == hipSuccess && pl->Rfx.alloc(TF * (size_t)E) == hipSuccess
                         : pl->P.alloc(TF * N) == hipSuccess && pl->R.alloc(TF * (size_t)E) == hipSuccess;
     return ok ? 0 : -2;
@@ -737,7 +963,8 @@ struct LayeredRun {
 };
 
 /* The launching code instantiates the kernels above: only the translation units that define LDPC_ENGINE_LAYERED compile
- * it, engine_layered.hip for StoreF32 and engine_layered_fx.hip for StoreFx; the host driver calls engine_layered_run. */
+ * it, engine_layered.hip for StoreF32, engine_layered_fx.hip for StoreFx and engine_layered_bpfx.hip for the kernel table of
+ * kLayerBpFx; the host driver calls engine_layered_run. */
 #ifdef LDPC_ENGINE_LAYERED
 template <class S> using LayerFn = void (*)(const typename S::Args, const MsCorr);
 /* t[D] = the kernel of the rule for rows of degree D = 1 .. kMaxUnrolledLayerDegree, t[0] = the one for wider rows */
@@ -748,6 +975,10 @@ inline void layer_table_fill(LayerFn<RuleStore<RULE>> *t, std::integer_sequence<
     else t[0] = layer_kernel_generic<V, RULE>;
     ((t[D0 + 1] = layer_kernel<D0 + 1, V, RULE>), ...);
 }
+
+/* the kernels of kLayerBpFx at V frames per lane, instantiated in engine_layered_bpfx.hip so that they build beside the
+ * other two units; the driver that launches them is engine_layered_fx.hip's */
+void layer_table_bpfx(int V, LayerFn<StoreFx> *t);
 
 template <int V, class S>
 inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_t s, int32_t *launched)
@@ -761,12 +992,18 @@ inline hipError_t layered_run_v(LayeredPlan *pl, const LayeredRun &r, hipStream_
     const size_t slot = (size_t)pl->T * V;
     LayerFn<S> table[kMaxUnrolledLayerDegree + 1];
     const std::make_integer_sequence<int, kMaxUnrolledLayerDegree> degrees;
-    if constexpr (S::kFixed) layer_table_fill<V, kLayerFx>(table, degrees);
+    if constexpr (S::kFixed) {
+        if (rule == kLayerBpFx) layer_table_bpfx(V, table);
+        else layer_table_fill<V, kLayerFx>(table, degrees);
+    }
     else if (rule == kLayerCorr) layer_table_fill<V, kLayerCorr>(table, degrees);
     else if (rule == kLayerBp) layer_table_fill<V, kLayerBp>(table, degrees);
     else if (rule == kLayerHost) layer_table_fill<V, kLayerHost>(table, degrees);
     else layer_table_fill<V, kLayerFused>(table, degrees);
-    const MsCorr corr{pl->ms_scale, pl->ms_offset};
+    MsCorr corr{pl->ms_scale, pl->ms_offset};
+    if constexpr (S::kFixed) {
+        if (rule == kLayerBpFx) corr = bpfx_table_arg(pl->bp_table.p);
+    }
     const int rounds = r.tap_iter ? (r.tap_iter < r.max_iter ? r.tap_iter : r.max_iter) : r.max_iter;
     hipError_t e;
     if ((e = hipMemsetAsync(r.failw, 0, (size_t)(r.max_iter + 2) * slot * sizeof(uint64_t), s))) return e;
@@ -887,7 +1124,7 @@ inline hipError_t layered_dump(LayeredPlan *pl, int which, float *host_out, int6
     if (which == 0 || which == 2) {
         const int64_t per = which == 0 ? pl->E : pl->N;
         if (count != frames * per) return hipErrorInvalidValue;
-        const bool fx = pl->rule == kLayerFx;       /* R bytes and P int16, widened */
+        const bool fx = pl->fixed();                /* R bytes and P int16, widened */
         std::vector<float> tile((size_t)per * F);
         for (int t = 0; t < tiles; ++t) {
             const size_t at = (size_t)t * per * F;

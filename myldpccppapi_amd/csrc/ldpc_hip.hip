@@ -44,7 +44,7 @@ int pick_frames_per_lane(const ldpc_decoder_config &cfg, int32_t max_row_deg, in
     int deg = (cfg.algo == LDPC_ALGO_LAYERED || cfg.algo == LDPC_ALGO_LAYERED_BP) ? max_row_deg : max_col_deg;
     /* fixed-point layered: a row's R is a dword and its P a dwordx2 per lane at 4 frames per lane, whatever the row degree
      * (the unrolled kernels hold the row in registers up to degree 24, the run-time kernel holds none of it) */
-    if (cfg.algo == LDPC_ALGO_LAYERED_FX) return cfg.max_batch >= 256 ? 4 : 1;
+    if (cfg.algo == LDPC_ALGO_LAYERED_FX || cfg.algo == LDPC_ALGO_LAYERED_BP_FX) return cfg.max_batch >= 256 ? 4 : 1;
     if (cfg.algo == LDPC_ALGO_MS || cfg.algo == LDPC_ALGO_BP) deg = (deg + 1) / 2;   /* min-sum variable nodes (BP's too) need half the registers */
     /* one-byte messages (fp8, fixed point): 4 values are one dword per lane, the least a lane should move -- from one full tile on */
     if ((cfg.msg_dtype == LDPC_MSG_F8 || cfg.msg_dtype == LDPC_MSG_I8) && cfg.max_batch >= 256 && deg <= 8) return 4;
@@ -103,6 +103,20 @@ int ldpc_device_count(int *count)
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess) return set_error(LDPC_ERR_HIP, "hipGetDeviceCount: %s", hipGetErrorString(e));
     *count = n;
+    return LDPC_OK;
+}
+
+int ldpc_bp_fx_table(int32_t f, int32_t *out, int32_t cap, int32_t *count)
+{
+    if (!count) return set_error(LDPC_ERR_ARG, "count is NULL");
+    *count = 0;
+    if (f < 0 || f > ldpc::kBpFxMaxFracBits) return set_error(LDPC_ERR_ARG, "bp_frac_bits=%d must be in [0, %d]", f, ldpc::kBpFxMaxFracBits);
+    int32_t t[ldpc::kBpFxTable];
+    const int n = ldpc::bp_fx_table_build(f, t, ldpc::kBpFxTable);
+    *count = n;
+    if (!out) return LDPC_OK;
+    if (cap < n) return set_error(LDPC_ERR_ARG, "the table of bp_frac_bits=%d has %d entries, out holds %d", f, n, cap);
+    std::copy(t, t + n, out);
     return LDPC_OK;
 }
 
@@ -232,18 +246,20 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     if (cfg->max_iter <= 0 || cfg->max_iter > 100000) return set_error(LDPC_ERR_ARG, "max_iter out of range");
     if (cfg->algo != LDPC_ALGO_SP && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED &&
         cfg->algo != LDPC_ALGO_MS_FUSED && cfg->algo != LDPC_ALGO_LAYERED_HOST && cfg->algo != LDPC_ALGO_BP &&
-        cfg->algo != LDPC_ALGO_LAYERED_BP && cfg->algo != LDPC_ALGO_LAYERED_FX)
+        cfg->algo != LDPC_ALGO_LAYERED_BP && cfg->algo != LDPC_ALGO_LAYERED_FX && cfg->algo != LDPC_ALGO_LAYERED_BP_FX)
         return set_error(LDPC_ERR_ARG, "unknown algo %d", cfg->algo);
-    const bool fx = cfg->algo == LDPC_ALGO_LAYERED_FX;
+    const bool bpfx = cfg->algo == LDPC_ALGO_LAYERED_BP_FX;     /* LAYERED_FX's configuration, storage and schedule, another row */
+    const bool fx = cfg->algo == LDPC_ALGO_LAYERED_FX || bpfx;
+    const char *const fx_name = bpfx ? "LDPC_ALGO_LAYERED_BP_FX" : "LDPC_ALGO_LAYERED_FX";
     /* comparisons written so that NaN fails them */
     if (!(cfg->ms_scale >= 0.0f && cfg->ms_scale <= 1.0f))
         return set_error(LDPC_ERR_ARG, "ms_scale must be 0 (off) or in (0, 1]");
     if (!(cfg->ms_offset >= 0.0f && cfg->ms_offset < 1000.0f))
         return set_error(LDPC_ERR_ARG, "ms_offset must be 0 (off) or in (0, 1000)");
     const bool ms_corr = cfg->ms_scale != 0.0f || cfg->ms_offset != 0.0f;
-    if (ms_corr && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED && !fx)
+    if (ms_corr && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED && !(fx && !bpfx))
         return set_error(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset apply to LDPC_ALGO_MS and LDPC_ALGO_LAYERED only "
-                    "(SP, BP and LAYERED_BP have no minimum to correct; MS_FUSED and LAYERED_HOST reproduce reference kernels)");
+                    "(SP, BP, LAYERED_BP and LAYERED_BP_FX have no minimum to correct; MS_FUSED and LAYERED_HOST reproduce reference kernels)");
     const bool bp_row = cfg->algo == LDPC_ALGO_BP || cfg->algo == LDPC_ALGO_LAYERED_BP;      /* box-plus check node */
     if (bp_row && !(cfg->llr_scale > 0.0f && cfg->llr_scale <= 3.402823466e38f))
         return set_error(LDPC_ERR_ARG, "%s: llr_scale must be positive and finite (chan = llr_scale * y is the LLR)",
@@ -265,26 +281,30 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         return set_error(LDPC_ERR_ARG, "frames_per_lane must be 0, 1, 2 or 4");
     if (cfg->msg_dtype != LDPC_MSG_F32 && cfg->msg_dtype != LDPC_MSG_F16 && cfg->msg_dtype != LDPC_MSG_F8 && cfg->msg_dtype != LDPC_MSG_I8)
         return set_error(LDPC_ERR_ARG, "unknown msg_dtype %d", cfg->msg_dtype);
-    if (cfg->msg_reserved2[0] || cfg->msg_reserved2[1])
+    if (cfg->msg_reserved3)
         return set_error(LDPC_ERR_ARG, "msg_reserved must be 0");
+    if (cfg->bp_frac_bits != 0 && !bpfx)
+        return set_error(LDPC_ERR_ARG, "bp_frac_bits=%d belongs to LDPC_ALGO_LAYERED_BP_FX (algo is %d)", cfg->bp_frac_bits, cfg->algo);
+    if (bpfx && (cfg->bp_frac_bits < 0 || cfg->bp_frac_bits > ldpc::kBpFxMaxFracBits))
+        return set_error(LDPC_ERR_ARG, "bp_frac_bits=%d must be in [0, %d]", cfg->bp_frac_bits, ldpc::kBpFxMaxFracBits);
     if (cfg->post_bits != 0 && !fx)
-        return set_error(LDPC_ERR_ARG, "post_bits=%d belongs to LDPC_ALGO_LAYERED_FX (algo is %d)", cfg->post_bits, cfg->algo);
+        return set_error(LDPC_ERR_ARG, "post_bits=%d belongs to LDPC_ALGO_LAYERED_FX and LDPC_ALGO_LAYERED_BP_FX (algo is %d)", cfg->post_bits, cfg->algo);
     if (fx && cfg->msg_dtype != LDPC_MSG_I8)
-        return set_error(LDPC_ERR_ARG, "LDPC_ALGO_LAYERED_FX is defined on fixed-point messages: msg_dtype must be LDPC_MSG_I8, not %d", cfg->msg_dtype);
+        return set_error(LDPC_ERR_ARG, "%s is defined on fixed-point messages: msg_dtype must be LDPC_MSG_I8, not %d", fx_name, cfg->msg_dtype);
     if (cfg->msg_bits != 0 && cfg->msg_dtype != LDPC_MSG_I8)
         return set_error(LDPC_ERR_ARG, "msg_bits=%d belongs to LDPC_MSG_I8 (msg_dtype is %d)", cfg->msg_bits, cfg->msg_dtype);
     if (cfg->msg_bits != 0 && cfg->msg_bits != 4 && cfg->msg_bits != 5 && cfg->msg_bits != 6 && cfg->msg_bits != 8)
         return set_error(LDPC_ERR_ARG, "msg_bits must be 0 (8), 4, 5, 6 or 8, not %d", cfg->msg_bits);
     if (cfg->msg_dtype == LDPC_MSG_I8 && cfg->algo != LDPC_ALGO_MS && !fx)
         return set_error(LDPC_ERR_UNSUPPORTED, "fixed-point messages (LDPC_MSG_I8) are built for flooding min-sum and, as an algorithm of "
-                    "its own, LDPC_ALGO_LAYERED_FX (SP and BP have no integer datapath here; LDPC_ALGO_LAYERED, LAYERED_BP and the "
+                    "their own, LDPC_ALGO_LAYERED_FX and LDPC_ALGO_LAYERED_BP_FX (SP and BP have no integer datapath here; LDPC_ALGO_LAYERED, LAYERED_BP and the "
                     "reference-reproducing decoders are fp32)");
     if (fx) {
         const int q = cfg->msg_bits ? cfg->msg_bits : 8;
         if (cfg->post_bits != 0 && (cfg->post_bits < q || cfg->post_bits > 16))
             return set_error(LDPC_ERR_ARG, "post_bits=%d must be 0 (16) or in [msg_bits=%d, 16]", cfg->post_bits, q);
         if (cfg->layer_rows <= 0 || g->M % cfg->layer_rows)
-            return set_error(LDPC_ERR_ARG, "LDPC_ALGO_LAYERED_FX: layer_rows=%d must be positive and divide M=%d", cfg->layer_rows, g->M);
+            return set_error(LDPC_ERR_ARG, "%s: layer_rows=%d must be positive and divide M=%d", fx_name, cfg->layer_rows, g->M);
     }
     /* written so that NaN fails it */
     if (cfg->msg_dtype == LDPC_MSG_I8 && !(cfg->llr_scale > 0.0f && cfg->llr_scale <= 3.402823466e38f))
@@ -410,13 +430,20 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     } else if (cfg->algo == LDPC_ALGO_LAYERED_HOST || cfg->algo == LDPC_ALGO_LAYERED_BP || fx) {
         /* the streaming layered engine always.  LAYERED_BP: the record kernels' 16-byte check record holds two minima and
          * cannot hold a row's D independent messages, and the LDS-resident kernel carries no box-plus row */
-        d->layered.rule = fx ? ldpc::kLayerFx : cfg->algo == LDPC_ALGO_LAYERED_BP ? ldpc::kLayerBp : ldpc::kLayerHost;
+        d->layered.rule = bpfx ? ldpc::kLayerBpFx : fx ? ldpc::kLayerFx : cfg->algo == LDPC_ALGO_LAYERED_BP ? ldpc::kLayerBp : ldpc::kLayerHost;
         d->layered.llr_scale = cfg->llr_scale;
         if (fx) {       /* plain min-sum is the corrected row with scale 1, offset 0: the identity on [0, L] */
             d->layered.L = (float)((1 << ((cfg->msg_bits ? cfg->msg_bits : 8) - 1)) - 1);
             d->layered.LP = (float)((1 << ((cfg->post_bits ? cfg->post_bits : 16) - 1)) - 1);
             d->layered.ms_scale = d->ms_scale;
             d->layered.ms_offset = d->ms_offset;
+        }
+        if (bpfx) {     /* the kernels index the table with |a| + |b| <= 254 and never clamp: zeros behind its last entry */
+            int32_t t[ldpc::kBpFxTable];
+            const int n = ldpc::bp_fx_table_build(cfg->bp_frac_bits, t, ldpc::kBpFxTable);
+            std::vector<uint8_t> bytes((size_t)ldpc::kBpFxTable, 0);
+            for (int i = 0; i < n; ++i) bytes[(size_t)i] = (uint8_t)t[i];
+            LDPC_HIP_TRY(d->layered.bp_table.upload(bytes));
         }
         int rc = ldpc::layered_plan_create(&d->layered, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows, d->T, d->V);
         if (rc == -1) return set_error(LDPC_ERR_ARG, "layer_rows=%d must divide M=%d and rows of a layer "
@@ -659,7 +686,7 @@ static int decode_device_in(ldpc_decoder *d, const ldpc::LlrIn &in, int64_t fram
         if (e == hipSuccess) e = ldpc::span_end(d, s);
         rc = (e == hipSuccess) ? LDPC_OK : set_error(LDPC_ERR_HIP, "fused decode: %s", hipGetErrorString(e));
     } else if (d->cfg.algo == LDPC_ALGO_LAYERED || d->cfg.algo == LDPC_ALGO_LAYERED_HOST || d->cfg.algo == LDPC_ALGO_LAYERED_BP ||
-               d->cfg.algo == LDPC_ALGO_LAYERED_FX) {
+               d->cfg.algo == LDPC_ALGO_LAYERED_FX || d->cfg.algo == LDPC_ALGO_LAYERED_BP_FX) {
         ldpc::LayeredRun run;
         run.span_begin = [](void *c, hipStream_t st, int kind, int deg, int64_t bytes) {
             return ldpc::span_begin((ldpc_decoder *)c, st, kind, deg, bytes);

@@ -7,10 +7,10 @@ b is frame b*frames + f of the seed's stream, so a point can be extended or re-r
 and errors counted by ldpc_count_errors_device; nothing crosses PCIe but the counts.  The
 reference counts differing BYTES (Test.cpp:105-110); this prints byte errors too.
 
-    python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N> | --alist PATH] [--algo sp|ms|layered|bp|layered_bp|layered_fx]
+    python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N> | --alist PATH] [--algo sp|ms|layered|bp|layered_bp|layered_fx|layered_bp_fx]
                               [--payload zero|random] [--rate-match P,FLO,FHI,E[,K0]] [--erasure-llr X]
                               [--modulation bpsk|qpsk|qam16|qam64|qam256] [--no-interleave] [--transport-block A[,C]] [--crc-stop] [--bch T[,N]]
-                              [--msg-dtype f32|f16|f8|i8 [--msg-bits Q --llr-scale S]] [--post-bits P] [--soft-check] [--osd 0|1 [--osd-scale S]]
+                              [--msg-dtype f32|f16|f8|i8 [--msg-bits Q --llr-scale S]] [--post-bits P] [--frac-bits F] [--soft-check] [--osd 0|1 [--osd-scale S]]
                               [--snr=1.0,1.5,...]  (write --snr=-0.5,0 for a list that starts with a minus) [--frames 4096] [--iters 50]
 --rate-match: code bits [0, P) punctured, [FLO, FHI) filler bits (known zeros; multiples of 8, inside the information part),
 E bits per frame sent from circular-buffer position K0 (default 0): ldpc_rate_match_device between the encoder and the
@@ -29,6 +29,9 @@ per point, with any modulation and with none, unless --llr-scale is given; --msg
 layered it needs a code with a circulant size (bg1, wimax:...), it is fp32 only, and it takes exact zeros (no --erasure-llr).
 --algo layered_fx (LDPC_ALGO_LAYERED_FX: the layered schedule in fixed point) takes --msg-bits Q, --post-bits P (the
 saturating posterior memory) and --llr-scale S, the LSBs per unit of channel value; --ms-offset is in LSBs.
+--algo layered_bp_fx (LDPC_ALGO_LAYERED_BP_FX: layered_fx with box-plus rows from a correction table) takes --msg-bits Q,
+--post-bits P, --frac-bits F (one LSB is 2^-F LLR units, 0 ... 4) and --llr-scale S, the LSBs per unit of channel value;
+without --llr-scale it follows the noise, 2^F * 2 / sd^2 per point: the channel LLR in LSBs.  No --ms-scale / --ms-offset.
 --transport-block A[,C] (with --payload random): the random bytes are transport blocks of A payload bits; ldpc_tb_attach_device
 in front of the encoder adds the transport block's CRC, cuts it into C code blocks with CRC24B each (C omitted: the rule of
 ldpc_tb_spec_init) and fills up to K with zeros; ldpc_tb_check_device and ldpc_tb_tally_device behind the decoder judge the
@@ -94,10 +97,12 @@ ap.add_argument("--transport-block", default=None, metavar="A[,C]",
 ap.add_argument("--bch", default=None, metavar="T[,N]",
                 help="with --payload random: outer BCH code that corrects T errors over N code bits (default: K)")
 ap.add_argument("--msg-dtype", choices=("f32", "f16", "f8", "i8"), default="f32",
-                help="message storage (f16: --algo ms and bp; f8: --algo ms; i8: --algo ms and layered_fx, saturating integers of "
-                     "--msg-bits bits, channel c = sq(--llr-scale * y), --ms-offset in LSBs; --algo layered_fx implies i8)")
+                help="message storage (f16: --algo ms and bp; f8: --algo ms; i8: --algo ms, layered_fx and layered_bp_fx, saturating "
+                     "integers of --msg-bits bits, channel c = sq(--llr-scale * y), --ms-offset in LSBs; --algo layered_fx and "
+                     "layered_bp_fx imply i8)")
 ap.add_argument("--msg-bits", type=int, default=0, help="with --msg-dtype i8: 4, 5, 6 or 8 bits per message (0 = 8)")
-ap.add_argument("--post-bits", type=int, default=0, help="--algo layered_fx: bits of the saturating posterior memory, --msg-bits ... 16 (0 = 16)")
+ap.add_argument("--post-bits", type=int, default=0, help="--algo layered_fx and layered_bp_fx: bits of the saturating posterior memory, --msg-bits ... 16 (0 = 16)")
+ap.add_argument("--frac-bits", type=int, default=0, help="--algo layered_bp_fx: fractional bits of an LSB, 0 ... 4 (one LSB = 2^-F LLR units)")
 ap.add_argument("--llr-type", choices=("f32", "f16", "i8"), default="f32",
                 help="quantise the channel values on the device (ldpc_llr_quantize_device) behind the channel / rate-recover step "
                      "and decode them through ldpc_decode_typed_device")
@@ -110,7 +115,7 @@ ap.add_argument("--soft-check", action="store_true",
 ap.add_argument("--osd", type=int, choices=(0, 1), default=None, help="ordered-statistics decoding of that order behind the decoder (not --algo sp)")
 ap.add_argument("--osd-scale", type=float, default=256.0, help="with --osd: weight_scale")
 args = ap.parse_args()
-if args.algo == "layered_fx":
+if args.algo in ("layered_fx", "layered_bp_fx"):
     args.msg_dtype = "i8"           # the algorithm is defined on fixed-point messages alone
 assert args.osd is None or args.algo != "sp", "--osd: sum-product has no soft output (include/ldpc_hip.h)"
 assert not (args.soft_check and args.algo == "sp"), "--soft-check: sum-product has no soft output (include/ldpc_hip.h)"
@@ -121,7 +126,9 @@ assert not (args.bch and args.transport_block), "--bch and --transport-block exc
 assert args.modulation or not args.no_interleave, "--no-interleave needs --modulation"
 QM = {None: 0, "bpsk": 1, "qpsk": 2, "qam16": 4, "qam64": 6, "qam256": 8}[args.modulation]
 # llr_scale = 2 / sd^2 per SNR point: sp behind a demapper, bp always (its messages are LLRs)
-matched = ((bool(QM) and args.algo == "sp") or args.algo in ("bp", "layered_bp")) and args.llr_scale is None
+matched = ((bool(QM) and args.algo == "sp") or args.algo in ("bp", "layered_bp", "layered_bp_fx")) and args.llr_scale is None
+# the matched scale in the decoder's units: LLR units, for layered_bp_fx LSBs of 2^-F LLR units
+llr_unit_scale = float(1 << args.frac_bits) if args.algo == "layered_bp_fx" else 1.0
 
 layer = 0
 if args.alist:
@@ -150,7 +157,7 @@ else:
     K, M, layer = codes.wimax_dims(rate, N)
     rows, cols = codes.wimax_edges(rate, N)
 M = M0 if args.alist else N - K
-assert layer or args.algo not in ("layered", "layered_bp", "layered_fx"), "--algo %s needs the code's circulant size z: --code bg1 or wimax:<rate>:<N>" % args.algo
+assert layer or args.algo not in ("layered", "layered_bp", "layered_fx", "layered_bp_fx"), "--algo %s needs the code's circulant size z: --code bg1 or wimax:<rate>:<N>" % args.algo
 g = L.Graph(rows, cols, M, N)
 B = args.frames
 tb = None
@@ -167,7 +174,8 @@ if args.bch:
 def make_decoder(llr_scale):
     return L.Decoder(g, K, max_batch=B, algo=args.algo, max_iter=args.iters, llr_scale=llr_scale,
                      layer_rows=layer, poll_interval=2, ms_scale=args.ms_scale, ms_offset=args.ms_offset,
-                     crc_kind=crc_kind, crc_bits=crc_bits, msg_dtype=args.msg_dtype, msg_bits=args.msg_bits, post_bits=args.post_bits)
+                     crc_kind=crc_kind, crc_bits=crc_bits, msg_dtype=args.msg_dtype, msg_bits=args.msg_bits, post_bits=args.post_bits,
+                     bp_frac_bits=args.frac_bits)
 
 
 dec = None if matched else make_decoder(8.0 if args.llr_scale is None else args.llr_scale)
@@ -298,7 +306,7 @@ def point_decoder(sd):
         return
     if dec is not None:
         dec.close()
-    scale = 2.0 / (sd * sd)
+    scale = llr_unit_scale * 2.0 / (sd * sd)
     if rm is not None and args.algo == "sp":                         # exp(llr_scale * fill_llr) must stay finite
         rm.spec.fill_llr = min(10.0, 80.0 / scale)
     dec = make_decoder(scale)
@@ -420,9 +428,9 @@ for snr in points:
     if md is not None:
         es_n0 = 1.0 / (2.0 * sd * sd)
         res.update({"es_n0_db": round(10.0 * np.log10(es_n0), 3), "eb_n0_db": round(10.0 * np.log10(es_n0 / (QM * rate)), 3),
-                    "llr_scale": round(2.0 / (sd * sd), 3) if matched else (8.0 if args.llr_scale is None else args.llr_scale)})
-    if md is None and args.algo in ("bp", "layered_bp"):
-        res["llr_scale"] = round(2.0 / (sd * sd), 3) if matched else args.llr_scale
+                    "llr_scale": round(llr_unit_scale * 2.0 / (sd * sd), 3) if matched else (8.0 if args.llr_scale is None else args.llr_scale)})
+    if md is None and args.algo in ("bp", "layered_bp", "layered_bp_fx"):
+        res["llr_scale"] = round(llr_unit_scale * 2.0 / (sd * sd), 3) if matched else args.llr_scale
     if tb is not None:
         n = TBS * args.batches
         res.update({"blocks": n, "bler": blocks[1] / n, "blocks_crc_failed": blocks[0], "blocks_undetected": blocks[2],
