@@ -92,7 +92,13 @@ static ldpc::CheckArgs check_args(const ldpc_decoder *d, const ldpc::TailRef &tr
     ldpc::CheckArgs a{d->flood.Q.p, d->flood.R.p, e0, d->done.p, d->E, n_rows, rows_per_wave, degree, d->ms_scale, tr};
     a.ms_offset = d->ms_offset;
     a.qpos = d->flood.qpos.p;
-    if (from_chan) { a.first_chan = d->flood.chan.p; a.edge_col = d->edge_col.p; a.N = d->N; }
+    /* both index tables in every launch, whichever one the round reads through: check_rows chooses by a per-lane
+     * pointer, and where the compiler lowers that choice to exec masks without a skip branch -- the degree-1 body of the
+     * corrected arithmetics, short enough -- the wave-uniform load of the side not taken is a scalar load, which no
+     * exec mask holds back.  From a null edge_col it faulted in every round that read Q (CheckArgs::edge_col). */
+    a.edge_col = d->edge_col.p;
+    a.N = d->N;
+    if (from_chan) a.first_chan = d->flood.chan.p;
     return a;
 }
 

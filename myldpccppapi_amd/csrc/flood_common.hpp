@@ -306,7 +306,9 @@ struct CheckArgs {
      * decodeCL.c:121: q = y), so they are read from the channel array by column instead of from Q, which the input
      * transpose then does not have to write at all (a third of its traffic).  nullptr: read Q. */
     const void *__restrict__ first_chan = nullptr;     /* [T][N][F] */
-    const int32_t *__restrict__ edge_col = nullptr;    /* [E] column of every edge */
+    /* [E] column of every edge; like qpos never null in a launch, also where first_chan is: the side of check_rows'
+     * choice that is not taken may still issue its wave-uniform (scalar) index load under an empty exec mask */
+    const int32_t *__restrict__ edge_col = nullptr;
     int32_t N = 0;
     /* Where the variable->check message of edge e lives in Q: slot qpos[e] (nullptr: slot e).  Q is stored in the
      * order its WRITERS produce it -- the variable-node kernels column by column, then the column-fused check

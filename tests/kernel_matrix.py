@@ -2,7 +2,12 @@
 
 The wimax, DVB-S2-profile and BG1-profile codes of the other tests have few degree mixes.  The codes made here
 put rows and columns of every degree class the streaming flooding kernels distinguish on one graph, so that every
-unrolled body, bucket launch and generic kernel runs against the oracle."""
+unrolled body, bucket launch and generic kernel runs against the oracle.
+
+Who runs the matrix code: sp, ms and ms16 in tests/test_gpu_kernel_matrix.py, bp and bp16 in tests/test_gpu_bp.py
+(bp_cases.matrix()); the corrected and one-byte arithmetics -- msc, msc16, ms8, msc8, msi4/5/6/8, msci4/5/6/8 -- in
+tests/test_gpu_flood_matrix.py (flood_matrix_cases.py), which also holds the matrix code without its rows above degree 32,
+the one on which round 1 reads the channel array."""
 import numpy as np
 
 from myldpccppapi_amd import capi, channel, codes
@@ -122,7 +127,10 @@ def ira_code(d, n_link, extra, info_col_deg=3, seed=1):
 # One entry per tuning key of capi.TUNE_FIELDS / capi.TUNE_INTS: the tuning dict of a case the kernel-matrix
 # module runs, and the test that runs it.  Keys that other modules already cover name that test instead
 # ("tune": None).  The forms of the column-fused check kernel (link_*) run in fp32 and sum-product there; with fp16
-# messages, plain and corrected, tests/test_gpu_fp16.py::test_fp16_column_fused_forms runs them all again.
+# messages, plain and corrected, tests/test_gpu_fp16.py::test_fp16_column_fused_forms runs them all again.  The launch
+# plans of the streaming kernels (FLOOD_PLANS below: merge, check_wide, rows_per_wave, cols_per_wave, q_order, syn_xcd,
+# tiles_first) run in fp32 here; the corrected and one-byte arithmetics (msc, msc16, ms8, msc8, msi*, msci*) get their degree
+# matrix, under the same plans, in tests/test_gpu_flood_matrix.py::test_every_degree_class.
 _KM = "test_gpu_kernel_matrix"
 TUNE_CASES = {
     "fused": dict(tune={"fused": True, "ldsp": False}, test=_KM + "::test_one_launch_kernels_on_qc_shapes"),
