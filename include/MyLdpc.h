@@ -144,6 +144,11 @@ public:
      * include/ldpc_hip.h: post_bits); anything else makes addDecodeType fail as ldpc_decoder_create does.  Read by no other
      * decode type.  Before addDecodeType(). */
     void setPosteriorBits(int bits) { postBits = bits; }
+    /* DecodeLayeredFixed: true runs the same rule, bit for bit, on the fixed-point record kernel (include/ldpc_hip.h:
+     * LDPC_TUNE_FX_RECORD) where the code fits it, and on the streaming layered engine where it does not; with
+     * setCrcEarlyStop addDecodeType then fails as ldpc_decoder_create does.  Off by default.  Read by no other decode type.
+     * Before addDecodeType(). */
+    void setFixedRecordKernel(bool on) { fxRecord = on; }
     /* DecodeLayeredBPFixed: one LSB of a message is 2^-bits LLR units, 0 <= bits <= 4 (include/ldpc_hip.h: bp_frac_bits);
      * anything else makes addDecodeType fail as ldpc_decoder_create does.  Read by no other decode type.  Before
      * addDecodeType(). */
@@ -250,6 +255,7 @@ private:
     int msgBits = 0;                 /* setMessageType(): bits per message with LDPC_MSG_I8 */
     int postBits = 0;                /* setPosteriorBits(): DecodeLayeredFixed, DecodeLayeredBPFixed */
     int fracBits = 0;                /* setLlrFractionBits(): DecodeLayeredBPFixed */
+    bool fxRecord = false;           /* setFixedRecordKernel(): DecodeLayeredFixed */
     int makeDecoder(const ldpc_decoder_config &cfg, ldpc_decoder **out);
     const signed char *hSeed;
     int seedRowLength;

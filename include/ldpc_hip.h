@@ -168,11 +168,29 @@ enum ldpc_algo {
  * Properties: with p = 16 and (1 + column degree) * 127 <= 32767 the posterior never saturates, and the rule is the
  * plain layered schedule on integers.  The kernels compute in fp32 on integers far below 2^24, which is exact.
  * Refusals, all before the device is touched: the LDPC_ERR_ARG cases above, and LDPC_TUNE_ON(FUSED) or LDPC_TUNE_ON(LDSP)
- * is LDPC_ERR_UNSUPPORTED: it always runs the streaming layered engine.  post_bits != 0 with any other algorithm is
- * LDPC_ERR_ARG.  LDPC_ALGO_LAYERED with LDPC_MSG_I8 stays LDPC_ERR_UNSUPPORTED: a different rule with different state is an
+ * is LDPC_ERR_UNSUPPORTED: it runs the streaming layered engine unless LDPC_TUNE_FX_RECORD is on (below).  post_bits != 0
+ * with any other algorithm is LDPC_ERR_ARG.  LDPC_ALGO_LAYERED with LDPC_MSG_I8 stays LDPC_ERR_UNSUPPORTED: a different rule with different state is an
  * algorithm of its own here, as LAYERED_HOST and LAYERED_BP are.  ldpc_decode, ldpc_decode_device, ldpc_decode_soft*,
  * ldpc_decode_typed*, ldpc_decoder_create_multi, the debug taps, crc_kind and kernel times (spans named lfx) work as
- * for LDPC_ALGO_LAYERED. */
+ * for LDPC_ALGO_LAYERED.
+ *   LDPC_TUNE_ON(LDPC_TUNE_FX_RECORD): the same rule, bit for bit, in one launch on the record organisation of
+ *                 LDPC_ALGO_LAYERED (layered_ldsp_fx_kernel): a persistent workgroup per frame, the posteriors of the block
+ *                 columns met by two or more layers as int16 in LDS, and per row and layer one 8-byte record that only the
+ *                 row's own lane reads and writes:
+ *                   word 0: signs of R_0 .. R_{D-1} in bits 0 .. 23, argmin in bits 24 .. 28
+ *                   word 1: m1' in bits 0 .. 7, m2' in bits 8 .. 15 (the two magnitudes after correction and the clamp to
+ *                           L), the int16 posterior of the row's single-layer column in bits 16 .. 31
+ *                 R_k = (sign_k ? -1 : 1) * (k == argmin ? m2' : m1').  A magnitude of 0 makes the sign immaterial; among
+ *                 entries that tie for the minimum m1' = m2', so the argmin kept does not matter.
+ *                 Off by default; the automatic choice stays the streaming engine.  Refusals, before the device is touched:
+ *                 with LDPC_ALGO_LAYERED_BP_FX it is LDPC_ERR_UNSUPPORTED (a box-plus row sends D independent messages,
+ *                 which two minima cannot hold); with crc_kind != 0 it is LDPC_ERR_UNSUPPORTED.  A code the kernel cannot
+ *                 serve -- not quasi-cyclic at layer_rows, a row of more than 24 entries, posteriors beyond the LDS limit,
+ *                 LDPC_PACK_BITS with K % 8 != 0 -- decodes on the streaming engine with the same result.  Every entry
+ *                 point, early_term 0 or 1, soft output and the debug taps work as without it; the kernel time is one span
+ *                 named layered_ldsp_fx_kernel[grid x block, frames per workgroup].  tune_ldsp_grid, the per-CU and waves
+ *                 fields of tune_ldsp_shape and LDPC_TUNE_LDSP_EXT act as on the float record kernel; LDPC_TUNE_LDSP_PACK
+ *                 is ignored (circulants of <= 32 rows run one frame per one-wave workgroup). */
 
 /* LDPC_ALGO_LAYERED_BP_FX, bit for bit, in integers: LDPC_ALGO_LAYERED_FX with the check node of LDPC_ALGO_LAYERED_BP, the
  * way a hardware box-plus decoder computes it: the minimum plus a small correction read from a table.
@@ -402,9 +420,14 @@ enum ldpc_tune_field {
     LDPC_TUNE_LINK_HALF = 24,   /* column-fused check kernel with 2 values per lane (tiles of 256)  */
     LDPC_TUNE_LINK_GUIDED = 26, /* column-fused check kernel: its launch ends with shorter row chunks
                                    (default on from 4 tiles)                                         */
-    LDPC_TUNE_TILES_FIRST = 28  /* flooding launches as grids of (tiles, blocks): the blocks in flight
+    LDPC_TUNE_TILES_FIRST = 28, /* flooding launches as grids of (tiles, blocks): the blocks in flight
                                    are spread over all tiles of the batch (default: the column-fused
                                    check launch only; on: all; off: none)                               */
+    LDPC_TUNE_FX_RECORD = 30    /* LDPC_ALGO_LAYERED_FX on the fixed-point record kernel (layered_ldsp_fx_kernel).
+                                   Values: 0 (off, the default) and LDPC_TUNE_ON(LDPC_TUNE_FX_RECORD); LDPC_TUNE_OFF
+                                   is not defined for it (it does not fit an int32_t; a negative tune_flags is
+                                   LDPC_ERR_ARG), and with any algorithm other than LDPC_ALGO_LAYERED_FX /
+                                   LDPC_ALGO_LAYERED_BP_FX the bit is LDPC_ERR_ARG                         */
 };
 #define LDPC_TUNE_ON(field) (1 << (field))
 #define LDPC_TUNE_OFF(field) (2 << (field))

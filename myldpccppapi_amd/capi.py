@@ -33,18 +33,22 @@ ALGOS = {"sp": ALGO_SP, "ms": ALGO_MS, "layered": ALGO_LAYERED, "ms_fused": ALGO
 TUNE_FIELDS = {"fused": 0, "ldsp": 2, "ldsp_ext": 4, "ldsp_pack": 6, "link_narrow": 8, "check_wide": 10,
                "syn_xcd": 12, "fused_pack": 14, "fused_loop": 16, "device_tail": 18, "merge": 20, "link_deep": 22, "link_half": 24,
                "link_guided": 26, "tiles_first": 28}
+TUNE_ON_ONLY = {"fx_record": 30}      # LDPC_TUNE_FX_RECORD: on or absent (its "off" would not fit the int32 word)
 TUNE_INTS = ("rows_per_wave", "cols_per_wave", "link_rows", "compact", "ldsp_grid", "ldsp_per_cu", "ldsp_waves", "place", "q_order")
 
 
 def apply_tune(cfg, tune):
     """Fill the tuning fields of a DecoderConfig from a dict: tri-state names of TUNE_FIELDS
-    (True / False / None = automatic) and integers of TUNE_INTS (link_rows=-1: column-local fusion
+    (True / False / None = automatic), "fx_record" (True = on; False / None = off) and integers of TUNE_INTS (link_rows=-1: column-local fusion
     off; compact=-1: tail compaction off).  Kernel selection and launch shapes only."""
     flags, shape = 0, 0
     for k, v in (tune or {}).items():
         if k in TUNE_FIELDS:
             if v is not None:
                 flags |= (1 if v else 2) << TUNE_FIELDS[k]
+        elif k in TUNE_ON_ONLY:
+            if v:
+                flags |= 1 << TUNE_ON_ONLY[k]
         elif k == "ldsp_per_cu":
             shape |= int(v) & 255
         elif k == "ldsp_waves":
@@ -92,7 +96,7 @@ def tune_from_env(env=None):
     for name, key in (("FUSED", "fused"), ("LDSP", "ldsp"), ("LDSP_EXT", "ldsp_ext"), ("LDSP_PACK", "ldsp_pack"),
                       ("LINK_NARROW", "link_narrow"), ("CHECK_WIDE", "check_wide"), ("SYN_XCD", "syn_xcd"),
                       ("FUSED_LOOP", "fused_loop"), ("DEVICE_TAIL", "device_tail"), ("MERGE", "merge"), ("LINK_DEEP", "link_deep"), ("LINK_HALF", "link_half"),
-                      ("LINK_GUIDED", "link_guided"), ("TILES_FIRST", "tiles_first")):
+                      ("LINK_GUIDED", "link_guided"), ("TILES_FIRST", "tiles_first"), ("FX_RECORD", "fx_record")):
         if "LDPC_TUNE_" + name in env:
             t[key] = int(env["LDPC_TUNE_" + name]) != 0
     if "LDPC_TUNE_NO_PACK" in env:

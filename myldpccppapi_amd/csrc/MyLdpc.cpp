@@ -508,6 +508,7 @@ int Coder::addDecodeType(enum decodeType deType)
                : (deType == DecodeLayeredBPFixed) ? LDPC_ALGO_LAYERED_BP_FX : LDPC_ALGO_LAYERED;
     if (deType == DecodeLayeredFixed || deType == DecodeLayeredBPFixed) cfg.post_bits = postBits;     /* setPosteriorBits(); the circulant size as DecodeTDMPCL */
     if (deType == DecodeLayeredBPFixed) cfg.bp_frac_bits = fracBits;    /* setLlrFractionBits() */
+    if (deType == DecodeLayeredFixed && fxRecord) cfg.tune_flags |= LDPC_TUNE_ON(LDPC_TUNE_FX_RECORD);   /* setFixedRecordKernel() */
     if (deType == DecodeTDMP) {
         /* The reference's host-layered path (MyLdpc.cpp:889-976) sizes layer l as
          * hRowRange[l + z] - hRowRange[l] (:907, :958): right only when all rows of H have one weight

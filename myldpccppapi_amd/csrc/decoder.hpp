@@ -249,7 +249,8 @@ struct ldpc_decoder {
     ldpc::LayeredPlan layered;          /* LDPC_ALGO_LAYERED / LAYERED_HOST / LAYERED_BP, streaming (one launch per layer) */
     ldpc::FusedPlan fused;              /* LDPC_ALGO_LAYERED, short QC codes: whole decode in LDS */
     bool use_fused = false;
-    ldpc::LdspPlan ldsp;                /* LDPC_ALGO_LAYERED, mid-size QC codes: posterior in LDS, check records in cache */
+    ldpc::LdspPlan ldsp;                /* LDPC_ALGO_LAYERED, mid-size QC codes: posterior in LDS, check records in cache;
+                                           LDPC_ALGO_LAYERED_FX with LDPC_TUNE_FX_RECORD: the same in fixed point (ldsp.fx) */
     bool use_ldsp = false;
     /* normalized / offset min-sum (cfg.ms_scale / ms_offset): the streaming kernels of kAlgoMSC (flooding) or
      * layer_corr_kernel (layered) run with alpha = ms_scale (1 when 0) and beta = ms_offset */

@@ -1,6 +1,6 @@
 /*
  * engines.hpp -- the entry points of the engines that instantiate kernels, compiled in translation units of
- * their own (engine_ldsp.hip, engine_fused.hip, engine_layered.hip, engine_layered_fx.hip, engine_layered_bpfx.hip, engine_flood.hip) so that the library
+ * their own (engine_ldsp.hip, engine_ldsp_fx.hip, engine_fused.hip, engine_layered.hip, engine_layered_fx.hip, engine_layered_bpfx.hip, engine_flood.hip) so that the library
  * builds in parallel.  The host driver calls these instead of the inline functions of the kernel headers;
  * plan structs and everything without kernels stay in the headers.
  */
@@ -29,6 +29,11 @@ hipError_t engine_ldsp_plan_create(LdspPlan *pl, int32_t M, int32_t N, int64_t E
                                    const std::vector<int32_t> &cols, int32_t z, int32_t K, int64_t max_batch, int device,
                                    const Tune &tune, int flood);
 hipError_t engine_ldsp_run(LdspPlan *pl, const FusedRun &r, hipStream_t s, int32_t *launched);
+/* engine_ldsp_fx.hip: layered_ldsp_fx_kernel (ldsp_fx_kernels.hpp), LDPC_ALGO_LAYERED_FX on the record organisation */
+hipError_t engine_ldsp_fx_plan_create(LdspPlan *pl, int32_t M, int32_t N, int64_t E, const std::vector<int32_t> &row_ptr,
+                                      const std::vector<int32_t> &cols, int32_t z, int32_t K, int64_t max_batch, int device,
+                                      const Tune &tune);
+hipError_t engine_ldsp_fx_run(LdspPlan *pl, const FusedRun &r, hipStream_t s, int32_t *launched);
 hipError_t engine_fused_run(FusedPlan *pl, const FusedRun &r, hipStream_t s, int32_t *launched);
 /* every rule of the streaming layered engine (LayeredPlan::rule); engine_layered_fx.hip holds the fixed-point storage's half,
  * engine_layered_bpfx.hip the kernels of the fixed-point box-plus rule */

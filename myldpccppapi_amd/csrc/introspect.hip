@@ -169,6 +169,8 @@ int ldpc_decoder_kernel_times(ldpc_decoder *d, ldpc_kernel_time *out, int32_t ca
         if (sp.kind == 3) snprintf(name, sizeof name, "other");
         else if (sp.kind == 7) snprintf(name, sizeof name, "soft_settle_kernel");     /* soft calls only */
         else if (sp.kind == 8) snprintf(name, sizeof name, "llr_widen_kernel");       /* typed calls on a one-launch kernel only */
+        else if (d->use_fused && d->use_ldsp && d->ldsp.fx)
+            snprintf(name, sizeof name, "layered_ldsp_fx_kernel[%dx%d,%d]", d->ldsp.grid, d->ldsp.block, d->ldsp.wg_frames);
         else if (d->use_fused && d->use_ldsp)   /* whole decode in one launch; [persistent grid x workgroup size, frames per workgroup] */
             snprintf(name, sizeof name, "%s[%dx%d,%d]", d->cfg.algo == LDPC_ALGO_LAYERED
                      ? (d->ms_corr ? "layered_ldsp_corr_kernel" : "layered_ldsp_kernel")

@@ -343,6 +343,13 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
             return set_error(LDPC_ERR_UNSUPPORTED, "crc_kind: the LDS-resident one-launch kernels and the record kernels (LDPC_TUNE_FUSED / "
                         "LDPC_TUNE_LDSP forced on) do not carry the CRC rule; the streaming kernels do");
     }
+    const bool fx_record = ldpc::tune_from_config(*cfg).fx_record != 0;      /* tune_valid: a fixed-point layered algorithm */
+    if (fx_record && bpfx)
+        return set_error(LDPC_ERR_UNSUPPORTED, "LDPC_TUNE_FX_RECORD: a box-plus row sends D independent messages and the record "
+                    "kernel's two-minimum record cannot hold them; LDPC_ALGO_LAYERED_BP_FX runs the streaming layered engine");
+    if (fx_record && crc_term)
+        return set_error(LDPC_ERR_UNSUPPORTED, "crc_kind: the fixed-point record kernel (LDPC_TUNE_FX_RECORD) does not carry the CRC "
+                    "rule; the streaming kernels do");
 
     int ndev = 0;
     LDPC_HIP_TRY(hipGetDeviceCount(&ndev));
@@ -428,7 +435,7 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         }
         d->use_fused = true;
     } else if (cfg->algo == LDPC_ALGO_LAYERED_HOST || cfg->algo == LDPC_ALGO_LAYERED_BP || fx) {
-        /* the streaming layered engine always.  LAYERED_BP: the record kernels' 16-byte check record holds two minima and
+        /* the streaming layered engine (LAYERED_FX: unless LDPC_TUNE_FX_RECORD, below).  LAYERED_BP: the record kernels' 16-byte check record holds two minima and
          * cannot hold a row's D independent messages, and the LDS-resident kernel carries no box-plus row */
         d->layered.rule = bpfx ? ldpc::kLayerBpFx : fx ? ldpc::kLayerFx : cfg->algo == LDPC_ALGO_LAYERED_BP ? ldpc::kLayerBp : ldpc::kLayerHost;
         d->layered.llr_scale = cfg->llr_scale;
@@ -445,7 +452,20 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
             for (int i = 0; i < n; ++i) bytes[(size_t)i] = (uint8_t)t[i];
             LDPC_HIP_TRY(d->layered.bp_table.upload(bytes));
         }
-        int rc = ldpc::layered_plan_create(&d->layered, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows, d->T, d->V);
+        /* LDPC_TUNE_FX_RECORD: layered_ldsp_fx_kernel (int16 posteriors in LDS, 8-byte check records in cache) where the code
+         * fits it -- quasi-cyclic at layer_rows, rows of at most 24 entries, posteriors within the LDS limit, whole bytes per
+         * frame -- and the streaming engine, with the same result, where it does not */
+        if (fx_record && (cfg->pack_mode == LDPC_PACK_BYTES || cfg->K % 8 == 0)) {
+            d->ldsp.mc = ldpc::MsCorr{d->ms_scale, d->ms_offset};
+            d->ldsp.fx_L = (int32_t)d->layered.L;
+            d->ldsp.fx_LP = (int32_t)d->layered.LP;
+            LDPC_HIP_TRY(ldpc::engine_ldsp_fx_plan_create(&d->ldsp, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows,
+                                              cfg->K, cfg->max_batch, cfg->device, tune));
+            if (d->ldsp.eligible) d->use_fused = d->use_ldsp = true;
+            else d->ldsp = ldpc::LdspPlan();
+        }
+        /* the streaming plan (and its P / R arrays in HBM) only when the record kernel does not apply */
+        int rc = d->use_fused ? 0 : ldpc::layered_plan_create(&d->layered, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows, d->T, d->V);
         if (rc == -1) return set_error(LDPC_ERR_ARG, "layer_rows=%d must divide M=%d and rows of a layer "
                                   "must not share a column", cfg->layer_rows, g->M);
         if (rc) return set_error(LDPC_ERR_HIP, "layered plan allocation failed: %s", hipGetErrorString(hipGetLastError()));
@@ -681,8 +701,9 @@ static int decode_device_in(ldpc_decoder *d, const ldpc::LlrIn &in, int64_t fram
         run.soft_extrinsic = d->soft.kind == LDPC_SOFT_EXTRINSIC ? 1 : 0;
         hipError_t e = ldpc::span_begin(d, s, 2, 0, (int64_t)frames * (4 * d->N + d->cfg.K / 8));
         if (e == hipSuccess)
-            e = d->use_ldsp ? ldpc::engine_ldsp_run(&d->ldsp, run, s, &d->last_iterations)
-                            : ldpc::engine_fused_run(&d->fused, run, s, &d->last_iterations);
+            e = !d->use_ldsp ? ldpc::engine_fused_run(&d->fused, run, s, &d->last_iterations)
+                : d->ldsp.fx ? ldpc::engine_ldsp_fx_run(&d->ldsp, run, s, &d->last_iterations)
+                             : ldpc::engine_ldsp_run(&d->ldsp, run, s, &d->last_iterations);
         if (e == hipSuccess) e = ldpc::span_end(d, s);
         rc = (e == hipSuccess) ? LDPC_OK : set_error(LDPC_ERR_HIP, "fused decode: %s", hipGetErrorString(e));
     } else if (d->cfg.algo == LDPC_ALGO_LAYERED || d->cfg.algo == LDPC_ALGO_LAYERED_HOST || d->cfg.algo == LDPC_ALGO_LAYERED_BP ||

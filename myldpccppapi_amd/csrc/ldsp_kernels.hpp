@@ -327,7 +327,7 @@ __device__ __forceinline__ void ldsp_dump_r(const LdspArgs &a, const uint4 *recs
 }
 
 /* the frame's iteration count and its share of the summary; by one thread per frame */
-__device__ __forceinline__ void ldsp_report(const LdspArgs &a, int64_t frame, int it, bool clean)
+template <class Args> __device__ __forceinline__ void ldsp_report(const Args &a, int64_t frame, int it, bool clean)
 {
     if (a.iters) a.iters[frame] = it;
     atomicMax(&a.summary[0], it);
@@ -1037,9 +1037,113 @@ struct LdspPlan {
                                            before ldsp_plan_create */
     MsCorr mc{1.0f, 0.0f};
     size_t lds_bytes = 0;
+    /* layered_ldsp_fx_kernel (ldsp_fx_kernels.hpp, LDPC_ALGO_LAYERED_FX with LDPC_TUNE_FX_RECORD): int16 posteriors, the
+     * tables in units of 2 bytes, 8-byte records in recs_fx; recs and zf stay empty.  fx_L / fx_LP and mc (scale 1 = plain)
+     * are set before the plan is made */
+    int fx = 0;
+    int32_t fx_L = 127, fx_LP = 32767;
+    DevBuf<uint2> recs_fx;
+    bool laid_out = false;              /* ldsp_plan_layout found a code that fits and filled the tables */
     const void *kernel = nullptr;       /* ldsp_select_kernel's choice: the function whose dynamic-LDS limit was raised,
                                            whose occupancy sized the grid and which ldsp_run launches */
 };
+
+/* Detect the QC structure, decide which block columns travel with a record (met by one layer
+ * only, last entry of that layer's rows, not an information column), lay the others out in LDS in cells of `cell` bytes
+ * (4: float posteriors; 2: the int16 posteriors of layered_ldsp_fx_kernel, which has no packed form) and upload the
+ * tables.  laid_out = false (and hipSuccess) when the code does not fit these kernels.  References no kernel: shared by
+ * engine_ldsp.hip and engine_ldsp_fx.hip. */
+inline hipError_t ldsp_plan_layout(LdspPlan *pl, int32_t M, int32_t N, int64_t E, const std::vector<int32_t> &row_ptr,
+                                   const std::vector<int32_t> &cols, int32_t z, int32_t K, const Tune &tune, int flood, int cell)
+{
+    std::vector<int32_t> lp, bc, sh, e0;
+    pl->eligible = pl->laid_out = false;
+    if (z <= 0 || z > 1024 || !fused_detect_qc(M, N, row_ptr, cols, z, lp, bc, sh, e0)) return hipSuccess;
+    const int layers = M / z, nb = N / z;
+    int max_deg = 0;
+    for (int l = 0; l < layers; ++l) max_deg = std::max(max_deg, lp[l + 1] - lp[l]);
+    if (max_deg > kLdspMaxDeg) return hipSuccess;
+    std::vector<int32_t> deg(nb, 0);
+    for (int32_t b : bc) ++deg[b];
+    const bool will_pack = cell == 4 && z <= 32 && !tune_forced_off(tune.ldsp_pack);
+    const bool allow_ext = !tune_forced_off(tune.ldsp_ext) && !(flood && will_pack);   /* the packed flooding kernel keeps every column in LDS */
+    std::vector<int32_t> slot(nb, 0), hdr((size_t)layers * 4, 0), pack((size_t)layers * kLdspPackStride, 0);
+    std::vector<char> external(nb, 0);
+    int ext_cols = 0;
+    for (int l = 0; l < layers; ++l) {
+        const int last = bc[lp[l + 1] - 1];
+        if (allow_ext && deg[last] == 1 && (int64_t)last * z >= K) { external[last] = 1; ++ext_cols; }
+    }
+    int lds_cols = 0;
+    for (int b = 0; b < nb; ++b) slot[b] = external[b] ? -1 : lds_cols++;
+    for (int l = 0; l < layers; ++l) {
+        const int d = lp[l + 1] - lp[l], last = lp[l + 1] - 1;
+        const int ext = external[bc[last]] ? 1 : 0;
+        hdr[l * 4 + 0] = d - ext;
+        hdr[l * 4 + 1] = ext;
+        hdr[l * 4 + 2] = ext ? bc[last] * z : 0;
+        hdr[l * 4 + 3] = ext ? sh[last] : 0;
+        for (int k = 0; k < d - ext; ++k) {
+            const int32_t colb = slot[bc[lp[l] + k]] * z * cell, shiftb = sh[lp[l] + k] * cell;
+            int32_t *row = &pack[(size_t)l * kLdspPackStride];
+            row[k] = colb;
+            row[kLdspMaxDeg + k] = shiftb;
+            row[2 * kLdspMaxDeg + k] = colb + shiftb;
+            row[3 * kLdspMaxDeg + k] = z * cell - shiftb;
+        }
+    }
+    int mw = (z + 63) / 64;
+    if (tune.ldsp_waves) mw = std::min(16, std::max(mw, tune.ldsp_waves));   /* idle waves appended */
+    int frames_per_wg = 1;
+    if (mw == 1 && will_pack) frames_per_wg = 64 / z;
+    /* a frame's posteriors, rounded up to 8 bytes (float cells) or 4 (int16 cells); flooding: old and new image */
+    const size_t frame_bytes = ((((size_t)lds_cols * z + 1) & ~(size_t)1)) * (size_t)cell * (flood ? 2 : 1);
+    while (frames_per_wg > 1 && frames_per_wg * frame_bytes + (size_t)layers * sizeof(uint64_t) + 8 > 60 * 1024) --frames_per_wg;
+    /* behind the posteriors: a flag word, and (all kernels but layered_ldsp_kernel and layered_ldsp_fx_kernel, which read
+     * them from their records) the lane masks of the external columns' hard decisions */
+    const bool masks = flood || frames_per_wg > 1;
+    const size_t lds_bytes = frames_per_wg * frame_bytes + (masks ? (size_t)layers * mw * sizeof(uint64_t) : 0) + 8;
+    if (lds_bytes > kLdspMaxLds || lds_cols >= 32768) return hipSuccess;
+    pl->wg_frames = frames_per_wg;
+    pl->flood = flood;
+    pl->z = z; pl->layers = layers; pl->N = N; pl->E = (int32_t)E; pl->M = M; pl->nb = nb;
+    pl->lds_cols = lds_cols; pl->ext_cols = ext_cols; pl->lds_bytes = lds_bytes;
+    pl->maxw = mw <= 8 ? 8 : 16;
+    pl->block = 64 * mw;
+    hipError_t e;
+    if ((e = pl->hdr.upload(hdr)) || (e = pl->pack.upload(pack)) || (e = pl->col_slot.upload(slot)) || (e = pl->layer_e0.upload(e0)))
+        return e;
+    pl->laid_out = true;
+    return hipSuccess;
+}
+
+/* Size the persistent grid of pl->kernel (set by the caller) for rings of M records of rec_bytes each per frame slot.
+ * per_cu_cap > 0: a further bound on the automatic number of workgroups per CU (a forced value ignores it as well). */
+inline hipError_t ldsp_plan_grid(LdspPlan *pl, int64_t max_batch, int device, const Tune &tune, size_t rec_bytes, int per_cu_cap = 0)
+{
+    const void *k = pl->kernel;
+    if (!k) return hipErrorInvalidValue;
+    hipError_t e;
+    /* the attribute belongs to the function, not to this plan: always the maximum, so that decoders
+     * of different codes can coexist */
+    if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdspMaxLds))) return e;
+    int per_cu = 0, cus = 0;
+    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, pl->block, pl->lds_bytes))) return e;
+    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device))) return e;
+    if (per_cu < 1 || cus < 1) return hipErrorInvalidValue;
+    /* The record rings of all resident workgroups are re-read once per iteration: they must stay in the
+     * Infinity Cache (256 MiB less what streams through between two uses).  BG1 at Z = 384: 276 KiB per frame;
+     * 3 workgroups per CU = 207 MiB: 23.5 ms per batch; 4 per CU (LDS and registers allow it) = 276 MiB: 27.7 ms
+     * (profiles/r02_ab_ldsp_resident.txt). */
+    const size_t ring_bytes = (size_t)pl->wg_frames * pl->M * rec_bytes;
+    const int cache_cap = (int)std::max<size_t>(1, ((size_t)224 << 20) / ((size_t)cus * ring_bytes));
+    if (tune.ldsp_per_cu) per_cu = std::max(1, tune.ldsp_per_cu);   /* a forced value ignores both rules: the grid is persistent */
+    else per_cu = std::min(per_cu, per_cu_cap > 0 ? std::min(cache_cap, per_cu_cap) : cache_cap);
+    pl->per_cu = per_cu;
+    pl->grid = (int32_t)std::min<int64_t>((std::max<int64_t>(max_batch, 1) + pl->wg_frames - 1) / pl->wg_frames, (int64_t)per_cu * cus);
+    if (tune.ldsp_grid) pl->grid = std::max(1, std::min(pl->grid, tune.ldsp_grid));
+    return hipSuccess;
+}
 
 /* the plan builder and the launcher reference every kernel above: compiled by engine_ldsp.hip only
  * (LDPC_ENGINE_LDSP); the host driver calls engine_ldsp_plan_create / engine_ldsp_run */
@@ -1063,90 +1167,17 @@ inline const void *ldsp_select_kernel(int flood, bool corr, bool packed, int max
     return packed ? p : u;
 }
 
-/* Detect the QC structure, decide which block columns travel with a record (met by one layer
- * only, last entry of that layer's rows, not an information column), lay the others out in LDS,
- * size the persistent grid and allocate its record rings.  eligible = false (and hipSuccess)
- * when the code does not fit this kernel. */
+/* The plan of the float record kernels: the layout in 4-byte cells, the kernel of the arithmetic, its persistent grid and
+ * the record rings.  eligible = false (and hipSuccess) when the code does not fit this kernel. */
 inline hipError_t ldsp_plan_create(LdspPlan *pl, int32_t M, int32_t N, int64_t E, const std::vector<int32_t> &row_ptr,
                                    const std::vector<int32_t> &cols, int32_t z, int32_t K, int64_t max_batch, int device,
                                    const Tune &tune, int flood = 0)
 {
-    std::vector<int32_t> lp, bc, sh, e0;
-    pl->eligible = false;
-    if (z <= 0 || z > 1024 || !fused_detect_qc(M, N, row_ptr, cols, z, lp, bc, sh, e0)) return hipSuccess;
-    const int layers = M / z, nb = N / z;
-    int max_deg = 0;
-    for (int l = 0; l < layers; ++l) max_deg = std::max(max_deg, lp[l + 1] - lp[l]);
-    if (max_deg > kLdspMaxDeg) return hipSuccess;
-    std::vector<int32_t> deg(nb, 0);
-    for (int32_t b : bc) ++deg[b];
-    const bool will_pack = z <= 32 && !tune_forced_off(tune.ldsp_pack);
-    const bool allow_ext = !tune_forced_off(tune.ldsp_ext) && !(flood && will_pack);   /* the packed flooding kernel keeps every column in LDS */
-    std::vector<int32_t> slot(nb, 0), hdr((size_t)layers * 4, 0), pack((size_t)layers * kLdspPackStride, 0);
-    std::vector<char> external(nb, 0);
-    int ext_cols = 0;
-    for (int l = 0; l < layers; ++l) {
-        const int last = bc[lp[l + 1] - 1];
-        if (allow_ext && deg[last] == 1 && (int64_t)last * z >= K) { external[last] = 1; ++ext_cols; }
-    }
-    int lds_cols = 0;
-    for (int b = 0; b < nb; ++b) slot[b] = external[b] ? -1 : lds_cols++;
-    for (int l = 0; l < layers; ++l) {
-        const int d = lp[l + 1] - lp[l], last = lp[l + 1] - 1;
-        const int ext = external[bc[last]] ? 1 : 0;
-        hdr[l * 4 + 0] = d - ext;
-        hdr[l * 4 + 1] = ext;
-        hdr[l * 4 + 2] = ext ? bc[last] * z : 0;
-        hdr[l * 4 + 3] = ext ? sh[last] : 0;
-        for (int k = 0; k < d - ext; ++k) {
-            const int32_t col4 = slot[bc[lp[l] + k]] * z * 4, shift4 = sh[lp[l] + k] * 4;
-            int32_t *row = &pack[(size_t)l * kLdspPackStride];
-            row[k] = col4;
-            row[kLdspMaxDeg + k] = shift4;
-            row[2 * kLdspMaxDeg + k] = col4 + shift4;
-            row[3 * kLdspMaxDeg + k] = z * 4 - shift4;
-        }
-    }
-    int mw = (z + 63) / 64;
-    if (tune.ldsp_waves) mw = std::min(16, std::max(mw, tune.ldsp_waves));   /* idle waves appended */
-    int frames_per_wg = 1;
-    if (mw == 1 && will_pack) frames_per_wg = 64 / z;
-    const size_t frame_bytes = ((((size_t)lds_cols * z + 1) & ~(size_t)1)) * sizeof(float) * (flood ? 2 : 1);   /* flooding: old and new image */
-    while (frames_per_wg > 1 && frames_per_wg * frame_bytes + (size_t)layers * sizeof(uint64_t) + 8 > 60 * 1024) --frames_per_wg;
-    /* behind the posteriors: a flag word, and (all kernels but layered_ldsp_kernel, which reads them from its
-     * records) the lane masks of the external columns' hard decisions */
-    const bool masks = flood || frames_per_wg > 1;
-    const size_t lds_bytes = frames_per_wg * frame_bytes + (masks ? (size_t)layers * mw * sizeof(uint64_t) : 0) + 8;
-    if (lds_bytes > kLdspMaxLds || lds_cols >= 32768) return hipSuccess;
-    pl->wg_frames = frames_per_wg;
-    pl->flood = flood;
-    pl->z = z; pl->layers = layers; pl->N = N; pl->E = (int32_t)E; pl->M = M; pl->nb = nb;
-    pl->lds_cols = lds_cols; pl->ext_cols = ext_cols; pl->lds_bytes = lds_bytes;
-    pl->maxw = mw <= 8 ? 8 : 16;
-    pl->block = 64 * mw;
     hipError_t e;
-    if ((e = pl->hdr.upload(hdr)) || (e = pl->pack.upload(pack)) || (e = pl->col_slot.upload(slot)) || (e = pl->layer_e0.upload(e0)))
-        return e;
-    const void *k = pl->kernel = ldsp_select_kernel(flood, pl->corr != 0, pl->wg_frames > 1, pl->maxw);
-    if (!k) return hipErrorInvalidValue;
-    /* the attribute belongs to the function, not to this plan: always the maximum, so that decoders
-     * of different codes can coexist */
-    if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdspMaxLds))) return e;
-    int per_cu = 0, cus = 0;
-    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, pl->block, lds_bytes))) return e;
-    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device))) return e;
-    if (per_cu < 1 || cus < 1) return hipErrorInvalidValue;
-    /* The record rings of all resident workgroups are re-read once per iteration: they must stay in the
-     * Infinity Cache (256 MiB less what streams through between two uses).  BG1 at Z = 384: 276 KiB per frame;
-     * 3 workgroups per CU = 207 MiB: 23.5 ms per batch; 4 per CU (LDS and registers allow it) = 276 MiB: 27.7 ms
-     * (profiles/r02_ab_ldsp_resident.txt). */
-    const size_t ring_bytes = (size_t)frames_per_wg * M * sizeof(uint4);
-    const int cache_cap = (int)std::max<size_t>(1, ((size_t)224 << 20) / ((size_t)cus * ring_bytes));
-    if (tune.ldsp_per_cu) per_cu = std::max(1, tune.ldsp_per_cu);   /* a forced value ignores both rules: the grid is persistent */
-    else per_cu = std::min(per_cu, cache_cap);
-    pl->per_cu = per_cu;
-    pl->grid = (int32_t)std::min<int64_t>((std::max<int64_t>(max_batch, 1) + pl->wg_frames - 1) / pl->wg_frames, (int64_t)per_cu * cus);
-    if (tune.ldsp_grid) pl->grid = std::max(1, std::min(pl->grid, tune.ldsp_grid));
+    if ((e = ldsp_plan_layout(pl, M, N, E, row_ptr, cols, z, K, tune, flood, /*cell=*/4))) return e;
+    if (!pl->laid_out) return hipSuccess;
+    pl->kernel = ldsp_select_kernel(flood, pl->corr != 0, pl->wg_frames > 1, pl->maxw);
+    if ((e = ldsp_plan_grid(pl, max_batch, device, tune, sizeof(uint4)))) return e;
     /* + 1024 (the largest workgroup): lanes beyond the last row request records too (never used) */
     if ((e = pl->recs.alloc((size_t)pl->grid * pl->wg_frames * M + 1024))) return e;
     if ((e = pl->zf.alloc((size_t)pl->grid * pl->wg_frames * M + 1024))) return e;

@@ -19,6 +19,7 @@ struct Tune {
     int ldsp_grid = 0, ldsp_per_cu = 0, ldsp_waves = 0;
     int place = 0;              /* array sets timed at creation: 0 automatic, 1 none, 2..8 */
     int q_order = 0;            /* Q stored in the order its writers produce it: 0 automatic (on), 1 on, -1 off */
+    int fx_record = 0;          /* LDPC_TUNE_FX_RECORD: 0 off, 1 on (LDPC_ALGO_LAYERED_FX on the record kernel); no forced-off value */
 };
 
 inline Tune tune_from_config(const ldpc_decoder_config &c)
@@ -40,6 +41,7 @@ inline Tune tune_from_config(const ldpc_decoder_config &c)
     t.link_half = f(LDPC_TUNE_LINK_HALF);
     t.link_guided = f(LDPC_TUNE_LINK_GUIDED);
     t.tiles_first = f(LDPC_TUNE_TILES_FIRST);
+    t.fx_record = (c.tune_flags >> LDPC_TUNE_FX_RECORD) & 1;
     t.rows_per_wave = c.tune_rows_per_wave;
     t.cols_per_wave = c.tune_cols_per_wave;
     t.link_rows = c.tune_link_rows;
@@ -57,12 +59,15 @@ inline bool tune_pick(int tri, bool dflt) { return tri == 1 ? true : (tri == 2 ?
 inline bool tune_forced_on(int tri) { return tri == 1; }
 inline bool tune_forced_off(int tri) { return tri == 2; }
 
-/* field 3 (both bits) is not a value */
+/* field 3 (both bits) is not a value.  LDPC_TUNE_FX_RECORD (bit 30, on or absent: its "off" would be the sign bit, and
+ * a negative word is no value) belongs to the fixed-point layered algorithms; with any other it is out of range. */
 inline bool tune_valid(const ldpc_decoder_config &c)
 {
     for (int field = 0; field <= LDPC_TUNE_TILES_FIRST; field += 2)
         if (((c.tune_flags >> field) & 3) == 3) return false;
-    if (c.tune_flags >> (LDPC_TUNE_TILES_FIRST + 2)) return false;
+    const bool fx = c.algo == LDPC_ALGO_LAYERED_FX || c.algo == LDPC_ALGO_LAYERED_BP_FX;
+    const int32_t above = c.tune_flags >> (LDPC_TUNE_TILES_FIRST + 2);
+    if (above != 0 && !(fx && above == 1)) return false;
     return c.tune_rows_per_wave >= 0 && c.tune_rows_per_wave <= 4096 && c.tune_cols_per_wave >= 0 &&
            c.tune_cols_per_wave <= 4096 && c.tune_link_rows >= -1 && c.tune_link_rows <= 4096 &&
            c.tune_compact >= -1 && c.tune_ldsp_grid >= 0 && c.tune_ldsp_shape >= 0 && c.tune_ldsp_shape < 65536 &&

@@ -10,7 +10,7 @@ reference counts differing BYTES (Test.cpp:105-110); this prints byte errors too
     python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N> | --alist PATH] [--algo sp|ms|layered|bp|layered_bp|layered_fx|layered_bp_fx]
                               [--payload zero|random] [--rate-match P,FLO,FHI,E[,K0]] [--erasure-llr X]
                               [--modulation bpsk|qpsk|qam16|qam64|qam256] [--no-interleave] [--transport-block A[,C]] [--crc-stop] [--bch T[,N]]
-                              [--msg-dtype f32|f16|f8|i8 [--msg-bits Q --llr-scale S]] [--post-bits P] [--frac-bits F] [--soft-check] [--osd 0|1 [--osd-scale S]]
+                              [--msg-dtype f32|f16|f8|i8 [--msg-bits Q --llr-scale S]] [--post-bits P] [--fx-record] [--frac-bits F] [--soft-check] [--osd 0|1 [--osd-scale S]]
                               [--snr=1.0,1.5,...]  (write --snr=-0.5,0 for a list that starts with a minus) [--frames 4096] [--iters 50]
 --rate-match: code bits [0, P) punctured, [FLO, FHI) filler bits (known zeros; multiples of 8, inside the information part),
 E bits per frame sent from circular-buffer position K0 (default 0): ldpc_rate_match_device between the encoder and the
@@ -28,7 +28,8 @@ per point, with any modulation and with none, unless --llr-scale is given; --msg
 --algo layered_bp (LDPC_ALGO_LAYERED_BP: the layered schedule with bp's check node) reads LLRs in the same way; like --algo
 layered it needs a code with a circulant size (bg1, wimax:...), it is fp32 only, and it takes exact zeros (no --erasure-llr).
 --algo layered_fx (LDPC_ALGO_LAYERED_FX: the layered schedule in fixed point) takes --msg-bits Q, --post-bits P (the
-saturating posterior memory) and --llr-scale S, the LSBs per unit of channel value; --ms-offset is in LSBs.
+saturating posterior memory) and --llr-scale S, the LSBs per unit of channel value; --ms-offset is in LSBs; --fx-record runs it
+on the fixed-point record kernel (one launch, same results; not with --crc-stop).
 --algo layered_bp_fx (LDPC_ALGO_LAYERED_BP_FX: layered_fx with box-plus rows from a correction table) takes --msg-bits Q,
 --post-bits P, --frac-bits F (one LSB is 2^-F LLR units, 0 ... 4) and --llr-scale S, the LSBs per unit of channel value;
 without --llr-scale it follows the noise, 2^F * 2 / sd^2 per point: the channel LLR in LSBs.  No --ms-scale / --ms-offset.
@@ -101,6 +102,7 @@ ap.add_argument("--msg-dtype", choices=("f32", "f16", "f8", "i8"), default="f32"
                      "integers of --msg-bits bits, channel c = sq(--llr-scale * y), --ms-offset in LSBs; --algo layered_fx and "
                      "layered_bp_fx imply i8)")
 ap.add_argument("--msg-bits", type=int, default=0, help="with --msg-dtype i8: 4, 5, 6 or 8 bits per message (0 = 8)")
+ap.add_argument("--fx-record", action="store_true", help="--algo layered_fx: the fixed-point record kernel (LDPC_TUNE_FX_RECORD), same results")
 ap.add_argument("--post-bits", type=int, default=0, help="--algo layered_fx and layered_bp_fx: bits of the saturating posterior memory, --msg-bits ... 16 (0 = 16)")
 ap.add_argument("--frac-bits", type=int, default=0, help="--algo layered_bp_fx: fractional bits of an LSB, 0 ... 4 (one LSB = 2^-F LLR units)")
 ap.add_argument("--llr-type", choices=("f32", "f16", "i8"), default="f32",
@@ -175,7 +177,7 @@ def make_decoder(llr_scale):
     return L.Decoder(g, K, max_batch=B, algo=args.algo, max_iter=args.iters, llr_scale=llr_scale,
                      layer_rows=layer, poll_interval=2, ms_scale=args.ms_scale, ms_offset=args.ms_offset,
                      crc_kind=crc_kind, crc_bits=crc_bits, msg_dtype=args.msg_dtype, msg_bits=args.msg_bits, post_bits=args.post_bits,
-                     bp_frac_bits=args.frac_bits)
+                     bp_frac_bits=args.frac_bits, tune={"fx_record": True} if args.fx_record else None)
 
 
 dec = None if matched else make_decoder(8.0 if args.llr_scale is None else args.llr_scale)
