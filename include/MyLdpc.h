@@ -70,7 +70,12 @@ enum decodeType { DecodeCPU, DecodeMS, DecodeSP, DecodeTDMP, DecodeTDMPCL, Decod
                                      setLlrFractionBits() give the widths, setLlrScale() the LSBs per unit of channel value,
                                      chosen so that llrScale * y is the LLR in LSBs of 2^-fractionBits; it takes
                                      setCrcEarlyStop, decodeSoft (values in LSBs) and decodeTyped, and no
-                                     setMinSumCorrection (LDPC_ERR_UNSUPPORTED: there is no minimum to correct) */ };
+                                     setMinSumCorrection (LDPC_ERR_UNSUPPORTED: there is no minimum to correct) */,
+                  DecodeBitFlip /* not in the reference: hard-decision parallel bit flipping, LDPC_ALGO_BITFLIP
+                                     (include/ldpc_hip.h): only the sign of a channel value is read, setLlrScale() is ignored,
+                                     setBitFlipThresholds() gives the round offsets; it takes setCrcEarlyStop and
+                                     decodeTyped, and no decodeSoft, setMinSumCorrection or message type other than
+                                     LDPC_MSG_F32 (LDPC_ERR_UNSUPPORTED) */ };
 
 const int n_b = 24;
 
@@ -153,6 +158,13 @@ public:
      * anything else makes addDecodeType fail as ldpc_decoder_create does.  Read by no other decode type.  Before
      * addDecodeType(). */
     void setLlrFractionBits(int bits) { fracBits = bits; }
+    /* DecodeBitFlip: off(i) of rounds 1 .. count, count <= 16, the last one also for every later round (include/ldpc_hip.h:
+     * bf_threshold; each in [0, 62], all zero or count = 0: the default off(i) = i - 1); anything else makes addDecodeType
+     * fail as ldpc_decoder_create does.  Read by no other decode type.  Before addDecodeType(). */
+    void setBitFlipThresholds(const int *offsets, int count)
+    {
+        bfThreshold.assign(offsets, offsets + (count > 0 ? count : 0));
+    }
     /* encode() on the GPU `setDevice` names (ldpc_encode, include/ldpc_hip.h) instead of the host: same bytes.
      * forEncoder() then creates the device encoder and skips the host precompute, so it also serves the seed whose
      * parity part the host solves by dense elimination only (rate_3_4_b: any N, where the host path stops at
@@ -255,6 +267,7 @@ private:
     int msgBits = 0;                 /* setMessageType(): bits per message with LDPC_MSG_I8 */
     int postBits = 0;                /* setPosteriorBits(): DecodeLayeredFixed, DecodeLayeredBPFixed */
     int fracBits = 0;                /* setLlrFractionBits(): DecodeLayeredBPFixed */
+    std::vector<int> bfThreshold;    /* setBitFlipThresholds(): DecodeBitFlip */
     bool fxRecord = false;           /* setFixedRecordKernel(): DecodeLayeredFixed */
     int makeDecoder(const ldpc_decoder_config &cfg, ldpc_decoder **out);
     const signed char *hSeed;

@@ -79,9 +79,11 @@ enum ldpc_algo {
     LDPC_ALGO_LAYERED_FX = 8,/* layered (TDMP) min-sum in fixed point: q-bit messages (LDPC_MSG_I8, msg_bits) and a
                               posterior MEMORY of post_bits bits that saturates: this library's own definition, below;
                               the streaming layered engine, one byte per R and two per P, one launch per layer */
-    LDPC_ALGO_LAYERED_BP_FX = 9 /* LDPC_ALGO_LAYERED_FX's schedule, widths and storage with a box-plus check node in integers:
+    LDPC_ALGO_LAYERED_BP_FX = 9,/* LDPC_ALGO_LAYERED_FX's schedule, widths and storage with a box-plus check node in integers:
                               min plus a correction read from a table of bp_frac_bits fractional bits, as hardware box-plus
                               decoders compute it: this library's own definition, below */
+    LDPC_ALGO_BITFLIP = 10  /* hard-decision parallel bit flipping: one bit per code bit in, one bit per variable and per
+                              check as state, frames bit-sliced 64 to a word: this library's own definition, below */
 };
 
 /* LDPC_ALGO_BP, bit for bit.  The reference's sum-product (LDPC_ALGO_SP) works on probabilities in fp32 and saturates at
@@ -228,6 +230,45 @@ enum ldpc_algo {
  * 0 .. 4; a non-zero ms_scale or ms_offset is LDPC_ERR_UNSUPPORTED (there is no minimum to correct), as is
  * LDPC_TUNE_ON(FUSED) or LDPC_TUNE_ON(LDSP).  bp_frac_bits != 0 with any other algorithm is LDPC_ERR_ARG.  Kernel times
  * name its spans lbfx. */
+
+/* LDPC_ALGO_BITFLIP, bit for bit, in integers: the hard-decision decoder a storage controller or an optical link runs
+ * first.  Nothing in it is a float after the first comparison.
+ *   Input:        r_n = (y_n < 0): NaN and -0 read 0.  With typed input the test is on y = (float)x * llr_unit, so the sign
+ *                 of the stored value decides.  llr_scale is ignored.  Padding frames read y = 1.
+ *   State:        x_n, starting as r_n; r_n is kept.  d_n is the degree of column n.
+ *   Round i = 1 .. max_iter:
+ *                 s_m = XOR of x over row m.
+ *                 A frame whose s is all zero is done: frozen, iters = i - 1 (a frame that arrives as a codeword has
+ *                 iters = 0).  This is the freeze rule of the other decoders; early_term = 0 launches every round on every
+ *                 tile and changes no bit, iteration count or done flag: a done frame stays frozen either way.
+ *                 Otherwise, for every column: u_n = sum of s_m over the rows m of column n, E_n = u_n + (x_n != r_n),
+ *                 hit_n = (E_n >= T(d_n, i)).
+ *                 A frame with a hit in some column flips x_n in exactly its hit columns.  A frame without a hit flips the
+ *                 columns whose E_n is the frame's largest, if that largest E is >= 2.  All flips of a round are decided
+ *                 from the same s: parallel flipping.
+ *   Threshold:    T(d, i) = max(floor((d + 1) / 2) + 1, d + 1 - off(i)): of the d + 1 votes on a bit (its d checks and the
+ *                 received bit) all must disagree at off = 0, one fewer per unit of off, never fewer than a strict
+ *                 majority.  With bf_threshold (config field below) all zero, off(i) = i - 1.  Otherwise
+ *                 off(i) = bf_threshold[i - 1] for i <= 16 and bf_threshold[15] for every later round: entry j is the
+ *                 offset of round j + 1.  Entries must lie in [0, 62] (LDPC_ERR_ARG otherwise, as is a non-zero entry
+ *                 with any other algorithm); bf_threshold = {62, 62, ...} is strict majority from round 1.
+ *   After the last round: iters = max_iter for the frames not done (the bits of round max_iter are not tested again), the
+ *                 output bits are x, frames_converged counts the done frames.
+ *   crc_kind:     in round i a running frame whose x[0 .. crc_bits) passes the CRC is done as if its s were zero
+ *                 (iters = i - 1); ldpc_decoder_crc_stops counts those whose s was not.  Needs early_term = 1, as always.
+ *   Debug taps:   3 = x after the tapped round, 0 = the syndrome words s of the tapped round, M values per frame as
+ *                 floats 0 / 1 (ldpc_decoder_dump with count = frames * M).
+ * Why the fall-back: on the 802.16e rate-1/2 codes over a binary symmetric channel the thresholds alone leave 86 of 512
+ * frames at N = 576 and crossover 0.01 (strict majority from round 1: 85; only the largest E in every round: 28); with the
+ * fall-back 29 are left, in fewer rounds than the largest-E rule needs (DESIGN.md section 8v has the table).
+ * Served: both pack modes, ldpc_decode, ldpc_decode_device, the typed entry points, crc_kind, ldpc_decoder_create_multi.
+ * Refusals, all before the device is touched: soft output (ldpc_decode_soft*: there is none) is LDPC_ERR_UNSUPPORTED, as
+ * are a msg_dtype other than LDPC_MSG_F32 (there are no messages), a non-zero ms_scale / ms_offset and
+ * LDPC_TUNE_ON(FUSED) or LDPC_TUNE_ON(LDSP); LDPC_TUNE_FX_RECORD is LDPC_ERR_ARG as with every algorithm it does not belong
+ * to.  A column of degree above 62 is LDPC_ERR_UNSUPPORTED (E must fit six bits).  frames_per_lane is accepted and ignored: tiles
+ * are 64 frames.  Hand-over and tail compaction are switched off for this algorithm (poll_interval and tune_compact are
+ * accepted and ignored): a round is too cheap to be worth moving frames for.  Kernel times name bitflip_check_kernel,
+ * bitflip_vote_kernel and bitflip_flip_kernel. */
 
 /* How the streaming flooding min-sum decoder (LDPC_ALGO_MS) stores its messages; the arithmetic is fp32 in one
  * operation order for all four.  F16 and F8 are this library's own definitions (the reference is fp32 only) and are
@@ -398,6 +439,13 @@ typedef struct ldpc_decoder_config {
                                    it must be 0 (LDPC_ERR_ARG).  The first of the two words that were msg_reserved2[2]: size
                                    and offsets are unchanged                                                           */
     int32_t msg_reserved3;      /* must be 0 (LDPC_ERR_ARG otherwise)                                                  */
+    /* ---- bit-flipping thresholds (appended; a struct_size of offsetof(ldpc_decoder_config, bf_threshold), the size before
+     *      this field, is accepted and means all zero, as the shorter sizes do).  Sixteen words do not fit the one reserved
+     *      word left, so the struct grows; LDPC_HIP_ABI_VERSION stays 3 because nothing a caller built against version 3
+     *      passes is read differently: its struct_size says which fields it has. ------------------------------------------ */
+    int32_t bf_threshold[16];   /* LDPC_ALGO_BITFLIP: off(i) of rounds 1 .. 16 (the last entry also for every later round),
+                                   each in [0, 62]; all zero = the default off(i) = i - 1.  With any other algorithm every
+                                   entry must be 0 (LDPC_ERR_ARG)                                                       */
 } ldpc_decoder_config;
 
 /* two-bit fields of tune_flags: LDPC_TUNE_ON(f) forces the choice on, LDPC_TUNE_OFF(f) off */
@@ -469,8 +517,8 @@ int ldpc_graph_info(const ldpc_graph *g, int32_t *M, int32_t *N, int64_t *E, int
 /* ---- decoder: replaces Coder::forDecoder's device setup + addDecodeType,
  *      MyLdpc.cpp:226-305, 307-552 -------------------------------------------- */
 /* Reference defaults.  The caller says how large its struct is, so that the call never writes behind it:
- * ldpc_decoder_config_init_sized fills the first struct_size bytes -- one of the four sizes ldpc_decoder_create accepts:
- * offsetof(ms_scale), offsetof(crc_kind), offsetof(msg_bits), sizeof -- and stores struct_size itself; any other size is LDPC_ERR_ARG and
+ * ldpc_decoder_config_init_sized fills the first struct_size bytes -- one of the five sizes ldpc_decoder_create accepts:
+ * offsetof(ms_scale), offsetof(crc_kind), offsetof(msg_bits), offsetof(bf_threshold), sizeof -- and stores struct_size itself; any other size is LDPC_ERR_ARG and
  * nothing is written.  The exported function ldpc_decoder_config_init is what callers built against the header before
  * crc_kind / crc_bits call with their shorter struct: it fills offsetof(ldpc_decoder_config, crc_kind) bytes and stores
  * that as struct_size (CRC off).  Code compiled against THIS header gets its own struct's size through the macro below,

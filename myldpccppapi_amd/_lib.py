@@ -66,6 +66,12 @@ class DecoderConfigMsg(DecoderConfigCrc):
     _fields_ = [("msg_bits", ctypes.c_int32), ("_tail", _MsgTail)]
 
 
+class DecoderConfigBf(DecoderConfigMsg):
+    """The whole of `ldpc_decoder_config`: DecoderConfigMsg is the struct as it was before bf_threshold (a size the library
+    still accepts, all thresholds 0); this one has the sixteen round offsets of LDPC_ALGO_BITFLIP behind it."""
+    _fields_ = [("bf_threshold", ctypes.c_int32 * 16)]
+
+
 class DecodeStats(ctypes.Structure):
     """Mirror of `ldpc_decode_stats`."""
     _fields_ = [("iterations_launched", ctypes.c_int32), ("batch_time", ctypes.c_int32),

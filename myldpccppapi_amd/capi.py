@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import DecoderConfig, DecodeStats, LdpcError  # noqa: F401
 
 ALGO_SP, ALGO_MS, ALGO_LAYERED, ALGO_MS_FUSED, ALGO_LAYERED_HOST, ALGO_BP, ALGO_LAYERED_BP = 0, 1, 2, 3, 4, 5, 6
-ALGO_LAYERED_FX, ALGO_LAYERED_BP_FX = 8, 9                  # 7 is not assigned
+ALGO_LAYERED_FX, ALGO_LAYERED_BP_FX, ALGO_BITFLIP = 8, 9, 10   # 7 is not assigned
 MSG_F32, MSG_F16, MSG_F8, MSG_I8 = 0, 1, 2, 4    # 3 is not assigned
 PACK_BYTES, PACK_BITS = 0, 1
 CODE_PACKED, CODE_BITS = 0, 1                              # enum ldpc_code_format
@@ -27,7 +27,7 @@ LLR_TYPES = {"f32": LLR_F32, "f16": LLR_F16, "i8": LLR_I8}
 LLR_DTYPES = {np.dtype(np.float32): LLR_F32, np.dtype(np.float16): LLR_F16, np.dtype(np.int8): LLR_I8}
 ALGOS = {"sp": ALGO_SP, "ms": ALGO_MS, "layered": ALGO_LAYERED, "ms_fused": ALGO_MS_FUSED,
          "layered_host": ALGO_LAYERED_HOST, "bp": ALGO_BP, "layered_bp": ALGO_LAYERED_BP, "layered_fx": ALGO_LAYERED_FX,
-         "layered_bp_fx": ALGO_LAYERED_BP_FX}
+         "layered_bp_fx": ALGO_LAYERED_BP_FX, "bitflip": ALGO_BITFLIP}
 
 # two-bit fields of ldpc_decoder_config.tune_flags (enum ldpc_tune_field): True forces on, False off
 TUNE_FIELDS = {"fused": 0, "ldsp": 2, "ldsp_ext": 4, "ldsp_pack": 6, "link_narrow": 8, "check_wide": 10,
@@ -234,12 +234,23 @@ class Decoder:
     def __init__(self, graph, K, max_batch, algo="sp", max_iter=40, llr_scale=8.0, early_term=True,
                  device=0, layer_rows=0, pack_mode=PACK_BYTES, frames_per_lane=0, poll_interval=0,
                  msg_dtype=MSG_F32, tune=None, devices=None, host_input="auto", host_copy_threads=0,
-                 ms_scale=0.0, ms_offset=0.0, crc_kind=0, crc_bits=0, msg_bits=0, post_bits=0, bp_frac_bits=0):
+                 ms_scale=0.0, ms_offset=0.0, crc_kind=0, crc_bits=0, msg_bits=0, post_bits=0, bp_frac_bits=0,
+                 bf_threshold=None):
         L = _lib.load()
-        cfg = _lib.DecoderConfigMsg()
+        algo = ALGOS[algo] if isinstance(algo, str) else int(algo)
+        # algo "bitflip" (hard-decision bit flipping): the struct with the sixteen round offsets behind it; bf_threshold is a
+        # sequence of up to 16 offsets in [0, 62], the last one repeated (None or all zero: off(i) = i - 1).  Every other
+        # algorithm keeps the struct it always passed
+        bf = algo == ALGO_BITFLIP or bf_threshold is not None
+        cfg = _lib.DecoderConfigBf() if bf else _lib.DecoderConfigMsg()
         _lib.check(L.ldpc_decoder_config_init_sized(ctypes.byref(cfg), ctypes.sizeof(cfg)))
+        if bf_threshold is not None:
+            t = [int(v) for v in bf_threshold]
+            if not 1 <= len(t) <= 16:
+                raise ValueError("bf_threshold holds 1 to 16 round offsets")
+            cfg.bf_threshold[:] = t + [t[-1]] * (16 - len(t))
         cfg.K, cfg.max_batch = int(K), int(max_batch)
-        cfg.algo = ALGOS[algo] if isinstance(algo, str) else int(algo)
+        cfg.algo = algo
         cfg.msg_dtype = {"f32": MSG_F32, "f16": MSG_F16, "f8": MSG_F8, "i8": MSG_I8}.get(msg_dtype, msg_dtype)
         # fixed-point messages, msg_dtype "i8": saturating integers of msg_bits = 4, 5, 6 or 8 bits (0 = 8); llr_scale is
         # then the LSBs per unit of channel value (include/ldpc_hip.h: LDPC_MSG_I8)
@@ -393,6 +404,8 @@ class Decoder:
 
     def dump(self, which, frames):
         per = self.N if which in (2, 3) else self.E
+        if self.cfg.algo == ALGO_BITFLIP and which == 0:        # the syndrome words, one value per row
+            per = self.graph.M
         a = np.empty((frames, per), np.float32)
         _lib.check(_lib.load().ldpc_decoder_dump(self._h, which, a.ctypes.data, a.size))
         return a

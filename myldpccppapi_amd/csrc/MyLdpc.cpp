@@ -482,6 +482,8 @@ int Coder::addDecodeType(enum decodeType deType)
         if (deType == DecodeSP)
             return fail(LDPC_ERR_UNSUPPORTED, "addDecodeType: DecodeSP has no soft output for setOsd() (see decodeSoft); the min-sum "
                         "decode types, DecodeBP and DecodeLayeredBP have");
+        if (deType == DecodeBitFlip)
+            return fail(LDPC_ERR_UNSUPPORTED, "addDecodeType: DecodeBitFlip is a hard-decision decoder and has no soft output for setOsd()");
         if (deType == DecodeCPU)
             return fail(LDPC_ERR_UNSUPPORTED, "addDecodeType: DecodeCPU packs its bytes at bit offsets; setOsd() works on rows of K / 8 bytes");
         if (!osd)
@@ -505,9 +507,14 @@ int Coder::addDecodeType(enum decodeType deType)
                : (deType == DecodeMSCL) ? LDPC_ALGO_MS_FUSED : (deType == DecodeBP) ? LDPC_ALGO_BP
                : (deType == DecodeLayeredBP) ? LDPC_ALGO_LAYERED_BP
                : (deType == DecodeLayeredFixed) ? LDPC_ALGO_LAYERED_FX
-               : (deType == DecodeLayeredBPFixed) ? LDPC_ALGO_LAYERED_BP_FX : LDPC_ALGO_LAYERED;
+               : (deType == DecodeLayeredBPFixed) ? LDPC_ALGO_LAYERED_BP_FX
+               : (deType == DecodeBitFlip) ? LDPC_ALGO_BITFLIP : LDPC_ALGO_LAYERED;
     if (deType == DecodeLayeredFixed || deType == DecodeLayeredBPFixed) cfg.post_bits = postBits;     /* setPosteriorBits(); the circulant size as DecodeTDMPCL */
     if (deType == DecodeLayeredBPFixed) cfg.bp_frac_bits = fracBits;    /* setLlrFractionBits() */
+    if (deType == DecodeBitFlip && !bfThreshold.empty()) {             /* setBitFlipThresholds(): the last offset repeats */
+        if (bfThreshold.size() > 16) return fail(LDPC_ERR_ARG, "addDecodeType: setBitFlipThresholds takes at most 16 round offsets");
+        for (size_t j = 0; j < 16; ++j) cfg.bf_threshold[j] = bfThreshold[j < bfThreshold.size() ? j : bfThreshold.size() - 1];
+    }
     if (deType == DecodeLayeredFixed && fxRecord) cfg.tune_flags |= LDPC_TUNE_ON(LDPC_TUNE_FX_RECORD);   /* setFixedRecordKernel() */
     if (deType == DecodeTDMP) {
         /* The reference's host-layered path (MyLdpc.cpp:889-976) sizes layer l as

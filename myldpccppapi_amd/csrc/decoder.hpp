@@ -19,6 +19,7 @@
 #include "../../include/ldpc_hip.h"
 #include "flood_tables.hpp"
 #include "layered_kernels.hpp"
+#include "bitflip_kernels.hpp"
 #include "fused_kernels.hpp"
 #include "ldsp_kernels.hpp"
 #include "engines.hpp"
@@ -247,6 +248,7 @@ struct ldpc_decoder {
     ldpc::DevBuf<uint32_t> crc_w;       /* cfg.crc_kind != 0: [crc_bits] column weights of crc_term_kernel (crc_term_host.hpp) */
 
     ldpc::LayeredPlan layered;          /* LDPC_ALGO_LAYERED / LAYERED_HOST / LAYERED_BP, streaming (one launch per layer) */
+    ldpc::BitflipPlan bitflip;          /* LDPC_ALGO_BITFLIP: received bits, syndrome words, votes (hard holds x at V = 1) */
     ldpc::FusedPlan fused;              /* LDPC_ALGO_LAYERED, short QC codes: whole decode in LDS */
     bool use_fused = false;
     ldpc::LdspPlan ldsp;                /* LDPC_ALGO_LAYERED, mid-size QC codes: posterior in LDS, check records in cache;

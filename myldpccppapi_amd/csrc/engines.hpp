@@ -1,6 +1,6 @@
 /*
  * engines.hpp -- the entry points of the engines that instantiate kernels, compiled in translation units of
- * their own (engine_ldsp.hip, engine_ldsp_fx.hip, engine_fused.hip, engine_layered.hip, engine_layered_fx.hip, engine_layered_bpfx.hip, engine_flood.hip) so that the library
+ * their own (engine_ldsp.hip, engine_ldsp_fx.hip, engine_fused.hip, engine_layered.hip, engine_layered_fx.hip, engine_layered_bpfx.hip, engine_bitflip.hip, engine_flood.hip) so that the library
  * builds in parallel.  The host driver calls these instead of the inline functions of the kernel headers;
  * plan structs and everything without kernels stay in the headers.
  */
@@ -24,6 +24,8 @@ struct FusedPlan;
 struct FusedRun;
 struct LayeredPlan;
 struct LayeredRun;
+struct BitflipPlan;
+struct BitflipRun;
 
 hipError_t engine_ldsp_plan_create(LdspPlan *pl, int32_t M, int32_t N, int64_t E, const std::vector<int32_t> &row_ptr,
                                    const std::vector<int32_t> &cols, int32_t z, int32_t K, int64_t max_batch, int device,
@@ -38,6 +40,8 @@ hipError_t engine_fused_run(FusedPlan *pl, const FusedRun &r, hipStream_t s, int
 /* every rule of the streaming layered engine (LayeredPlan::rule); engine_layered_fx.hip holds the fixed-point storage's half,
  * engine_layered_bpfx.hip the kernels of the fixed-point box-plus rule */
 hipError_t engine_layered_run(LayeredPlan *pl, const LayeredRun &r, hipStream_t s, int32_t *launched);
+/* engine_bitflip.hip: LDPC_ALGO_BITFLIP, bits only (bitflip_kernels.hpp) */
+hipError_t engine_bitflip_run(BitflipPlan *pl, const BitflipRun &r, hipStream_t s, int32_t *launched);
 /* llr_input.hip: y[i] = x[i] * unit for count elements of a narrow type (LlrIn::type != kLlrF32), enqueued on s */
 hipError_t engine_llr_widen(const LlrIn &in, float *y_dev, int64_t count, hipStream_t s);
 

@@ -157,7 +157,7 @@ int decode_host(ldpc_decoder *d, const ldpc::LlrIn &in, int64_t frames, uint8_t 
     ldpc::CallCounts counts;
     const bool flooding_counts = !d->use_fused && d->cfg.algo != LDPC_ALGO_LAYERED && d->cfg.algo != LDPC_ALGO_LAYERED_HOST &&
                                  d->cfg.algo != LDPC_ALGO_LAYERED_BP && d->cfg.algo != LDPC_ALGO_LAYERED_FX &&
-                                 d->cfg.algo != LDPC_ALGO_LAYERED_BP_FX;
+                                 d->cfg.algo != LDPC_ALGO_LAYERED_BP_FX && d->cfg.algo != LDPC_ALGO_BITFLIP;
     auto drain = [&](ldpc::HostSlot &sl) -> int {
         if (!sl.busy) return LDPC_OK;
         sl.busy = false;
@@ -437,6 +437,8 @@ static int decode_soft_in(ldpc_decoder *d, const ldpc::LlrIn &in, int64_t frames
     if (d->cfg.algo == LDPC_ALGO_SP)
         return set_error(LDPC_ERR_UNSUPPORTED, "soft output: LDPC_ALGO_SP has no usable soft value (include/ldpc_hip.h); "
                     "the min-sum algorithms, LDPC_ALGO_BP and LDPC_ALGO_LAYERED_BP carry it");
+    if (d->cfg.algo == LDPC_ALGO_BITFLIP)
+        return set_error(LDPC_ERR_UNSUPPORTED, "soft output: LDPC_ALGO_BITFLIP is a hard-decision decoder, its state is one bit per variable");
     if (d->tm.tap_iter) return set_error(LDPC_ERR_STATE, "soft output while a debug tap is set");
     if (frames > 0 && !soft_host) return set_error(LDPC_ERR_ARG, "soft is NULL");
     if (frames > 0 && soft_floats < frames * (int64_t)d->N)

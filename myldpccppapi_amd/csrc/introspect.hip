@@ -75,7 +75,7 @@ int ldpc_decoder_stats(ldpc_decoder *d, ldpc_decode_stats *st)
      * one-launch kernels (frames leave individually inside the launch) report 0 */
     st->frame_rounds = 0;
     if (!d->use_fused && d->cfg.algo != LDPC_ALGO_LAYERED && d->cfg.algo != LDPC_ALGO_LAYERED_HOST && d->cfg.algo != LDPC_ALGO_LAYERED_BP &&
-        d->cfg.algo != LDPC_ALGO_LAYERED_FX && d->cfg.algo != LDPC_ALGO_LAYERED_BP_FX) {
+        d->cfg.algo != LDPC_ALGO_LAYERED_FX && d->cfg.algo != LDPC_ALGO_LAYERED_BP_FX && d->cfg.algo != LDPC_ALGO_BITFLIP) {
         st->frame_rounds = d->cfg.early_term ? (int64_t)summary[2] * d->F
                                              : (int64_t)d->last_iterations * d->last_tiles * d->F;
         for (const ldpc_decoder *p = d->flood.handed_to; p; p = p->flood.handed_to) {      /* the child, and whom it handed over to */
@@ -179,6 +179,8 @@ int ldpc_decoder_kernel_times(ldpc_decoder *d, ldpc_kernel_time *out, int32_t ca
         else if (d->use_fused)      /* bytes = channel values in + packed bits out */
             snprintf(name, sizeof name, "%s", d->cfg.algo == LDPC_ALGO_SP ? "fused_sp_kernel"
                      : d->cfg.algo == LDPC_ALGO_LAYERED ? "fused_layered_kernel" : "fused_flood_kernel");
+        else if (d->cfg.algo == LDPC_ALGO_BITFLIP)         /* check, and the two passes of the variable phase (degree 1, 2) */
+            snprintf(name, sizeof name, "%s", sp.kind == 0 ? "bitflip_check_kernel" : sp.degree == 1 ? "bitflip_vote_kernel" : "bitflip_flip_kernel");
         else if (d->cfg.algo == LDPC_ALGO_LAYERED_FX)      /* the tables above end at LAYERED_BP; every layer launch is one rule */
             snprintf(name, sizeof name, "layer_kernel<lfx,%d,%d>", sp.degree, d->V);
         else if (d->cfg.algo == LDPC_ALGO_LAYERED_BP_FX)
@@ -303,6 +305,13 @@ int ldpc_decoder_dump(ldpc_decoder *d, int32_t which, float *host_out, int64_t c
         LDPC_HIP_TRY(hipMemcpy(host_out, src, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
         return LDPC_OK;
     }
+    if (d->cfg.algo == LDPC_ALGO_BITFLIP && which == 0) {       /* the syndrome words; which == 3 (bits) is read below */
+        hipError_t e = ldpc::bitflip_dump_syndrome(&d->bitflip, host_out, count, frames);
+        if (e == hipErrorInvalidValue) return set_error(LDPC_ERR_ARG, "count must be frames*M");
+        if (e != hipSuccess) return set_error(LDPC_ERR_HIP, "bit-flipping dump: %s", hipGetErrorString(e));
+        return LDPC_OK;
+    }
+    if (d->cfg.algo == LDPC_ALGO_BITFLIP && which != 3) return set_error(LDPC_ERR_ARG, "LDPC_ALGO_BITFLIP taps: 0 = syndrome words, 3 = bits");
     if (d->cfg.algo == LDPC_ALGO_LAYERED || d->cfg.algo == LDPC_ALGO_LAYERED_HOST || d->cfg.algo == LDPC_ALGO_LAYERED_BP ||
         d->cfg.algo == LDPC_ALGO_LAYERED_FX || d->cfg.algo == LDPC_ALGO_LAYERED_BP_FX) {
         hipError_t e = ldpc::layered_dump(&d->layered, which, host_out, count, frames, d->hard.p,

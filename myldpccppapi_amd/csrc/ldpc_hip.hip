@@ -189,11 +189,12 @@ int ldpc_graph_info(const ldpc_graph *g, int32_t *M, int32_t *N, int64_t *E, int
 int ldpc_decoder_config_init_sized(ldpc_decoder_config *cfg, uint32_t struct_size)
 {
     if (!cfg) return set_error(LDPC_ERR_ARG, "config is NULL");
-    if (struct_size != sizeof(ldpc_decoder_config) && struct_size != offsetof(ldpc_decoder_config, msg_bits) &&
+    if (struct_size != sizeof(ldpc_decoder_config) && struct_size != offsetof(ldpc_decoder_config, bf_threshold) &&
+        struct_size != offsetof(ldpc_decoder_config, msg_bits) &&
         struct_size != offsetof(ldpc_decoder_config, crc_kind) && struct_size != offsetof(ldpc_decoder_config, ms_scale))
-        return set_error(LDPC_ERR_ARG, "config struct_size %u is none of %zu, %zu, %zu, %zu (ABI mismatch)", struct_size,
-                    sizeof(ldpc_decoder_config), offsetof(ldpc_decoder_config, msg_bits), offsetof(ldpc_decoder_config, crc_kind),
-                    offsetof(ldpc_decoder_config, ms_scale));
+        return set_error(LDPC_ERR_ARG, "config struct_size %u is none of %zu, %zu, %zu, %zu, %zu (ABI mismatch)", struct_size,
+                    sizeof(ldpc_decoder_config), offsetof(ldpc_decoder_config, bf_threshold), offsetof(ldpc_decoder_config, msg_bits),
+                    offsetof(ldpc_decoder_config, crc_kind), offsetof(ldpc_decoder_config, ms_scale));
     /* every field that has a non-zero default lies in front of ms_scale */
     memset(cfg, 0, struct_size);
     cfg->struct_size = struct_size;
@@ -216,17 +217,18 @@ void ldpc_decoder_config_init(ldpc_decoder_config *cfg)
 }
 
 /* The caller's config as the current struct: callers built against the header before ms_scale / ms_offset, before
- * crc_kind / crc_bits or before msg_bits pass a shorter struct, of which only struct_size bytes are read; the fields it
- * lacks are 0 (off; msg_bits: 8). */
+ * crc_kind / crc_bits, before msg_bits or before bf_threshold pass a shorter struct, of which only struct_size bytes are
+ * read; the fields it lacks are 0 (off; msg_bits: 8; bf_threshold: the default schedule). */
 static int config_in(const ldpc_decoder_config *cfg, ldpc_decoder_config *full)
 {
     constexpr size_t kSizeBeforeMsCorr = offsetof(ldpc_decoder_config, ms_scale);
     constexpr size_t kSizeBeforeCrc = offsetof(ldpc_decoder_config, crc_kind);
     constexpr size_t kSizeBeforeMsgBits = offsetof(ldpc_decoder_config, msg_bits);
-    if (cfg->struct_size != sizeof(ldpc_decoder_config) && cfg->struct_size != kSizeBeforeMsgBits && cfg->struct_size != kSizeBeforeCrc &&
-        cfg->struct_size != kSizeBeforeMsCorr)
-        return set_error(LDPC_ERR_ARG, "config struct_size %u is none of %zu, %zu, %zu, %zu (ABI mismatch)", cfg->struct_size,
-                    sizeof(ldpc_decoder_config), kSizeBeforeMsgBits, kSizeBeforeCrc, kSizeBeforeMsCorr);
+    constexpr size_t kSizeBeforeBitflip = offsetof(ldpc_decoder_config, bf_threshold);
+    if (cfg->struct_size != sizeof(ldpc_decoder_config) && cfg->struct_size != kSizeBeforeBitflip && cfg->struct_size != kSizeBeforeMsgBits &&
+        cfg->struct_size != kSizeBeforeCrc && cfg->struct_size != kSizeBeforeMsCorr)
+        return set_error(LDPC_ERR_ARG, "config struct_size %u is none of %zu, %zu, %zu, %zu, %zu (ABI mismatch)", cfg->struct_size,
+                    sizeof(ldpc_decoder_config), kSizeBeforeBitflip, kSizeBeforeMsgBits, kSizeBeforeCrc, kSizeBeforeMsCorr);
     memset(full, 0, sizeof *full);
     memcpy(full, cfg, cfg->struct_size);
     full->struct_size = sizeof *full;
@@ -246,8 +248,10 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     if (cfg->max_iter <= 0 || cfg->max_iter > 100000) return set_error(LDPC_ERR_ARG, "max_iter out of range");
     if (cfg->algo != LDPC_ALGO_SP && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED &&
         cfg->algo != LDPC_ALGO_MS_FUSED && cfg->algo != LDPC_ALGO_LAYERED_HOST && cfg->algo != LDPC_ALGO_BP &&
-        cfg->algo != LDPC_ALGO_LAYERED_BP && cfg->algo != LDPC_ALGO_LAYERED_FX && cfg->algo != LDPC_ALGO_LAYERED_BP_FX)
+        cfg->algo != LDPC_ALGO_LAYERED_BP && cfg->algo != LDPC_ALGO_LAYERED_FX && cfg->algo != LDPC_ALGO_LAYERED_BP_FX &&
+        cfg->algo != LDPC_ALGO_BITFLIP)
         return set_error(LDPC_ERR_ARG, "unknown algo %d", cfg->algo);
+    const bool bitflip = cfg->algo == LDPC_ALGO_BITFLIP;
     const bool bpfx = cfg->algo == LDPC_ALGO_LAYERED_BP_FX;     /* LAYERED_FX's configuration, storage and schedule, another row */
     const bool fx = cfg->algo == LDPC_ALGO_LAYERED_FX || bpfx;
     const char *const fx_name = bpfx ? "LDPC_ALGO_LAYERED_BP_FX" : "LDPC_ALGO_LAYERED_FX";
@@ -259,7 +263,7 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     const bool ms_corr = cfg->ms_scale != 0.0f || cfg->ms_offset != 0.0f;
     if (ms_corr && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED && !(fx && !bpfx))
         return set_error(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset apply to LDPC_ALGO_MS and LDPC_ALGO_LAYERED only "
-                    "(SP, BP, LAYERED_BP and LAYERED_BP_FX have no minimum to correct; MS_FUSED and LAYERED_HOST reproduce reference kernels)");
+                    "(SP, BP, LAYERED_BP, LAYERED_BP_FX and BITFLIP have no minimum to correct; MS_FUSED and LAYERED_HOST reproduce reference kernels)");
     const bool bp_row = cfg->algo == LDPC_ALGO_BP || cfg->algo == LDPC_ALGO_LAYERED_BP;      /* box-plus check node */
     if (bp_row && !(cfg->llr_scale > 0.0f && cfg->llr_scale <= 3.402823466e38f))
         return set_error(LDPC_ERR_ARG, "%s: llr_scale must be positive and finite (chan = llr_scale * y is the LLR)",
@@ -283,6 +287,17 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         return set_error(LDPC_ERR_ARG, "unknown msg_dtype %d", cfg->msg_dtype);
     if (cfg->msg_reserved3)
         return set_error(LDPC_ERR_ARG, "msg_reserved must be 0");
+    for (int j = 0; j < ldpc::kBitflipThresholds; ++j) {
+        if (cfg->bf_threshold[j] != 0 && !bitflip)
+            return set_error(LDPC_ERR_ARG, "bf_threshold[%d]=%d belongs to LDPC_ALGO_BITFLIP (algo is %d)", j, cfg->bf_threshold[j], cfg->algo);
+        if (cfg->bf_threshold[j] < 0 || cfg->bf_threshold[j] > ldpc::kBitflipMaxDegree)
+            return set_error(LDPC_ERR_ARG, "bf_threshold[%d]=%d must be in [0, %d]", j, cfg->bf_threshold[j], ldpc::kBitflipMaxDegree);
+    }
+    if (bitflip && cfg->msg_dtype != LDPC_MSG_F32)
+        return set_error(LDPC_ERR_UNSUPPORTED, "LDPC_ALGO_BITFLIP has no messages: msg_dtype must be LDPC_MSG_F32, not %d", cfg->msg_dtype);
+    if (bitflip && g->max_col_deg > ldpc::kBitflipMaxDegree)
+        return set_error(LDPC_ERR_UNSUPPORTED, "LDPC_ALGO_BITFLIP counts a column's votes in six bits: column degree %d > %d", g->max_col_deg,
+                    ldpc::kBitflipMaxDegree);
     if (cfg->bp_frac_bits != 0 && !bpfx)
         return set_error(LDPC_ERR_ARG, "bp_frac_bits=%d belongs to LDPC_ALGO_LAYERED_BP_FX (algo is %d)", cfg->bp_frac_bits, cfg->algo);
     if (bpfx && (cfg->bp_frac_bits < 0 || cfg->bp_frac_bits > ldpc::kBpFxMaxFracBits))
@@ -317,6 +332,12 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         return set_error(LDPC_ERR_UNSUPPORTED, "fp16 messages are built for flooding min-sum and BP only "
                     "(the probability-domain SP needs fp32 range; the layered engine, LAYERED and LAYERED_BP, is fp32)");
     if (!ldpc::tune_valid(*cfg)) return set_error(LDPC_ERR_ARG, "tuning / streams config fields out of range");
+    if (bitflip) {
+        const ldpc::Tune t = ldpc::tune_from_config(*cfg);
+        if (ldpc::tune_forced_on(t.fused) || ldpc::tune_forced_on(t.ldsp))
+            return set_error(LDPC_ERR_UNSUPPORTED, "LDPC_ALGO_BITFLIP runs the bit-flipping engine: the one-launch and the record kernels "
+                        "(LDPC_TUNE_FUSED / LDPC_TUNE_LDSP forced on) are soft decoders");
+    }
     if (bp_row) {
         const ldpc::Tune t = ldpc::tune_from_config(*cfg);
         if (ldpc::tune_forced_on(t.fused) || ldpc::tune_forced_on(t.ldsp))
@@ -378,7 +399,7 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     d->flood.link_deep = ldpc::tune_pick(tune.link_deep, false);
     if (tune.link_rows) d->flood.link_rpw = tune.link_rows < 0 ? 0 : tune.link_rows;
     LDPC_HIP_TRY(hipDeviceGetAttribute(&d->flood.cus, hipDeviceAttributeMultiprocessorCount, cfg->device));
-    d->V = pick_frames_per_lane(*cfg, g->max_row_deg, g->max_col_deg);
+    d->V = bitflip ? 1 : pick_frames_per_lane(*cfg, g->max_row_deg, g->max_col_deg);       /* bit flipping: a word is 64 frames */
     d->F = 64 * d->V;
     d->T = (cfg->max_batch + d->F - 1) / d->F;
     /* a single tile is latency-bound (one wave walks its rows one after the other): shorter row
@@ -416,7 +437,12 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         LDPC_HIP_TRY(d->crc_w.upload(w));
     }
 
-    if (cfg->algo == LDPC_ALGO_MS_FUSED) {
+    if (bitflip) {
+        /* the bit-flipping engine: x lives in `hard`; received bits, syndrome words and votes in the plan.  No hand-over
+         * child and no device-side tail: a round is too cheap to be worth moving frames for */
+        const hipError_t e = ldpc::bitflip_plan_create(&d->bitflip, g->M, g->N, g->E, g->rows, g->col_edge, d->T, cfg->bf_threshold);
+        if (e != hipSuccess) return set_error(LDPC_ERR_HIP, "bit-flipping plan allocation failed: %s", hipGetErrorString(e));
+    } else if (cfg->algo == LDPC_ALGO_MS_FUSED) {
         if (cfg->pack_mode != LDPC_PACK_BYTES && cfg->K % 8)
             return set_error(LDPC_ERR_UNSUPPORTED, "MS_FUSED packs whole bytes per frame only");
         /* flood_ldsp_kernel<.., CHAIN = false> (posteriors in LDS, 16-byte check records) wherever it fits
@@ -725,6 +751,22 @@ static int decode_device_in(ldpc_decoder *d, const ldpc::LlrIn &in, int64_t fram
         hipError_t e = ldpc::engine_layered_run(&d->layered, run, s, &d->last_iterations);
         rc = (e == hipSuccess) ? LDPC_OK
                                : set_error(LDPC_ERR_HIP, "layered decode: %s", hipGetErrorString(e));
+    } else if (d->cfg.algo == LDPC_ALGO_BITFLIP) {
+        ldpc::BitflipRun run;
+        run.span_begin = [](void *c, hipStream_t st, int kind, int deg, int64_t bytes) {
+            return ldpc::span_begin((ldpc_decoder *)c, st, kind, deg, bytes);
+        };
+        run.span_end = [](void *c, hipStream_t st) { return ldpc::span_end((ldpc_decoder *)c, st); };
+        run.span_ctx = d;
+        run.llr = in; run.frames = frames; run.out_dev = out_dev;
+        run.out_bytes = room; run.iters_dev = iters_dev;
+        run.K = d->cfg.K; run.max_iter = d->cfg.max_iter; run.tap_iter = d->tm.tap_iter;
+        run.early_term = d->cfg.early_term; run.pack_mode = d->cfg.pack_mode;
+        run.hard = d->hard.p; run.failw = d->failw.p; run.done = d->done.p; run.iters = d->iters.p;
+        run.row_ptr = d->row_ptr.p; run.edge_col = d->edge_col.p; run.col_ptr = d->col_ptr.p; run.summary = d->summary.p;
+        run.crc_w = d->crc_w.p; run.crc_bits = d->cfg.crc_kind ? d->cfg.crc_bits : 0;
+        hipError_t e = ldpc::engine_bitflip_run(&d->bitflip, run, s, &d->last_iterations);
+        rc = (e == hipSuccess) ? LDPC_OK : set_error(LDPC_ERR_HIP, "bit-flipping decode: %s", hipGetErrorString(e));
     } else {
         rc = ldpc::engine_flood_run(d, in, frames, out_dev, room, iters_dev, s);
     }
@@ -761,6 +803,8 @@ static int decode_soft_device_in(ldpc_decoder *d, const ldpc::LlrIn &in, int64_t
         return set_error(LDPC_ERR_UNSUPPORTED, "soft output: LDPC_ALGO_SP works in the probability domain in fp32, where the "
                     "posterior saturates to exactly +-1 on nearly every bit of a frame that converges and is 0/0 on frames "
                     "that do not; the min-sum algorithms (MS, MS_FUSED, LAYERED, LAYERED_HOST) and the log-domain LDPC_ALGO_BP / LDPC_ALGO_LAYERED_BP carry it");
+    if (d->cfg.algo == LDPC_ALGO_BITFLIP)
+        return set_error(LDPC_ERR_UNSUPPORTED, "soft output: LDPC_ALGO_BITFLIP is a hard-decision decoder, its state is one bit per variable");
     if (d->tm.tap_iter)
         return set_error(LDPC_ERR_STATE, "soft output while a debug tap is set (ldpc_decoder_set_tap(d, 0) clears it)");
     if (frames < 0 || frames > d->cfg.max_batch)

@@ -7,7 +7,7 @@ b is frame b*frames + f of the seed's stream, so a point can be extended or re-r
 and errors counted by ldpc_count_errors_device; nothing crosses PCIe but the counts.  The
 reference counts differing BYTES (Test.cpp:105-110); this prints byte errors too.
 
-    python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N> | --alist PATH] [--algo sp|ms|layered|bp|layered_bp|layered_fx|layered_bp_fx]
+    python tools/ber_sweep.py [--code dvbs2_12|dvbs2_910|bg1|wimax:<rate>:<N> | --alist PATH] [--algo sp|ms|layered|bp|layered_bp|layered_fx|layered_bp_fx|bitflip]
                               [--payload zero|random] [--rate-match P,FLO,FHI,E[,K0]] [--erasure-llr X]
                               [--modulation bpsk|qpsk|qam16|qam64|qam256] [--no-interleave] [--transport-block A[,C]] [--crc-stop] [--bch T[,N]]
                               [--msg-dtype f32|f16|f8|i8 [--msg-bits Q --llr-scale S]] [--post-bits P] [--fx-record] [--frac-bits F] [--soft-check] [--osd 0|1 [--osd-scale S]]
@@ -65,6 +65,13 @@ the systematic order of ldpc_graph_systematic_order (include/ldpc_hip.h, "encode
 whether the order was the identity are printed), the decoder runs on the re-ordered matrix, and --payload random encodes with the
 dense encoder (ldpc_encoder_create_dense).  Flooding algorithms only (--algo sp, ms or bp; no circulant size is known).  K % 8 != 0
 is fine: the bits between the frames of the byte stream are zero on both sides and the frame errors are counted per frame's bytes.
+--algo bitflip (LDPC_ALGO_BITFLIP: hard-decision parallel bit flipping) reads only the sign of a channel value: the
+hard-decision baseline of a code.  --bf-threshold O1,O2,... gives up to 16 round offsets (the last one repeats).  No --soft-check,
+--osd, --ms-scale / --ms-offset or --msg-dtype.
+--channel bsc --crossover P1,P2,... (in place of --snr; BPSK without --modulation or --rate-match): a binary symmetric channel.
+Every value is the SIGN (+-1) of the ldpc_awgn_device value at sd = 1 / Qinv(P), the noise at which a hard decision on BPSK
+is wrong with probability P: the same counter-based generator, identical on the host, and no second channel kernel.  Every
+point prints crossover and the sd it used; snr_db is that sd's.  Any --algo takes it: a soft decoder then sees what bitflip sees.
 The DVB-S2 / BG1 codes are PROFILE SURROGATES (codes.py): the numbers are not the standards'."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -105,6 +112,9 @@ ap.add_argument("--msg-bits", type=int, default=0, help="with --msg-dtype i8: 4,
 ap.add_argument("--fx-record", action="store_true", help="--algo layered_fx: the fixed-point record kernel (LDPC_TUNE_FX_RECORD), same results")
 ap.add_argument("--post-bits", type=int, default=0, help="--algo layered_fx and layered_bp_fx: bits of the saturating posterior memory, --msg-bits ... 16 (0 = 16)")
 ap.add_argument("--frac-bits", type=int, default=0, help="--algo layered_bp_fx: fractional bits of an LSB, 0 ... 4 (one LSB = 2^-F LLR units)")
+ap.add_argument("--bf-threshold", default=None, metavar="O1,O2,...", help="--algo bitflip: up to 16 round offsets in [0, 62], the last one repeats (default: off(i) = i - 1)")
+ap.add_argument("--channel", choices=("awgn", "bsc"), default="awgn", help="bsc: the sign of the AWGN value at the sd whose hard decision errs with --crossover")
+ap.add_argument("--crossover", default="0.01,0.02,0.03", help="with --channel bsc: the crossover probabilities, in place of --snr")
 ap.add_argument("--llr-type", choices=("f32", "f16", "i8"), default="f32",
                 help="quantise the channel values on the device (ldpc_llr_quantize_device) behind the channel / rate-recover step "
                      "and decode them through ldpc_decode_typed_device")
@@ -119,6 +129,8 @@ ap.add_argument("--osd-scale", type=float, default=256.0, help="with --osd: weig
 args = ap.parse_args()
 if args.algo in ("layered_fx", "layered_bp_fx"):
     args.msg_dtype = "i8"           # the algorithm is defined on fixed-point messages alone
+assert args.algo != "bitflip" or (args.osd is None and not args.soft_check), "--algo bitflip has no soft output (include/ldpc_hip.h)"
+assert args.channel == "awgn" or not (args.modulation or args.rate_match), "--channel bsc: BPSK without --modulation or --rate-match"
 assert args.osd is None or args.algo != "sp", "--osd: sum-product has no soft output (include/ldpc_hip.h)"
 assert not (args.soft_check and args.algo == "sp"), "--soft-check: sum-product has no soft output (include/ldpc_hip.h)"
 assert not args.transport_block or args.payload == "random", "--transport-block needs --payload random"
@@ -177,7 +189,8 @@ def make_decoder(llr_scale):
     return L.Decoder(g, K, max_batch=B, algo=args.algo, max_iter=args.iters, llr_scale=llr_scale,
                      layer_rows=layer, poll_interval=2, ms_scale=args.ms_scale, ms_offset=args.ms_offset,
                      crc_kind=crc_kind, crc_bits=crc_bits, msg_dtype=args.msg_dtype, msg_bits=args.msg_bits, post_bits=args.post_bits,
-                     bp_frac_bits=args.frac_bits, tune={"fx_record": True} if args.fx_record else None)
+                     bp_frac_bits=args.frac_bits, tune={"fx_record": True} if args.fx_record else None,
+                     bf_threshold=[int(v) for v in args.bf_threshold.split(",")] if args.bf_threshold else None)
 
 
 dec = None if matched else make_decoder(8.0 if args.llr_scale is None else args.llr_scale)
@@ -250,6 +263,13 @@ if QM:
 
 
 def channel_batch(first, sd, seed):
+    """Channel values of one batch into y (channel_values), and with --channel bsc their signs in their place."""
+    channel_values(first, sd, seed)
+    if args.channel == "bsc":
+        torch.sign(y, out=y)
+
+
+def channel_values(first, sd, seed):
     """Channel values of one batch into y; with a random payload: fresh source bytes -> code bits -> BPSK + noise."""
     stream = torch.cuda.current_stream().cuda_stream
     if enc is not None:
@@ -373,7 +393,16 @@ if args.crc_stop:
     print("crc stop: crc_kind=%d over the first %d bits of every frame" % (crc_kind, crc_bits))
 print("code=%s algo=%s payload=%s ms_scale=%g ms_offset=%g frames=%d x %d max_iter=%d (info bits per point: %d)" % (
     args.code, args.algo, args.payload, args.ms_scale, args.ms_offset, B, args.batches, args.iters, B * K * args.batches))
-points = [float(x) for x in args.snr.split(",")]
+crossover = {}
+if args.channel == "bsc":           # a hard decision on BPSK +-1 in noise sd errs with probability Q(1 / sd)
+    from statistics import NormalDist
+    for p in (float(x) for x in args.crossover.split(",")):
+        assert 0.0 < p < 0.5, "--crossover: probabilities inside (0, 0.5)"
+        snr = 20.0 * np.log10(NormalDist().inv_cdf(1.0 - p))
+        crossover[snr] = p
+    points = list(crossover)
+else:
+    points = [float(x) for x in args.snr.split(",")]
 # one untimed batch first: the first launch of every kernel (the library's and torch's) pays one-time costs
 point_decoder(10.0 ** (-points[-1] / 20.0))
 channel_batch(0, 10.0 ** (-points[-1] / 20.0), args.seed + 1)
@@ -427,6 +456,8 @@ for snr in points:
            "byte_errors": tot[1], "fer": tot[2] / frames, "avg_iters": round(it_sum / frames, 2),
            "frames_converged": conv, "frames": frames, "frame_rounds": rounds, "decode_ms_per_batch": round(dec_ms / args.batches, 3),
            "end_to_end_Mbit_s": round(frames * K / dt / 1e6, 1)}
+    if args.channel == "bsc":
+        res["crossover"] = crossover[snr]
     if md is not None:
         es_n0 = 1.0 / (2.0 * sd * sd)
         res.update({"es_n0_db": round(10.0 * np.log10(es_n0), 3), "eb_n0_db": round(10.0 * np.log10(es_n0 / (QM * rate)), 3),
