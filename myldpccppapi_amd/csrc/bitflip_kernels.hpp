@@ -38,6 +38,7 @@
 #include "crc_term_kernels.hpp"
 #include "hip_host.hpp"
 #include "llr_input.hpp"
+#include "engines.hpp"
 
 namespace ldpc {
 
@@ -294,22 +295,8 @@ inline hipError_t bitflip_plan_create(BitflipPlan *pl, int32_t M, int32_t N, int
     return e;
 }
 
-struct BitflipRun {
-    hipError_t (*span_begin)(void *ctx, hipStream_t s, int kind, int degree, int64_t bytes) = nullptr;
-    hipError_t (*span_end)(void *ctx, hipStream_t s) = nullptr;
-    void *span_ctx = nullptr;
-    LlrIn llr;
-    int64_t frames;
-    uint8_t *out_dev;
-    int64_t out_bytes;
-    int32_t *iters_dev;
-    int32_t K, max_iter, tap_iter, early_term, pack_mode;
-    uint64_t *hard, *failw, *done;      /* [T][N], [max_iter + 2][T], [T] */
-    int32_t *iters;
-    const int32_t *row_ptr, *edge_col, *col_ptr;
-    int32_t *summary;
-    const uint32_t *crc_w = nullptr;
-    int32_t crc_bits = 0;
+struct BitflipRun : StreamRun {     /* engines.hpp; hard is [T][N], failw [max_iter + 2][T], done [T] */
+    const int32_t *col_ptr = nullptr;
 };
 
 /* which: 0 = the syndrome words of the last round run, [frame][M] as 0 / 1 */

@@ -24,6 +24,7 @@
 #include "ldsp_kernels.hpp"
 #include "engines.hpp"
 #include "tune.hpp"
+#include "decoder_config_host.hpp"
 #include "host_stage.hpp"
 #include "hip_host.hpp"
 
@@ -247,13 +248,16 @@ struct ldpc_decoder {
                                            frames stopped by the CRC alone (cfg.crc_kind) */
     ldpc::DevBuf<uint32_t> crc_w;       /* cfg.crc_kind != 0: [crc_bits] column weights of crc_term_kernel (crc_term_host.hpp) */
 
-    ldpc::LayeredPlan layered;          /* LDPC_ALGO_LAYERED / LAYERED_HOST / LAYERED_BP, streaming (one launch per layer) */
-    ldpc::BitflipPlan bitflip;          /* LDPC_ALGO_BITFLIP: received bits, syndrome words, votes (hard holds x at V = 1) */
-    ldpc::FusedPlan fused;              /* LDPC_ALGO_LAYERED, short QC codes: whole decode in LDS */
-    bool use_fused = false;
-    ldpc::LdspPlan ldsp;                /* LDPC_ALGO_LAYERED, mid-size QC codes: posterior in LDS, check records in cache;
-                                           LDPC_ALGO_LAYERED_FX with LDPC_TUNE_FX_RECORD: the same in fixed point (ldsp.fx) */
-    bool use_ldsp = false;
+    /* The engine this handle runs, chosen once at creation (decoder_config_host.hpp: engine_candidates); only that
+     * engine's plan below is filled. */
+    ldpc::Engine engine = ldpc::Engine::Flood;
+    /* whole decode in one launch: frames leave inside it, the kernels read float channel values */
+    bool one_launch() const { return engine == ldpc::Engine::Fused || engine == ldpc::Engine::Ldsp || engine == ldpc::Engine::LdspFx; }
+    ldpc::LayeredPlan layered;          /* Engine::Layered: streaming, one launch per layer */
+    ldpc::BitflipPlan bitflip;          /* Engine::Bitflip: received bits, syndrome words, votes (hard holds x at V = 1) */
+    ldpc::FusedPlan fused;              /* Engine::Fused, short QC codes: whole decode in LDS */
+    ldpc::LdspPlan ldsp;                /* Engine::Ldsp, mid-size QC codes: posterior in LDS, check records in cache;
+                                           Engine::LdspFx (LDPC_ALGO_LAYERED_FX with LDPC_TUNE_FX_RECORD): the same in fixed point */
     /* normalized / offset min-sum (cfg.ms_scale / ms_offset): the streaming kernels of kAlgoMSC (flooding) or
      * layer_corr_kernel (layered) run with alpha = ms_scale (1 when 0) and beta = ms_offset */
     bool ms_corr = false;

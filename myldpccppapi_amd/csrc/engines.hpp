@@ -27,6 +27,28 @@ struct LayeredRun;
 struct BitflipPlan;
 struct BitflipRun;
 
+/* What one call hands a streaming engine that keeps its state in the handle's own arrays (layered, bit flipping): the
+ * host driver fills it in one place; LayeredRun and BitflipRun add what is their own. */
+struct StreamRun {
+    /* optional per-launch timing hooks (HIP events on the decode stream) */
+    hipError_t (*span_begin)(void *ctx, hipStream_t s, int kind, int degree, int64_t bytes) = nullptr;
+    hipError_t (*span_end)(void *ctx, hipStream_t s) = nullptr;
+    void *span_ctx = nullptr;
+    LlrIn llr;                      /* the caller's channel values: pointer, element type, unit (llr_input.hpp) */
+    int64_t frames;
+    uint8_t *out_dev;
+    int64_t out_bytes;
+    int32_t *iters_dev;
+    int32_t K, max_iter, tap_iter, early_term, pack_mode;
+    uint64_t *hard, *failw, *done;  /* [T][N][V], [max_iter + 2][T][V], [T][V] */
+    int32_t *iters;
+    const int32_t *row_ptr, *edge_col;
+    int32_t *summary;
+    /* CRC-aided early termination (ldpc_decoder_config::crc_kind): column weights and covered bits, 0 = off */
+    const uint32_t *crc_w = nullptr;
+    int32_t crc_bits = 0;
+};
+
 hipError_t engine_ldsp_plan_create(LdspPlan *pl, int32_t M, int32_t N, int64_t E, const std::vector<int32_t> &row_ptr,
                                    const std::vector<int32_t> &cols, int32_t z, int32_t K, int64_t max_batch, int device,
                                    const Tune &tune, int flood);

@@ -155,9 +155,7 @@ int decode_host(ldpc_decoder *d, const ldpc::LlrIn &in, int64_t frames, uint8_t 
     ldpc::PageLockRegistry &registry = ldpc::PageLockRegistry::instance();
     /* a finished group's bytes go from the pinned slot to the caller's buffers */
     ldpc::CallCounts counts;
-    const bool flooding_counts = !d->use_fused && d->cfg.algo != LDPC_ALGO_LAYERED && d->cfg.algo != LDPC_ALGO_LAYERED_HOST &&
-                                 d->cfg.algo != LDPC_ALGO_LAYERED_BP && d->cfg.algo != LDPC_ALGO_LAYERED_FX &&
-                                 d->cfg.algo != LDPC_ALGO_LAYERED_BP_FX && d->cfg.algo != LDPC_ALGO_BITFLIP;
+    const bool flooding_counts = d->engine == ldpc::Engine::Flood;
     auto drain = [&](ldpc::HostSlot &sl) -> int {
         if (!sl.busy) return LDPC_OK;
         sl.busy = false;

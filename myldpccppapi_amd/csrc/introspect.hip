@@ -74,8 +74,7 @@ int ldpc_decoder_stats(ldpc_decoder *d, ldpc_decode_stats *st)
      * at kernel entry): counted on the device with early termination, all launched rounds without; the
      * one-launch kernels (frames leave individually inside the launch) report 0 */
     st->frame_rounds = 0;
-    if (!d->use_fused && d->cfg.algo != LDPC_ALGO_LAYERED && d->cfg.algo != LDPC_ALGO_LAYERED_HOST && d->cfg.algo != LDPC_ALGO_LAYERED_BP &&
-        d->cfg.algo != LDPC_ALGO_LAYERED_FX && d->cfg.algo != LDPC_ALGO_LAYERED_BP_FX && d->cfg.algo != LDPC_ALGO_BITFLIP) {
+    if (d->engine == ldpc::Engine::Flood) {
         st->frame_rounds = d->cfg.early_term ? (int64_t)summary[2] * d->F
                                              : (int64_t)d->last_iterations * d->last_tiles * d->F;
         for (const ldpc_decoder *p = d->flood.handed_to; p; p = p->flood.handed_to) {      /* the child, and whom it handed over to */
@@ -143,23 +142,18 @@ int ldpc_decoder_kernel_times(ldpc_decoder *d, ldpc_kernel_time *out, int32_t ca
     LDPC_HIP_TRY(hipEventSynchronize(d->tm.ev_end.e));
     /* the half form exists for tiles of 256 frames only: below that the launch takes the narrow kernel (enqueue_check_phase) */
     const int link_form = (d->flood.link_form == 2 && d->V != 4) ? 1 : d->flood.link_form;
-    const char *phase_name[] = {"check_kernel", "var_kernel", d->ms_corr ? "layer_corr_kernel" : "layer_kernel", "other",
+    const ldpc::AlgoInfo &a = *ldpc::algo_info(d->cfg.algo);
+    const bool layered = a.family == ldpc::Family::Layered;
+    /* the fixed-point layered algorithms launch one rule, corrected or not */
+    const char *phase_name[] = {"check_kernel", "var_kernel", d->ms_corr && !a.fixed ? "layer_corr_kernel" : "layer_kernel", "other",
                                 link_form == 2 ? "check_link_half_kernel"
                                 : link_form ? "check_link_narrow_kernel" : "check_link_kernel"};
-    static const char *algo_name_f32[] = {"sp", "ms", "layered", "ms_fused", "layered_host", "bp", "layered_bp"};
-    static const char *algo_name_f16[] = {"sp16", "ms16", "layered16", "ms_fused16", "layered_host16", "bp16", "layered_bp16"};
-    static const char *algo_name_corr_f32[] = {"sp", "msc", "layered", "ms_fused", "layered_host", "bp", "layered_bp"};  /* kAlgoMSC; index = enum ldpc_algo */
-    static const char *algo_name_corr_f16[] = {"sp16", "msc16", "layered16", "ms_fused16", "layered_host16", "bp16", "layered_bp16"};
-    static const char *algo_name_f8[] = {"sp8", "ms8", "layered8", "ms_fused8", "layered_host8", "bp8", "layered_bp8"};
-    static const char *algo_name_corr_f8[] = {"sp8", "msc8", "layered8", "ms_fused8", "layered_host8", "bp8", "layered_bp8"};
-    const int msz = d->flood.msg_size;
-    /* fixed point (LDPC_MSG_I8, min-sum only): msi<q> / msci<q> */
-    char name_i8[8];
-    snprintf(name_i8, sizeof name_i8, "%s%d", d->ms_corr ? "msci" : "msi", d->flood.msg_bits);
-    const char *algo_name_i8[] = {"sp", name_i8, "layered", "ms_fused", "layered_host", "bp", "layered_bp"};
-    const char **algo_name = d->flood.msg_kind == LDPC_MSG_I8 ? algo_name_i8
-                             : d->ms_corr ? (msz == 1 ? algo_name_corr_f8 : msz == 2 ? algo_name_corr_f16 : algo_name_corr_f32)
-                                          : (msz == 1 ? algo_name_f8 : msz == 2 ? algo_name_f16 : algo_name_f32);
+    /* the arithmetic a streaming kernel was instantiated for: the algorithm's short name, `c` for corrected flooding
+     * min-sum (kAlgoMSC), then the message type: none fp32, 16 fp16, 8 fp8, i<q> fixed point of q bits */
+    char algo_name[32], suffix[8] = "";
+    if (d->flood.msg_kind == LDPC_MSG_I8) snprintf(suffix, sizeof suffix, "i%d", d->flood.msg_bits);
+    else if (d->flood.msg_size != 4) snprintf(suffix, sizeof suffix, "%d", d->flood.msg_size == 1 ? 8 : 16);
+    snprintf(algo_name, sizeof algo_name, "%s%s%s", a.short_name, d->ms_corr && a.family == ldpc::Family::Flood ? "c" : "", suffix);
     for (size_t i = 0; i < d->tm.spans_used; ++i) {
         const ldpc::TimedSpan &sp = d->tm.spans[i];
         float ms = 0;
@@ -169,26 +163,20 @@ int ldpc_decoder_kernel_times(ldpc_decoder *d, ldpc_kernel_time *out, int32_t ca
         if (sp.kind == 3) snprintf(name, sizeof name, "other");
         else if (sp.kind == 7) snprintf(name, sizeof name, "soft_settle_kernel");     /* soft calls only */
         else if (sp.kind == 8) snprintf(name, sizeof name, "llr_widen_kernel");       /* typed calls on a one-launch kernel only */
-        else if (d->use_fused && d->use_ldsp && d->ldsp.fx)
+        else if (d->engine == ldpc::Engine::LdspFx)
             snprintf(name, sizeof name, "layered_ldsp_fx_kernel[%dx%d,%d]", d->ldsp.grid, d->ldsp.block, d->ldsp.wg_frames);
-        else if (d->use_fused && d->use_ldsp)   /* whole decode in one launch; [persistent grid x workgroup size, frames per workgroup] */
-            snprintf(name, sizeof name, "%s[%dx%d,%d]", d->cfg.algo == LDPC_ALGO_LAYERED
-                     ? (d->ms_corr ? "layered_ldsp_corr_kernel" : "layered_ldsp_kernel")
-                     : (d->ms_corr ? "flood_ldsp_corr_kernel" : "flood_ldsp_kernel"),
+        else if (d->engine == ldpc::Engine::Ldsp)   /* whole decode in one launch; [persistent grid x workgroup size, frames per workgroup] */
+            snprintf(name, sizeof name, "%s_ldsp%s_kernel[%dx%d,%d]", layered ? "layered" : "flood", d->ms_corr ? "_corr" : "",
                      d->ldsp.grid, d->ldsp.block, d->ldsp.wg_frames);
-        else if (d->use_fused)      /* bytes = channel values in + packed bits out */
+        else if (d->engine == ldpc::Engine::Fused)      /* bytes = channel values in + packed bits out */
             snprintf(name, sizeof name, "%s", d->cfg.algo == LDPC_ALGO_SP ? "fused_sp_kernel"
-                     : d->cfg.algo == LDPC_ALGO_LAYERED ? "fused_layered_kernel" : "fused_flood_kernel");
-        else if (d->cfg.algo == LDPC_ALGO_BITFLIP)         /* check, and the two passes of the variable phase (degree 1, 2) */
+                     : layered ? "fused_layered_kernel" : "fused_flood_kernel");
+        else if (d->engine == ldpc::Engine::Bitflip)       /* check, and the two passes of the variable phase (degree 1, 2) */
             snprintf(name, sizeof name, "%s", sp.kind == 0 ? "bitflip_check_kernel" : sp.degree == 1 ? "bitflip_vote_kernel" : "bitflip_flip_kernel");
-        else if (d->cfg.algo == LDPC_ALGO_LAYERED_FX)      /* the tables above end at LAYERED_BP; every layer launch is one rule */
-            snprintf(name, sizeof name, "layer_kernel<lfx,%d,%d>", sp.degree, d->V);
-        else if (d->cfg.algo == LDPC_ALGO_LAYERED_BP_FX)
-            snprintf(name, sizeof name, "layer_kernel<lbfx,%d,%d>", sp.degree, d->V);
         else if (sp.kind == 5 || sp.kind == 6)
             snprintf(name, sizeof name, "%s<%s,%d-%d,%d>", sp.kind == 5 ? "check_group_kernel" : "var_group_kernel",
-                     algo_name[d->cfg.algo], sp.lo, sp.degree, d->V);
-        else snprintf(name, sizeof name, "%s<%s,%d,%d>", phase_name[sp.kind], algo_name[d->cfg.algo], sp.degree, d->V);
+                     algo_name, sp.lo, sp.degree, d->V);
+        else snprintf(name, sizeof name, "%s<%s,%d,%d>", phase_name[sp.kind], algo_name, sp.degree, d->V);
         int k = 0;
         for (; k < *count; ++k)
             if (!strcmp(out[k].name, name)) break;
@@ -274,7 +262,7 @@ int ldpc_decoder_dump(ldpc_decoder *d, int32_t which, float *host_out, int64_t c
     const int64_t frames = d->last_frames;
     const int V = d->V, F = d->F;
     const int tiles = (int)((frames + F - 1) / F);
-    if (d->use_fused && d->cfg.algo == LDPC_ALGO_SP) {
+    if (d->engine == ldpc::Engine::Fused && d->cfg.algo == LDPC_ALGO_SP) {
         if (!d->fused.dump_p.p) return set_error(LDPC_ERR_STATE, "fused dump needs set_tap() before the decode");
         const int64_t per = (which == 0 || which == 1) ? d->E : d->N;
         if (which < 0 || which > 3 || count != frames * per) return set_error(LDPC_ERR_ARG, "bad `which`/count");
@@ -288,9 +276,10 @@ int ldpc_decoder_dump(ldpc_decoder *d, int32_t which, float *host_out, int64_t c
         LDPC_HIP_TRY(hipMemcpy(host_out, src, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
         return LDPC_OK;
     }
-    if (d->use_fused) {
-        const float *dump_r = d->use_ldsp ? d->ldsp.dump_r.p : d->fused.dump_r.p;
-        const float *dump_p = d->use_ldsp ? d->ldsp.dump_p.p : d->fused.dump_p.p;
+    if (d->one_launch()) {
+        const bool lds_resident = d->engine == ldpc::Engine::Fused;
+        const float *dump_r = lds_resident ? d->fused.dump_r.p : d->ldsp.dump_r.p;
+        const float *dump_p = lds_resident ? d->fused.dump_p.p : d->ldsp.dump_p.p;
         const float *src = which == 0 ? dump_r : (which == 2 ? dump_p : nullptr);
         const int64_t per = which == 0 ? d->E : d->N;
         if (which == 3) {           /* hard bits = P < 0 */
@@ -305,15 +294,14 @@ int ldpc_decoder_dump(ldpc_decoder *d, int32_t which, float *host_out, int64_t c
         LDPC_HIP_TRY(hipMemcpy(host_out, src, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
         return LDPC_OK;
     }
-    if (d->cfg.algo == LDPC_ALGO_BITFLIP && which == 0) {       /* the syndrome words; which == 3 (bits) is read below */
+    if (d->engine == ldpc::Engine::Bitflip && which == 0) {       /* the syndrome words; which == 3 (bits) is read below */
         hipError_t e = ldpc::bitflip_dump_syndrome(&d->bitflip, host_out, count, frames);
         if (e == hipErrorInvalidValue) return set_error(LDPC_ERR_ARG, "count must be frames*M");
         if (e != hipSuccess) return set_error(LDPC_ERR_HIP, "bit-flipping dump: %s", hipGetErrorString(e));
         return LDPC_OK;
     }
-    if (d->cfg.algo == LDPC_ALGO_BITFLIP && which != 3) return set_error(LDPC_ERR_ARG, "LDPC_ALGO_BITFLIP taps: 0 = syndrome words, 3 = bits");
-    if (d->cfg.algo == LDPC_ALGO_LAYERED || d->cfg.algo == LDPC_ALGO_LAYERED_HOST || d->cfg.algo == LDPC_ALGO_LAYERED_BP ||
-        d->cfg.algo == LDPC_ALGO_LAYERED_FX || d->cfg.algo == LDPC_ALGO_LAYERED_BP_FX) {
+    if (d->engine == ldpc::Engine::Bitflip && which != 3) return set_error(LDPC_ERR_ARG, "LDPC_ALGO_BITFLIP taps: 0 = syndrome words, 3 = bits");
+    if (d->engine == ldpc::Engine::Layered) {
         hipError_t e = ldpc::layered_dump(&d->layered, which, host_out, count, frames, d->hard.p,
                                           d->h_cols.data());
         if (e == hipErrorInvalidValue) return set_error(LDPC_ERR_ARG, "bad `which`/count for layered dump");

@@ -56,6 +56,7 @@
 #include "crc_term_kernels.hpp"
 #include "soft_kernels.hpp"
 #include "hip_host.hpp"
+#include "engines.hpp"
 
 namespace ldpc {
 
@@ -939,24 +940,7 @@ inline int layered_plan_create(LayeredPlan *pl, int32_t M, int32_t N, int64_t E,
     return ok ? 0 : -2;
 }
 
-struct LayeredRun {
-    /* optional per-launch timing hooks (HIP events on the decode stream) */
-    hipError_t (*span_begin)(void *ctx, hipStream_t s, int kind, int degree, int64_t bytes) = nullptr;
-    hipError_t (*span_end)(void *ctx, hipStream_t s) = nullptr;
-    void *span_ctx = nullptr;
-    LlrIn llr;                      /* the caller's channel values: pointer, element type, unit (llr_input.hpp) */
-    int64_t frames;
-    uint8_t *out_dev;
-    int64_t out_bytes;
-    int32_t *iters_dev;
-    int32_t K, max_iter, tap_iter, early_term, pack_mode;
-    uint64_t *hard, *failw, *done;
-    int32_t *iters;
-    const int32_t *row_ptr, *edge_col;
-    int32_t *summary;
-    /* CRC-aided early termination (ldpc_decoder_config::crc_kind): column weights and covered bits, 0 = off */
-    const uint32_t *crc_w = nullptr;
-    int32_t crc_bits = 0;
+struct LayeredRun : StreamRun {     /* engines.hpp */
     /* soft output (ldpc_decode_soft_device): the caller's [frames][N] buffer, nullptr = a plain call; extrinsic: P - y */
     float *soft = nullptr;
     int32_t soft_extrinsic = 0;

@@ -1,8 +1,13 @@
 /*
  * ldpc_hip.hip -- the handle's life behind the C ABI (include/ldpc_hip.h): the calling thread's error message, the
- * graph, config validation, ldpc_decoder_create with its choice of engine and the tail-compaction child, destruction,
- * decoders over several devices (ldpc_decoder_create_multi: one host thread per device range) and ldpc_decode_device,
- * which hands the call to the engine chosen at creation.
+ * graph, ldpc_decoder_create, destruction, decoders over several devices (ldpc_decoder_create_multi: one host thread per
+ * device range) and ldpc_decode_device, which hands the call to the engine chosen at creation.
+ *
+ * ldpc_decoder_create is a sequence: config_in, config_check, the device, the arrays every engine shares, then the walk
+ * over engine_candidates with one plan per engine tried (make_plan) and, for the streaming flooding engine, the
+ * hand-over child (create_handover_child).  What a configuration means -- accepted struct sizes, the table of
+ * algorithms, every refusal in front of the device check, frames per lane, which engines may run it and in what order --
+ * is decided in decoder_config_host.hpp, which needs no HIP; this file allocates what was decided there.
  *
  * Not here: the handle itself (decoder.hpp), the engines (engines.hpp: engine_flood / engine_ldsp / engine_fused /
  * engine_layered, each a translation unit that instantiates its kernels; this one launches none), the host-buffer path
@@ -26,7 +31,7 @@
 
 #include "decoder.hpp"
 #include "graph.hpp"
-#include "crc_term_host.hpp"
+#include "decoder_config_host.hpp"
 
 using ldpc::set_error;
 
@@ -34,24 +39,11 @@ namespace {
 
 thread_local std::string g_err;
 
-int pick_frames_per_lane(const ldpc_decoder_config &cfg, int32_t max_row_deg, int32_t max_col_deg)
-{
-    if (cfg.frames_per_lane) return cfg.frames_per_lane;
-    /* Wide tiles (4 values = 16 B fp32 / 8 B fp16 per lane) once there are enough frames to
-     * fill them and the register arrays of the unrolled kernels stay moderate.  Flooding check
-     * kernels run in narrow waves, so only the column degree counts there; the layered kernel
-     * holds a whole row (P and R) per lane. */
-    int deg = (cfg.algo == LDPC_ALGO_LAYERED || cfg.algo == LDPC_ALGO_LAYERED_BP) ? max_row_deg : max_col_deg;
-    /* fixed-point layered: a row's R is a dword and its P a dwordx2 per lane at 4 frames per lane, whatever the row degree
-     * (the unrolled kernels hold the row in registers up to degree 24, the run-time kernel holds none of it) */
-    if (cfg.algo == LDPC_ALGO_LAYERED_FX || cfg.algo == LDPC_ALGO_LAYERED_BP_FX) return cfg.max_batch >= 256 ? 4 : 1;
-    if (cfg.algo == LDPC_ALGO_MS || cfg.algo == LDPC_ALGO_BP) deg = (deg + 1) / 2;   /* min-sum variable nodes (BP's too) need half the registers */
-    /* one-byte messages (fp8, fixed point): 4 values are one dword per lane, the least a lane should move -- from one full tile on */
-    if ((cfg.msg_dtype == LDPC_MSG_F8 || cfg.msg_dtype == LDPC_MSG_I8) && cfg.max_batch >= 256 && deg <= 8) return 4;
-    if (cfg.max_batch >= 1024 && deg <= 8) return 4;
-    if (cfg.max_batch >= 256 && deg <= ldpc::kMaxUnrolledDegree) return 2;
-    return 1;
-}
+/* the limits config_check quotes are the kernels' own */
+static_assert(ldpc::kCfgUnrolledDegree == ldpc::kMaxUnrolledDegree && ldpc::kCfgUnrolledLayerDegree == ldpc::kMaxUnrolledLayerDegree &&
+              ldpc::kCfgBitflipDegree == ldpc::kBitflipMaxDegree && ldpc::kCfgBpFracBits == ldpc::kBpFxMaxFracBits,
+              "decoder_config_host.hpp quotes a limit its kernel header has changed");
+static_assert(sizeof(ldpc_decoder_config::bf_threshold) / sizeof(int32_t) == ldpc::kBitflipThresholds, "bf_threshold[] and kBitflipThresholds");
 
 }  // namespace
 
@@ -189,12 +181,8 @@ int ldpc_graph_info(const ldpc_graph *g, int32_t *M, int32_t *N, int64_t *E, int
 int ldpc_decoder_config_init_sized(ldpc_decoder_config *cfg, uint32_t struct_size)
 {
     if (!cfg) return set_error(LDPC_ERR_ARG, "config is NULL");
-    if (struct_size != sizeof(ldpc_decoder_config) && struct_size != offsetof(ldpc_decoder_config, bf_threshold) &&
-        struct_size != offsetof(ldpc_decoder_config, msg_bits) &&
-        struct_size != offsetof(ldpc_decoder_config, crc_kind) && struct_size != offsetof(ldpc_decoder_config, ms_scale))
-        return set_error(LDPC_ERR_ARG, "config struct_size %u is none of %zu, %zu, %zu, %zu, %zu (ABI mismatch)", struct_size,
-                    sizeof(ldpc_decoder_config), offsetof(ldpc_decoder_config, bf_threshold), offsetof(ldpc_decoder_config, msg_bits),
-                    offsetof(ldpc_decoder_config, crc_kind), offsetof(ldpc_decoder_config, ms_scale));
+    char msg[512];
+    if (int rc = ldpc::config_size_check(struct_size, msg, sizeof msg)) return set_error(rc, "%s", msg);
     /* every field that has a non-zero default lies in front of ms_scale */
     memset(cfg, 0, struct_size);
     cfg->struct_size = struct_size;
@@ -216,23 +204,155 @@ void ldpc_decoder_config_init(ldpc_decoder_config *cfg)
     (void)ldpc_decoder_config_init_sized(cfg, (uint32_t)offsetof(ldpc_decoder_config, crc_kind));
 }
 
-/* The caller's config as the current struct: callers built against the header before ms_scale / ms_offset, before
- * crc_kind / crc_bits, before msg_bits or before bf_threshold pass a shorter struct, of which only struct_size bytes are
- * read; the fields it lacks are 0 (off; msg_bits: 8; bf_threshold: the default schedule). */
+/* ---- ldpc_decoder_create: the pieces ---- */
+
+using ldpc::Engine;
+using ldpc::Family;
+
+/* the caller's config as the current struct (decoder_config_host.hpp), the refusal as the thread's message */
 static int config_in(const ldpc_decoder_config *cfg, ldpc_decoder_config *full)
 {
-    constexpr size_t kSizeBeforeMsCorr = offsetof(ldpc_decoder_config, ms_scale);
-    constexpr size_t kSizeBeforeCrc = offsetof(ldpc_decoder_config, crc_kind);
-    constexpr size_t kSizeBeforeMsgBits = offsetof(ldpc_decoder_config, msg_bits);
-    constexpr size_t kSizeBeforeBitflip = offsetof(ldpc_decoder_config, bf_threshold);
-    if (cfg->struct_size != sizeof(ldpc_decoder_config) && cfg->struct_size != kSizeBeforeBitflip && cfg->struct_size != kSizeBeforeMsgBits &&
-        cfg->struct_size != kSizeBeforeCrc && cfg->struct_size != kSizeBeforeMsCorr)
-        return set_error(LDPC_ERR_ARG, "config struct_size %u is none of %zu, %zu, %zu, %zu, %zu (ABI mismatch)", cfg->struct_size,
-                    sizeof(ldpc_decoder_config), kSizeBeforeBitflip, kSizeBeforeMsgBits, kSizeBeforeCrc, kSizeBeforeMsCorr);
-    memset(full, 0, sizeof *full);
-    memcpy(full, cfg, cfg->struct_size);
-    full->struct_size = sizeof *full;
+    char msg[512];
+    const int rc = ldpc::config_in(cfg, full, msg, sizeof msg);
+    return rc ? set_error(rc, "%s", msg) : LDPC_OK;
+}
+
+static ldpc::GraphFacts graph_facts(const ldpc_graph *g)
+{
+    ldpc::GraphFacts f;
+    f.M = g->M; f.N = g->N; f.E = g->E;
+    f.max_row_deg = g->max_row_deg; f.max_col_deg = g->max_col_deg;
+    f.rows_one_weight = true;
+    for (int32_t m = 1; m < g->M; ++m)
+        if (g->row_ptr[m + 1] - g->row_ptr[m] != g->row_ptr[1] - g->row_ptr[0]) f.rows_one_weight = false;
+    return f;
+}
+
+/* Tail compaction: with host polling on, the last running frames of a batch of several tiles are finished by a small
+ * child decoder (cfg.tune_compact = -1: off, n: threshold), itself made by ldpc_decoder_create one level down. */
+static int create_handover_child(ldpc_decoder *d, const ldpc_graph *g)
+{
+    const ldpc_decoder_config *cfg = &d->cfg;
+    /* the child takes over once at most a quarter of the batch still runs: 1024 frames for the 4096-frame
+     * batches of the benchmark configurations (rate 9/10, fp16: 681 frames still run after round 5 of 8 and
+     * sit in all 16 tiles; a 512-frame child had to wait for round 6), 512 otherwise */
+    if (t_child_depth == 0) d->flood.child_capacity = cfg->max_batch >= 4096 ? 2 * ldpc::kCompactCapacity : ldpc::kCompactCapacity;
+    else d->flood.child_capacity = cfg->max_batch > ldpc::kCompactCapacity ? ldpc::kCompactCapacity : ldpc::kLastCapacity;
+    d->flood.compact_threshold = d->flood.child_capacity;
+    if (d->tune.compact) d->flood.compact_threshold = d->tune.compact < 0 ? 0 : std::min(d->flood.child_capacity, d->tune.compact);
+    /* the 1024-frame child has a 512-frame child of its own (rate 9/10: of the 681 frames handed over after round 5
+     * only 41 still run after round 6, spread over the child's three tiles of 256), and that one a single tile of 64
+     * frames (sum-product at 5 dB: a handful of frames in 4096 run all 50 rounds, one in each of its tiles) */
+    const bool may_have_child = t_child_depth == 0 || cfg->max_batch > ldpc::kLastCapacity;
+    if (!(cfg->early_term && cfg->poll_interval > 0 && d->T > 1 && d->flood.compact_threshold > 0 && may_have_child)) return LDPC_OK;
+    ldpc_decoder_config cc = *cfg;
+    cc.max_batch = d->flood.child_capacity;
+    /* tiles of 64 frames for the 512-frame child (the last few stragglers of a batch); tiles of 256 for the
+     * 1024-frame child, which takes over hundreds of frames: dense tiles, 8- / 16-byte accesses */
+    cc.frames_per_lane = (d->flood.child_capacity > ldpc::kCompactCapacity && d->V == 4) ? 4 : 1;
+    cc.layer_rows = 0;                 /* streaming kernels, same arithmetic */
+    cc.tune_compact = d->flood.child_capacity > ldpc::kLastCapacity ? 0 : -1;     /* all but the last hand over once more */
+    ++t_child_depth;
+    ldpc_decoder *child = nullptr;
+    const int rc = ldpc_decoder_create(g, &cc, &child);
+    --t_child_depth;
+    if (rc) return rc;
+    d->flood.child.reset(child);
+    d->flood.child->flood.is_child = true;
+    LDPC_HIP_TRY(hipSetDevice(cfg->device));
+    LDPC_HIP_TRY(d->flood.cmap.alloc((size_t)d->flood.child_capacity));
+    LDPC_HIP_TRY(d->flood.cinv.alloc((size_t)d->T * d->F));
+    LDPC_HIP_TRY(d->flood.cmoved.alloc((size_t)d->T * d->V));
     return LDPC_OK;
+}
+
+/* the saturation limits of the fixed-point layered algorithms: q-bit messages, post_bits-bit posteriors */
+static float fx_msg_limit(const ldpc_decoder_config &c) { return (float)((1 << ((c.msg_bits ? c.msg_bits : 8) - 1)) - 1); }
+static float fx_post_limit(const ldpc_decoder_config &c) { return (float)((1 << ((c.post_bits ? c.post_bits : 16) - 1)) - 1); }
+
+/* The plan of one candidate engine (decoder_config_host.hpp: engine_candidates).  *taken: the candidate's guard holds and
+ * the handle runs this engine; a plan that is not taken is dropped, the next candidate gets its turn. */
+static int make_plan(ldpc_decoder *d, const ldpc_graph *g, const ldpc::Candidate &c, size_t TF, bool *taken)
+{
+    const ldpc_decoder_config *cfg = &d->cfg;
+    const ldpc::AlgoInfo &a = *ldpc::algo_info(cfg->algo);
+    *taken = true;
+    switch (c.engine) {
+    case Engine::Bitflip: {
+        /* x lives in `hard`; received bits, syndrome words and votes in the plan.  No hand-over child and no
+         * device-side tail: a round is too cheap to be worth moving frames for */
+        const hipError_t e = ldpc::bitflip_plan_create(&d->bitflip, g->M, g->N, g->E, g->rows, g->col_edge, d->T, cfg->bf_threshold);
+        if (e != hipSuccess) return set_error(LDPC_ERR_HIP, "bit-flipping plan allocation failed: %s", hipGetErrorString(e));
+        return LDPC_OK;
+    }
+    case Engine::Ldsp: {
+        /* flood_ldsp_kernel / layered_ldsp_kernel (posteriors in LDS, 16-byte check records in cache), the CORR forms with
+         * ms_scale / ms_offset.  Layered: 1.2-2.9x the LDS-resident kernel on short codes (exact-width rows, bit-level sign
+         * algebra: 800 against 280 G edge updates/s).  Flooding min-sum: 2-2.9x the LDS-resident and the streaming kernels
+         * on the 802.16e codes at any batch size, 2.4 / 2.0 / 1.7 / 1.2x the streaming kernels on BG1-profile codes at
+         * Z = 64 / 128 / 256 / 384. */
+        d->ldsp.corr = d->ms_corr;
+        d->ldsp.mc = ldpc::MsCorr{d->ms_scale, d->ms_offset};
+        const int flood = a.family == Family::Reference ? 2 : a.family == Family::Flood ? 1 : 0;
+        LDPC_HIP_TRY(ldpc::engine_ldsp_plan_create(&d->ldsp, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows, cfg->K,
+                                                   cfg->max_batch, cfg->device, d->tune, flood));
+        *taken = d->ldsp.eligible && (!c.lds_limit || d->ldsp.lds_bytes <= (size_t)ldpc::kCfgLdsLimit);
+        if (!*taken) d->ldsp = ldpc::LdspPlan();
+        return LDPC_OK;
+    }
+    case Engine::LdspFx:
+        /* layered_ldsp_fx_kernel (int16 posteriors in LDS, 8-byte check records in cache) where the code fits it:
+         * quasi-cyclic at layer_rows, rows of at most 24 entries, posteriors within the LDS limit */
+        d->ldsp.mc = ldpc::MsCorr{d->ms_scale, d->ms_offset};
+        d->ldsp.fx_L = (int32_t)fx_msg_limit(*cfg);
+        d->ldsp.fx_LP = (int32_t)fx_post_limit(*cfg);
+        LDPC_HIP_TRY(ldpc::engine_ldsp_fx_plan_create(&d->ldsp, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows, cfg->K,
+                                                      cfg->max_batch, cfg->device, d->tune));
+        *taken = d->ldsp.eligible;
+        if (!*taken) d->ldsp = ldpc::LdspPlan();
+        return LDPC_OK;
+    case Engine::Fused:
+        /* fused_flood_kernel / fused_sp_kernel / fused_layered_kernel: the same arithmetic in one LDS-resident launch */
+        LDPC_HIP_TRY(ldpc::fused_plan_create(&d->fused, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows));
+        *taken = d->fused.eligible && (!c.needs_sp || d->fused.eligible_sp);
+        return LDPC_OK;
+    case Engine::Layered: {
+        /* the streaming plan and its P / R arrays in HBM: made only when no one-launch kernel was taken */
+        ldpc::LayeredPlan &pl = d->layered;
+        pl.rule = a.fixed ? (a.box_plus ? ldpc::kLayerBpFx : ldpc::kLayerFx)
+                  : a.box_plus ? ldpc::kLayerBp
+                  : cfg->algo == LDPC_ALGO_LAYERED_HOST ? ldpc::kLayerHost : d->ms_corr ? ldpc::kLayerCorr : ldpc::kLayerFused;
+        if (cfg->algo != LDPC_ALGO_LAYERED) pl.llr_scale = cfg->llr_scale;      /* LDPC_ALGO_LAYERED reads y as it is */
+        pl.ms_scale = d->ms_scale;      /* plain min-sum is the corrected row with scale 1, offset 0: the identity on [0, L] */
+        pl.ms_offset = d->ms_offset;
+        if (a.fixed) { pl.L = fx_msg_limit(*cfg); pl.LP = fx_post_limit(*cfg); }
+        if (a.fixed && a.box_plus) {    /* the kernels index the table with |a| + |b| <= 254 and never clamp: zeros behind its last entry */
+            int32_t t[ldpc::kBpFxTable];
+            const int n = ldpc::bp_fx_table_build(cfg->bp_frac_bits, t, ldpc::kBpFxTable);
+            std::vector<uint8_t> bytes((size_t)ldpc::kBpFxTable, 0);
+            for (int i = 0; i < n; ++i) bytes[(size_t)i] = (uint8_t)t[i];
+            LDPC_HIP_TRY(pl.bp_table.upload(bytes));
+        }
+        /* a detected QC structure already implies that rows of a layer share no column; here nothing was detected */
+        const int rc = ldpc::layered_plan_create(&pl, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows, d->T, d->V);
+        if (rc == -1) return set_error(LDPC_ERR_ARG, "layer_rows=%d must divide M=%d and rows of a layer "
+                                  "must not share a column", cfg->layer_rows, g->M);
+        if (rc) return set_error(LDPC_ERR_HIP, "layered plan allocation failed: %s", hipGetErrorString(hipGetLastError()));
+        return LDPC_OK;
+    }
+    case Engine::Flood: {
+        /* work lists, kernel tables, launch plan; the column-fused check kernel's form and the arrays' placement are
+         * measured there unless the caller says which (engine_flood.hip) */
+        if (int rc = ldpc::engine_flood_setup(d, g, TF, t_child_depth == 0)) return rc;
+        if (d->flood.tail_enabled) {
+            LDPC_HIP_TRY(d->flood.tail_state.alloc(4));
+            LDPC_HIP_TRY(d->flood.tail_map.alloc((size_t)d->flood.TO * d->F));
+            LDPC_HIP_TRY(d->flood.running.alloc((size_t)cfg->max_iter + 2));
+        }
+        return create_handover_child(d, g);
+    }
+    }
+    return set_error(LDPC_ERR_STATE, "unknown engine");
 }
 
 int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, ldpc_decoder **out)
@@ -243,134 +363,12 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     ldpc_decoder_config cfg_full;
     if (int rc = config_in(cfg_in, &cfg_full)) return rc;
     const ldpc_decoder_config *cfg = &cfg_full;
-    if (cfg->K <= 0 || cfg->K > g->N) return set_error(LDPC_ERR_ARG, "K=%d out of range", cfg->K);
-    if (cfg->max_batch <= 0) return set_error(LDPC_ERR_ARG, "max_batch must be positive");
-    if (cfg->max_iter <= 0 || cfg->max_iter > 100000) return set_error(LDPC_ERR_ARG, "max_iter out of range");
-    if (cfg->algo != LDPC_ALGO_SP && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED &&
-        cfg->algo != LDPC_ALGO_MS_FUSED && cfg->algo != LDPC_ALGO_LAYERED_HOST && cfg->algo != LDPC_ALGO_BP &&
-        cfg->algo != LDPC_ALGO_LAYERED_BP && cfg->algo != LDPC_ALGO_LAYERED_FX && cfg->algo != LDPC_ALGO_LAYERED_BP_FX &&
-        cfg->algo != LDPC_ALGO_BITFLIP)
-        return set_error(LDPC_ERR_ARG, "unknown algo %d", cfg->algo);
-    const bool bitflip = cfg->algo == LDPC_ALGO_BITFLIP;
-    const bool bpfx = cfg->algo == LDPC_ALGO_LAYERED_BP_FX;     /* LAYERED_FX's configuration, storage and schedule, another row */
-    const bool fx = cfg->algo == LDPC_ALGO_LAYERED_FX || bpfx;
-    const char *const fx_name = bpfx ? "LDPC_ALGO_LAYERED_BP_FX" : "LDPC_ALGO_LAYERED_FX";
-    /* comparisons written so that NaN fails them */
-    if (!(cfg->ms_scale >= 0.0f && cfg->ms_scale <= 1.0f))
-        return set_error(LDPC_ERR_ARG, "ms_scale must be 0 (off) or in (0, 1]");
-    if (!(cfg->ms_offset >= 0.0f && cfg->ms_offset < 1000.0f))
-        return set_error(LDPC_ERR_ARG, "ms_offset must be 0 (off) or in (0, 1000)");
-    const bool ms_corr = cfg->ms_scale != 0.0f || cfg->ms_offset != 0.0f;
-    if (ms_corr && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_LAYERED && !(fx && !bpfx))
-        return set_error(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset apply to LDPC_ALGO_MS and LDPC_ALGO_LAYERED only "
-                    "(SP, BP, LAYERED_BP, LAYERED_BP_FX and BITFLIP have no minimum to correct; MS_FUSED and LAYERED_HOST reproduce reference kernels)");
-    const bool bp_row = cfg->algo == LDPC_ALGO_BP || cfg->algo == LDPC_ALGO_LAYERED_BP;      /* box-plus check node */
-    if (bp_row && !(cfg->llr_scale > 0.0f && cfg->llr_scale <= 3.402823466e38f))
-        return set_error(LDPC_ERR_ARG, "%s: llr_scale must be positive and finite (chan = llr_scale * y is the LLR)",
-                    cfg->algo == LDPC_ALGO_BP ? "LDPC_ALGO_BP" : "LDPC_ALGO_LAYERED_BP");
-    if (cfg->algo == LDPC_ALGO_LAYERED_BP && (cfg->layer_rows <= 0 || g->M % cfg->layer_rows))
-        return set_error(LDPC_ERR_ARG, "LDPC_ALGO_LAYERED_BP: layer_rows=%d must be positive and divide M=%d", cfg->layer_rows, g->M);
-    if (cfg->algo == LDPC_ALGO_LAYERED_HOST) {
-        for (int32_t m = 1; m < g->M; ++m)
-            if (g->row_ptr[m + 1] - g->row_ptr[m] != g->row_ptr[1] - g->row_ptr[0])
-                return set_error(LDPC_ERR_UNSUPPORTED, "LAYERED_HOST follows the reference's host-layered path, which sizes its "
-                            "layers correctly only when every row of H has the same weight (MyLdpc.cpp:907,958)");
-        if (g->max_row_deg > ldpc::kMaxUnrolledLayerDegree)
-            return set_error(LDPC_ERR_UNSUPPORTED, "LAYERED_HOST: row weight %d > %d", g->max_row_deg, ldpc::kMaxUnrolledLayerDegree);
-    }
-    if (cfg->pack_mode != LDPC_PACK_BYTES && cfg->pack_mode != LDPC_PACK_BITS)
-        return set_error(LDPC_ERR_ARG, "unknown pack_mode %d", cfg->pack_mode);
-    if (cfg->frames_per_lane != 0 && cfg->frames_per_lane != 1 && cfg->frames_per_lane != 2 &&
-        cfg->frames_per_lane != 4)
-        return set_error(LDPC_ERR_ARG, "frames_per_lane must be 0, 1, 2 or 4");
-    if (cfg->msg_dtype != LDPC_MSG_F32 && cfg->msg_dtype != LDPC_MSG_F16 && cfg->msg_dtype != LDPC_MSG_F8 && cfg->msg_dtype != LDPC_MSG_I8)
-        return set_error(LDPC_ERR_ARG, "unknown msg_dtype %d", cfg->msg_dtype);
-    if (cfg->msg_reserved3)
-        return set_error(LDPC_ERR_ARG, "msg_reserved must be 0");
-    for (int j = 0; j < ldpc::kBitflipThresholds; ++j) {
-        if (cfg->bf_threshold[j] != 0 && !bitflip)
-            return set_error(LDPC_ERR_ARG, "bf_threshold[%d]=%d belongs to LDPC_ALGO_BITFLIP (algo is %d)", j, cfg->bf_threshold[j], cfg->algo);
-        if (cfg->bf_threshold[j] < 0 || cfg->bf_threshold[j] > ldpc::kBitflipMaxDegree)
-            return set_error(LDPC_ERR_ARG, "bf_threshold[%d]=%d must be in [0, %d]", j, cfg->bf_threshold[j], ldpc::kBitflipMaxDegree);
-    }
-    if (bitflip && cfg->msg_dtype != LDPC_MSG_F32)
-        return set_error(LDPC_ERR_UNSUPPORTED, "LDPC_ALGO_BITFLIP has no messages: msg_dtype must be LDPC_MSG_F32, not %d", cfg->msg_dtype);
-    if (bitflip && g->max_col_deg > ldpc::kBitflipMaxDegree)
-        return set_error(LDPC_ERR_UNSUPPORTED, "LDPC_ALGO_BITFLIP counts a column's votes in six bits: column degree %d > %d", g->max_col_deg,
-                    ldpc::kBitflipMaxDegree);
-    if (cfg->bp_frac_bits != 0 && !bpfx)
-        return set_error(LDPC_ERR_ARG, "bp_frac_bits=%d belongs to LDPC_ALGO_LAYERED_BP_FX (algo is %d)", cfg->bp_frac_bits, cfg->algo);
-    if (bpfx && (cfg->bp_frac_bits < 0 || cfg->bp_frac_bits > ldpc::kBpFxMaxFracBits))
-        return set_error(LDPC_ERR_ARG, "bp_frac_bits=%d must be in [0, %d]", cfg->bp_frac_bits, ldpc::kBpFxMaxFracBits);
-    if (cfg->post_bits != 0 && !fx)
-        return set_error(LDPC_ERR_ARG, "post_bits=%d belongs to LDPC_ALGO_LAYERED_FX and LDPC_ALGO_LAYERED_BP_FX (algo is %d)", cfg->post_bits, cfg->algo);
-    if (fx && cfg->msg_dtype != LDPC_MSG_I8)
-        return set_error(LDPC_ERR_ARG, "%s is defined on fixed-point messages: msg_dtype must be LDPC_MSG_I8, not %d", fx_name, cfg->msg_dtype);
-    if (cfg->msg_bits != 0 && cfg->msg_dtype != LDPC_MSG_I8)
-        return set_error(LDPC_ERR_ARG, "msg_bits=%d belongs to LDPC_MSG_I8 (msg_dtype is %d)", cfg->msg_bits, cfg->msg_dtype);
-    if (cfg->msg_bits != 0 && cfg->msg_bits != 4 && cfg->msg_bits != 5 && cfg->msg_bits != 6 && cfg->msg_bits != 8)
-        return set_error(LDPC_ERR_ARG, "msg_bits must be 0 (8), 4, 5, 6 or 8, not %d", cfg->msg_bits);
-    if (cfg->msg_dtype == LDPC_MSG_I8 && cfg->algo != LDPC_ALGO_MS && !fx)
-        return set_error(LDPC_ERR_UNSUPPORTED, "fixed-point messages (LDPC_MSG_I8) are built for flooding min-sum and, as an algorithm of "
-                    "their own, LDPC_ALGO_LAYERED_FX and LDPC_ALGO_LAYERED_BP_FX (SP and BP have no integer datapath here; LDPC_ALGO_LAYERED, LAYERED_BP and the "
-                    "reference-reproducing decoders are fp32)");
-    if (fx) {
-        const int q = cfg->msg_bits ? cfg->msg_bits : 8;
-        if (cfg->post_bits != 0 && (cfg->post_bits < q || cfg->post_bits > 16))
-            return set_error(LDPC_ERR_ARG, "post_bits=%d must be 0 (16) or in [msg_bits=%d, 16]", cfg->post_bits, q);
-        if (cfg->layer_rows <= 0 || g->M % cfg->layer_rows)
-            return set_error(LDPC_ERR_ARG, "%s: layer_rows=%d must be positive and divide M=%d", fx_name, cfg->layer_rows, g->M);
-    }
-    /* written so that NaN fails it */
-    if (cfg->msg_dtype == LDPC_MSG_I8 && !(cfg->llr_scale > 0.0f && cfg->llr_scale <= 3.402823466e38f))
-        return set_error(LDPC_ERR_ARG, "LDPC_MSG_I8: llr_scale must be positive and finite (the LSBs per unit of channel value)");
-    if (cfg->msg_dtype == LDPC_MSG_F8 && cfg->algo != LDPC_ALGO_MS)
-        return set_error(LDPC_ERR_UNSUPPORTED, "fp8 messages are built for flooding min-sum only "
-                    "(the probability-domain SP needs fp32 range; BP is fp32 / fp16; the layered decoders, LAYERED_BP among them, and the "
-                    "reference-reproducing ones are fp32)");
-    if (cfg->msg_dtype == LDPC_MSG_F16 && cfg->algo != LDPC_ALGO_MS && cfg->algo != LDPC_ALGO_BP)
-        return set_error(LDPC_ERR_UNSUPPORTED, "fp16 messages are built for flooding min-sum and BP only "
-                    "(the probability-domain SP needs fp32 range; the layered engine, LAYERED and LAYERED_BP, is fp32)");
-    if (!ldpc::tune_valid(*cfg)) return set_error(LDPC_ERR_ARG, "tuning / streams config fields out of range");
-    if (bitflip) {
-        const ldpc::Tune t = ldpc::tune_from_config(*cfg);
-        if (ldpc::tune_forced_on(t.fused) || ldpc::tune_forced_on(t.ldsp))
-            return set_error(LDPC_ERR_UNSUPPORTED, "LDPC_ALGO_BITFLIP runs the bit-flipping engine: the one-launch and the record kernels "
-                        "(LDPC_TUNE_FUSED / LDPC_TUNE_LDSP forced on) are soft decoders");
-    }
-    if (bp_row) {
-        const ldpc::Tune t = ldpc::tune_from_config(*cfg);
-        if (ldpc::tune_forced_on(t.fused) || ldpc::tune_forced_on(t.ldsp))
-            return set_error(LDPC_ERR_UNSUPPORTED, "LDPC_ALGO_BP / LDPC_ALGO_LAYERED_BP: the LDS-resident one-launch kernels and the record kernels (LDPC_TUNE_FUSED / "
-                        "LDPC_TUNE_LDSP forced on) carry no box-plus check node; the streaming kernels do");
-    }
-    if (cfg->msg_dtype == LDPC_MSG_F8 || cfg->msg_dtype == LDPC_MSG_I8) {
-        const ldpc::Tune t = ldpc::tune_from_config(*cfg);
-        if (ldpc::tune_forced_on(t.fused) || ldpc::tune_forced_on(t.ldsp))
-            return set_error(LDPC_ERR_UNSUPPORTED, "%s messages: the LDS-resident one-launch kernels and the record kernels (LDPC_TUNE_FUSED / "
-                        "LDPC_TUNE_LDSP forced on) are fp32; the streaming kernels carry the %s rule",
-                        cfg->msg_dtype == LDPC_MSG_F8 ? "fp8" : "fixed-point", cfg->msg_dtype == LDPC_MSG_F8 ? "fp8" : "fixed-point");
-    }
-    /* CRC-aided early termination: the streaming kernels carry the rule (crc_term_kernel), nothing else does */
-    const bool crc_term = cfg->crc_kind != 0;
+    const ldpc::GraphFacts facts = graph_facts(g);
     {
-        char msg[256];
-        if (ldpc::crc_term_check(cfg->crc_kind, cfg->crc_bits, cfg->K, cfg->early_term, msg, sizeof msg)) return set_error(LDPC_ERR_ARG, "%s", msg);
-        if (crc_term && (cfg->algo == LDPC_ALGO_MS_FUSED || cfg->algo == LDPC_ALGO_LAYERED_HOST))
-            return set_error(LDPC_ERR_UNSUPPORTED, "crc_kind: LDPC_ALGO_MS_FUSED and LDPC_ALGO_LAYERED_HOST reproduce reference kernels, which "
-                        "stop on the syndrome alone; LDPC_ALGO_SP, LDPC_ALGO_MS, LDPC_ALGO_BP, LDPC_ALGO_LAYERED and LDPC_ALGO_LAYERED_BP carry the CRC rule");
-        const ldpc::Tune t = ldpc::tune_from_config(*cfg);
-        if (crc_term && (ldpc::tune_forced_on(t.fused) || ldpc::tune_forced_on(t.ldsp)))
-            return set_error(LDPC_ERR_UNSUPPORTED, "crc_kind: the LDS-resident one-launch kernels and the record kernels (LDPC_TUNE_FUSED / "
-                        "LDPC_TUNE_LDSP forced on) do not carry the CRC rule; the streaming kernels do");
+        char msg[512];
+        if (int rc = ldpc::config_check(*cfg, facts, msg, sizeof msg)) return set_error(rc, "%s", msg);
     }
-    const bool fx_record = ldpc::tune_from_config(*cfg).fx_record != 0;      /* tune_valid: a fixed-point layered algorithm */
-    if (fx_record && bpfx)
-        return set_error(LDPC_ERR_UNSUPPORTED, "LDPC_TUNE_FX_RECORD: a box-plus row sends D independent messages and the record "
-                    "kernel's two-minimum record cannot hold them; LDPC_ALGO_LAYERED_BP_FX runs the streaming layered engine");
-    if (fx_record && crc_term)
-        return set_error(LDPC_ERR_UNSUPPORTED, "crc_kind: the fixed-point record kernel (LDPC_TUNE_FX_RECORD) does not carry the CRC "
-                    "rule; the streaming kernels do");
+    const ldpc::AlgoInfo &a = *ldpc::algo_info(cfg->algo);
 
     int ndev = 0;
     LDPC_HIP_TRY(hipGetDeviceCount(&ndev));
@@ -378,11 +376,12 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
         return set_error(LDPC_ERR_HIP, "device %d not present (%d HIP devices)", cfg->device, ndev);
     LDPC_HIP_TRY(hipSetDevice(cfg->device));
 
+    /* the arrays and choices every engine shares */
     ldpc_decoder *d = new (std::nothrow) ldpc_decoder;
     if (!d) return set_error(LDPC_ERR_NOMEM, "out of memory");
     std::unique_ptr<ldpc_decoder> guard(d);
     d->cfg = *cfg;
-    d->ms_corr = ms_corr;
+    d->ms_corr = ldpc::has_ms_corr(*cfg);
     d->ms_scale = cfg->ms_scale != 0.0f ? cfg->ms_scale : 1.0f;
     d->ms_offset = cfg->ms_offset;
     d->M = g->M; d->N = g->N; d->E = g->E;
@@ -393,13 +392,13 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
      * where every row has one (degree <= kMaxUnrolledDegree; above, the bucket launches, V values per lane), the
      * column-fused kernel wide unless the creation-time measurement prefers the half form.  The narrow forms move one
      * byte per lane; the tuning fields still select them, results never depend on the choice. */
-    const bool f8 = cfg->msg_dtype == LDPC_MSG_F8 || cfg->msg_dtype == LDPC_MSG_I8;
+    const bool f8 = ldpc::one_byte_messages(*cfg);
     d->flood.check_wide = ldpc::tune_pick(tune.check_wide, f8 && g->max_row_deg <= ldpc::kMaxUnrolledDegree);
     d->flood.link_form = ldpc::tune_pick(tune.link_half, false) ? 2 : (ldpc::tune_pick(tune.link_narrow, !f8 || ldpc::tune_forced_on(tune.link_deep)) ? 1 : 0);   /* deep is a narrow form */
     d->flood.link_deep = ldpc::tune_pick(tune.link_deep, false);
     if (tune.link_rows) d->flood.link_rpw = tune.link_rows < 0 ? 0 : tune.link_rows;
     LDPC_HIP_TRY(hipDeviceGetAttribute(&d->flood.cus, hipDeviceAttributeMultiprocessorCount, cfg->device));
-    d->V = bitflip ? 1 : pick_frames_per_lane(*cfg, g->max_row_deg, g->max_col_deg);       /* bit flipping: a word is 64 frames */
+    d->V = a.family == Family::Bitflip ? 1 : ldpc::pick_frames_per_lane(*cfg, g->max_row_deg, g->max_col_deg);       /* bit flipping: a word is 64 frames */
     d->F = 64 * d->V;
     d->T = (cfg->max_batch + d->F - 1) / d->F;
     /* a single tile is latency-bound (one wave walks its rows one after the other): shorter row
@@ -421,7 +420,7 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
      * LDPC_TUNE_OFF(LDPC_TUNE_DEVICE_TAIL) switches it off. */
     d->flood.TO = (ldpc::kCompactCapacity + d->F - 1) / d->F;
     d->flood.tail_enabled = cfg->early_term && cfg->poll_interval == 0 && ldpc::tune_pick(tune.device_tail, true) &&
-                      (cfg->algo == LDPC_ALGO_SP || cfg->algo == LDPC_ALGO_MS || cfg->algo == LDPC_ALGO_BP) && d->T >= 4 * d->flood.TO && t_child_depth == 0;
+                      a.handover && d->T >= 4 * d->flood.TO && t_child_depth == 0;
     if (!d->flood.tail_enabled) d->flood.TO = 0;
     d->flood.TA = d->T + d->flood.TO;
     const size_t TF = (size_t)d->flood.TA * d->F;
@@ -431,188 +430,23 @@ int ldpc_decoder_create(const ldpc_graph *g, const ldpc_decoder_config *cfg_in, 
     LDPC_HIP_TRY(d->iters.alloc(TF));
     LDPC_HIP_TRY(d->active.alloc(1));
     LDPC_HIP_TRY(d->summary.alloc(4));
-    if (crc_term) {
+    if (cfg->crc_kind) {
         std::vector<uint32_t> w((size_t)cfg->crc_bits);
         ldpc::crc_term_weights(cfg->crc_kind, cfg->crc_bits, w.data());
         LDPC_HIP_TRY(d->crc_w.upload(w));
     }
 
-    if (bitflip) {
-        /* the bit-flipping engine: x lives in `hard`; received bits, syndrome words and votes in the plan.  No hand-over
-         * child and no device-side tail: a round is too cheap to be worth moving frames for */
-        const hipError_t e = ldpc::bitflip_plan_create(&d->bitflip, g->M, g->N, g->E, g->rows, g->col_edge, d->T, cfg->bf_threshold);
-        if (e != hipSuccess) return set_error(LDPC_ERR_HIP, "bit-flipping plan allocation failed: %s", hipGetErrorString(e));
-    } else if (cfg->algo == LDPC_ALGO_MS_FUSED) {
-        if (cfg->pack_mode != LDPC_PACK_BYTES && cfg->K % 8)
-            return set_error(LDPC_ERR_UNSUPPORTED, "MS_FUSED packs whole bytes per frame only");
-        /* flood_ldsp_kernel<.., CHAIN = false> (posteriors in LDS, 16-byte check records) wherever it fits
-         * with two workgroups per CU, else / with LDPC_TUNE_OFF(LDPC_TUNE_LDSP) the LDS-resident fused_flood_kernel */
-        if (!ldpc::tune_forced_off(tune.ldsp)) {
-            LDPC_HIP_TRY(ldpc::engine_ldsp_plan_create(&d->ldsp, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows, cfg->K,
-                                           cfg->max_batch, cfg->device, tune, /*flood=*/2));
-            if (d->ldsp.eligible && (ldpc::tune_forced_on(tune.ldsp) || d->ldsp.lds_bytes <= 80 * 1024)) d->use_ldsp = true;
-            else d->ldsp = ldpc::LdspPlan();
-        }
-        if (!d->use_ldsp) {
-            LDPC_HIP_TRY(ldpc::fused_plan_create(&d->fused, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows));
-            if (!d->fused.eligible)
-                return set_error(LDPC_ERR_UNSUPPORTED, "MS_FUSED needs a quasi-cyclic H (circulant size = layer_rows) whose "
-                            "posteriors fit in LDS");
-        }
-        d->use_fused = true;
-    } else if (cfg->algo == LDPC_ALGO_LAYERED_HOST || cfg->algo == LDPC_ALGO_LAYERED_BP || fx) {
-        /* the streaming layered engine (LAYERED_FX: unless LDPC_TUNE_FX_RECORD, below).  LAYERED_BP: the record kernels' 16-byte check record holds two minima and
-         * cannot hold a row's D independent messages, and the LDS-resident kernel carries no box-plus row */
-        d->layered.rule = bpfx ? ldpc::kLayerBpFx : fx ? ldpc::kLayerFx : cfg->algo == LDPC_ALGO_LAYERED_BP ? ldpc::kLayerBp : ldpc::kLayerHost;
-        d->layered.llr_scale = cfg->llr_scale;
-        if (fx) {       /* plain min-sum is the corrected row with scale 1, offset 0: the identity on [0, L] */
-            d->layered.L = (float)((1 << ((cfg->msg_bits ? cfg->msg_bits : 8) - 1)) - 1);
-            d->layered.LP = (float)((1 << ((cfg->post_bits ? cfg->post_bits : 16) - 1)) - 1);
-            d->layered.ms_scale = d->ms_scale;
-            d->layered.ms_offset = d->ms_offset;
-        }
-        if (bpfx) {     /* the kernels index the table with |a| + |b| <= 254 and never clamp: zeros behind its last entry */
-            int32_t t[ldpc::kBpFxTable];
-            const int n = ldpc::bp_fx_table_build(cfg->bp_frac_bits, t, ldpc::kBpFxTable);
-            std::vector<uint8_t> bytes((size_t)ldpc::kBpFxTable, 0);
-            for (int i = 0; i < n; ++i) bytes[(size_t)i] = (uint8_t)t[i];
-            LDPC_HIP_TRY(d->layered.bp_table.upload(bytes));
-        }
-        /* LDPC_TUNE_FX_RECORD: layered_ldsp_fx_kernel (int16 posteriors in LDS, 8-byte check records in cache) where the code
-         * fits it -- quasi-cyclic at layer_rows, rows of at most 24 entries, posteriors within the LDS limit, whole bytes per
-         * frame -- and the streaming engine, with the same result, where it does not */
-        if (fx_record && (cfg->pack_mode == LDPC_PACK_BYTES || cfg->K % 8 == 0)) {
-            d->ldsp.mc = ldpc::MsCorr{d->ms_scale, d->ms_offset};
-            d->ldsp.fx_L = (int32_t)d->layered.L;
-            d->ldsp.fx_LP = (int32_t)d->layered.LP;
-            LDPC_HIP_TRY(ldpc::engine_ldsp_fx_plan_create(&d->ldsp, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows,
-                                              cfg->K, cfg->max_batch, cfg->device, tune));
-            if (d->ldsp.eligible) d->use_fused = d->use_ldsp = true;
-            else d->ldsp = ldpc::LdspPlan();
-        }
-        /* the streaming plan (and its P / R arrays in HBM) only when the record kernel does not apply */
-        int rc = d->use_fused ? 0 : ldpc::layered_plan_create(&d->layered, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows, d->T, d->V);
-        if (rc == -1) return set_error(LDPC_ERR_ARG, "layer_rows=%d must divide M=%d and rows of a layer "
-                                  "must not share a column", cfg->layer_rows, g->M);
-        if (rc) return set_error(LDPC_ERR_HIP, "layered plan allocation failed: %s", hipGetErrorString(hipGetLastError()));
-    } else if (cfg->algo == LDPC_ALGO_LAYERED) {
-        /* short quasi-cyclic codes decode entirely in LDS, one launch (fused_kernels.hpp);
-         * LDPC_TUNE_OFF(LDPC_TUNE_FUSED) keeps the streaming kernels (same results, bit for bit) */
-        /* the correction (ms_scale / ms_offset) is carried by the record kernel (layered_ldsp_corr_kernel) and the
-         * streaming one (layer_corr_kernel), not by the LDS-resident fused_layered_kernel */
-        if (d->ms_corr && ldpc::tune_forced_on(tune.fused) && ldpc::tune_forced_off(tune.ldsp))
-            return set_error(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset: the LDS-resident layered kernel (LDPC_TUNE_FUSED on, "
-                        "LDPC_TUNE_LDSP off) carries no correction; the record or the streaming kernels do");
-        if (!crc_term && !ldpc::tune_forced_off(tune.fused) && (cfg->pack_mode == LDPC_PACK_BYTES || cfg->K % 8 == 0)) {
-            if (!d->ms_corr) {
-                LDPC_HIP_TRY(ldpc::fused_plan_create(&d->fused, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows));
-                d->use_fused = d->fused.eligible;
-            }
-            /* layered_ldsp_kernel (posterior in LDS, 16-byte check records in cache) is the default for
-             * every QC code it fits: larger codes cannot use the fully LDS-resident kernel at all, and on
-             * short ones it is 1.2-2.9x faster (exact-width rows, bit-level sign algebra: 800 against 280 G
-             * edge updates/s; circulants of <= 32 rows run several frames per wave in both).
-             * LDPC_TUNE_OFF(LDPC_TUNE_LDSP) forbids it (the LDS-resident kernel is then used where it applies). */
-            if (!ldpc::tune_forced_off(tune.ldsp)) {
-                d->ldsp.corr = d->ms_corr;
-                d->ldsp.mc = ldpc::MsCorr{d->ms_scale, d->ms_offset};
-                LDPC_HIP_TRY(ldpc::engine_ldsp_plan_create(&d->ldsp, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows,
-                                               cfg->K, cfg->max_batch, cfg->device, tune, /*flood=*/0));
-                if (d->ldsp.eligible) d->use_fused = d->use_ldsp = true;
-            }
-        }
-        /* the streaming plan (and its P / R arrays in HBM) only when no LDS-resident kernel applies;
-         * a detected QC structure already implies that rows of a layer share no column */
-        d->layered.rule = d->ms_corr ? ldpc::kLayerCorr : ldpc::kLayerFused;
-        d->layered.ms_scale = d->ms_scale;
-        d->layered.ms_offset = d->ms_offset;
-        int rc = d->use_fused ? 0 : ldpc::layered_plan_create(&d->layered, g->M, g->N, g->E, g->row_ptr, g->cols,
-                                                              cfg->layer_rows, d->T, d->V);
-        if (rc == -1) return set_error(LDPC_ERR_ARG, "layer_rows=%d must divide M=%d and rows of a layer "
-                                  "must not share a column", cfg->layer_rows, g->M);
-        if (rc) return set_error(LDPC_ERR_HIP, "layered plan allocation failed: %s",
-                            hipGetErrorString(hipGetLastError()));
-    } else {
-        /* flooding min-sum on a short quasi-cyclic code (layer_rows = circulant size given): the
-         * same arithmetic in one LDS-resident launch (fused_flood_kernel<.., CHAIN>) */
-        /* Measured (tools/gpu_short.py): for the flooding schedules the streaming kernels win at
-         * full work once the batch is large (HBM-bound, 1.3-1.9x), the fused kernels win on latency
-         * and for small batches; crossover near max_batch * E = 2^23 edge-frames.
-         * LDPC_TUNE_ON(LDPC_TUNE_FUSED) forces the fused kernels, LDPC_TUNE_OFF the streaming ones. */
-        /* the correction (ms_scale / ms_offset) is carried by the record kernel (flood_ldsp_corr_kernel) and the streaming
-         * kernels (kAlgoMSC), not by the LDS-resident fused_flood_kernel */
-        if (d->ms_corr && ldpc::tune_forced_on(tune.fused) && ldpc::tune_forced_off(tune.ldsp))
-            return set_error(LDPC_ERR_UNSUPPORTED, "ms_scale / ms_offset: the LDS-resident flooding kernel (LDPC_TUNE_FUSED on, "
-                        "LDPC_TUNE_LDSP off) carries no correction; the record or the streaming kernels do");
-        /* LDPC_ALGO_BP: the streaming kernels always (layer_rows does not select an engine) */
-        if (cfg->algo != LDPC_ALGO_BP && !crc_term && cfg->msg_dtype == LDPC_MSG_F32 && cfg->layer_rows > 0 && cfg->frames_per_lane == 0 &&
-            (cfg->pack_mode == LDPC_PACK_BYTES || cfg->K % 8 == 0)) {
-            const bool small = (int64_t)cfg->max_batch * g->E <= (int64_t)1 << 23;
-            if (!d->ms_corr && ldpc::tune_pick(tune.fused, small)) {
-                LDPC_HIP_TRY(ldpc::fused_plan_create(&d->fused, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows));
-                d->use_fused = d->fused.eligible && (cfg->algo == LDPC_ALGO_MS || d->fused.eligible_sp);
-            }
-            /* min-sum: posteriors in LDS (two images), one 16-byte record per check row (flood_ldsp_kernel).
-             * Default wherever it fits with >= 2 workgroups per CU: 2-2.9x the LDS-resident kernel and the
-             * streaming kernels on the 802.16e codes at any batch size ((2304, 1152): 9.9 / 4.0 / 2.9 Gbit/s
-             * at 16 384 frames, 2.6 / 0.9 / 1.3 at full work), 2.4 / 2.0 / 1.7 / 1.2x the streaming kernels on
-             * BG1-profile codes at Z = 64 / 128 / 256 / 384.  LDPC_TUNE_ON / OFF(LDPC_TUNE_LDSP) forces / forbids it. */
-            if (cfg->algo == LDPC_ALGO_MS && !ldpc::tune_forced_off(tune.fused) && !ldpc::tune_forced_off(tune.ldsp)) {
-                d->ldsp.corr = d->ms_corr;
-                d->ldsp.mc = ldpc::MsCorr{d->ms_scale, d->ms_offset};
-                LDPC_HIP_TRY(ldpc::engine_ldsp_plan_create(&d->ldsp, g->M, g->N, g->E, g->row_ptr, g->cols, cfg->layer_rows,
-                                               cfg->K, cfg->max_batch, cfg->device, tune, /*flood=*/1));
-                if (d->ldsp.eligible && (ldpc::tune_forced_on(tune.ldsp) || d->ldsp.lds_bytes <= 80 * 1024))
-                    d->use_fused = d->use_ldsp = true;
-                else
-                    d->ldsp = ldpc::LdspPlan();
-            }
-        }
-        if (!d->use_fused) {
-            /* work lists, kernel tables, launch plan; the column-fused check kernel's form and the arrays' placement are
-             * measured there unless the caller says which (engine_flood.hip) */
-            int rc = ldpc::engine_flood_setup(d, g, TF, t_child_depth == 0);
-            if (rc) return rc;
-            if (d->flood.tail_enabled) {
-                LDPC_HIP_TRY(d->flood.tail_state.alloc(4));
-                LDPC_HIP_TRY(d->flood.tail_map.alloc((size_t)d->flood.TO * d->F));
-                LDPC_HIP_TRY(d->flood.running.alloc((size_t)cfg->max_iter + 2));
-            }
-            /* tail compaction: with host polling on, the last <= 512 running frames of a batch of several
-             * tiles are finished by a small (8 x 64 frames) child decoder (cfg.tune_compact = -1: off, n: threshold) */
-            /* the child takes over once at most a quarter of the batch still runs: 1024 frames for the 4096-frame
-             * batches of the benchmark configurations (rate 9/10, fp16: 681 frames still run after round 5 of 8 and
-             * sit in all 16 tiles; a 512-frame child had to wait for round 6), 512 otherwise */
-            if (t_child_depth == 0) d->flood.child_capacity = cfg->max_batch >= 4096 ? 2 * ldpc::kCompactCapacity : ldpc::kCompactCapacity;
-            else d->flood.child_capacity = cfg->max_batch > ldpc::kCompactCapacity ? ldpc::kCompactCapacity : ldpc::kLastCapacity;
-            d->flood.compact_threshold = d->flood.child_capacity;
-            if (tune.compact) d->flood.compact_threshold = tune.compact < 0 ? 0 : std::min(d->flood.child_capacity, tune.compact);
-            /* the 1024-frame child has a 512-frame child of its own (rate 9/10: of the 681 frames handed over after round 5
-             * only 41 still run after round 6, spread over the child's three tiles of 256), and that one a single tile of 64
-             * frames (sum-product at 5 dB: a handful of frames in 4096 run all 50 rounds, one in each of its tiles) */
-            const bool may_have_child = t_child_depth == 0 || cfg->max_batch > ldpc::kLastCapacity;
-            if (cfg->early_term && cfg->poll_interval > 0 && d->T > 1 && d->flood.compact_threshold > 0 && may_have_child) {
-                ldpc_decoder_config cc = *cfg;
-                cc.max_batch = d->flood.child_capacity;
-                /* tiles of 64 frames for the 512-frame child (the last few stragglers of a batch); tiles of 256 for the
-                 * 1024-frame child, which takes over hundreds of frames: dense tiles, 8- / 16-byte accesses */
-                cc.frames_per_lane = (d->flood.child_capacity > ldpc::kCompactCapacity && d->V == 4) ? 4 : 1;
-                cc.layer_rows = 0;                 /* streaming kernels, same arithmetic */
-                cc.tune_compact = d->flood.child_capacity > ldpc::kLastCapacity ? 0 : -1;     /* all but the last hand over once more */
-                ++t_child_depth;
-                ldpc_decoder *child = nullptr;
-                rc = ldpc_decoder_create(g, &cc, &child);
-                --t_child_depth;
-                if (rc) return rc;
-                d->flood.child.reset(child);
-                d->flood.child->flood.is_child = true;
-                LDPC_HIP_TRY(hipSetDevice(cfg->device));
-                LDPC_HIP_TRY(d->flood.cmap.alloc((size_t)d->flood.child_capacity));
-                LDPC_HIP_TRY(d->flood.cinv.alloc((size_t)d->T * d->F));
-                LDPC_HIP_TRY(d->flood.cmoved.alloc((size_t)d->T * d->V));
-            }
-        }
+    /* the first candidate engine whose plan takes the code runs it */
+    const ldpc::Candidates cand = ldpc::engine_candidates(*cfg, facts, tune);
+    if (cand.code) return set_error(cand.code, "%s", cand.refusal);
+    bool taken = false;
+    for (int k = 0; k < cand.n && !taken; ++k) {
+        if (int rc = make_plan(d, g, cand.c[k], TF, &taken)) return rc;
+        if (taken) d->engine = cand.c[k].engine;
     }
+    if (!taken)         /* only LDPC_ALGO_MS_FUSED has no streaming engine behind its one-launch kernels */
+        return set_error(LDPC_ERR_UNSUPPORTED, "MS_FUSED needs a quasi-cyclic H (circulant size = layer_rows) whose "
+                    "posteriors fit in LDS");
     *out = guard.release();
     return LDPC_OK;
 }
@@ -705,8 +539,26 @@ static int decode_device_in(ldpc_decoder *d, const ldpc::LlrIn &in, int64_t fram
     LDPC_HIP_TRY(hipEventRecord(d->tm.ev_begin.e, s));
     /* gaps between frames (K % 8 != 0, decodeCL.c:191-192 leaves them alone) read as 0 */
     if (out_dev) LDPC_HIP_TRY(hipMemsetAsync(out_dev, 0, (size_t)room, s));
-    int rc;
-    if (d->use_fused) {
+    int rc = LDPC_OK;
+    /* what the streaming engines that work on the handle's own arrays are handed (engines.hpp: StreamRun) */
+    auto fill = [&](ldpc::StreamRun &run) {
+        run.span_begin = [](void *c, hipStream_t st, int kind, int deg, int64_t bytes) {
+            return ldpc::span_begin((ldpc_decoder *)c, st, kind, deg, bytes);
+        };
+        run.span_end = [](void *c, hipStream_t st) { return ldpc::span_end((ldpc_decoder *)c, st); };
+        run.span_ctx = d;
+        run.llr = in; run.frames = frames; run.out_dev = out_dev;
+        run.out_bytes = room; run.iters_dev = iters_dev;
+        run.K = d->cfg.K; run.max_iter = d->cfg.max_iter; run.tap_iter = d->tm.tap_iter;
+        run.early_term = d->cfg.early_term; run.pack_mode = d->cfg.pack_mode;
+        run.hard = d->hard.p; run.failw = d->failw.p; run.done = d->done.p; run.iters = d->iters.p;
+        run.row_ptr = d->row_ptr.p; run.edge_col = d->edge_col.p; run.summary = d->summary.p;
+        run.crc_w = d->crc_w.p; run.crc_bits = d->cfg.crc_kind ? d->cfg.crc_bits : 0;
+    };
+    switch (d->engine) {
+    case Engine::Fused:
+    case Engine::Ldsp:
+    case Engine::LdspFx: {
         /* the one-launch and record kernels read floats: a typed call widens into the handle's own buffer first, made by
          * the handle's first typed call (a plain call launches and moves what it always did) */
         const float *llr_dev = static_cast<const float *>(in.p);
@@ -727,48 +579,32 @@ static int decode_device_in(ldpc_decoder *d, const ldpc::LlrIn &in, int64_t fram
         run.soft_extrinsic = d->soft.kind == LDPC_SOFT_EXTRINSIC ? 1 : 0;
         hipError_t e = ldpc::span_begin(d, s, 2, 0, (int64_t)frames * (4 * d->N + d->cfg.K / 8));
         if (e == hipSuccess)
-            e = !d->use_ldsp ? ldpc::engine_fused_run(&d->fused, run, s, &d->last_iterations)
-                : d->ldsp.fx ? ldpc::engine_ldsp_fx_run(&d->ldsp, run, s, &d->last_iterations)
-                             : ldpc::engine_ldsp_run(&d->ldsp, run, s, &d->last_iterations);
+            e = d->engine == Engine::Fused ? ldpc::engine_fused_run(&d->fused, run, s, &d->last_iterations)
+                : d->engine == Engine::LdspFx ? ldpc::engine_ldsp_fx_run(&d->ldsp, run, s, &d->last_iterations)
+                                              : ldpc::engine_ldsp_run(&d->ldsp, run, s, &d->last_iterations);
         if (e == hipSuccess) e = ldpc::span_end(d, s);
-        rc = (e == hipSuccess) ? LDPC_OK : set_error(LDPC_ERR_HIP, "fused decode: %s", hipGetErrorString(e));
-    } else if (d->cfg.algo == LDPC_ALGO_LAYERED || d->cfg.algo == LDPC_ALGO_LAYERED_HOST || d->cfg.algo == LDPC_ALGO_LAYERED_BP ||
-               d->cfg.algo == LDPC_ALGO_LAYERED_FX || d->cfg.algo == LDPC_ALGO_LAYERED_BP_FX) {
+        if (e != hipSuccess) rc = set_error(LDPC_ERR_HIP, "fused decode: %s", hipGetErrorString(e));
+        break;
+    }
+    case Engine::Layered: {
         ldpc::LayeredRun run;
-        run.span_begin = [](void *c, hipStream_t st, int kind, int deg, int64_t bytes) {
-            return ldpc::span_begin((ldpc_decoder *)c, st, kind, deg, bytes);
-        };
-        run.span_end = [](void *c, hipStream_t st) { return ldpc::span_end((ldpc_decoder *)c, st); };
-        run.span_ctx = d;
-        run.llr = in; run.frames = frames; run.out_dev = out_dev;
-        run.out_bytes = room; run.iters_dev = iters_dev;
-        run.K = d->cfg.K; run.max_iter = d->cfg.max_iter; run.tap_iter = d->tm.tap_iter;
-        run.early_term = d->cfg.early_term; run.pack_mode = d->cfg.pack_mode;
-        run.hard = d->hard.p; run.failw = d->failw.p; run.done = d->done.p; run.iters = d->iters.p;
-        run.row_ptr = d->row_ptr.p; run.edge_col = d->edge_col.p; run.summary = d->summary.p;
-        run.crc_w = d->crc_w.p; run.crc_bits = d->cfg.crc_kind ? d->cfg.crc_bits : 0;
+        fill(run);
         run.soft = d->soft.dst; run.soft_extrinsic = d->soft.kind == LDPC_SOFT_EXTRINSIC ? 1 : 0;
-        hipError_t e = ldpc::engine_layered_run(&d->layered, run, s, &d->last_iterations);
-        rc = (e == hipSuccess) ? LDPC_OK
-                               : set_error(LDPC_ERR_HIP, "layered decode: %s", hipGetErrorString(e));
-    } else if (d->cfg.algo == LDPC_ALGO_BITFLIP) {
+        const hipError_t e = ldpc::engine_layered_run(&d->layered, run, s, &d->last_iterations);
+        if (e != hipSuccess) rc = set_error(LDPC_ERR_HIP, "layered decode: %s", hipGetErrorString(e));
+        break;
+    }
+    case Engine::Bitflip: {
         ldpc::BitflipRun run;
-        run.span_begin = [](void *c, hipStream_t st, int kind, int deg, int64_t bytes) {
-            return ldpc::span_begin((ldpc_decoder *)c, st, kind, deg, bytes);
-        };
-        run.span_end = [](void *c, hipStream_t st) { return ldpc::span_end((ldpc_decoder *)c, st); };
-        run.span_ctx = d;
-        run.llr = in; run.frames = frames; run.out_dev = out_dev;
-        run.out_bytes = room; run.iters_dev = iters_dev;
-        run.K = d->cfg.K; run.max_iter = d->cfg.max_iter; run.tap_iter = d->tm.tap_iter;
-        run.early_term = d->cfg.early_term; run.pack_mode = d->cfg.pack_mode;
-        run.hard = d->hard.p; run.failw = d->failw.p; run.done = d->done.p; run.iters = d->iters.p;
-        run.row_ptr = d->row_ptr.p; run.edge_col = d->edge_col.p; run.col_ptr = d->col_ptr.p; run.summary = d->summary.p;
-        run.crc_w = d->crc_w.p; run.crc_bits = d->cfg.crc_kind ? d->cfg.crc_bits : 0;
-        hipError_t e = ldpc::engine_bitflip_run(&d->bitflip, run, s, &d->last_iterations);
-        rc = (e == hipSuccess) ? LDPC_OK : set_error(LDPC_ERR_HIP, "bit-flipping decode: %s", hipGetErrorString(e));
-    } else {
+        fill(run);
+        run.col_ptr = d->col_ptr.p;
+        const hipError_t e = ldpc::engine_bitflip_run(&d->bitflip, run, s, &d->last_iterations);
+        if (e != hipSuccess) rc = set_error(LDPC_ERR_HIP, "bit-flipping decode: %s", hipGetErrorString(e));
+        break;
+    }
+    case Engine::Flood:
         rc = ldpc::engine_flood_run(d, in, frames, out_dev, room, iters_dev, s);
+        break;
     }
     if (rc) return rc;
     LDPC_HIP_TRY(hipEventRecord(d->tm.ev_end.e, s));
